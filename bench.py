@@ -3,8 +3,20 @@
 loop on the RTIOW book-1 final scene, 1920x1080x100 spp, depth 50 (BASELINE.json
 configs[1]), on N MI355X GPUs of one node.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: it sets up the scene, warms up, times the K steps, writes the
+last timed step's outputs if --dump-outputs is given, and prints the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step).  Everything else below -- the pinned
+framebuffer digest, the other visiting order, the roofline and its measured ceilings, the f32 mode (--f32), the
+other BASELINE configs, the CPU baseline and, on N > 1, the C ABI multi-GPU path -- runs only with --full, where
+the --no-* options still switch parts of it off.
+
+--dump-outputs DIR: the arrays a caller of the timed path receives from its last timed step, as DIR/<name>.npy:
+image.npy, the linear framebuffer (float64, H x W x 3), and rgb8.npy, the 8-bit image (as float32).  The files
+stay within 64 MB in all: an array that does not fit in full is written as a fixed, seeded sample of its pixels
+(<name>_sample.npy, one row per pixel, and <name>_sample_pixels.npy, their row-major indices as float64).
 
 A "step" is one full render of the image: every rank renders its interleaved 8x8
 tiles (no collective while rendering), then ONE gather of the compact tile buffers
@@ -25,8 +37,8 @@ Visiting order: by default ("--order auto") the scene is rendered in the fast or
 rtk_scene_optimize (same primitives, SAH grouping, fewer aabb::hit calls per ray) when
 the pass reports it bit-identical to the reference's bvh_node order -- it does for every
 BASELINE config: exact ties follow the reference's visiting ranks, constant media keep
-their positions in the reference's order -- otherwise in the reference order.  The other
-order is rendered too, outside the timed region, and reported under "other_order" with
+their positions in the reference's order -- otherwise in the reference order.  With --full the
+other order is rendered too, outside the timed region, and reported under "other_order" with
 its own rate; when the fast order claims exactness the two framebuffers must be
 byte-identical or the run fails.
 
@@ -39,7 +51,7 @@ Launching: `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the enviro
 its own N ranks (a `python -m torch.distributed.run` child process, spawned before this
 process imports torch or touches the GPU) and forwards rank 0's JSON line and exit code.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (null unless --full):
   roofline      what bounds the render kernel is VALU issue on partially filled waves, not
                 HBM (the program is served from LDS: measured HBM traffic is < 1 % of peak).
                 bound = "valu"; achieved = VALU pipe-cycles the launch consumed per second
@@ -260,7 +272,7 @@ def parse_args():
     p.add_argument("--order", default="auto", choices=["auto", "reference", "fast"],
                    help="visiting order: the reference's bvh_node order, rtk_scene_optimize's fast order, or fast where it is bit-identical (auto)")
     p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--f32", action="store_true", help="also time the f32 kernels (throughput mode, statistical parity only) and report them under f32_mode; "
+    p.add_argument("--f32", action="store_true", help="with --full: also time the f32 kernels (throughput mode, statistical parity only) and report them under f32_mode; "
                                                        "off by default: on C2 that mode is no faster than the f64 parity kernels since their box step moved to f32 culling boxes")
     p.add_argument("--no-f32", action="store_true", help="(accepted for older command lines; the f32 measurement is off unless --f32)")
     p.add_argument("--no-microbench", action="store_true", help="skip the measured ceilings (HBM copy, LDS read, VALU issue rates); nominal issue costs are used")
@@ -281,7 +293,14 @@ def parse_args():
     p.add_argument("--abi-timeout", type=float, default=150.0)
     p.add_argument("--rehearse-one-gpu", action="store_true",
                    help="dev only: run all ranks on device 0 with a gloo gather through host memory, to rehearse the N>1 control flow on a 1-GPU box")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run every check and secondary measurement (pinned digest, other order, roofline, f32 mode, other configs, CPU baseline, "
+                        "the abi path on N > 1); a plain run times the headline only")
+    p.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32/float64, 64 MB at most)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def host_cores():
@@ -294,6 +313,37 @@ def host_cores():
     except Exception:
         pass
     return max(1, n)
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 20260101
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write each (name, H x W x C array, dtype) as out_dir/<name>.npy in that dtype (float32 / float64), in order,
+    within `limit` bytes in all.  An array that does not fit in full is written as a fixed, seeded sample of its pixels instead:
+    <name>_sample.npy (pixels x C) and <name>_sample_pixels.npy (their row-major indices, float64).  Returns the files written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = limit, []
+    for name, arr, dtype in arrays:
+        arr = np.asarray(arr)
+        h, w, ch = arr.shape
+        item = np.dtype(dtype).itemsize
+        if arr.size * item + 128 <= left:
+            out = {name: arr.astype(dtype)}
+        else:
+            per_pixel = ch * item + 8
+            k = min(h * w, max(0, (left - 256) // per_pixel))
+            pixels = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, size=k, replace=False))
+            out = {name + "_sample": arr.reshape(h * w, ch)[pixels].astype(dtype), name + "_sample_pixels": pixels.astype(np.float64)}
+        for fname, data in out.items():
+            path = os.path.join(out_dir, fname + ".npy")
+            np.save(path, data)
+            left -= os.path.getsize(path)
+            written.append(path)
+    return written
 
 
 def cpu_baseline(rt, scene_name, cam, earth, target_seconds):
@@ -367,6 +417,8 @@ def run_abi(args):
     sync_all()
     elapsed = time.perf_counter() - t0
     last = images[(args.steps - 1) % 2]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("image", last.cpu().numpy(), "float64"), ("rgb8", rgb8s[(args.steps - 1) % 2].cpu().numpy(), "float32")])
     checksum = hashlib.sha256(last.cpu().numpy().tobytes()).hexdigest()[:16]
     t0 = time.perf_counter()
     for k in range(args.steps):  # the blocking form: what a single camera::render() call costs per frame
@@ -462,10 +514,13 @@ def main():
     reduced = bool(args.width or args.height or args.spp)
     fast_scene = scene.fast_order(cam.center)
     use_fast = args.order == "fast" or (args.order == "auto" and fast_scene.exact)
-    order_name = order_label(fast_scene, use_fast, not args.no_other_order)
+    with_other_order = args.full and not args.no_other_order
+    order_name = order_label(fast_scene, use_fast, with_other_order)
     renderer = rt.Renderer(local_rank)
-    other_renderer = rt.Renderer(local_rank)
+    other_renderer = rt.Renderer(local_rank) if with_other_order else None
     for r_, fast_ in ((renderer, use_fast), (other_renderer, not use_fast)):
+        if r_ is None:
+            continue
         if fast_:
             r_.upload_fast(scene, cam.center)   # rtk_scene_optimize + upload, fused slab test on the grown boxes
         else:
@@ -539,17 +594,18 @@ def main():
             if pipe is not None:
                 pipe.flush()
 
-        def last_image():
-            return images[(state["frame"] - 1) % slots]
-        return step, flush, last_image, slots
+        def last_outputs():  # what the last step handed its caller (rank 0): the linear image and its 8-bit bytes
+            i = (state["frame"] - 1) % slots
+            return images[i], rgb8s[i]
+        return step, flush, last_outputs, slots
 
     def barrier():
         if n > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(real_mode, steps, warmup, renderers=None):
-        step, flush, last_image, slots = make_step(real_mode, renderers or main_renderers)
+    def timed(real_mode, steps, warmup, renderers=None, kernel_time=True, keep_outputs=False):
+        step, flush, last_outputs, slots = make_step(real_mode, renderers or main_renderers)
         if warmup > 0:
             for _ in range(max(0, slots - warmup)):  # every context needs one untimed frame to learn its tile order
                 step()
@@ -567,21 +623,28 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        # the last timed step's outputs, copied to the host before anything else runs on them
+        outputs = [t.cpu().numpy() for t in last_outputs()] if keep_outputs and rank == 0 else None
+        if not kernel_time:
+            return elapsed, None, last_outputs()[0], outputs
         # kernel duration: separate, event-bracketed launches on the same stream (not inside the timed region)
         kernel_ms = []
         for _ in range(min(steps, 5)):
             step(kernel_ms)
         flush()
         barrier()
-        return elapsed, sum(kernel_ms) / len(kernel_ms), last_image()
+        return elapsed, sum(kernel_ms) / len(kernel_ms), last_outputs()[0], outputs
 
     import hashlib
 
-    elapsed, kernel_ms, image = timed(rt.RTK_REAL_F64, args.steps, args.warmup)
+    # a plain run times the headline only; the per-launch kernel time (roofline, other order) is measured with --full
+    elapsed, kernel_ms, image, outputs = timed(rt.RTK_REAL_F64, args.steps, args.warmup, kernel_time=args.full, keep_outputs=bool(args.dump_outputs))
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, [("image", outputs[0], "float64"), ("rgb8", outputs[1], "float32")])
     checksum = None
-    if rank == 0:  # a digest of the framebuffer: must not depend on the number of GPUs
+    if rank == 0 and args.full:  # a digest of the framebuffer: must not depend on the number of GPUs
         checksum = hashlib.sha256(image.cpu().numpy().tobytes()).hexdigest()[:16]
-    if rank == 0 and not reduced and checksum != PINNED_SHA256.get(args.config, checksum):  # the same frame on any GPU count, in any round
+    if rank == 0 and args.full and not reduced and checksum != PINNED_SHA256.get(args.config, checksum):  # the same frame on any GPU count, in any round
         raise SystemExit(f"{args.config}: framebuffer digest {checksum} differs from the pinned one {PINNED_SHA256[args.config]}")
     samples_per_step = W * H * spp
     value = samples_per_step * args.steps / elapsed / 1e6
@@ -589,16 +652,16 @@ def main():
     # ---- the other visiting order, outside the timed region: its rate, and the proof that both orders give the same bytes
     other_steps = max(1, min(args.steps, 3))
     other = None
-    if not args.no_other_order:
-        o_elapsed, o_kernel_ms, o_image = timed(rt.RTK_REAL_F64, other_steps, 1, [other_renderer])
-    if rank == 0 and not args.no_other_order:
+    if with_other_order:
+        o_elapsed, o_kernel_ms, o_image, _ = timed(rt.RTK_REAL_F64, other_steps, 1, [other_renderer])
+    if rank == 0 and with_other_order:
         o_sum = hashlib.sha256(o_image.cpu().numpy().tobytes()).hexdigest()[:16]
         other = {"order": "reference (bvh.h)" if use_fast else "fast (rtk_scene_upload_fast)", "value": round(samples_per_step * other_steps / o_elapsed / 1e6, 2),
                  "unit": "Msamples/s", "kernel_ms": round(o_kernel_ms, 4), "framebuffer_sha256": o_sum, "identical_framebuffer": o_sum == checksum,
                  "fast_order_exact": fast_scene.exact, "fast_order_info": fast_scene.info}
         if fast_scene.exact and o_sum != checksum:
             raise SystemExit(f"fast order claims bit-identity but the framebuffers differ: {checksum} vs {o_sum}")
-    if not args.no_other_order:
+    if with_other_order:
         del o_image
 
     # ---- roofline of the render kernel on rank 0.  Bound: VALU issue (see the module docstring); the HBM byte model of
@@ -606,7 +669,7 @@ def main():
     roofline = None
     counters = None
     workload = f"{scene_name} {W}x{H}x{spp}"
-    if rank == 0:
+    if rank == 0 and args.full:
         d_cnt = torch.zeros(12, dtype=torch.int64, device=dev)
         tpr = tiling.tiles_per_rank(W, H, n)
         scratch = torch.empty((tpr * 192,), dtype=torch.float64, device=dev) if n > 1 else torch.empty((H, W, 3), dtype=torch.float64, device=dev)
@@ -692,8 +755,8 @@ def main():
                             "launch stream, one launch alone on the device")
 
     f32_mode = None
-    if args.f32 and not args.no_f32:
-        e32, k32, _ = timed(rt.RTK_REAL_F32, max(1, min(args.steps, 3)), 1)
+    if args.full and args.f32 and not args.no_f32:
+        e32, k32, _, _ = timed(rt.RTK_REAL_F32, max(1, min(args.steps, 3)), 1)
         if rank == 0:
             f32_mode = {"value": round(samples_per_step * max(1, min(args.steps, 3)) / e32 / 1e6, 2), "unit": "Msamples/s", "kernel_ms": round(k32, 4),
                         "note": "throughput mode; parity vs the double reference is statistical only (SURVEY.md 8(d)); not the headline"}
@@ -701,7 +764,7 @@ def main():
     # ---- the other BASELINE configs (parity-test cases, not the headline): a few frames each at full size, in the order and
     # with the kernel `--config cN` would time, so that their rates are on the driver's record too.  N = 1, default config only.
     other_configs = None
-    if rank == 0 and n == 1 and args.config == "c2" and not reduced and not args.variant and not args.no_other_configs:
+    if args.full and rank == 0 and n == 1 and args.config == "c2" and not reduced and not args.variant and not args.no_other_configs:
         other_configs = {}
         for cfg in ("c3", "c4", "c5"):
             # A failure here fails the run: an exception propagates, and a fast order that claims bit-identity is checked
@@ -744,7 +807,7 @@ def main():
             del r_, r2_, img_, u8_, scene_
 
     cpu = None
-    if rank == 0 and n == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(rt, scene_name, cam, earth, args.cpu_seconds)
         except Exception as exc:  # the baseline is reported, never required
@@ -753,7 +816,7 @@ def main():
     # ---- N > 1: the product's own multi-GPU path (rtk_render_multi_enqueue behind the C ABI: one process, N devices) beside the
     # torch.distributed ranks that were just timed -- in a child process of rank 0, while every rank idles at a CPU barrier
     multi_paths = None
-    if n > 1 and not args.no_abi_path:
+    if args.full and n > 1 and not args.no_abi_path:
         idle = dist.new_group(backend="gloo")
         torch.cuda.synchronize()
         dist.barrier(group=idle)

@@ -8,6 +8,9 @@ Runs only where /root/reference exists (the build container).  Outputs are data:
                              the reference's pointer graph (bvh topology, perlin tables, texels ...)
   img_<scene>.npz            seed-matched linear framebuffers (+ bytes, + RNG-draw/segment counts)
                              rendered through the reference's hittable/material/texture classes
+  reference_assets.json      (--assets, with REFERENCE=<the reference tree>) data files of the reference
+                             copied here -- monkey.obj and four of its textures -- with the sha256 of the
+                             description its OBJ loader gives and of the texels its image loader gives
 The reference has no tests or fixtures of its own; these vectors are what pins
 oracle/rt_oracle.cpp, and through it the device kernels.
 """
@@ -227,7 +230,39 @@ def make_png_fixtures():
     encode("png_rgb8_64x48_fixedhuff", 64, 48, 2, 8, 0, level=1)
 
 
+# Data files of the reference tree (never its sources) that the loaders are compared on.  male_texture.jpg (2048x2048,
+# 2.4 MB) stays out: its 4:2:0 baseline decode is what the jpg_420_* fixtures pin at a size that fits the repository.
+REFERENCE_ASSETS = {"monkey.obj": "monkey.obj", "Images/earthmap.jpg": "ref_earthmap.jpg", "Images/Sky.png": "ref_sky.png",
+                    "Images/ImageOutputColors.png": "ref_image_output_colors.png", "Images/final.png": "ref_final.png"}
+
+
+def make_reference_assets():
+    import shutil
+
+    reference = os.environ.get("REFERENCE")
+    if not (reference and os.path.isdir(reference) and os.path.exists(REF)):
+        raise SystemExit("--assets needs REFERENCE=<the reference tree> and oracle/_ref/ref_driver")
+    tmp = tempfile.mkdtemp()
+    out = {"obj_desc_sha256": {}, "texels": {}}
+    for src, dst in REFERENCE_ASSETS.items():
+        path = os.path.join(HERE, dst)
+        shutil.copyfile(os.path.join(reference, src), path)
+        if dst.endswith(".obj"):
+            desc = os.path.join(tmp, "obj.rtks")
+            subprocess.check_call([REF, "desc", "obj_mesh", str(SCENE_SEED), path, desc], stderr=subprocess.DEVNULL)
+            out["obj_desc_sha256"][dst] = hashlib.sha256(open(desc, "rb").read()).hexdigest()
+        else:
+            prefix = os.path.join(tmp, "t")
+            subprocess.check_call([REF, "texels", path, prefix])
+            w, h = np.fromfile(prefix + ".dims", np.int32).tolist()
+            out["texels"][dst] = {"width": w, "height": h, "sha256": hashlib.sha256(open(prefix + ".u8", "rb").read()).hexdigest()}
+    json.dump(out, open(os.path.join(HERE, "reference_assets.json"), "w"), indent=1, sort_keys=True)
+
+
 if __name__ == "__main__":
+    if "--assets" in sys.argv:
+        make_reference_assets()
+        raise SystemExit(0)
     if "--jpeg-only" not in sys.argv and "--png-only" not in sys.argv:
         main()
     if "--png-only" not in sys.argv:

@@ -307,38 +307,21 @@ def test_reference_style_program_compiles_and_links_against_the_drop_in_headers(
 
 def test_obj_loader_matches_reference_on_its_own_asset(rt, tmp_path):
     """mesh::loadObj (host/mesh.h + the minimal GLM) against the reference's loader on the reference's monkey.obj
-    (968 triangles, rotate/scale/translate transform).  The asset cannot travel with the repository, so this runs
-    only where /root/reference exists; tests/golden/quad_tri.obj covers the loader everywhere else."""
+    (968 triangles, rotate/scale/translate transform), stored as tests/golden/monkey.obj with the sha256 of the description
+    the reference's loader gives for it (make_goldens.py --assets); where oracle/_ref is built it is compared live as well."""
     from oracle import orc
 
-    asset = "/root/reference/monkey.obj"
-    if not (os.path.exists(asset) and os.path.exists(orc.REF_DRIVER)):
-        pytest.skip("reference asset / driver not available here")
-    mine, ref = tmp_path / "mine.rtks", tmp_path / "ref.rtks"
+    asset = os.path.join(GOLDEN, "monkey.obj")
+    want = json.load(open(os.path.join(GOLDEN, "reference_assets.json")))["obj_desc_sha256"]["monkey.obj"]
+    mine = tmp_path / "mine.rtks"
     rt.Scene.build("obj_mesh", SCENE_SEED, asset).save(str(mine))
-    subprocess.check_call([orc.REF_DRIVER, "desc", "obj_mesh", str(SCENE_SEED), asset, str(ref)], stderr=subprocess.DEVNULL)
     blob = mine.read_bytes()
-    assert blob == ref.read_bytes()
+    assert hashlib.sha256(blob).hexdigest() == want
     assert np.frombuffer(blob[8:8 + 64], np.int32)[5] == 968  # n_triangles
-
-
-def test_reference_main_cpp_compiles_unmodified_against_the_drop_in_headers(rt, tmp_path):
-    """The drop-in claim, literally: the reference's own main.cpp (all eight scenes, mesh.h, the Win32 shell) builds
-    and links against host/ + host/compat/ + librtk_hip.so without a single edit.  The file is copied to a scratch
-    directory only so that its quote-includes resolve to this package's headers; it never enters the repository.
-    Runs where /root/reference exists."""
-    src = "/root/reference/main.cpp"
-    if not os.path.exists(src):
-        pytest.skip("reference tree not available here")
-    import shutil
-
-    shutil.copy(src, tmp_path / "main.cpp")
-    pkg = os.path.dirname(rt.HIP_LIB_PATH)
-    exe = tmp_path / "reference_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", str(tmp_path / "main.cpp"), "-I" + os.path.join(pkg, "host"),
-                           "-I" + os.path.join(pkg, "host", "compat"), "-I" + os.path.join(ROOT, "include"), "-L" + pkg, "-lrtk_hip",
-                           "-Wl,-rpath," + pkg, "-o", str(exe)])
-    assert exe.exists()
+    if os.path.exists(orc.REF_DRIVER):
+        ref = tmp_path / "ref.rtks"
+        subprocess.check_call([orc.REF_DRIVER, "desc", "obj_mesh", str(SCENE_SEED), asset, str(ref)], stderr=subprocess.DEVNULL)
+        assert blob == ref.read_bytes()
 
 
 def test_the_library_is_loaded_after_torch_so_that_one_hip_runtime_serves_both():

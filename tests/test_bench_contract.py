@@ -141,10 +141,56 @@ def test_isa_cost_table_is_derived_from_the_kernel_sources():
             assert committed["costs"] == c
 
 
+def test_dump_outputs_writes_whole_arrays_or_a_seeded_sample_within_the_limit(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, whole where they fit, else the same seeded pixel sample every run."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(1)
+    image = rng.random((20, 30, 3))
+    rgb8 = rng.integers(0, 256, (20, 30, 3), dtype=np.uint8)
+    whole = bench.dump_outputs(str(tmp_path / "whole"), [("image", image, "float64"), ("rgb8", rgb8, "float32")])
+    assert [os.path.basename(f) for f in whole] == ["image.npy", "rgb8.npy"]
+    assert np.array_equal(np.load(whole[0]), image) and np.load(whole[0]).dtype == np.float64
+    assert np.array_equal(np.load(whole[1]), rgb8.astype(np.float32)) and np.load(whole[1]).dtype == np.float32
+    limit = image.nbytes + 128 + 2000     # the image fits whole, the 8-bit image only as a sample
+    runs = [bench.dump_outputs(str(tmp_path / f"cut{i}"), [("image", image, "float64"), ("rgb8", rgb8, "float32")], limit=limit) for i in range(2)]
+    for files in runs:
+        assert [os.path.basename(f) for f in files] == ["image.npy", "rgb8_sample.npy", "rgb8_sample_pixels.npy"]
+        assert sum(os.path.getsize(f) for f in files) <= limit
+    sample, pixels = np.load(runs[0][1]), np.load(runs[0][2])
+    assert sample.dtype == np.float32 and pixels.dtype == np.float64 and 0 < len(pixels) < 600 and sample.shape == (len(pixels), 3)
+    assert np.array_equal(sample, rgb8.reshape(-1, 3)[pixels.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(np.load(runs[1][2]), pixels) and np.array_equal(np.load(runs[1][1]), sample)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run: the contract's keys, the requested number of timed steps, nothing of --full, and the last step's
+    framebuffer and 8-bit image under --dump-outputs."""
+    import numpy as np
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "320", "--height", "200", "--spp", "24",
+           "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [line for line in p.stdout.splitlines() if line.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Msamples/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 320 * 200 * 24 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-3
+    assert all(d[key] is None for key in ("roofline", "cpu_baseline", "f32_mode", "other_order", "other_configs", "multi_paths"))
+    image, rgb8 = np.load(tmp_path / "out" / "image.npy"), np.load(tmp_path / "out" / "rgb8.npy")
+    assert image.dtype == np.float64 and image.shape == (200, 320, 3) and np.isfinite(image).all() and image.max() > 0
+    assert rgb8.dtype == np.float32 and rgb8.shape == (200, 320, 3) and rgb8.min() >= 0 and rgb8.max() <= 255 and rgb8.max() > 0
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "320", "--height", "200", "--spp", "24",
-           "--cpu-seconds", "1"]
+           "--cpu-seconds", "1", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [line for line in p.stdout.splitlines() if line.startswith("{")]
@@ -178,22 +224,26 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 
 
 @pytest.mark.gpu
-def test_bench_multi_abi_mode_reproduces_the_one_gpu_framebuffer():
+def test_bench_multi_abi_mode_reproduces_the_one_gpu_framebuffer(tmp_path):
     """`bench.py --multi abi`: ONE process driving the product's own multi-GPU path (rtk_render_multi_enqueue / rtk_multi_wait,
     two frames in flight) -- rehearsed on this one-GPU box with the device listed four times -- must print the same
-    framebuffer digest as the N = 1 line of the same workload, and the contract's keys."""
+    framebuffer digest as the N = 1 line of the same workload, dump the same outputs, and print the contract's keys."""
+    import numpy as np
+
     common = ["--steps", "3", "--warmup", "1", "--width", "320", "--height", "200", "--spp", "24"]
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *common, "--no-cpu-baseline", "--no-f32", "--no-other-configs"],
-                         capture_output=True, text=True, timeout=600)
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *common, "--no-cpu-baseline", "--no-f32", "--no-other-configs", "--full",
+                          "--dump-outputs", str(tmp_path / "one")], capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads([line for line in one.stdout.splitlines() if line.startswith("{")][-1])
-    abi = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--multi", "abi", "--gpus", "4", "--multi-devices", "0,0,0,0", *common],
-                         capture_output=True, text=True, timeout=600)
+    abi = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--multi", "abi", "--gpus", "4", "--multi-devices", "0,0,0,0", *common,
+                          "--dump-outputs", str(tmp_path / "abi")], capture_output=True, text=True, timeout=600)
     assert abi.returncode == 0, abi.stderr[-2000:]
     lines = [line for line in abi.stdout.splitlines() if line.startswith("{")]
     assert len(lines) == 1
     d4 = json.loads(lines[0])
     assert d4["multi"] == "abi" and d4["n_gpus"] == 4 and d4["devices"] == [0, 0, 0, 0] and d4["uses_rccl"] is False
     assert d4["framebuffer_sha256"] == d1["framebuffer_sha256"]
+    for name in ("image.npy", "rgb8.npy"):
+        assert np.array_equal(np.load(tmp_path / "one" / name), np.load(tmp_path / "abi" / name)), name
     assert d4["value"] > 0 and d4["blocking_render_multi"]["value"] > 0
     assert abs(d4["value"] - 320 * 200 * 24 / (d4["ms_per_step"] * 1e-3) / 1e6) / d4["value"] < 1e-3
