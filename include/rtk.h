@@ -437,6 +437,82 @@ int rtk_render_multi(rtk_multi* multi, const rtk_camera* cam, const rtk_render_o
 typedef void (*rtk_progress_fn)(int64_t done, int64_t total, void* user);
 int rtk_set_progress_callback(rtk_ctx* ctx, rtk_progress_fn fn, void* user, int interval_ms);
 
+/* Progressive, resumable rendering ------------------------------------------------
+ * A session (rtk_progressive) owns the running sums of ONE frame -- this rank's [local tile][3][64] reals, the layout of the
+ * resolve's running sum -- and renders it in steps: a step adds samples [done, done + n) of every pixel.  The target spp is
+ * cam->samples_per_pixel at creation, and the frame is cut into the chunks a one-shot render of the target uses
+ * (rtk_progressive_chunk_size: 8 samples up to 512 spp).  Because every sample's random stream is f(seed, pixel, absolute
+ * sample) and the chunks are added in the one-shot order (c0, + c1, + c2, ...), the finished session's image is BIT-IDENTICAL
+ * to rtk_render_device's for the same scene, camera, seed and real mode, whatever the steps; and after each step the preview is
+ * bit-identical to a one-shot render with samples_per_pixel = samples_done (and pixel_samples_scale = 1.0 / samples_done) as
+ * long as that render uses the same chunk size (target <= 512).  One device, one rank's tiles; not through rtk_multi.
+ *
+ * Rules:
+ *   - n_samples must be a multiple of the chunk size, except for the step that ends exactly at the target.  A step that would
+ *     pass the target, a step on a finished session and n_samples <= 0 return RTK_ERR_INVALID and change nothing.
+ *   - the session records a 64-bit digest of the program uploaded when it was created; a step after the context's scene changed
+ *     (another scene, or the same one in the other visiting order) fails with RTK_ERR_INVALID.
+ *   - a step that fails in a HIP call poisons the session: every later call on it fails (rtk_progressive_destroy excepted).
+ *   - the session's sums are its own device memory: one-shot renders may be enqueued on the same context between steps.
+ *
+ * Noise estimate (batch means over chunks): for every full chunk k of a pixel, y_k = (s.x + s.y + s.z) / (3 c) (c = chunk
+ * size, s = the chunk's sample sum); the session keeps S1 = sum y_k and S2 = sum y_k^2 in double.  With K >= 2 full chunks:
+ * m = S1 / K, v = max(0, (S2 - K m^2) / (K - 1)), se = sqrt(v / K), rel = se / max(m, 1e-3).  A final partial chunk is in the
+ * image, not in the estimate.  rtk_noise_stats reduces se / rel over this rank's in-image pixels in a fixed order (the same
+ * inputs give the same bits); valid = 0 while K < 2. */
+typedef struct rtk_progressive rtk_progressive;
+
+typedef struct rtk_noise_stats {
+    int64_t samples_done;
+    int32_t full_chunks;     /* K */
+    int32_t valid;           /* K >= 2 */
+    double mean_se;          /* mean over in-image pixels of se */
+    double max_se;
+    double mean_rel_se;      /* mean over in-image pixels of se / max(m, 1e-3) */
+} rtk_noise_stats;
+
+/* Checkpoint (rtk_progressive_save): a little-endian byte string, version 1:
+ *   offset  0  char[8]     magic "RTKPROG\0"
+ *           8  int32       version (1)
+ *          12  int32 x 8   width, height, rank, n_ranks, real_mode, target_spp, chunk_size, samples_done
+ *          44  uint32      seed
+ *          48  uint64      scene_digest
+ *          56  rtk_camera  the session's camera (200 bytes)
+ *         256  real  [tiles_per_rank][3][64]   running sum (8-byte reals for F64, 4-byte for F32)
+ *              double[tiles_per_rank][64]      S1, then S2
+ *              uint64      FNV-1a 64 of every byte before it
+ * (tiles_per_rank = rtk_tiles_per_rank(width, height, n_ranks)). */
+#define RTK_CHECKPOINT_VERSION 1
+typedef struct rtk_checkpoint_info {
+    int32_t version, width, height, rank, n_ranks, real_mode, target_spp, chunk_size, samples_done;
+    uint32_t seed;
+    uint64_t scene_digest;
+} rtk_checkpoint_info;
+
+/* A session for cam (samples_per_pixel = target) and opts (seed, real_mode, rank / n_ranks, stream; count_work and variant
+ * are ignored: a step counts work when it is given counters).  Needs an uploaded scene. */
+int rtk_progressive_create(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, rtk_progressive** out);
+/* Enqueue the next n_samples of every pixel on opts->stream and write the preview (scaled by 1 / samples_done): n_ranks == 1:
+ * d_linear row-major H*W*3 reals, d_rgb8 H*W*3 bytes, d_noise H*W floats (se); n_ranks > 1: d_linear this rank's compact tile
+ * buffer, d_rgb8 NULL, d_noise [tiles_per_rank][64].  Any output may be NULL.  d_counters (zeroed by the caller) receives this
+ * step's work counters when given. */
+int rtk_progressive_step(rtk_progressive* p, int32_t n_samples, void* d_linear, uint8_t* d_rgb8, float* d_noise, rtk_work_counters* d_counters);
+/* The same into host buffers (h_linear doubles -- F32 widened -- of the layout above); blocking.  counters may be NULL. */
+int rtk_progressive_step_host(rtk_progressive* p, int32_t n_samples, double* h_linear, uint8_t* h_rgb8, float* h_noise, rtk_work_counters* counters);
+int rtk_progressive_samples_done(const rtk_progressive* p);
+int rtk_progressive_chunk_size(const rtk_progressive* p);
+/* Frame noise statistics of the samples done so far (synchronises the session's stream). */
+int rtk_progressive_noise(rtk_progressive* p, rtk_noise_stats* out);
+int64_t rtk_progressive_checkpoint_bytes(const rtk_progressive* p);
+/* Write the checkpoint into h_buf (n >= rtk_progressive_checkpoint_bytes); synchronises the session's stream. */
+int rtk_progressive_save(rtk_progressive* p, void* h_buf, int64_t n);
+/* A session that continues a checkpoint.  Refused (RTK_ERR_INVALID, reason in rtk_last_error) when the checkpoint is truncated or
+ * corrupted, or its camera, seed, real mode, rank / n_ranks, target or scene digest differ from the call's / the context's. */
+int rtk_progressive_resume(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const void* h_buf, int64_t n, rtk_progressive** out);
+/* Host-only (no context, no device): parse and check a checkpoint (magic, version, sizes, checksum). */
+int rtk_checkpoint_read_info(const void* h_buf, int64_t n, rtk_checkpoint_info* out);
+int rtk_progressive_destroy(rtk_progressive* p);
+
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and
  * hit-record code as the render kernel.  Host buffers:

@@ -146,6 +146,26 @@ def algorithmic_bytes_per_sample(counters: dict, spp: int, real_mode: int, f32_b
     return total / n + fb / max(1, spp)
 
 
+class NoiseStats(C.Structure):
+    """rtk_noise_stats: frame noise statistics of a progressive session (batch means over sample chunks)."""
+
+    _fields_ = [("samples_done", C.c_int64), ("full_chunks", C.c_int32), ("valid", C.c_int32),
+                ("mean_se", C.c_double), ("max_se", C.c_double), ("mean_rel_se", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class CheckpointInfo(C.Structure):
+    """rtk_checkpoint_info: the header of a progressive session's checkpoint."""
+
+    _fields_ = [(name, C.c_int32) for name in ("version", "width", "height", "rank", "n_ranks", "real_mode", "target_spp", "chunk_size",
+                                                 "samples_done")] + [("seed", C.c_uint32), ("scene_digest", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 # ----------------------------------------------------------------------------- libraries
 _host_lib = None
 _hip_lib = None
@@ -239,6 +259,22 @@ def hip_lib() -> C.CDLL:
         lib.rtk_render_multi_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_void_p, C.c_void_p]
         lib.rtk_render_multi.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_void_p, C.c_void_p]
         lib.rtk_set_progress_callback.argtypes = [C.c_void_p, PROGRESS_FN, C.c_void_p, C.c_int]
+        try:
+            lib.rtk_progressive_create.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(C.c_void_p)]
+            lib.rtk_progressive_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rtk_progressive_step_host.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rtk_progressive_samples_done.argtypes = [C.c_void_p]
+            lib.rtk_progressive_chunk_size.argtypes = [C.c_void_p]
+            lib.rtk_progressive_noise.argtypes = [C.c_void_p, C.POINTER(NoiseStats)]
+            lib.rtk_progressive_checkpoint_bytes.restype = C.c_int64
+            lib.rtk_progressive_checkpoint_bytes.argtypes = [C.c_void_p]
+            lib.rtk_progressive_save.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+            lib.rtk_progressive_resume.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+            lib.rtk_checkpoint_read_info.argtypes = [C.c_void_p, C.c_int64, C.POINTER(CheckpointInfo)]
+            lib.rtk_progressive_destroy.argtypes = [C.c_void_p]
+        except AttributeError:
+            if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
+                raise
         if lib.rtk_abi_version() != RTK_ABI_VERSION and HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:
             raise RuntimeError("librtk_hip.so ABI version mismatch")
         _hip_lib = lib
@@ -514,6 +550,24 @@ class Renderer:
         self._check(self._lib.rtk_debug_get_ray(self._ctx, real_mode, C.byref(cam), seed, n, ijs.ctypes.data, out.ctypes.data, draws.ctypes.data))
         return out, draws
 
+    def progressive(self, cam: Camera, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
+                    stream: int = 0) -> "Progressive":
+        """rtk_progressive_create: a session that renders the frame of ``cam`` (samples_per_pixel = the target) in steps."""
+        opts = RenderOpts(seed, real_mode, rank, n_ranks, 0, 0, stream or None)
+        h = C.c_void_p()
+        self._check(self._lib.rtk_progressive_create(self._ctx, C.byref(cam), C.byref(opts), C.byref(h)))
+        return Progressive(self, h, cam, real_mode, n_ranks)
+
+    def resume(self, cam: Camera, blob: bytes, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
+               stream: int = 0) -> "Progressive":
+        """rtk_progressive_resume: continue a session from ``Progressive.save()``'s bytes (refused -- RtkError -- when they were
+        made with another camera, seed, real mode, rank split, target or scene)."""
+        opts = RenderOpts(seed, real_mode, rank, n_ranks, 0, 0, stream or None)
+        buf = C.create_string_buffer(bytes(blob), len(blob))
+        h = C.c_void_p()
+        self._check(self._lib.rtk_progressive_resume(self._ctx, C.byref(cam), C.byref(opts), buf, len(blob), C.byref(h)))
+        return Progressive(self, h, cam, real_mode, n_ranks)
+
     def set_progress(self, fn=None, interval_ms: int = 100) -> None:
         """rtk_set_progress_callback: ``fn(done, total)`` is called from the thread that runs a blocking render
         (render_host), at most every ``interval_ms``; None switches it off."""
@@ -530,6 +584,86 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+
+class Progressive:
+    """A progressive session (rtk_progressive): one frame rendered in steps of whole sample chunks, with a per-pixel noise
+    estimate and checkpoints.  The finished frame is bit-identical to ``Renderer.render_host`` of the same camera."""
+
+    def __init__(self, renderer: Renderer, handle: C.c_void_p, cam: Camera, real_mode: int, n_ranks: int):
+        self._r = renderer      # keeps the context alive
+        self._lib = renderer._lib
+        self._h = handle
+        self.width, self.height, self.target = cam.image_width, cam.image_height, cam.samples_per_pixel
+        self.real_mode, self.n_ranks = real_mode, n_ranks
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise RtkError(rc, self._lib.rtk_last_error().decode())
+
+    @property
+    def samples_done(self) -> int:
+        return self._lib.rtk_progressive_samples_done(self._h)
+
+    @property
+    def chunk_size(self) -> int:
+        return self._lib.rtk_progressive_chunk_size(self._h)
+
+    def step(self, n: int, *, count: bool = False):
+        """Add the next ``n`` samples of every pixel.  Returns (linear float64, rgb8, noise float32) -- (H, W, 3), (H, W, 3),
+        (H, W) for one rank; the compact [tiles, 3, 64] buffer, None and [tiles, 64] for one of several -- plus the step's work
+        counters when ``count``."""
+        import numpy as np
+
+        if self.n_ranks == 1:
+            linear, rgb8, noise = np.zeros((self.height, self.width, 3)), np.zeros((self.height, self.width, 3), np.uint8), np.zeros((self.height, self.width), np.float32)
+        else:
+            t = tiles_per_rank(self.width, self.height, self.n_ranks)
+            linear, rgb8, noise = np.zeros((t, 3, 64)), None, np.zeros((t, 64), np.float32)
+        counters = WorkCounters()
+        self._check(self._lib.rtk_progressive_step_host(self._h, n, linear.ctypes.data, rgb8.ctypes.data if rgb8 is not None else None,
+                                                        noise.ctypes.data, C.byref(counters) if count else None))
+        return (linear, rgb8, noise, counters.as_dict()) if count else (linear, rgb8, noise)
+
+    def step_device(self, n: int, d_linear: int = 0, d_rgb8: int = 0, d_noise: int = 0, d_counters: int = 0) -> None:
+        """rtk_progressive_step with raw device pointers (any may be 0); asynchronous on the session's stream."""
+        self._check(self._lib.rtk_progressive_step(self._h, n, d_linear or None, d_rgb8 or None, d_noise or None, d_counters or None))
+
+    def noise(self) -> dict:
+        out = NoiseStats()
+        self._check(self._lib.rtk_progressive_noise(self._h, C.byref(out)))
+        return out.as_dict()
+
+    def save(self) -> bytes:
+        n = self._lib.rtk_progressive_checkpoint_bytes(self._h)
+        if n <= 0:
+            self._check(int(n) or -1)
+        buf = C.create_string_buffer(n)
+        self._check(self._lib.rtk_progressive_save(self._h, buf, n))
+        return buf.raw
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.rtk_progressive_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def checkpoint_info(blob: bytes) -> dict:
+    """rtk_checkpoint_read_info: the header of a checkpoint, checked (magic, version, size, checksum).  Host-only, no GPU.
+    Raises RtkError for a blob the library would refuse."""
+    lib = hip_lib()
+    info = CheckpointInfo()
+    buf = C.create_string_buffer(bytes(blob), max(1, len(blob)))
+    rc = lib.rtk_checkpoint_read_info(buf, len(blob), C.byref(info))
+    if rc != 0:
+        raise RtkError(rc, lib.rtk_last_error().decode())
+    return info.as_dict()
 
 
 class MultiRenderer:

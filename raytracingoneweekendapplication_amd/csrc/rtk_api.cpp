@@ -916,6 +916,7 @@ struct rtk_ctx {
     uint32_t features = 0;
     int32_t n_ops = 0;
     int32_t n_materials = 0, n_textures = 0;  // of the uploaded description (index checks of the known-answer entry points)
+    uint64_t scene_digest = 0;                // of the uploaded program and tables (progressive sessions refuse another scene)
     DeviceScene<double> scene64;
     DeviceScene<float> scene32;
     // Words the persistent waves pull tile indices from; one per launch in a
@@ -1236,6 +1237,43 @@ int rtk_scene_validate(const rtk_scene_desc* scene, int32_t* n_program_ops) {
     }
 }
 
+
+// What a frame depends on besides the camera and the seed: the compiled program (ops, tie ranks, chains), every table of the
+// description, the kernel features and the visiting order with its culling margin.
+static uint64_t scene_digest(const rtk_scene_desc& sc, const Program& prog, uint32_t features, bool fast_order, double eye_extent) {
+    Fnv64 f;
+    f.add_pod(features);
+    f.add_pod(fast_order);
+    f.add_pod(eye_extent);
+    f.add(prog.ops.data(), prog.ops.size() * sizeof(Op));
+    f.add(prog.ranks.data(), prog.ranks.size() * sizeof(uint32_t));
+    f.add(prog.extra.data(), prog.extra.size() * sizeof(uint32_t));
+    for (const Chain& ch : prog.chains) {
+        f.add_pod(uint64_t(ch.size()));
+        for (const ChainStep& st : ch) {
+            f.add_pod(st.rotate);
+            f.add_pod(st.index);
+        }
+    }
+    f.add_pod(sc.root);
+    f.add_table(sc.nodes, sc.n_nodes);
+    f.add_table(sc.list_children, sc.n_list_children);
+    f.add_table(sc.spheres, sc.n_spheres);
+    f.add_table(sc.quads, sc.n_quads);
+    f.add_table(sc.triangles, sc.n_triangles);
+    f.add_table(sc.bvh_boxes, sc.n_bvh_boxes);
+    f.add_table(sc.translates, sc.n_translates);
+    f.add_table(sc.rotates, sc.n_rotates);
+    f.add_table(sc.media, sc.n_media);
+    f.add_table(sc.materials, sc.n_materials);
+    f.add_table(sc.textures, sc.n_textures);
+    f.add_table(sc.images, sc.n_images);
+    f.add_table(sc.texels, sc.n_texel_bytes);
+    f.add_table(sc.perlins, sc.n_perlins);
+    f.add_table(sc.lights, sc.n_lights);
+    return f.h;
+}
+
 static int upload_scene(rtk_ctx* ctx, const rtk_scene_desc* scene, UploadOrder order, double eye_extent) {
     Program prog;
     int rc = compile_scene(scene, prog);
@@ -1271,6 +1309,7 @@ static int upload_scene(rtk_ctx* ctx, const rtk_scene_desc* scene, UploadOrder o
     ctx->n_ops = int32_t(prog.ops.size());
     ctx->n_materials = scene->n_materials;
     ctx->n_textures = scene->n_textures;
+    ctx->scene_digest = scene_digest(*scene, prog, ctx->features, fast_order, eye_extent);
     ctx->has_scene = true;
     return RTK_OK;
 }
@@ -1637,6 +1676,55 @@ size_t hot_program_lds_bytes(const rtk_scene_desc* scene) {
     } catch (const std::bad_alloc&) {
         return 0;
     }
+}
+
+}  // namespace rtk
+
+// ------------------------------------------------------------------------------------------------ progressive sessions --
+// What csrc/rtk_progressive.cpp needs of a context (rtk_internal.h).
+namespace rtk {
+
+int ctx_scene(const rtk_ctx* ctx, uint64_t* digest) {
+    *digest = ctx->scene_digest;
+    return ctx->has_scene ? 1 : 0;
+}
+
+int frame_chunk_size(int spp) { return chunk_size_for(spp, 0); }
+
+int chunks_per_launch(size_t plane_bytes) { return planes_per_pass_for(plane_bytes, 0); }
+
+hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst) {
+    if (real_mode == RTK_REAL_F64) {
+        const CameraRec<double> rec = to_device_camera<double>(cam);
+        return hipMemcpy(d_dst, &rec, sizeof rec, hipMemcpyHostToDevice);
+    }
+    const CameraRec<float> rec = to_device_camera<float>(cam);
+    return hipMemcpy(d_dst, &rec, sizeof rec, hipMemcpyHostToDevice);
+}
+
+size_t camera_record_bytes() { return kCameraStride; }
+
+hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
+                         const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial) {
+    hipError_t e = hipSuccess;
+    if (workspace_bytes > ctx->partial_bytes) {
+        if (ctx->d_partial) {
+            if ((e = hipDeviceSynchronize()) != hipSuccess) return e;  // earlier launches may still read the old workspace
+            if ((e = hipFree(ctx->d_partial)) != hipSuccess) return e;
+            ctx->d_partial = nullptr;
+            ctx->partial_bytes = 0;
+        }
+        if ((e = hipMalloc(&ctx->d_partial, workspace_bytes)) != hipSuccess) return e;
+        ctx->partial_bytes = workspace_bytes;
+    }
+    *partial = ctx->d_partial;
+    unsigned int* tile_counter = ctx->tile_counters + (ctx->next_counter++ % kCounterRing);
+    const bool count = counters != nullptr;
+    if (real_mode == RTK_REAL_F64)
+        return launch_render<double>(ctx->scene64.view, static_cast<const CameraRec<double>*>(d_cam), tp, seed, ctx->features, count, true, 0u, ctx->d_partial,
+                                     counters, tile_counter, tile_order, tile_cost, stream);
+    return launch_render<float>(ctx->scene32.view, static_cast<const CameraRec<float>*>(d_cam), tp, seed, ctx->features, count, true, 0u, ctx->d_partial,
+                                counters, tile_counter, tile_order, tile_cost, stream);
 }
 
 }  // namespace rtk

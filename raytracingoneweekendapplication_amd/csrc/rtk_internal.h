@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
+
+#include "rtk_device_layout.h"
 
 #include "rtk.h"
 
@@ -13,7 +16,36 @@ namespace rtk {
 extern thread_local std::string g_error;            // text behind rtk_last_error()
 int fail(int code, const char* fmt, ...);           // records the text, returns `code`
 
+// FNV-1a 64 over byte ranges: the scene digest of progressive sessions and the checksum of their checkpoints.
+struct Fnv64 {
+    uint64_t h = 1469598103934665603ull;
+    void add(const void* p, size_t n) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        for (size_t k = 0; k < n; k++) h = (h ^ b[k]) * 1099511628211ull;
+    }
+    template <typename T>
+    void add_pod(const T& v) { add(&v, sizeof v); }
+    template <typename T>
+    void add_table(const T* t, int64_t n) {  // explicit _pad fields are zeroed: a caller may leave them unset
+        for (int64_t k = 0; k < n; k++) {
+            T v = t[k];
+            if constexpr (std::is_same_v<T, rtk_sphere> || std::is_same_v<T, rtk_quad> || std::is_same_v<T, rtk_triangle> || std::is_same_v<T, rtk_medium>)
+                v._pad = 0;
+            add_pod(v);
+        }
+    }
+};
+
 int ctx_device(const rtk_ctx* ctx);
+// Progressive sessions (rtk_progressive.cpp) -- what they use of a context and of the one-shot frame's rules:
+int ctx_scene(const rtk_ctx* ctx, uint64_t* digest);  // 1 when a scene is uploaded; *digest = its digest
+int frame_chunk_size(int spp);                        // the one-shot frame's chunk size (variant 0)
+int chunks_per_launch(size_t plane_bytes);            // ... and chunk planes per launch
+size_t camera_record_bytes();
+hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst);  // the kernel's camera record, blocking copy
+// One render launch over tp's chunks into the context's partial-sum workspace (grown to workspace_bytes; *partial = it).
+hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
+                         const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial);
 
 // Block until streams[i] (on ctxs[i]'s device) has drained, i = 0..n-1, feeding ctxs[0]'s progress callback
 // (rtk_set_progress_callback) from the work-item counters of the launches in flight.

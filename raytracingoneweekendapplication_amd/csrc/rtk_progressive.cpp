@@ -1,0 +1,410 @@
+// rtk_progressive.cpp -- progressive, resumable rendering (include/rtk.h, "Progressive, resumable rendering").
+//
+// A session renders one frame in steps into running sums of its own (include/rtk.h, "Progressive, resumable rendering").  A
+// step is the one-shot frame's chunk loop restricted to an absolute chunk range: the render kernel is launched unchanged on a
+// TileMap whose chunk_start holds the step's absolute sample indices (in launches of at most chunks_per_launch chunks, into
+// the context's partial-sum workspace), and rtk_accumulate_kernel folds every launch's planes into the session's sum in the
+// resolve's order -- so the image does not depend on how the frame was cut into steps.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rtk.h"
+#include "rtk_device_layout.h"
+#include "rtk_internal.h"
+#include "rtk_trace.h"
+
+using namespace rtk;
+
+#define RTK_HIP(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+struct rtk_progressive {
+    rtk_ctx* ctx = nullptr;
+    rtk_camera cam{};
+    uint32_t seed = 0;
+    int real_mode = RTK_REAL_F64;
+    int rank = 0, n_ranks = 1;
+    hipStream_t stream = nullptr;
+    int target = 0, chunk = 0, done = 0;
+    uint64_t digest = 0;
+    bool poisoned = false;
+    TileMap tm{};        // tile geometry; chunk fields are filled per launch
+    size_t elem = 8;     // bytes per real
+    void* d_sum = nullptr;              // [local tile][3][64] reals
+    double* d_s1 = nullptr;             // [local tile][64]
+    double* d_s2 = nullptr;
+    void* d_cam = nullptr;              // CameraRec<real>
+    unsigned int* d_cost = nullptr;     // tile costs measured by the first step's first launch ...
+    int32_t* d_order = nullptr;         // ... become the hand-out order of the later launches
+    bool order_valid = false;
+    double* d_stats = nullptr;          // noise partials [blocks][3] + the 3 reduced values
+    int full_chunks() const { return done / chunk; }  // every chunk before the target's end is full
+    size_t n_slots() const { return size_t(tm.n_tiles_local) * 64; }
+};
+
+namespace {
+
+constexpr char kCheckpointMagic[8] = {'R', 'T', 'K', 'P', 'R', 'O', 'G', '\0'};
+constexpr size_t kCheckpointHeader = 256;
+static_assert(sizeof(rtk_camera) == 200, "checkpoint layout: rtk_camera is 200 bytes");
+static_assert(56 + sizeof(rtk_camera) == kCheckpointHeader, "checkpoint header");
+
+int64_t checkpoint_bytes_for(int width, int height, int n_ranks, int real_mode) {
+    const int64_t tiles = rtk_tiles_per_rank(width, height, n_ranks);
+    return int64_t(kCheckpointHeader) + tiles * 192 * (real_mode == RTK_REAL_F64 ? 8 : 4) + 2 * tiles * 64 * 8 + 8;
+}
+
+void release(rtk_progressive* p) {
+    if (!p) return;
+    if (p->ctx) (void)hipSetDevice(ctx_device(p->ctx));
+    for (void* d : {p->d_sum, static_cast<void*>(p->d_s1), static_cast<void*>(p->d_s2), p->d_cam, static_cast<void*>(p->d_cost),
+                    static_cast<void*>(p->d_order), static_cast<void*>(p->d_stats)})
+        if (d) (void)hipFree(d);
+    delete p;
+}
+
+// Argument checks and device state of a new session (sums zeroed).
+int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, rtk_progressive** out) {
+    if (!ctx || !cam || !opts || !out) return fail(RTK_ERR_INVALID, "%s: null argument", who);
+    *out = nullptr;
+    uint64_t digest = 0;
+    if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
+    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
+        return fail(RTK_ERR_INVALID, "%s: bad camera dimensions (samples_per_pixel must be 1..32767)", who);
+    if (opts->n_ranks < 1 || opts->rank < 0 || opts->rank >= opts->n_ranks) return fail(RTK_ERR_INVALID, "%s: bad rank %d of %d", who, opts->rank, opts->n_ranks);
+    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, opts->real_mode);
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    auto* p = new rtk_progressive;
+    p->ctx = ctx;
+    p->cam = *cam;
+    p->seed = opts->seed;
+    p->real_mode = opts->real_mode;
+    p->rank = opts->rank;
+    p->n_ranks = opts->n_ranks;
+    p->stream = static_cast<hipStream_t>(opts->stream);
+    p->target = cam->samples_per_pixel;
+    p->chunk = frame_chunk_size(p->target);
+    p->digest = digest;
+    p->elem = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
+    TileMap& tm = p->tm;
+    tm.tiles_x = (cam->image_width + RTK_TILE_W - 1) / RTK_TILE_W;
+    tm.tiles_y = (cam->image_height + RTK_TILE_H - 1) / RTK_TILE_H;
+    tm.rank = opts->rank;
+    tm.n_ranks = opts->n_ranks;
+    tm.n_tiles_local = int32_t(rtk_tiles_per_rank(cam->image_width, cam->image_height, opts->n_ranks));
+    tm.compact = opts->n_ranks > 1 ? 1 : 0;
+    const size_t slots = p->n_slots();
+    hipError_t e = hipMalloc(&p->d_sum, slots * 3 * p->elem);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_s1), slots * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_s2), slots * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&p->d_cam, camera_record_bytes());
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_cost), size_t(tm.n_tiles_local) * sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_order), size_t(tm.n_tiles_local) * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_stats), (size_t(noise_partial_blocks(tm)) + 1) * 3 * sizeof(double));
+    // zeroed sums: a checkpoint holds defined bytes for the pixels outside the image too
+    if (e == hipSuccess) e = hipMemset(p->d_sum, 0, slots * 3 * p->elem);
+    if (e == hipSuccess) e = hipMemset(p->d_s1, 0, slots * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(p->d_s2, 0, slots * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(p->d_cost, 0, size_t(tm.n_tiles_local) * sizeof(unsigned int));
+    if (e == hipSuccess) e = upload_camera(*cam, p->real_mode, p->d_cam);
+    if (e != hipSuccess) {
+        release(p);
+        return fail(RTK_ERR_HIP, "%s: device allocation failed: %s", who, hipGetErrorString(e));
+    }
+    *out = p;
+    return RTK_OK;
+}
+
+// Every check of a call on an existing session: poisoned, scene changed.
+int usable(const rtk_progressive* p, const char* who) {
+    if (!p) return fail(RTK_ERR_INVALID, "%s: null session", who);
+    if (p->poisoned) return fail(RTK_ERR_INVALID, "%s: the session is poisoned by an earlier failed step", who);
+    uint64_t now = 0;
+    if (!ctx_scene(p->ctx, &now) || now != p->digest)
+        return fail(RTK_ERR_INVALID, "%s: the context's scene changed since the session was created (digest %016llx, now %016llx)", who,
+                    (unsigned long long)p->digest, (unsigned long long)now);
+    return RTK_OK;
+}
+
+// The step's launches: render + accumulate per range of at most chunks_per_launch chunks.
+hipError_t enqueue_step(rtk_progressive* p, int n_samples, void* d_linear, uint8_t* d_rgb8, float* d_noise, rtk_work_counters* d_counters, bool& launched) {
+    const int c = p->chunk, s_end = p->done + n_samples;
+    const int k0 = p->done / c, k1 = (s_end + c - 1) / c;  // absolute chunk range [k0, k1)
+    const size_t plane = size_t(p->tm.n_tiles_local) * 192 * p->elem;
+    const int per_launch = chunks_per_launch(plane);
+    const size_t workspace = plane * size_t(std::min(per_launch, k1 - k0));
+    const int32_t* order = p->order_valid ? p->d_order : nullptr;
+    auto* counters = reinterpret_cast<unsigned long long*>(d_counters);
+    hipError_t e = hipSuccess;
+    for (int a = k0; a < k1 && e == hipSuccess; a += per_launch) {
+        const int b = std::min(k1, a + per_launch);
+        TileMap tp = p->tm;
+        tp.n_chunks = b - a;
+        for (int k = 0; k <= kMaxChunks; k++) tp.chunk_start[k] = int16_t(std::min(std::min(a + k, b) * c, p->target));
+        unsigned int* cost = (!p->order_valid && a == k0) ? p->d_cost : nullptr;  // a tile's cost is measured on its first launch
+        void* partial = nullptr;
+        e = render_chunks(p->ctx, p->real_mode, p->d_cam, tp, p->seed, counters, order, cost, workspace, p->stream, &partial);
+        launched = launched || e == hipSuccess;
+        if (e != hipSuccess) break;
+        const bool last = b == k1;
+        const int k_full = s_end / c;  // full chunks after the step (every chunk but a final partial one; read on the last launch only)
+        e = p->real_mode == RTK_REAL_F64
+                ? launch_accumulate<double>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2, last,
+                                            1.0 / double(s_end), k_full, d_linear, d_rgb8, d_noise, p->stream)
+                : launch_accumulate<float>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2, last,
+                                           1.0 / double(s_end), k_full, d_linear, d_rgb8, d_noise, p->stream);
+    }
+    if (e == hipSuccess && !p->order_valid) {  // the first step's costs become the hand-out order of every later launch
+        e = launch_tile_order(p->d_cost, p->tm.n_tiles_local, p->d_order, p->stream);
+        p->order_valid = e == hipSuccess;
+    }
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtk_progressive_create(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, rtk_progressive** out) {
+    return make_session(ctx, cam, opts, "rtk_progressive_create", out);
+}
+
+int rtk_progressive_step(rtk_progressive* p, int32_t n_samples, void* d_linear, uint8_t* d_rgb8, float* d_noise, rtk_work_counters* d_counters) {
+    int rc = usable(p, "rtk_progressive_step");
+    if (rc != RTK_OK) return rc;
+    if (p->done >= p->target) return fail(RTK_ERR_INVALID, "rtk_progressive_step: the session is finished (%d samples)", p->target);
+    if (n_samples <= 0) return fail(RTK_ERR_INVALID, "rtk_progressive_step: n_samples must be positive (%d)", n_samples);
+    if (n_samples > p->target - p->done)
+        return fail(RTK_ERR_INVALID, "rtk_progressive_step: %d samples after %d pass the target of %d", n_samples, p->done, p->target);
+    if (n_samples % p->chunk != 0 && p->done + n_samples != p->target)
+        return fail(RTK_ERR_INVALID, "rtk_progressive_step: %d samples is not a multiple of the chunk size %d (only the step that ends at the target may be)",
+                    n_samples, p->chunk);
+    if (p->n_ranks > 1 && d_rgb8) return fail(RTK_ERR_INVALID, "rtk_progressive_step: d_rgb8 must be null when n_ranks > 1 (use rtk_tiles_unpermute)");
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    bool launched = false;
+    const hipError_t e = enqueue_step(p, n_samples, d_linear, d_rgb8, d_noise, d_counters, launched);
+    if (e != hipSuccess) {
+        if (launched) p->poisoned = true;  // part of the step is in the sums: the session cannot continue
+        return fail(RTK_ERR_HIP, "rtk_progressive_step: launch failed: %s%s", hipGetErrorString(e), launched ? " (the session is poisoned)" : "");
+    }
+    p->done += n_samples;
+    return RTK_OK;
+}
+
+int rtk_progressive_step_host(rtk_progressive* p, int32_t n_samples, double* h_linear, uint8_t* h_rgb8, float* h_noise, rtk_work_counters* counters) {
+    int rc = usable(p, "rtk_progressive_step_host");
+    if (rc != RTK_OK) return rc;
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    const bool compact = p->n_ranks > 1;
+    const size_t pixels = compact ? p->n_slots() : size_t(p->cam.image_width) * p->cam.image_height;
+    const size_t n_lin = pixels * 3;
+    void* d_linear = nullptr;
+    uint8_t* d_rgb8 = nullptr;
+    float* d_noise = nullptr;
+    rtk_work_counters* d_cnt = nullptr;
+    auto cleanup = [&]() {
+        for (void* d : {d_linear, static_cast<void*>(d_rgb8), static_cast<void*>(d_noise), static_cast<void*>(d_cnt)})
+            if (d) (void)hipFree(d);
+    };
+    hipError_t e = hipSuccess;
+    if (h_linear) e = hipMalloc(&d_linear, n_lin * p->elem);
+    if (e == hipSuccess && h_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), n_lin);
+    if (e == hipSuccess && h_noise) e = hipMalloc(reinterpret_cast<void**>(&d_noise), pixels * sizeof(float));
+    if (e == hipSuccess && counters) e = hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(rtk_work_counters));
+    if (e == hipSuccess && counters) e = hipMemsetAsync(d_cnt, 0, sizeof(rtk_work_counters), p->stream);
+    if (e != hipSuccess) {
+        cleanup();
+        return fail(RTK_ERR_HIP, "rtk_progressive_step_host: device buffers: %s", hipGetErrorString(e));
+    }
+    rc = rtk_progressive_step(p, n_samples, d_linear, d_rgb8, d_noise, d_cnt);
+    if (rc != RTK_OK) {
+        const std::string msg = g_error;
+        cleanup();
+        return fail(rc, "%s", msg.c_str());
+    }
+    e = hipStreamSynchronize(p->stream);
+    if (e == hipSuccess && h_linear) {
+        if (p->real_mode == RTK_REAL_F64) {
+            e = hipMemcpy(h_linear, d_linear, n_lin * sizeof(double), hipMemcpyDeviceToHost);
+        } else {
+            std::vector<float> tmp(n_lin);
+            e = hipMemcpy(tmp.data(), d_linear, n_lin * sizeof(float), hipMemcpyDeviceToHost);
+            for (size_t k = 0; k < n_lin; k++) h_linear[k] = double(tmp[k]);
+        }
+    }
+    if (e == hipSuccess && h_rgb8) e = hipMemcpy(h_rgb8, d_rgb8, n_lin, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && h_noise) e = hipMemcpy(h_noise, d_noise, pixels * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && counters) e = hipMemcpy(counters, d_cnt, sizeof(rtk_work_counters), hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) {
+        p->poisoned = true;
+        return fail(RTK_ERR_HIP, "rtk_progressive_step_host: %s (the session is poisoned)", hipGetErrorString(e));
+    }
+    return RTK_OK;
+}
+
+int rtk_progressive_samples_done(const rtk_progressive* p) { return p ? p->done : fail(RTK_ERR_INVALID, "rtk_progressive_samples_done: null session"); }
+
+int rtk_progressive_chunk_size(const rtk_progressive* p) { return p ? p->chunk : fail(RTK_ERR_INVALID, "rtk_progressive_chunk_size: null session"); }
+
+int rtk_progressive_noise(rtk_progressive* p, rtk_noise_stats* out) {
+    if (!out) return fail(RTK_ERR_INVALID, "rtk_progressive_noise: null argument");
+    if (!p || p->poisoned) return fail(RTK_ERR_INVALID, "rtk_progressive_noise: null or poisoned session");
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    const int k = p->full_chunks();
+    *out = rtk_noise_stats{};
+    out->samples_done = p->done;
+    out->full_chunks = k;
+    out->valid = k >= 2 ? 1 : 0;
+    if (k < 2) return RTK_OK;
+    const int blocks = noise_partial_blocks(p->tm);
+    double* result = p->d_stats + size_t(blocks) * 3;
+    RTK_HIP(launch_noise_stats(p->d_s1, p->d_s2, p->tm, p->cam.image_width, p->cam.image_height, k, p->d_stats, result, p->stream));
+    double h[3];
+    RTK_HIP(hipMemcpyAsync(h, result, sizeof h, hipMemcpyDeviceToHost, p->stream));
+    RTK_HIP(hipStreamSynchronize(p->stream));
+    // in-image pixels of this rank
+    int64_t n_px = 0;
+    for (int64_t lt = 0; lt < p->tm.n_tiles_local; lt++) {
+        const int64_t t = lt * p->n_ranks + p->rank;
+        if (t >= int64_t(p->tm.tiles_x) * p->tm.tiles_y) break;
+        const int w = std::min(8, p->cam.image_width - int(t % p->tm.tiles_x) * 8), hgt = std::min(8, p->cam.image_height - int(t / p->tm.tiles_x) * 8);
+        n_px += int64_t(w) * hgt;
+    }
+    out->mean_se = n_px > 0 ? h[0] / double(n_px) : 0.0;
+    out->max_se = h[1];
+    out->mean_rel_se = n_px > 0 ? h[2] / double(n_px) : 0.0;
+    return RTK_OK;
+}
+
+int64_t rtk_progressive_checkpoint_bytes(const rtk_progressive* p) {
+    if (!p) return fail(RTK_ERR_INVALID, "rtk_progressive_checkpoint_bytes: null session");
+    return checkpoint_bytes_for(p->cam.image_width, p->cam.image_height, p->n_ranks, p->real_mode);
+}
+
+int rtk_progressive_save(rtk_progressive* p, void* h_buf, int64_t n) {
+    if (!p || !h_buf) return fail(RTK_ERR_INVALID, "rtk_progressive_save: null argument");
+    if (p->poisoned) return fail(RTK_ERR_INVALID, "rtk_progressive_save: the session is poisoned by an earlier failed step");
+    const int64_t size = rtk_progressive_checkpoint_bytes(p);
+    if (n < size) return fail(RTK_ERR_INVALID, "rtk_progressive_save: buffer of %lld bytes, the checkpoint needs %lld", (long long)n, (long long)size);
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    RTK_HIP(hipStreamSynchronize(p->stream));
+    unsigned char* b = static_cast<unsigned char*>(h_buf);
+    std::memset(b, 0, kCheckpointHeader);
+    std::memcpy(b, kCheckpointMagic, 8);
+    const int32_t fields[9] = {RTK_CHECKPOINT_VERSION, p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, p->real_mode, p->target, p->chunk, p->done};
+    std::memcpy(b + 8, fields, sizeof fields);
+    std::memcpy(b + 44, &p->seed, 4);
+    std::memcpy(b + 48, &p->digest, 8);
+    std::memcpy(b + 56, &p->cam, sizeof(rtk_camera));
+    const size_t slots = p->n_slots();
+    unsigned char* at = b + kCheckpointHeader;
+    RTK_HIP(hipMemcpy(at, p->d_sum, slots * 3 * p->elem, hipMemcpyDeviceToHost));
+    at += slots * 3 * p->elem;
+    RTK_HIP(hipMemcpy(at, p->d_s1, slots * sizeof(double), hipMemcpyDeviceToHost));
+    at += slots * sizeof(double);
+    RTK_HIP(hipMemcpy(at, p->d_s2, slots * sizeof(double), hipMemcpyDeviceToHost));
+    at += slots * sizeof(double);
+    Fnv64 f;
+    f.add(b, size_t(at - b));
+    std::memcpy(at, &f.h, 8);
+    return RTK_OK;
+}
+
+int rtk_checkpoint_read_info(const void* h_buf, int64_t n, rtk_checkpoint_info* out) {
+    if (!h_buf || !out) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: null argument");
+    const unsigned char* b = static_cast<const unsigned char*>(h_buf);
+    if (n < int64_t(kCheckpointHeader) + 8) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: %lld bytes is too short for a checkpoint", (long long)n);
+    if (std::memcmp(b, kCheckpointMagic, 8) != 0) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: not a checkpoint (bad magic)");
+    int32_t f[9];
+    std::memcpy(f, b + 8, sizeof f);
+    rtk_checkpoint_info info{};
+    info.version = f[0];
+    info.width = f[1];
+    info.height = f[2];
+    info.rank = f[3];
+    info.n_ranks = f[4];
+    info.real_mode = f[5];
+    info.target_spp = f[6];
+    info.chunk_size = f[7];
+    info.samples_done = f[8];
+    std::memcpy(&info.seed, b + 44, 4);
+    std::memcpy(&info.scene_digest, b + 48, 8);
+    if (info.version != RTK_CHECKPOINT_VERSION)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: checkpoint version %d, this library reads version %d", info.version, RTK_CHECKPOINT_VERSION);
+    if (info.width <= 0 || info.height <= 0 || info.width > 65536 || info.height > 65536 || info.n_ranks < 1 || info.n_ranks > 65536 || info.rank < 0 ||
+        info.rank >= info.n_ranks || (info.real_mode != RTK_REAL_F64 && info.real_mode != RTK_REAL_F32) || info.target_spp < 1 || info.target_spp > 32767 ||
+        info.chunk_size != frame_chunk_size(info.target_spp) || info.samples_done < 0 || info.samples_done > info.target_spp)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: inconsistent header fields");
+    rtk_camera cam;
+    std::memcpy(&cam, b + 56, sizeof cam);
+    if (cam.image_width != info.width || cam.image_height != info.height || cam.samples_per_pixel != info.target_spp)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: the stored camera disagrees with the header");
+    const int64_t size = checkpoint_bytes_for(info.width, info.height, info.n_ranks, info.real_mode);
+    if (n != size)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: %lld bytes, a %dx%d checkpoint of rank %d of %d (%s) has %lld", (long long)n, info.width, info.height,
+                    info.rank, info.n_ranks, info.real_mode == RTK_REAL_F64 ? "f64" : "f32", (long long)size);
+    Fnv64 h;
+    h.add(b, size_t(size - 8));
+    uint64_t stored = 0;
+    std::memcpy(&stored, b + size - 8, 8);
+    if (stored != h.h) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: checksum mismatch (corrupted checkpoint)");
+    *out = info;
+    return RTK_OK;
+}
+
+int rtk_progressive_resume(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const void* h_buf, int64_t n, rtk_progressive** out) {
+    if (!ctx || !cam || !opts || !h_buf || !out) return fail(RTK_ERR_INVALID, "rtk_progressive_resume: null argument");
+    *out = nullptr;
+    rtk_checkpoint_info info;
+    int rc = rtk_checkpoint_read_info(h_buf, n, &info);
+    if (rc != RTK_OK) return fail(rc, "rtk_progressive_resume: %s", std::string(g_error).c_str());
+    const unsigned char* b = static_cast<const unsigned char*>(h_buf);
+    if (info.target_spp != cam->samples_per_pixel)
+        return fail(RTK_ERR_INVALID, "rtk_progressive_resume: the checkpoint's target is %d samples, the camera's %d", info.target_spp, cam->samples_per_pixel);
+    if (std::memcmp(b + 56, cam, sizeof(rtk_camera)) != 0) return fail(RTK_ERR_INVALID, "rtk_progressive_resume: the checkpoint was made with another camera");
+    if (info.seed != opts->seed) return fail(RTK_ERR_INVALID, "rtk_progressive_resume: the checkpoint's seed is %u, the call's %u", info.seed, opts->seed);
+    if (info.real_mode != opts->real_mode)
+        return fail(RTK_ERR_INVALID, "rtk_progressive_resume: the checkpoint's real mode is %d, the call's %d", info.real_mode, opts->real_mode);
+    if (info.rank != opts->rank || info.n_ranks != opts->n_ranks)
+        return fail(RTK_ERR_INVALID, "rtk_progressive_resume: the checkpoint is rank %d of %d, the call rank %d of %d", info.rank, info.n_ranks, opts->rank,
+                    opts->n_ranks);
+    uint64_t digest = 0;
+    if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "rtk_progressive_resume: no scene uploaded");
+    if (info.scene_digest != digest)
+        return fail(RTK_ERR_INVALID, "rtk_progressive_resume: the checkpoint was made on another scene or visiting order (digest %016llx, uploaded %016llx)",
+                    (unsigned long long)info.scene_digest, (unsigned long long)digest);
+    rtk_progressive* p = nullptr;
+    if ((rc = make_session(ctx, cam, opts, "rtk_progressive_resume", &p)) != RTK_OK) return rc;
+    const size_t slots = p->n_slots();
+    const unsigned char* at = b + kCheckpointHeader;
+    hipError_t e = hipMemcpy(p->d_sum, at, slots * 3 * p->elem, hipMemcpyHostToDevice);
+    at += slots * 3 * p->elem;
+    if (e == hipSuccess) e = hipMemcpy(p->d_s1, at, slots * sizeof(double), hipMemcpyHostToDevice);
+    at += slots * sizeof(double);
+    if (e == hipSuccess) e = hipMemcpy(p->d_s2, at, slots * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        release(p);
+        return fail(RTK_ERR_HIP, "rtk_progressive_resume: upload of the sums failed: %s", hipGetErrorString(e));
+    }
+    p->done = info.samples_done;
+    *out = p;
+    return RTK_OK;
+}
+
+int rtk_progressive_destroy(rtk_progressive* p) {
+    if (!p) return RTK_OK;
+    (void)hipSetDevice(ctx_device(p->ctx));
+    (void)hipStreamSynchronize(p->stream);  // launches in flight still read the session's buffers
+    release(p);
+    return RTK_OK;
+}
+
+}  // extern "C"

@@ -30,6 +30,20 @@ template <typename real>
 hipError_t launch_resolve(const void* partial, const TileMap& tmap, int width, int height, double samples_scale, void* out_linear, uint8_t* out_rgb8,
                           void* acc, bool first_pass, bool last_pass, hipStream_t stream);
 
+// Progressive sessions: fold this launch's chunk planes into the session's running sum `acc` [local tile][3][64] (the resolve's
+// additions in the resolve's order; `init` = plane 0 is the session's first chunk and becomes the sum) and every full chunk
+// (chunk_size samples) into the noise sums s1 / s2 [local tile][64] (double).  write_out: also write the preview scaled by
+// samples_scale (the resolve's outputs) and, when out_noise is given, the per-pixel standard error over k_full chunks.
+template <typename real>
+hipError_t launch_accumulate(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, bool init, void* acc, double* s1, double* s2,
+                             bool write_out, double samples_scale, int k_full, void* out_linear, uint8_t* out_rgb8, float* out_noise, hipStream_t stream);
+
+// Frame noise statistics over this rank's in-image pixels: out3 = {sum se, max se, sum se / max(mean, 1e-3)}, reduced in a fixed
+// order (per-block partials -- noise_partial_blocks(tmap) x 3 doubles -- then one single-block tree).
+int noise_partial_blocks(const TileMap& tmap);
+hipError_t launch_noise_stats(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int k_full, double* partials, double* out3,
+                              hipStream_t stream);
+
 // Known-answer helper: closest hit of the scene root for n caller-supplied rays (device buffers).
 template <typename real>
 hipError_t launch_debug_hit(const SceneView<real>& sc, int n, const double* d_rays, const uint32_t* d_keys, double* d_out, unsigned long long* d_draws,

@@ -2533,6 +2533,170 @@ __global__ __launch_bounds__(256) void rtk_resolve_kernel(const real* __restrict
     }
 }
 
+// Progressive sessions (rtk_progressive_*): a step renders an absolute range of sample chunks into the partial-sum planes and
+// this kernel folds them into the session's own running sum [local tile][3][64] -- the additions of rtk_resolve_kernel, in the
+// same order (c0, + c1, + c2, ...), so a frame rendered in steps is the one-shot frame bit for bit.  `init` = plane 0 is the
+// session's first chunk: it becomes the sum (0.0 + (-0.0) would not be -0.0).  Every FULL chunk (chunk_size samples; a final
+// partial chunk goes into the image only) also feeds the batch-means noise sums S1 = sum y_k, S2 = sum y_k^2 with
+// y_k = (s.x + s.y + s.z) / (3 c) in double.  On the step's last launch (`scale_out` != 0) the preview is written like the
+// resolve's output: scaled by 1 / samples_done, row-major linear + bytes or the compact tile buffer, plus the per-pixel
+// standard error (float, row-major or [local tile][64]) when out_noise is given.  One thread per (local tile, pixel).
+RTK_DEV double noise_se(double s1, double s2, int k) {  // batch means over k >= 2 chunk means: standard error of the pixel mean
+    if (k < 2) return 0.0;
+    const double m = s1 / double(k);
+    double v = (s2 - double(k) * m * m) / double(k - 1);
+    v = v > 0.0 ? v : 0.0;
+    return __builtin_sqrt(v / double(k));
+}
+
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_accumulate_kernel(const real* __restrict__ partial, TileMap tmap, int width, int height, int chunk_size, int init,
+                                                              real* __restrict__ acc, double* __restrict__ s1, double* __restrict__ s2, int scale_out,
+                                                              real samples_scale, int k_full, real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8,
+                                                              float* __restrict__ out_noise) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int pix = int(gid & 63);
+    const long long local_tile = gid >> 6;
+    if (local_tile >= tmap.n_tiles_local) return;
+    const long long tile = local_tile * tmap.n_ranks + tmap.rank;
+    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
+    const bool inside = tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height;
+    V3<real> sum = mk(real(0), real(0), real(0));
+    double se = 0.0;
+    if (inside) {
+        const real* src = partial + size_t(local_tile) * 192 + pix;
+        const size_t chunk_stride = size_t(tmap.n_tiles_local) * 192;
+        real* a = acc + size_t(local_tile) * 192 + pix;
+        double* p1 = s1 + size_t(local_tile) * 64 + pix;
+        double* p2 = s2 + size_t(local_tile) * 64 + pix;
+        double n1 = *p1, n2 = *p2;
+        const double three_c = 3.0 * double(chunk_size);
+        int c = 0;
+        if (init) {
+            sum = mk(src[0], src[64], src[128]);
+            c = 1;
+        } else {
+            sum = mk(a[0], a[64], a[128]);
+        }
+        for (int k = 0; k < tmap.n_chunks; k++) {
+            const real* q = src + size_t(k) * chunk_stride;
+            const V3<real> part = mk(q[0], q[64], q[128]);
+            if (k >= c) sum = sum + part;
+            if (tmap.chunk_start[k + 1] - tmap.chunk_start[k] == chunk_size) {
+                const double y = ((double(part.x) + double(part.y)) + double(part.z)) / three_c;
+                n1 = n1 + y;
+                n2 = n2 + y * y;
+            }
+        }
+        a[0] = sum.x;
+        a[64] = sum.y;
+        a[128] = sum.z;
+        *p1 = n1;
+        *p2 = n2;
+        sum = scale(samples_scale, sum);
+        se = noise_se(n1, n2, k_full);
+    }
+    if (!scale_out) return;
+    if (tmap.compact) {
+        if (out_linear) {
+            real* base = out_linear + size_t(local_tile) * 192 + pix;
+            base[0] = sum.x;
+            base[64] = sum.y;
+            base[128] = sum.z;
+        }
+        if (out_noise) out_noise[size_t(local_tile) * 64 + pix] = float(se);
+    } else if (inside) {
+        const size_t px = size_t(j) * width + i, idx = px * 3;
+        if (out_linear) {
+            out_linear[idx] = sum.x;
+            out_linear[idx + 1] = sum.y;
+            out_linear[idx + 2] = sum.z;
+        }
+        if (out_rgb8) {
+            out_rgb8[idx] = to_byte(double(sum.x));
+            out_rgb8[idx + 1] = to_byte(double(sum.y));
+            out_rgb8[idx + 2] = to_byte(double(sum.z));
+        }
+        if (out_noise) out_noise[px] = float(se);
+    }
+}
+
+// Frame noise statistics, deterministic (no float atomics): every block reduces its pixels' (se, max se, se / max(mean, 1e-3))
+// -- a wave64 butterfly, then the four waves in a fixed order -- into partials[block][3]; one single-block kernel reduces the
+// partials in a fixed tree.  The same inputs give the same bits on every run.
+RTK_DEV void wave_reduce3(double& a, double& b, double& c) {
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_xor(a, off);
+        const double bo = __shfl_xor(b, off);
+        b = bo > b ? bo : b;
+        c += __shfl_xor(c, off);
+    }
+}
+
+__global__ __launch_bounds__(256) void rtk_noise_partial_kernel(const double* __restrict__ s1, const double* __restrict__ s2, TileMap tmap, int width, int height,
+                                                                 int k_full, double* __restrict__ partials) {
+    __shared__ double s_w[4][3];
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int pix = int(gid & 63);
+    const long long local_tile = gid >> 6;
+    double se = 0.0, rel = 0.0;
+    if (local_tile < tmap.n_tiles_local) {
+        const long long tile = local_tile * tmap.n_ranks + tmap.rank;
+        const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
+        if (tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height && k_full >= 2) {
+            const double n1 = s1[size_t(local_tile) * 64 + pix], n2 = s2[size_t(local_tile) * 64 + pix];
+            se = noise_se(n1, n2, k_full);
+            const double m = n1 / double(k_full);
+            rel = se / (m > 1e-3 ? m : 1e-3);
+        }
+    }
+    double sum_se = se, max_se = se, sum_rel = rel;
+    wave_reduce3(sum_se, max_se, sum_rel);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_w[wave][0] = sum_se;
+        s_w[wave][1] = max_se;
+        s_w[wave][2] = sum_rel;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double a = (s_w[0][0] + s_w[1][0]) + (s_w[2][0] + s_w[3][0]);
+        const double b01 = s_w[0][1] > s_w[1][1] ? s_w[0][1] : s_w[1][1], b23 = s_w[2][1] > s_w[3][1] ? s_w[2][1] : s_w[3][1];
+        const double c = (s_w[0][2] + s_w[1][2]) + (s_w[2][2] + s_w[3][2]);
+        partials[size_t(blockIdx.x) * 3] = a;
+        partials[size_t(blockIdx.x) * 3 + 1] = b01 > b23 ? b01 : b23;
+        partials[size_t(blockIdx.x) * 3 + 2] = c;
+    }
+}
+
+__global__ __launch_bounds__(256) void rtk_noise_final_kernel(const double* __restrict__ partials, int n, double* __restrict__ out) {
+    __shared__ double s_v[3][256];
+    const int t = threadIdx.x;
+    double a = 0.0, b = 0.0, c = 0.0;
+    for (int k = t; k < n; k += 256) {  // each thread walks its strided slice in index order
+        a += partials[size_t(k) * 3];
+        b = partials[size_t(k) * 3 + 1] > b ? partials[size_t(k) * 3 + 1] : b;
+        c += partials[size_t(k) * 3 + 2];
+    }
+    s_v[0][t] = a;
+    s_v[1][t] = b;
+    s_v[2][t] = c;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {  // fixed pairwise tree
+        if (t < half) {
+            s_v[0][t] = s_v[0][t] + s_v[0][t + half];
+            s_v[1][t] = s_v[1][t + half] > s_v[1][t] ? s_v[1][t + half] : s_v[1][t];
+            s_v[2][t] = s_v[2][t] + s_v[2][t + half];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[0] = s_v[0][0];
+        out[1] = s_v[1][0];
+        out[2] = s_v[2][0];
+    }
+}
+
 // Gathered compact tiles -> row-major image (+ bytes).  One thread per pixel slot.
 template <typename real>
 __global__ __launch_bounds__(256) void rtk_unpermute_kernel(const real* __restrict__ gathered, int width, int height, int tiles_x, int n_tiles, int n_ranks,
@@ -2851,6 +3015,34 @@ hipError_t launch_resolve(const void* partial, const TileMap& tmap, int width, i
 }
 template hipError_t launch_resolve<double>(const void*, const TileMap&, int, int, double, void*, uint8_t*, void*, bool, bool, hipStream_t);
 template hipError_t launch_resolve<float>(const void*, const TileMap&, int, int, double, void*, uint8_t*, void*, bool, bool, hipStream_t);
+
+template <typename real>
+hipError_t launch_accumulate(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, bool init, void* acc, double* s1, double* s2,
+                             bool write_out, double samples_scale, int k_full, void* out_linear, uint8_t* out_rgb8, float* out_noise, hipStream_t stream) {
+    const long long slots = (long long)tmap.n_tiles_local * 64;
+    if (slots <= 0) return hipSuccess;
+    rtk_accumulate_kernel<real><<<dim3(int((slots + 255) / 256)), dim3(256), 0, stream>>>(
+        static_cast<const real*>(partial), tmap, width, height, chunk_size, init ? 1 : 0, static_cast<real*>(acc), s1, s2, write_out ? 1 : 0,
+        real(samples_scale), k_full, static_cast<real*>(out_linear), out_rgb8, out_noise);
+    return hipGetLastError();
+}
+template hipError_t launch_accumulate<double>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, bool, double, int, void*, uint8_t*,
+                                              float*, hipStream_t);
+template hipError_t launch_accumulate<float>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, bool, double, int, void*, uint8_t*,
+                                             float*, hipStream_t);
+
+int noise_partial_blocks(const TileMap& tmap) { return int(((long long)tmap.n_tiles_local * 64 + 255) / 256); }
+
+hipError_t launch_noise_stats(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int k_full, double* partials, double* out3,
+                              hipStream_t stream) {
+    const int blocks = noise_partial_blocks(tmap);
+    if (blocks <= 0) return hipErrorInvalidValue;
+    rtk_noise_partial_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(s1, s2, tmap, width, height, k_full, partials);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    rtk_noise_final_kernel<<<dim3(1), dim3(256), 0, stream>>>(partials, blocks, out3);
+    return hipGetLastError();
+}
 
 template <typename real>
 hipError_t launch_debug_hit(const SceneView<real>& sc, int n, const double* d_rays, const uint32_t* d_keys, double* d_out, unsigned long long* d_draws,

@@ -134,6 +134,21 @@ public:
     bool fast_order_exact = false;     // ... whether the fast order is bit-identical for this scene (proven or measured) ...
     int fast_order_exactness = 0;      // ... and which: rtk_optimize_info.exact (2 proven, 1 empirical, 0 statistical)
     double last_render_ms = 0;         // device render time of the last render()
+    // Progressive rendering (rtk_progressive_*; one device: devices[0] or `device` -- not split over rtk_multi's devices).
+    // progressive_step > 0: render() adds that many samples per step (rounded up to the session's chunk size, 8 up to 512 spp)
+    // and writes image_name after every step when write_previews is set; the finished image is bit-identical to the one-shot
+    // render's.  0 (default): the one-shot path.  With progressive_step > 0 only:
+    //   checkpoint_file  the session is saved there after every step, and render() resumes from it when it matches this
+    //                    scene, camera, seed and real mode (otherwise it warns and starts over);
+    //   noise_target     > 0: stop at the first step boundary where the frame's mean relative standard error
+    //                    (rtk_noise_stats.mean_rel_se) is <= noise_target; samples_per_pixel is then the maximum.
+    int progressive_step = 0;
+    bool write_previews = false;
+    const char* checkpoint_file = nullptr;
+    double noise_target = 0;
+    int last_samples_rendered = 0;     // set by a progressive render(): samples per pixel this call added ...
+    int last_samples_done = 0;         // ... the samples per pixel in the image it wrote ...
+    rtk_noise_stats last_noise{};      // ... and the noise estimate after its last step (valid = 0 before two full chunks)
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -188,23 +203,7 @@ public:
         rtk_multi* multi = nullptr;
         int rc = rtk_init_multi(int(devs.size()), devs.data(), RTK_GATHER_AUTO, &multi);
         if (rc != RTK_OK) return rc;
-        used_fast_order = false;
-        fast_order_exact = false;
-        fast_order_exactness = 0;
-        if (order != reference_order) {  // same primitives, SAH grouping, children ordered by distance to this camera
-            rtk_optimize_opts oo{};
-            oo.has_eye = 1;
-            oo.eye = cam.center;
-            oo.free_media_order = free_media_order ? 1 : 0;
-            rtk_optimize_info info{};
-            rc = rtk_multi_scene_upload_fast(multi, &desc, &oo, &info);
-            fast_order_exact = rc == RTK_OK && info.exact != 0;
-            fast_order_exactness = rc == RTK_OK ? info.exact : 0;
-            used_fast_order = rc == RTK_OK && (order == fast_order || info.exact == 2 || (info.exact == 1 && accept_empirical_order));
-            // auto_order never makes render() fail on a scene the reference order accepts: fall back to it
-            if (rc != RTK_OK && order == auto_order) rc = RTK_OK;
-        }
-        if (rc == RTK_OK && !used_fast_order) rc = rtk_multi_scene_upload(multi, &desc);  // the reference's own hierarchy and order
+        rc = upload(multi, desc, cam);
         if (rc == RTK_OK) {
             size_t n = size_t(cam.image_width) * cam.image_height * 3;
             if (linear) linear->assign(n, 0.0);
@@ -226,6 +225,99 @@ public:
         return rc;
     }
 
+    // The scene upload of render_to and render_progressive: the visiting order `order` asks for.
+    int upload(rtk_multi* multi, const rtk_scene_desc& desc, const rtk_camera& cam) {
+        int rc = RTK_OK;
+        used_fast_order = false;
+        fast_order_exact = false;
+        fast_order_exactness = 0;
+        if (order != reference_order) {  // same primitives, SAH grouping, children ordered by distance to this camera
+            rtk_optimize_opts oo{};
+            oo.has_eye = 1;
+            oo.eye = cam.center;
+            oo.free_media_order = free_media_order ? 1 : 0;
+            rtk_optimize_info info{};
+            rc = rtk_multi_scene_upload_fast(multi, &desc, &oo, &info);
+            fast_order_exact = rc == RTK_OK && info.exact != 0;
+            fast_order_exactness = rc == RTK_OK ? info.exact : 0;
+            used_fast_order = rc == RTK_OK && (order == fast_order || info.exact == 2 || (info.exact == 1 && accept_empirical_order));
+            // auto_order never makes render() fail on a scene the reference order accepts: fall back to it
+            if (rc != RTK_OK && order == auto_order) rc = RTK_OK;
+        }
+        if (rc == RTK_OK && !used_fast_order) rc = rtk_multi_scene_upload(multi, &desc);  // the reference's own hierarchy and order
+        return rc;
+    }
+
+    // render() with progressive_step > 0: one rtk_progressive session on one device, stepped to the target (or to noise_target),
+    // checkpointed to checkpoint_file after every step.  rgb8 receives the last step's preview.
+    int render_progressive(const hittable& world, const std::vector<point_light>& lights, std::vector<uint8_t>* rgb8) {
+        rtk::scene_builder sb;
+        rtk_scene_desc desc = rtk::flatten(world, lights, sb);
+        rtk_camera cam = derive();
+        int dev = devices.empty() ? device : devices[0];
+        rtk_multi* multi = nullptr;
+        int rc = rtk_init_multi(1, &dev, RTK_GATHER_PEER, &multi);
+        if (rc != RTK_OK) return rc;
+        rtk_progressive* p = nullptr;
+        last_samples_rendered = 0;
+        last_samples_done = 0;
+        last_noise = rtk_noise_stats{};
+        rc = upload(multi, desc, cam);
+        rtk_render_opts opts{};
+        opts.seed = seed;
+        opts.real_mode = real_mode;
+        opts.rank = 0;
+        opts.n_ranks = 1;
+        rtk_ctx* ctx = rtk_multi_ctx(multi, 0);
+        if (rc == RTK_OK && checkpoint_file) {
+            std::vector<unsigned char> blob;
+            if (FILE* f = std::fopen(checkpoint_file, "rb")) {
+                unsigned char buf[65536];
+                size_t got;
+                while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) blob.insert(blob.end(), buf, buf + got);
+                std::fclose(f);
+                if (rtk_progressive_resume(ctx, &cam, &opts, blob.data(), int64_t(blob.size()), &p) != RTK_OK) {
+                    std::cerr << "camera::render: " << checkpoint_file << " does not match this render (" << rtk_last_error() << "); starting over" << std::endl;
+                    p = nullptr;
+                } else if (rtk_progressive_samples_done(p) >= cam.samples_per_pixel) {  // finished: no step is left to write the image
+                    rtk_progressive_destroy(p);
+                    p = nullptr;
+                }
+            }
+        }
+        if (rc == RTK_OK && !p) rc = rtk_progressive_create(ctx, &cam, &opts, &p);
+        if (rc == RTK_OK) {
+            const int chunk = rtk_progressive_chunk_size(p);
+            const int step = (progressive_step + chunk - 1) / chunk * chunk;
+            const int start = rtk_progressive_samples_done(p);
+            rgb8->assign(size_t(cam.image_width) * cam.image_height * 3, 0);
+            std::vector<unsigned char> blob(checkpoint_file ? size_t(rtk_progressive_checkpoint_bytes(p)) : 0);
+            auto t0 = std::chrono::steady_clock::now();
+            for (int done = start; rc == RTK_OK && done < cam.samples_per_pixel;) {
+                rc = rtk_progressive_step_host(p, std::min(step, cam.samples_per_pixel - done), nullptr, rgb8->data(), nullptr, nullptr);
+                if (rc != RTK_OK) break;
+                done = rtk_progressive_samples_done(p);
+                last_samples_done = done;
+                last_samples_rendered = done - start;
+                if (checkpoint_file && (rc = rtk_progressive_save(p, blob.data(), int64_t(blob.size()))) == RTK_OK) {
+                    const std::string tmp = std::string(checkpoint_file) + ".tmp";  // replace the old checkpoint only once the new one is whole
+                    FILE* f = std::fopen(tmp.c_str(), "wb");
+                    const bool ok = f && std::fwrite(blob.data(), 1, blob.size(), f) == blob.size();
+                    if (f) std::fclose(f);
+                    if (!ok || std::rename(tmp.c_str(), checkpoint_file) != 0) std::cerr << "camera::render: cannot write " << checkpoint_file << std::endl;
+                }
+                if (rc == RTK_OK && write_previews && write_image) rtk::write_png(image_name, cam.image_width, cam.image_height, rgb8->data());
+                if (rc == RTK_OK && (noise_target > 0 || done >= cam.samples_per_pixel)) rc = rtk_progressive_noise(p, &last_noise);
+                if (rc == RTK_OK && noise_target > 0 && last_noise.valid && last_noise.mean_rel_se <= noise_target) break;
+                if (show_progress) print_progress(done, cam.samples_per_pixel, nullptr);
+            }
+            last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        if (p) rtk_progressive_destroy(p);
+        rtk_multi_destroy(multi);
+        return rc;
+    }
+
     // Camera.txt:102-106: "\rPercent Rendered: N% " on stderr.
     static void print_progress(int64_t done, int64_t total, void*) {
         const float percent = total > 0 ? 100.0f * float(done) / float(total) : 100.0f;
@@ -235,13 +327,13 @@ public:
     // Camera.txt:54.  Blocking; borrows world and lights for the call.
     void render(const hittable& world, std::vector<point_light>& lights) {
         std::vector<uint8_t> rgb8;
-        int rc = render_to(world, lights, nullptr, &rgb8);
+        int rc = progressive_step > 0 ? render_progressive(world, lights, &rgb8) : render_to(world, lights, nullptr, &rgb8);
         if (rc != RTK_OK) {
             std::cerr << "camera::render failed: " << rtk_last_error() << std::endl;
             return;
         }
         rtk_camera cam = derive();
-        double msamples = double(cam.image_width) * cam.image_height * samples_per_pixel / 1e6;
+        double msamples = double(cam.image_width) * cam.image_height * (progressive_step > 0 ? last_samples_rendered : samples_per_pixel) / 1e6;
         std::cout << "\nDone rendering " << image_name << " in " << last_render_ms / 1000.0 << " seconds ("
                   << msamples / (last_render_ms / 1000.0) << " Msamples/s)" << std::endl;
         if (write_image) rtk::write_png(image_name, cam.image_width, cam.image_height, rgb8.data());
