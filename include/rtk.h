@@ -513,6 +513,45 @@ int rtk_progressive_resume(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render
 int rtk_checkpoint_read_info(const void* h_buf, int64_t n, rtk_checkpoint_info* out);
 int rtk_progressive_destroy(rtk_progressive* p);
 
+/* Tile-adaptive sampling ------------------------------------------------------------
+ * An adaptive session puts its samples where the noise is, one 8x8 tile (the work of one wave) at a time.  Every tile of the
+ * rank is ACTIVE -- it holds samples_done samples -- or RETIRED: it keeps the tile_spp[t] samples it had when it retired and
+ * never renders again.  A step renders the next n samples of the active tiles only (the step rules above are unchanged).  At
+ * the end of a step, an active tile with min_samples <= samples_done < target retires when its metric -- the maximum over its
+ * in-image pixels of se / max(m, 1e-3), K = samples_done / chunk (the noise estimate above) -- is <= rel_target.  Padding
+ * tiles of a rank (outside the image) are never rendered and count as neither (tile_spp 0).
+ *   - previews scale each pixel by 1 / tile_spp[t] and its se uses the tile's own K; rtk_progressive_noise uses per-tile K.
+ *   - every pixel of tile t is BIT-IDENTICAL to a one-shot render of the same scene, camera, seed and real mode with
+ *     samples_per_pixel = tile_spp[t], as long as that render uses the same chunk size (target <= 512).  With a rel_target no
+ *     tile reaches, the finished image is the one-shot frame.
+ *   - a step when no tile is active is valid: it changes no pixel (the previews are still written) and stays asynchronous.
+ *   - checkpoints of an adaptive session are version 2 (see above: the version-1 layout, then double rel_target, int32
+ *     min_samples, int32 0, int32 tile_spp[tiles_per_rank], then the checksum); resume restores the adaptive state.
+ *     Non-adaptive sessions still write version 1.
+ *   - one rank or several, like progressive sessions; not through rtk_multi. */
+typedef struct rtk_adaptive_opts {
+    double rel_target;     /* > 0 */
+    int32_t min_samples;   /* a multiple of the chunk size, >= 2 chunks, <= the target */
+    int32_t reserved;      /* 0 */
+} rtk_adaptive_opts;
+
+typedef struct rtk_adaptive_state {
+    int32_t active_tiles;      /* this rank's tiles that still render */
+    int32_t retired_tiles;
+    int64_t pixel_samples;     /* sum over in-image pixels of their tile's sample count */
+    double mean_spp;           /* pixel_samples / in-image pixels of this rank */
+} rtk_adaptive_state;
+
+/* Make a session adaptive: only before its first step (RTK_ERR_INVALID afterwards, or for bad options). */
+int rtk_progressive_set_adaptive(rtk_progressive* p, const rtk_adaptive_opts* opts);
+/* Synchronises the session's stream.  A non-adaptive session reports every in-image tile active. */
+int rtk_adaptive_status(rtk_progressive* p, rtk_adaptive_state* out);
+/* tile_spp of this rank's tiles: h_out[rtk_tiles_per_rank(...)], local tile order; synchronises. */
+int rtk_adaptive_tile_samples(rtk_progressive* p, int32_t* h_out);
+/* Host-only: the adaptive part of a checkpoint (checked like rtk_checkpoint_read_info).  Version 1: *out = {0, 0, 0} and
+ * h_tile_spp is left alone.  Version 2: the options and, when h_tile_spp is given, tile_spp[tiles_per_rank]. */
+int rtk_checkpoint_read_adaptive(const void* h_buf, int64_t n, rtk_adaptive_opts* out, int32_t* h_tile_spp);
+
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and
  * hit-record code as the render kernel.  Host buffers:

@@ -166,6 +166,21 @@ class CheckpointInfo(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class AdaptiveOpts(C.Structure):
+    """rtk_adaptive_opts: the retire rule of a tile-adaptive progressive session."""
+
+    _fields_ = [("rel_target", C.c_double), ("min_samples", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AdaptiveState(C.Structure):
+    """rtk_adaptive_state: active / retired tiles and the samples rendered so far of one rank."""
+
+    _fields_ = [("active_tiles", C.c_int32), ("retired_tiles", C.c_int32), ("pixel_samples", C.c_int64), ("mean_spp", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # ----------------------------------------------------------------------------- libraries
 _host_lib = None
 _hip_lib = None
@@ -272,6 +287,10 @@ def hip_lib() -> C.CDLL:
             lib.rtk_progressive_resume.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
             lib.rtk_checkpoint_read_info.argtypes = [C.c_void_p, C.c_int64, C.POINTER(CheckpointInfo)]
             lib.rtk_progressive_destroy.argtypes = [C.c_void_p]
+            lib.rtk_progressive_set_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveOpts)]
+            lib.rtk_adaptive_status.argtypes = [C.c_void_p, C.POINTER(AdaptiveState)]
+            lib.rtk_adaptive_tile_samples.argtypes = [C.c_void_p, C.c_void_p]
+            lib.rtk_checkpoint_read_adaptive.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AdaptiveOpts), C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -551,12 +570,25 @@ class Renderer:
         return out, draws
 
     def progressive(self, cam: Camera, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
-                    stream: int = 0) -> "Progressive":
-        """rtk_progressive_create: a session that renders the frame of ``cam`` (samples_per_pixel = the target) in steps."""
+                    stream: int = 0, rel_target: float | None = None, min_samples: int | None = None) -> "Progressive":
+        """rtk_progressive_create: a session that renders the frame of ``cam`` (samples_per_pixel = the target) in steps.
+        ``rel_target`` makes it tile-adaptive (rtk_progressive_set_adaptive): a tile retires once, after at least ``min_samples``
+        samples (default: two chunks), the largest relative standard error of its pixels is <= rel_target."""
         opts = RenderOpts(seed, real_mode, rank, n_ranks, 0, 0, stream or None)
         h = C.c_void_p()
         self._check(self._lib.rtk_progressive_create(self._ctx, C.byref(cam), C.byref(opts), C.byref(h)))
-        return Progressive(self, h, cam, real_mode, n_ranks)
+        p = Progressive(self, h, cam, real_mode, n_ranks, rank)
+        if rel_target is not None or min_samples is not None:
+            if rel_target is None:
+                p.close()
+                raise ValueError("min_samples needs rel_target")
+            ms = 2 * p.chunk_size if min_samples is None else int(min_samples)
+            rc = self._lib.rtk_progressive_set_adaptive(p._h, C.byref(AdaptiveOpts(float(rel_target), ms, 0)))
+            if rc != 0:
+                err = RtkError(rc, self._lib.rtk_last_error().decode())
+                p.close()
+                raise err
+        return p
 
     def resume(self, cam: Camera, blob: bytes, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
                stream: int = 0) -> "Progressive":
@@ -566,7 +598,7 @@ class Renderer:
         buf = C.create_string_buffer(bytes(blob), len(blob))
         h = C.c_void_p()
         self._check(self._lib.rtk_progressive_resume(self._ctx, C.byref(cam), C.byref(opts), buf, len(blob), C.byref(h)))
-        return Progressive(self, h, cam, real_mode, n_ranks)
+        return Progressive(self, h, cam, real_mode, n_ranks, rank)
 
     def set_progress(self, fn=None, interval_ms: int = 100) -> None:
         """rtk_set_progress_callback: ``fn(done, total)`` is called from the thread that runs a blocking render
@@ -590,12 +622,12 @@ class Progressive:
     """A progressive session (rtk_progressive): one frame rendered in steps of whole sample chunks, with a per-pixel noise
     estimate and checkpoints.  The finished frame is bit-identical to ``Renderer.render_host`` of the same camera."""
 
-    def __init__(self, renderer: Renderer, handle: C.c_void_p, cam: Camera, real_mode: int, n_ranks: int):
+    def __init__(self, renderer: Renderer, handle: C.c_void_p, cam: Camera, real_mode: int, n_ranks: int, rank: int = 0):
         self._r = renderer      # keeps the context alive
         self._lib = renderer._lib
         self._h = handle
         self.width, self.height, self.target = cam.image_width, cam.image_height, cam.samples_per_pixel
-        self.real_mode, self.n_ranks = real_mode, n_ranks
+        self.real_mode, self.n_ranks, self.rank = real_mode, n_ranks, rank
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -634,6 +666,32 @@ class Progressive:
         self._check(self._lib.rtk_progressive_noise(self._h, C.byref(out)))
         return out.as_dict()
 
+    def adaptive_status(self) -> dict:
+        """rtk_adaptive_status: {active_tiles, retired_tiles, pixel_samples, mean_spp} of this rank (synchronises)."""
+        out = AdaptiveState()
+        self._check(self._lib.rtk_adaptive_status(self._h, C.byref(out)))
+        return out.as_dict()
+
+    def tile_samples(self):
+        """rtk_adaptive_tile_samples: int32 [tiles_per_rank], each local tile's sample count (0 for a rank's padding tiles)."""
+        import numpy as np
+
+        out = np.zeros(tiles_per_rank(self.width, self.height, self.n_ranks), np.int32)
+        self._check(self._lib.rtk_adaptive_tile_samples(self._h, out.ctypes.data))
+        return out
+
+    def sample_map(self):
+        """(H, W) int32: every pixel's sample count -- its tile's -- for this rank's tiles; 0 for the other ranks' pixels."""
+        import numpy as np
+
+        spp = self.tile_samples()
+        tx, ty = (self.width + 7) // 8, (self.height + 7) // 8
+        grid = np.zeros(tx * ty, np.int32)
+        tiles = np.arange(len(spp)) * self.n_ranks + self.rank
+        keep = tiles < tx * ty
+        grid[tiles[keep]] = spp[keep]
+        return np.repeat(np.repeat(grid.reshape(ty, tx), 8, 0), 8, 1)[: self.height, : self.width].copy()
+
     def save(self) -> bytes:
         n = self._lib.rtk_progressive_checkpoint_bytes(self._h)
         if n <= 0:
@@ -663,7 +721,17 @@ def checkpoint_info(blob: bytes) -> dict:
     rc = lib.rtk_checkpoint_read_info(buf, len(blob), C.byref(info))
     if rc != 0:
         raise RtkError(rc, lib.rtk_last_error().decode())
-    return info.as_dict()
+    out = info.as_dict()
+    if info.version == 2:  # an adaptive session's: its options and the tiles' sample counts as well
+        import numpy as np
+
+        ad = AdaptiveOpts()
+        spp = np.zeros(tiles_per_rank(info.width, info.height, info.n_ranks), np.int32)
+        rc = lib.rtk_checkpoint_read_adaptive(buf, len(blob), C.byref(ad), spp.ctypes.data)
+        if rc != 0:
+            raise RtkError(rc, lib.rtk_last_error().decode())
+        out.update(rel_target=ad.rel_target, min_samples=ad.min_samples, tile_spp=spp)
+    return out
 
 
 class MultiRenderer:

@@ -318,6 +318,9 @@ struct TileMap {  // which tiles this launch renders and where the pixels go
     // walks a record through data-dependent branches -- count, is_rotate[k], then that step's constants: up to six
     // DEPENDENT reads per chain switch, each an L2 round trip from memory
     int32_t chains_lds_offset;
+    // adaptive progressive steps: the number of tile_order positions handed out is this device word (written by the
+    // previous step's compaction, so the host never waits for it); null = all n_tiles_local positions
+    const int32_t* active_count = nullptr;
 };
 
 // Indices into the uint64 work-counter block (same order as rtk_work_counters).

@@ -45,6 +45,15 @@ struct rtk_progressive {
     int32_t* d_order = nullptr;         // ... become the hand-out order of the later launches
     bool order_valid = false;
     double* d_stats = nullptr;          // noise partials [blocks][3] + the 3 reduced values
+    // tile-adaptive sampling (rtk_progressive_set_adaptive): per local tile active (1 / 0) and sample count, the hand-out list
+    // of the active tiles and its length (built on the device after every step, read by the next step's render launches)
+    bool adaptive = false;
+    double rel_target = 0.0;
+    int min_samples = 0;
+    int32_t* d_active = nullptr;
+    int32_t* d_tile_spp = nullptr;
+    int32_t* d_list = nullptr;          // [n_tiles_local] + the count behind it
+    bool list_valid = false;
     int full_chunks() const { return done / chunk; }  // every chunk before the target's end is full
     size_t n_slots() const { return size_t(tm.n_tiles_local) * 64; }
 };
@@ -56,16 +65,33 @@ constexpr size_t kCheckpointHeader = 256;
 static_assert(sizeof(rtk_camera) == 200, "checkpoint layout: rtk_camera is 200 bytes");
 static_assert(56 + sizeof(rtk_camera) == kCheckpointHeader, "checkpoint header");
 
-int64_t checkpoint_bytes_for(int width, int height, int n_ranks, int real_mode) {
+constexpr int32_t kCheckpointAdaptive = 2;  // the version of an adaptive session's checkpoint
+
+// Version 1; version 2 inserts the adaptive block (rel_target, min_samples, pad, tile_spp[tiles]) before the checksum.
+int64_t checkpoint_bytes_for(int width, int height, int n_ranks, int real_mode, bool adaptive = false) {
     const int64_t tiles = rtk_tiles_per_rank(width, height, n_ranks);
-    return int64_t(kCheckpointHeader) + tiles * 192 * (real_mode == RTK_REAL_F64 ? 8 : 4) + 2 * tiles * 64 * 8 + 8;
+    return int64_t(kCheckpointHeader) + tiles * 192 * (real_mode == RTK_REAL_F64 ? 8 : 4) + 2 * tiles * 64 * 8 + (adaptive ? 16 + tiles * 4 : 0) + 8;
+}
+
+// In-image pixels of local tile lt of `rank` (0 for a rank's padding tiles past the last tile).
+int tile_pixels(int width, int height, int rank, int n_ranks, int64_t lt) {
+    const int tiles_x = (width + RTK_TILE_W - 1) / RTK_TILE_W, tiles_y = (height + RTK_TILE_H - 1) / RTK_TILE_H;
+    const int64_t t = lt * n_ranks + rank;
+    if (t >= int64_t(tiles_x) * tiles_y) return 0;
+    return std::min(8, width - int(t % tiles_x) * 8) * std::min(8, height - int(t / tiles_x) * 8);
+}
+
+// The adaptive options' rules (rtk_progressive_set_adaptive and version-2 checkpoints).
+bool adaptive_opts_ok(double rel_target, int min_samples, int chunk, int target) {
+    return rel_target > 0.0 && rel_target <= 1e300 && min_samples % chunk == 0 && min_samples >= 2 * chunk && min_samples <= target;
 }
 
 void release(rtk_progressive* p) {
     if (!p) return;
     if (p->ctx) (void)hipSetDevice(ctx_device(p->ctx));
     for (void* d : {p->d_sum, static_cast<void*>(p->d_s1), static_cast<void*>(p->d_s2), p->d_cam, static_cast<void*>(p->d_cost),
-                    static_cast<void*>(p->d_order), static_cast<void*>(p->d_stats)})
+                    static_cast<void*>(p->d_order), static_cast<void*>(p->d_stats), static_cast<void*>(p->d_active), static_cast<void*>(p->d_tile_spp),
+                    static_cast<void*>(p->d_list)})
         if (d) (void)hipFree(d);
     delete p;
 }
@@ -122,6 +148,30 @@ int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opt
     return RTK_OK;
 }
 
+// Device state of an adaptive session: every in-image tile active with 0 samples (tile_spp = h_spp when given: resume).
+hipError_t make_adaptive(rtk_progressive* p, const int32_t* h_spp) {
+    const size_t n = size_t(p->tm.n_tiles_local);
+    hipError_t e = hipSuccess;
+    if (!p->d_active) e = hipMalloc(reinterpret_cast<void**>(&p->d_active), n * sizeof(int32_t));
+    if (e == hipSuccess && !p->d_tile_spp) e = hipMalloc(reinterpret_cast<void**>(&p->d_tile_spp), n * sizeof(int32_t));
+    if (e == hipSuccess && !p->d_list) e = hipMalloc(reinterpret_cast<void**>(&p->d_list), (n + 1) * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(p->d_list, 0, (n + 1) * sizeof(int32_t));
+    std::vector<int32_t> active(n), spp(n, 0);
+    for (size_t lt = 0; lt < n; lt++) active[lt] = tile_pixels(p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, int64_t(lt)) > 0 ? 1 : 0;
+    if (e == hipSuccess) e = hipMemcpy(p->d_tile_spp, h_spp ? h_spp : spp.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_active, active.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
+    p->list_valid = false;
+    return e;
+}
+
+// The next step's hand-out list: the active tiles in the learned cost order (identity until there is one).
+hipError_t compact(rtk_progressive* p) {
+    const hipError_t e = launch_adaptive_compact(p->d_active, p->order_valid ? p->d_order : nullptr, p->tm.n_tiles_local, p->d_list,
+                                                 p->d_list + p->tm.n_tiles_local, p->stream);
+    p->list_valid = e == hipSuccess;
+    return e;
+}
+
 // Every check of a call on an existing session: poisoned, scene changed.
 int usable(const rtk_progressive* p, const char* who) {
     if (!p) return fail(RTK_ERR_INVALID, "%s: null session", who);
@@ -140,32 +190,117 @@ hipError_t enqueue_step(rtk_progressive* p, int n_samples, void* d_linear, uint8
     const size_t plane = size_t(p->tm.n_tiles_local) * 192 * p->elem;
     const int per_launch = chunks_per_launch(plane);
     const size_t workspace = plane * size_t(std::min(per_launch, k1 - k0));
-    const int32_t* order = p->order_valid ? p->d_order : nullptr;
-    auto* counters = reinterpret_cast<unsigned long long*>(d_counters);
+    // Adaptive sessions: a fresh session's first step renders every tile (all are active) and learns the cost order like any
+    // other; every later step hands out the compacted list of the active tiles, up to its device-side length.
+    const bool all_tiles = !p->adaptive || p->done == 0;
     hipError_t e = hipSuccess;
+    if (!all_tiles && !p->list_valid && (e = compact(p)) != hipSuccess) return e;  // (a resumed session)
+    const int32_t* order = !all_tiles ? p->d_list : (p->order_valid ? p->d_order : nullptr);
+    auto* counters = reinterpret_cast<unsigned long long*>(d_counters);
+    const bool measure = !p->order_valid && all_tiles;
     for (int a = k0; a < k1 && e == hipSuccess; a += per_launch) {
         const int b = std::min(k1, a + per_launch);
         TileMap tp = p->tm;
         tp.n_chunks = b - a;
         for (int k = 0; k <= kMaxChunks; k++) tp.chunk_start[k] = int16_t(std::min(std::min(a + k, b) * c, p->target));
-        unsigned int* cost = (!p->order_valid && a == k0) ? p->d_cost : nullptr;  // a tile's cost is measured on its first launch
+        if (!all_tiles) tp.active_count = p->d_list + p->tm.n_tiles_local;
+        unsigned int* cost = (measure && a == k0) ? p->d_cost : nullptr;  // a tile's cost is measured on its first launch
         void* partial = nullptr;
         e = render_chunks(p->ctx, p->real_mode, p->d_cam, tp, p->seed, counters, order, cost, workspace, p->stream, &partial);
         launched = launched || e == hipSuccess;
         if (e != hipSuccess) break;
         const bool last = b == k1;
         const int k_full = s_end / c;  // full chunks after the step (every chunk but a final partial one; read on the last launch only)
+        if (p->adaptive) {
+            const bool retire_ok = last && p->min_samples <= s_end && s_end < p->target;
+            e = p->real_mode == RTK_REAL_F64
+                    ? launch_accumulate_adaptive<double>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2,
+                                                         p->d_active, p->d_tile_spp, last, s_end, retire_ok, p->rel_target, d_linear, d_rgb8, d_noise,
+                                                         p->stream)
+                    : launch_accumulate_adaptive<float>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2,
+                                                        p->d_active, p->d_tile_spp, last, s_end, retire_ok, p->rel_target, d_linear, d_rgb8, d_noise,
+                                                        p->stream);
+            continue;
+        }
         e = p->real_mode == RTK_REAL_F64
                 ? launch_accumulate<double>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2, last,
                                             1.0 / double(s_end), k_full, d_linear, d_rgb8, d_noise, p->stream)
                 : launch_accumulate<float>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2, last,
                                            1.0 / double(s_end), k_full, d_linear, d_rgb8, d_noise, p->stream);
     }
-    if (e == hipSuccess && !p->order_valid) {  // the first step's costs become the hand-out order of every later launch
+    if (e == hipSuccess && measure) {  // the first step's costs become the hand-out order of every later launch
         e = launch_tile_order(p->d_cost, p->tm.n_tiles_local, p->d_order, p->stream);
         p->order_valid = e == hipSuccess;
     }
+    if (e == hipSuccess && p->adaptive) e = compact(p);
     return e;
+}
+
+// Parse and check a checkpoint of version 1 or 2 (rtk_checkpoint_read_info); a version-2 one also yields its adaptive options
+// and where its tile_spp table starts (*tile_spp_out stays null for version 1, *adaptive_out all 0).
+int parse_checkpoint(const void* h_buf, int64_t n, rtk_checkpoint_info* out, rtk_adaptive_opts* adaptive_out, const unsigned char** tile_spp_out) {
+    const unsigned char* b = static_cast<const unsigned char*>(h_buf);
+    if (n < int64_t(kCheckpointHeader) + 8) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: %lld bytes is too short for a checkpoint", (long long)n);
+    if (std::memcmp(b, kCheckpointMagic, 8) != 0) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: not a checkpoint (bad magic)");
+    int32_t f[9];
+    std::memcpy(f, b + 8, sizeof f);
+    rtk_checkpoint_info info{};
+    info.version = f[0];
+    info.width = f[1];
+    info.height = f[2];
+    info.rank = f[3];
+    info.n_ranks = f[4];
+    info.real_mode = f[5];
+    info.target_spp = f[6];
+    info.chunk_size = f[7];
+    info.samples_done = f[8];
+    std::memcpy(&info.seed, b + 44, 4);
+    std::memcpy(&info.scene_digest, b + 48, 8);
+    if (info.version != RTK_CHECKPOINT_VERSION && info.version != kCheckpointAdaptive)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: checkpoint version %d, this library reads versions %d and %d", info.version,
+                    RTK_CHECKPOINT_VERSION, kCheckpointAdaptive);
+    const bool adaptive = info.version == kCheckpointAdaptive;
+    if (info.width <= 0 || info.height <= 0 || info.width > 65536 || info.height > 65536 || info.n_ranks < 1 || info.n_ranks > 65536 || info.rank < 0 ||
+        info.rank >= info.n_ranks || (info.real_mode != RTK_REAL_F64 && info.real_mode != RTK_REAL_F32) || info.target_spp < 1 || info.target_spp > 32767 ||
+        info.chunk_size != frame_chunk_size(info.target_spp) || info.samples_done < 0 || info.samples_done > info.target_spp)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: inconsistent header fields");
+    rtk_camera cam;
+    std::memcpy(&cam, b + 56, sizeof cam);
+    if (cam.image_width != info.width || cam.image_height != info.height || cam.samples_per_pixel != info.target_spp)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: the stored camera disagrees with the header");
+    const int64_t size = checkpoint_bytes_for(info.width, info.height, info.n_ranks, info.real_mode, adaptive);
+    if (n != size)
+        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: %lld bytes, a %dx%d checkpoint of rank %d of %d (%s) has %lld", (long long)n, info.width, info.height,
+                    info.rank, info.n_ranks, info.real_mode == RTK_REAL_F64 ? "f64" : "f32", (long long)size);
+    Fnv64 h;
+    h.add(b, size_t(size - 8));
+    uint64_t stored = 0;
+    std::memcpy(&stored, b + size - 8, 8);
+    if (stored != h.h) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: checksum mismatch (corrupted checkpoint)");
+    rtk_adaptive_opts ad{};
+    const unsigned char* spp_at = nullptr;
+    if (adaptive) {  // the options' rules, and every tile either active (samples_done) or retired at a chunk boundary in [min_samples, samples_done)
+        const int64_t tiles = rtk_tiles_per_rank(info.width, info.height, info.n_ranks);
+        const unsigned char* at = b + size - 8 - tiles * 4 - 16;
+        std::memcpy(&ad.rel_target, at, 8);
+        std::memcpy(&ad.min_samples, at + 8, 4);
+        std::memcpy(&ad.reserved, at + 12, 4);
+        if (!adaptive_opts_ok(ad.rel_target, ad.min_samples, info.chunk_size, info.target_spp) || ad.reserved != 0)
+            return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: bad adaptive options (rel_target %g, min_samples %d)", ad.rel_target, ad.min_samples);
+        spp_at = at + 16;
+        for (int64_t lt = 0; lt < tiles; lt++) {
+            int32_t v;
+            std::memcpy(&v, spp_at + lt * 4, 4);
+            const bool ok = tile_pixels(info.width, info.height, info.rank, info.n_ranks, lt) == 0
+                                ? v == 0
+                                : (v == info.samples_done || (v % info.chunk_size == 0 && v >= ad.min_samples && v < info.samples_done));
+            if (!ok) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: tile %lld holds %d samples (samples_done %d)", (long long)lt, v, info.samples_done);
+        }
+    }
+    *out = info;
+    if (adaptive_out) *adaptive_out = ad;
+    if (tile_spp_out) *tile_spp_out = spp_at;
+    return RTK_OK;
 }
 
 }  // namespace
@@ -266,18 +401,17 @@ int rtk_progressive_noise(rtk_progressive* p, rtk_noise_stats* out) {
     if (k < 2) return RTK_OK;
     const int blocks = noise_partial_blocks(p->tm);
     double* result = p->d_stats + size_t(blocks) * 3;
-    RTK_HIP(launch_noise_stats(p->d_s1, p->d_s2, p->tm, p->cam.image_width, p->cam.image_height, k, p->d_stats, result, p->stream));
+    if (p->adaptive)  // per-tile K: a retired tile's estimate is the one it retired with
+        RTK_HIP(launch_noise_stats_adaptive(p->d_s1, p->d_s2, p->tm, p->cam.image_width, p->cam.image_height, p->chunk, p->d_tile_spp, p->d_stats, result,
+                                            p->stream));
+    else
+        RTK_HIP(launch_noise_stats(p->d_s1, p->d_s2, p->tm, p->cam.image_width, p->cam.image_height, k, p->d_stats, result, p->stream));
     double h[3];
     RTK_HIP(hipMemcpyAsync(h, result, sizeof h, hipMemcpyDeviceToHost, p->stream));
     RTK_HIP(hipStreamSynchronize(p->stream));
     // in-image pixels of this rank
     int64_t n_px = 0;
-    for (int64_t lt = 0; lt < p->tm.n_tiles_local; lt++) {
-        const int64_t t = lt * p->n_ranks + p->rank;
-        if (t >= int64_t(p->tm.tiles_x) * p->tm.tiles_y) break;
-        const int w = std::min(8, p->cam.image_width - int(t % p->tm.tiles_x) * 8), hgt = std::min(8, p->cam.image_height - int(t / p->tm.tiles_x) * 8);
-        n_px += int64_t(w) * hgt;
-    }
+    for (int64_t lt = 0; lt < p->tm.n_tiles_local; lt++) n_px += tile_pixels(p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, lt);
     out->mean_se = n_px > 0 ? h[0] / double(n_px) : 0.0;
     out->max_se = h[1];
     out->mean_rel_se = n_px > 0 ? h[2] / double(n_px) : 0.0;
@@ -286,7 +420,7 @@ int rtk_progressive_noise(rtk_progressive* p, rtk_noise_stats* out) {
 
 int64_t rtk_progressive_checkpoint_bytes(const rtk_progressive* p) {
     if (!p) return fail(RTK_ERR_INVALID, "rtk_progressive_checkpoint_bytes: null session");
-    return checkpoint_bytes_for(p->cam.image_width, p->cam.image_height, p->n_ranks, p->real_mode);
+    return checkpoint_bytes_for(p->cam.image_width, p->cam.image_height, p->n_ranks, p->real_mode, p->adaptive);
 }
 
 int rtk_progressive_save(rtk_progressive* p, void* h_buf, int64_t n) {
@@ -299,7 +433,7 @@ int rtk_progressive_save(rtk_progressive* p, void* h_buf, int64_t n) {
     unsigned char* b = static_cast<unsigned char*>(h_buf);
     std::memset(b, 0, kCheckpointHeader);
     std::memcpy(b, kCheckpointMagic, 8);
-    const int32_t fields[9] = {RTK_CHECKPOINT_VERSION, p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, p->real_mode, p->target, p->chunk, p->done};
+    const int32_t fields[9] = {p->adaptive ? kCheckpointAdaptive : RTK_CHECKPOINT_VERSION, p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, p->real_mode, p->target, p->chunk, p->done};
     std::memcpy(b + 8, fields, sizeof fields);
     std::memcpy(b + 44, &p->seed, 4);
     std::memcpy(b + 48, &p->digest, 8);
@@ -312,6 +446,14 @@ int rtk_progressive_save(rtk_progressive* p, void* h_buf, int64_t n) {
     at += slots * sizeof(double);
     RTK_HIP(hipMemcpy(at, p->d_s2, slots * sizeof(double), hipMemcpyDeviceToHost));
     at += slots * sizeof(double);
+    if (p->adaptive) {
+        const int32_t ms[2] = {p->min_samples, 0};
+        std::memcpy(at, &p->rel_target, 8);
+        std::memcpy(at + 8, ms, 8);
+        at += 16;
+        RTK_HIP(hipMemcpy(at, p->d_tile_spp, size_t(p->tm.n_tiles_local) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        at += size_t(p->tm.n_tiles_local) * sizeof(int32_t);
+    }
     Fnv64 f;
     f.add(b, size_t(at - b));
     std::memcpy(at, &f.h, 8);
@@ -320,51 +462,25 @@ int rtk_progressive_save(rtk_progressive* p, void* h_buf, int64_t n) {
 
 int rtk_checkpoint_read_info(const void* h_buf, int64_t n, rtk_checkpoint_info* out) {
     if (!h_buf || !out) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: null argument");
-    const unsigned char* b = static_cast<const unsigned char*>(h_buf);
-    if (n < int64_t(kCheckpointHeader) + 8) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: %lld bytes is too short for a checkpoint", (long long)n);
-    if (std::memcmp(b, kCheckpointMagic, 8) != 0) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: not a checkpoint (bad magic)");
-    int32_t f[9];
-    std::memcpy(f, b + 8, sizeof f);
-    rtk_checkpoint_info info{};
-    info.version = f[0];
-    info.width = f[1];
-    info.height = f[2];
-    info.rank = f[3];
-    info.n_ranks = f[4];
-    info.real_mode = f[5];
-    info.target_spp = f[6];
-    info.chunk_size = f[7];
-    info.samples_done = f[8];
-    std::memcpy(&info.seed, b + 44, 4);
-    std::memcpy(&info.scene_digest, b + 48, 8);
-    if (info.version != RTK_CHECKPOINT_VERSION)
-        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: checkpoint version %d, this library reads version %d", info.version, RTK_CHECKPOINT_VERSION);
-    if (info.width <= 0 || info.height <= 0 || info.width > 65536 || info.height > 65536 || info.n_ranks < 1 || info.n_ranks > 65536 || info.rank < 0 ||
-        info.rank >= info.n_ranks || (info.real_mode != RTK_REAL_F64 && info.real_mode != RTK_REAL_F32) || info.target_spp < 1 || info.target_spp > 32767 ||
-        info.chunk_size != frame_chunk_size(info.target_spp) || info.samples_done < 0 || info.samples_done > info.target_spp)
-        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: inconsistent header fields");
-    rtk_camera cam;
-    std::memcpy(&cam, b + 56, sizeof cam);
-    if (cam.image_width != info.width || cam.image_height != info.height || cam.samples_per_pixel != info.target_spp)
-        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: the stored camera disagrees with the header");
-    const int64_t size = checkpoint_bytes_for(info.width, info.height, info.n_ranks, info.real_mode);
-    if (n != size)
-        return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: %lld bytes, a %dx%d checkpoint of rank %d of %d (%s) has %lld", (long long)n, info.width, info.height,
-                    info.rank, info.n_ranks, info.real_mode == RTK_REAL_F64 ? "f64" : "f32", (long long)size);
-    Fnv64 h;
-    h.add(b, size_t(size - 8));
-    uint64_t stored = 0;
-    std::memcpy(&stored, b + size - 8, 8);
-    if (stored != h.h) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: checksum mismatch (corrupted checkpoint)");
-    *out = info;
-    return RTK_OK;
+    return parse_checkpoint(h_buf, n, out, nullptr, nullptr);
+}
+
+int rtk_checkpoint_read_adaptive(const void* h_buf, int64_t n, rtk_adaptive_opts* out, int32_t* h_tile_spp) {
+    if (!h_buf || !out) return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_adaptive: null argument");
+    rtk_checkpoint_info info;
+    const unsigned char* spp = nullptr;
+    const int rc = parse_checkpoint(h_buf, n, &info, out, &spp);
+    if (rc == RTK_OK && spp && h_tile_spp) std::memcpy(h_tile_spp, spp, size_t(rtk_tiles_per_rank(info.width, info.height, info.n_ranks)) * sizeof(int32_t));
+    return rc;
 }
 
 int rtk_progressive_resume(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const void* h_buf, int64_t n, rtk_progressive** out) {
     if (!ctx || !cam || !opts || !h_buf || !out) return fail(RTK_ERR_INVALID, "rtk_progressive_resume: null argument");
     *out = nullptr;
     rtk_checkpoint_info info;
-    int rc = rtk_checkpoint_read_info(h_buf, n, &info);
+    rtk_adaptive_opts ad{};
+    const unsigned char* spp_at = nullptr;
+    int rc = parse_checkpoint(h_buf, n, &info, &ad, &spp_at);
     if (rc != RTK_OK) return fail(rc, "rtk_progressive_resume: %s", std::string(g_error).c_str());
     const unsigned char* b = static_cast<const unsigned char*>(h_buf);
     if (info.target_spp != cam->samples_per_pixel)
@@ -390,12 +506,76 @@ int rtk_progressive_resume(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render
     if (e == hipSuccess) e = hipMemcpy(p->d_s1, at, slots * sizeof(double), hipMemcpyHostToDevice);
     at += slots * sizeof(double);
     if (e == hipSuccess) e = hipMemcpy(p->d_s2, at, slots * sizeof(double), hipMemcpyHostToDevice);
+    p->done = info.samples_done;
+    if (e == hipSuccess && spp_at) {  // version 2: the adaptive state -- retired tiles from the retire test of the step that ended at `done`
+        std::vector<int32_t> spp(size_t(p->tm.n_tiles_local));
+        std::memcpy(spp.data(), spp_at, spp.size() * sizeof(int32_t));
+        p->adaptive = true;
+        p->rel_target = ad.rel_target;
+        p->min_samples = ad.min_samples;
+        e = make_adaptive(p, spp.data());
+        if (e == hipSuccess)
+            e = launch_adaptive_restore(p->d_s1, p->d_s2, p->tm, p->cam.image_width, p->cam.image_height, p->chunk, p->d_tile_spp, p->done,
+                                        p->min_samples <= p->done && p->done < p->target, p->rel_target, p->d_active, p->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    }
     if (e != hipSuccess) {
         release(p);
         return fail(RTK_ERR_HIP, "rtk_progressive_resume: upload of the sums failed: %s", hipGetErrorString(e));
     }
-    p->done = info.samples_done;
     *out = p;
+    return RTK_OK;
+}
+
+int rtk_progressive_set_adaptive(rtk_progressive* p, const rtk_adaptive_opts* opts) {
+    int rc = usable(p, "rtk_progressive_set_adaptive");
+    if (rc != RTK_OK) return rc;
+    if (!opts) return fail(RTK_ERR_INVALID, "rtk_progressive_set_adaptive: null options");
+    if (p->done != 0) return fail(RTK_ERR_INVALID, "rtk_progressive_set_adaptive: only before the first step (%d samples done)", p->done);
+    if (!adaptive_opts_ok(opts->rel_target, opts->min_samples, p->chunk, p->target) || opts->reserved != 0)
+        return fail(RTK_ERR_INVALID,
+                    "rtk_progressive_set_adaptive: rel_target must be > 0 (%g); min_samples (%d) a multiple of the chunk size %d, at least 2 chunks and at "
+                    "most the target %d; reserved 0",
+                    opts->rel_target, opts->min_samples, p->chunk, p->target);
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    RTK_HIP(make_adaptive(p, nullptr));
+    p->adaptive = true;
+    p->rel_target = opts->rel_target;
+    p->min_samples = opts->min_samples;
+    return RTK_OK;
+}
+
+int rtk_adaptive_tile_samples(rtk_progressive* p, int32_t* h_out) {
+    if (!p || !h_out) return fail(RTK_ERR_INVALID, "rtk_adaptive_tile_samples: null argument");
+    if (p->poisoned) return fail(RTK_ERR_INVALID, "rtk_adaptive_tile_samples: the session is poisoned by an earlier failed step");
+    const int64_t n = p->tm.n_tiles_local;
+    if (!p->adaptive) {  // every in-image tile holds samples_done samples
+        for (int64_t lt = 0; lt < n; lt++) h_out[lt] = tile_pixels(p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, lt) > 0 ? p->done : 0;
+        return RTK_OK;
+    }
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    RTK_HIP(hipStreamSynchronize(p->stream));
+    RTK_HIP(hipMemcpy(h_out, p->d_tile_spp, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RTK_OK;
+}
+
+int rtk_adaptive_status(rtk_progressive* p, rtk_adaptive_state* out) {
+    if (!p || !out) return fail(RTK_ERR_INVALID, "rtk_adaptive_status: null argument");
+    const int64_t n = p->tm.n_tiles_local;
+    std::vector<int32_t> spp(static_cast<size_t>(n)), active(static_cast<size_t>(n), 1);
+    int rc = rtk_adaptive_tile_samples(p, spp.data());
+    if (rc != RTK_OK) return fail(rc, "rtk_adaptive_status: %s", std::string(g_error).c_str());
+    if (p->adaptive) RTK_HIP(hipMemcpy(active.data(), p->d_active, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *out = rtk_adaptive_state{};
+    int64_t pixels = 0;
+    for (int64_t lt = 0; lt < n; lt++) {
+        const int px = tile_pixels(p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, lt);
+        if (px == 0) continue;  // a padding tile
+        (active[size_t(lt)] ? out->active_tiles : out->retired_tiles)++;
+        out->pixel_samples += int64_t(px) * spp[size_t(lt)];
+        pixels += px;
+    }
+    out->mean_spp = pixels > 0 ? double(out->pixel_samples) / double(pixels) : 0.0;
     return RTK_OK;
 }
 

@@ -44,6 +44,22 @@ int noise_partial_blocks(const TileMap& tmap);
 hipError_t launch_noise_stats(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int k_full, double* partials, double* out3,
                               hipStream_t stream);
 
+// Adaptive sessions (per-tile state: active[t] 1 / 0, tile_spp[t] = the tile's sample count).  launch_accumulate with the state:
+// folds only the tiles active in this launch; on the last launch (`last`) writes the preview (per-tile scale and K), sets
+// tile_spp = s_end of the active tiles and, when retire_ok, retires those whose metric is <= rel_target.
+template <typename real>
+hipError_t launch_accumulate_adaptive(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, bool init, void* acc, double* s1,
+                                      double* s2, int32_t* active, int32_t* tile_spp, bool last, int s_end, bool retire_ok, double rel_target,
+                                      void* out_linear, uint8_t* out_rgb8, float* out_noise, hipStream_t stream);
+// Resume: active[t] from tile_spp, done and the retire test of the step that ended at `done`.
+hipError_t launch_adaptive_restore(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
+                                   int done, bool retire_ok, double rel_target, int32_t* active, hipStream_t stream);
+// list = the positions of `order` (identity when null; n entries) whose tile is active, in order; *count = their number.
+hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, int n, int32_t* list, int32_t* count, hipStream_t stream);
+// launch_noise_stats with per-tile K = tile_spp[t] / chunk_size.
+hipError_t launch_noise_stats_adaptive(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
+                                       double* partials, double* out3, hipStream_t stream);
+
 // Known-answer helper: closest hit of the scene root for n caller-supplied rays (device buffers).
 template <typename real>
 hipError_t launch_debug_hit(const SceneView<real>& sc, int n, const double* d_rays, const uint32_t* d_keys, double* d_out, unsigned long long* d_draws,

@@ -1783,7 +1783,8 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
 
     // Wave-uniform hand-out state: pixels of work item `refill_item` from
     // `refill_next` on have not been given to a lane yet.
-    const int n_items = tmap.n_tiles_local * tmap.n_chunks;
+    const int n_positions = tmap.active_count ? int(__builtin_amdgcn_readfirstlane(*tmap.active_count)) : tmap.n_tiles_local;
+    const int n_items = n_positions * tmap.n_chunks;
     int refill_item = 0, refill_next = 64;
     // The index of the NEXT work item is fetched one item ahead: the returning atomic is issued when an item is
     // taken and only waited for when its 64 pixels have been handed out, so its ~2 us round trip never stalls the wave.
@@ -2697,6 +2698,215 @@ __global__ __launch_bounds__(256) void rtk_noise_final_kernel(const double* __re
     }
 }
 
+// Adaptive progressive sessions (include/rtk.h, "Tile-adaptive sampling"): every local tile is active (it holds the session's
+// samples_done samples) or retired (it keeps tile_spp[t] samples for good).  A step renders the active tiles only -- the render
+// kernel hands out the compacted list `tile_order` up to the device word `active_count` -- and the kernels below keep the
+// per-tile state.  The retire metric of a tile is the maximum over its in-image pixels of se / max(m, 1e-3) over K chunks.
+RTK_DEV double noise_rel(double se, double s1, int k) {
+    const double m = s1 / double(k);
+    return se / (m > 1e-3 ? m : 1e-3);
+}
+
+RTK_DEV double wave_max(double v) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(v, off);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// rtk_accumulate_kernel with per-tile state: folds this launch's planes only into the tiles that were active in it (the same
+// additions in the same order) and leaves retired tiles' sums and S1 / S2 alone.  On the step's last launch (`last`) it writes
+// the preview -- each tile scaled by 1 / its own sample count, se over its own K -- and fuses the retire test: one wave64 per
+// tile (a 256-thread block is 4 tiles), the wave max of the metric through __shfl_xor, lane 0 writes the tile's new state.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_accumulate_adaptive_kernel(const real* __restrict__ partial, TileMap tmap, int width, int height, int chunk_size,
+                                                                       int init, real* __restrict__ acc, double* __restrict__ s1, double* __restrict__ s2,
+                                                                       int32_t* __restrict__ active, int32_t* __restrict__ tile_spp, int last, int s_end,
+                                                                       int retire_ok, double rel_target, real samples_scale, real* __restrict__ out_linear,
+                                                                       uint8_t* __restrict__ out_rgb8, float* __restrict__ out_noise) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int pix = int(gid & 63);
+    const long long local_tile = gid >> 6;
+    if (local_tile >= tmap.n_tiles_local) return;  // (wave-uniform: one wave is one tile)
+    const long long tile = local_tile * tmap.n_ranks + tmap.rank;
+    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
+    const bool inside = tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height;
+    const bool is_active = active[local_tile] != 0;
+    V3<real> sum = mk(real(0), real(0), real(0));
+    double n1 = 0.0, n2 = 0.0;
+    real* a = acc + size_t(local_tile) * 192 + pix;
+    double* p1 = s1 + size_t(local_tile) * 64 + pix;
+    double* p2 = s2 + size_t(local_tile) * 64 + pix;
+    if (inside && is_active) {
+        const real* src = partial + size_t(local_tile) * 192 + pix;
+        const size_t chunk_stride = size_t(tmap.n_tiles_local) * 192;
+        n1 = *p1;
+        n2 = *p2;
+        const double three_c = 3.0 * double(chunk_size);
+        int c = 0;
+        if (init) {
+            sum = mk(src[0], src[64], src[128]);
+            c = 1;
+        } else {
+            sum = mk(a[0], a[64], a[128]);
+        }
+        for (int k = 0; k < tmap.n_chunks; k++) {
+            const real* q = src + size_t(k) * chunk_stride;
+            const V3<real> part = mk(q[0], q[64], q[128]);
+            if (k >= c) sum = sum + part;
+            if (tmap.chunk_start[k + 1] - tmap.chunk_start[k] == chunk_size) {
+                const double y = ((double(part.x) + double(part.y)) + double(part.z)) / three_c;
+                n1 = n1 + y;
+                n2 = n2 + y * y;
+            }
+        }
+        a[0] = sum.x;
+        a[64] = sum.y;
+        a[128] = sum.z;
+        *p1 = n1;
+        *p2 = n2;
+    } else if (inside && last) {
+        sum = mk(a[0], a[64], a[128]);
+        n1 = *p1;
+        n2 = *p2;
+    }
+    if (!last) return;
+    const int spp = is_active ? s_end : tile_spp[local_tile];
+    const int k_full = spp / chunk_size;
+    double se = 0.0, rel = 0.0;
+    if (inside) {
+        sum = scale(is_active ? samples_scale : real(1.0 / double(spp)), sum);
+        se = noise_se(n1, n2, k_full);
+        if (k_full >= 2) rel = noise_rel(se, n1, k_full);
+    }
+    if (is_active) {  // the retire test: wave-uniform branch, every lane of the tile takes part in the reduction
+        const double metric = wave_max(rel);
+        if (pix == 0) {
+            tile_spp[local_tile] = s_end;
+            if (retire_ok && metric <= rel_target) active[local_tile] = 0;
+        }
+    }
+    if (tmap.compact) {
+        if (out_linear) {
+            real* base = out_linear + size_t(local_tile) * 192 + pix;
+            base[0] = sum.x;
+            base[64] = sum.y;
+            base[128] = sum.z;
+        }
+        if (out_noise) out_noise[size_t(local_tile) * 64 + pix] = float(se);
+    } else if (inside) {
+        const size_t px = size_t(j) * width + i, idx = px * 3;
+        if (out_linear) {
+            out_linear[idx] = sum.x;
+            out_linear[idx + 1] = sum.y;
+            out_linear[idx + 2] = sum.z;
+        }
+        if (out_rgb8) {
+            out_rgb8[idx] = to_byte(double(sum.x));
+            out_rgb8[idx + 1] = to_byte(double(sum.y));
+            out_rgb8[idx + 2] = to_byte(double(sum.z));
+        }
+        if (out_noise) out_noise[px] = float(se);
+    }
+}
+
+// Resume of an adaptive checkpoint: the retired state is not stored, it is recomputed -- a tile is active when it holds
+// samples_done samples and the retire test of the step that ended there (the same metric, from the same S1 / S2) did not
+// retire it.  One wave64 per tile, as in the accumulate pass.
+__global__ __launch_bounds__(256) void rtk_adaptive_restore_kernel(const double* __restrict__ s1, const double* __restrict__ s2, TileMap tmap, int width,
+                                                                    int height, int chunk_size, const int32_t* __restrict__ tile_spp, int done,
+                                                                    int retire_ok, double rel_target, int32_t* __restrict__ active) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int pix = int(gid & 63);
+    const long long local_tile = gid >> 6;
+    if (local_tile >= tmap.n_tiles_local) return;
+    const long long tile = local_tile * tmap.n_ranks + tmap.rank;
+    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
+    const bool in_tiles = tile < (long long)tmap.tiles_x * tmap.tiles_y;
+    const int k_full = done / chunk_size;
+    double rel = 0.0;
+    if (in_tiles && i < width && j < height && k_full >= 2) {
+        const double n1 = s1[size_t(local_tile) * 64 + pix], n2 = s2[size_t(local_tile) * 64 + pix];
+        rel = noise_rel(noise_se(n1, n2, k_full), n1, k_full);
+    }
+    const double metric = wave_max(rel);
+    if (pix == 0) active[local_tile] = (in_tiles && tile_spp[local_tile] == done && !(retire_ok && metric <= rel_target)) ? 1 : 0;
+}
+
+// The next step's hand-out list: a stable filter of `order` (identity when null) keeping the active tiles, and its length.
+// One block walks the positions 1024 at a time: a 64-bit ballot per wave, the waves' counts summed in wave order -- the same
+// list on every run.
+__global__ __launch_bounds__(1024) void rtk_adaptive_compact_kernel(const int32_t* __restrict__ active, const int32_t* __restrict__ order, int n,
+                                                                     int32_t* __restrict__ list, int32_t* __restrict__ count) {
+    __shared__ int s_wave[16];
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += 1024) {
+        const int pos = base + tid;
+        int t = 0;
+        bool keep = false;
+        if (pos < n) {
+            t = order ? order[pos] : pos;
+            keep = active[t] != 0;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int at = s_base;
+        for (int w = 0; w < wave; w++) at += s_wave[w];
+        if (keep) list[at + __popcll(m & ((1ull << lane) - 1ull))] = t;
+        __syncthreads();
+        if (tid == 0) {
+            int total = 0;
+            for (int w = 0; w < 16; w++) total += s_wave[w];
+            s_base += total;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) *count = s_base;
+}
+
+// rtk_noise_partial_kernel with per-tile K = tile_spp[t] / chunk_size (feeds rtk_noise_final_kernel).
+__global__ __launch_bounds__(256) void rtk_noise_partial_adaptive_kernel(const double* __restrict__ s1, const double* __restrict__ s2, TileMap tmap, int width,
+                                                                          int height, int chunk_size, const int32_t* __restrict__ tile_spp,
+                                                                          double* __restrict__ partials) {
+    __shared__ double s_w[4][3];
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int pix = int(gid & 63);
+    const long long local_tile = gid >> 6;
+    double se = 0.0, rel = 0.0;
+    if (local_tile < tmap.n_tiles_local) {
+        const long long tile = local_tile * tmap.n_ranks + tmap.rank;
+        const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
+        const int k_full = tile_spp[local_tile] / chunk_size;
+        if (tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height && k_full >= 2) {
+            const double n1 = s1[size_t(local_tile) * 64 + pix], n2 = s2[size_t(local_tile) * 64 + pix];
+            se = noise_se(n1, n2, k_full);
+            rel = noise_rel(se, n1, k_full);
+        }
+    }
+    double sum_se = se, max_se = se, sum_rel = rel;
+    wave_reduce3(sum_se, max_se, sum_rel);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_w[wave][0] = sum_se;
+        s_w[wave][1] = max_se;
+        s_w[wave][2] = sum_rel;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double a = (s_w[0][0] + s_w[1][0]) + (s_w[2][0] + s_w[3][0]);
+        const double b01 = s_w[0][1] > s_w[1][1] ? s_w[0][1] : s_w[1][1], b23 = s_w[2][1] > s_w[3][1] ? s_w[2][1] : s_w[3][1];
+        const double c = (s_w[0][2] + s_w[1][2]) + (s_w[2][2] + s_w[3][2]);
+        partials[size_t(blockIdx.x) * 3] = a;
+        partials[size_t(blockIdx.x) * 3 + 1] = b01 > b23 ? b01 : b23;
+        partials[size_t(blockIdx.x) * 3 + 2] = c;
+    }
+}
+
 // Gathered compact tiles -> row-major image (+ bytes).  One thread per pixel slot.
 template <typename real>
 __global__ __launch_bounds__(256) void rtk_unpermute_kernel(const real* __restrict__ gathered, int width, int height, int tiles_x, int n_tiles, int n_ranks,
@@ -3038,6 +3248,48 @@ hipError_t launch_noise_stats(const double* s1, const double* s2, const TileMap&
     const int blocks = noise_partial_blocks(tmap);
     if (blocks <= 0) return hipErrorInvalidValue;
     rtk_noise_partial_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(s1, s2, tmap, width, height, k_full, partials);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    rtk_noise_final_kernel<<<dim3(1), dim3(256), 0, stream>>>(partials, blocks, out3);
+    return hipGetLastError();
+}
+
+template <typename real>
+hipError_t launch_accumulate_adaptive(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, bool init, void* acc, double* s1,
+                                      double* s2, int32_t* active, int32_t* tile_spp, bool last, int s_end, bool retire_ok, double rel_target,
+                                      void* out_linear, uint8_t* out_rgb8, float* out_noise, hipStream_t stream) {
+    const long long slots = (long long)tmap.n_tiles_local * 64;
+    if (slots <= 0) return hipSuccess;
+    rtk_accumulate_adaptive_kernel<real><<<dim3(int((slots + 255) / 256)), dim3(256), 0, stream>>>(
+        static_cast<const real*>(partial), tmap, width, height, chunk_size, init ? 1 : 0, static_cast<real*>(acc), s1, s2, active, tile_spp, last ? 1 : 0,
+        s_end, retire_ok ? 1 : 0, rel_target, real(1.0 / double(s_end)), static_cast<real*>(out_linear), out_rgb8, out_noise);
+    return hipGetLastError();
+}
+template hipError_t launch_accumulate_adaptive<double>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, int32_t*, int32_t*, bool, int,
+                                                       bool, double, void*, uint8_t*, float*, hipStream_t);
+template hipError_t launch_accumulate_adaptive<float>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, int32_t*, int32_t*, bool, int,
+                                                      bool, double, void*, uint8_t*, float*, hipStream_t);
+
+hipError_t launch_adaptive_restore(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
+                                   int done, bool retire_ok, double rel_target, int32_t* active, hipStream_t stream) {
+    const long long slots = (long long)tmap.n_tiles_local * 64;
+    if (slots <= 0) return hipSuccess;
+    rtk_adaptive_restore_kernel<<<dim3(int((slots + 255) / 256)), dim3(256), 0, stream>>>(s1, s2, tmap, width, height, chunk_size, tile_spp, done,
+                                                                                         retire_ok ? 1 : 0, rel_target, active);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, int n, int32_t* list, int32_t* count, hipStream_t stream) {
+    if (n <= 0) return hipErrorInvalidValue;
+    rtk_adaptive_compact_kernel<<<dim3(1), dim3(1024), 0, stream>>>(active, order, n, list, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_noise_stats_adaptive(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
+                                       double* partials, double* out3, hipStream_t stream) {
+    const int blocks = noise_partial_blocks(tmap);
+    if (blocks <= 0) return hipErrorInvalidValue;
+    rtk_noise_partial_adaptive_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(s1, s2, tmap, width, height, chunk_size, tile_spp, partials);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     rtk_noise_final_kernel<<<dim3(1), dim3(256), 0, stream>>>(partials, blocks, out3);

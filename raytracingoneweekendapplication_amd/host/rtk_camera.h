@@ -142,13 +142,20 @@ public:
     //                    scene, camera, seed and real mode (otherwise it warns and starts over);
     //   noise_target     > 0: stop at the first step boundary where the frame's mean relative standard error
     //                    (rtk_noise_stats.mean_rel_se) is <= noise_target; samples_per_pixel is then the maximum.
+    //   adaptive_target  > 0: tile-adaptive sampling (rtk_progressive_set_adaptive, rel_target): an 8x8 tile stops rendering once,
+    //                    after adaptive_min_samples (0 = two chunks), the largest relative standard error of its pixels is <=
+    //                    adaptive_target; render() stops at samples_per_pixel or when no tile is active.  A resumed
+    //                    checkpoint keeps the options it was made with.
     int progressive_step = 0;
     bool write_previews = false;
     const char* checkpoint_file = nullptr;
     double noise_target = 0;
+    double adaptive_target = 0;
+    int adaptive_min_samples = 0;
     int last_samples_rendered = 0;     // set by a progressive render(): samples per pixel this call added ...
     int last_samples_done = 0;         // ... the samples per pixel in the image it wrote ...
     rtk_noise_stats last_noise{};      // ... and the noise estimate after its last step (valid = 0 before two full chunks)
+    rtk_adaptive_state last_adaptive{};  // ... and the tiles' state after it (without adaptive_target every tile is active)
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -262,6 +269,7 @@ public:
         last_samples_rendered = 0;
         last_samples_done = 0;
         last_noise = rtk_noise_stats{};
+        last_adaptive = rtk_adaptive_state{};
         rc = upload(multi, desc, cam);
         rtk_render_opts opts{};
         opts.seed = seed;
@@ -285,7 +293,15 @@ public:
                 }
             }
         }
-        if (rc == RTK_OK && !p) rc = rtk_progressive_create(ctx, &cam, &opts, &p);
+        if (rc == RTK_OK && !p) {
+            rc = rtk_progressive_create(ctx, &cam, &opts, &p);
+            if (rc == RTK_OK && adaptive_target > 0) {
+                rtk_adaptive_opts ad{};
+                ad.rel_target = adaptive_target;
+                ad.min_samples = adaptive_min_samples > 0 ? adaptive_min_samples : 2 * rtk_progressive_chunk_size(p);
+                rc = rtk_progressive_set_adaptive(p, &ad);
+            }
+        }
         if (rc == RTK_OK) {
             const int chunk = rtk_progressive_chunk_size(p);
             const int step = (progressive_step + chunk - 1) / chunk * chunk;
@@ -308,7 +324,9 @@ public:
                 }
                 if (rc == RTK_OK && write_previews && write_image) rtk::write_png(image_name, cam.image_width, cam.image_height, rgb8->data());
                 if (rc == RTK_OK && (noise_target > 0 || done >= cam.samples_per_pixel)) rc = rtk_progressive_noise(p, &last_noise);
+                if (rc == RTK_OK) rc = rtk_adaptive_status(p, &last_adaptive);
                 if (rc == RTK_OK && noise_target > 0 && last_noise.valid && last_noise.mean_rel_se <= noise_target) break;
+                if (rc == RTK_OK && adaptive_target > 0 && last_adaptive.active_tiles == 0) break;  // every tile retired
                 if (show_progress) print_progress(done, cam.samples_per_pixel, nullptr);
             }
             last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
