@@ -192,7 +192,9 @@ typedef struct rtk_camera {
 
 typedef enum rtk_real_mode {
     RTK_REAL_F64 = 0,   /* the reference's arithmetic type; the parity mode        */
-    RTK_REAL_F32 = 1    /* throughput mode; parity is statistical only */
+    RTK_REAL_F32 = 1    /* throughput mode: images agree statistically;
+                         * hit / scatter / texture / get_ray match the reference's
+                         * known answers within f32 rounding, case by case        */
 } rtk_real_mode;
 
 /* Image tiles: one 8x8-pixel tile per 64-lane wavefront.  Tile t (row-major

@@ -627,6 +627,36 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
     auto pack = [&](Slot<real>* rec, const double* vals, int n) {
         for (int e = 0; e < n; e++) rec[e / Slot<real>::kReals].v[e % Slot<real>::kReals] = real(vals[e]);
     };
+    // Float boxes: the slab test computes (b - o) * inv in float, which places a plane only to ~2^-24 (|b| + |o|).  A box
+    // thinner than that on an axis -- the 1e-4 padding of an axis-aligned quad at z = 555 seen from z = -800 -- collapses to
+    // near == far and culls every ray (the fast order tests such a box before the Cornell box's back wall: f32 lost 20 % of
+    // its light there).  So every axis of a float box is at least 2^-20 x the scene's largest box coordinate thick, with its
+    // bounds rounded outward; culling stays conservative and the primitive tests decide every hit, as in f64.
+    double min_thick = 0.0;
+    if constexpr (sizeof(real) == 4) {
+        double coord = 1.0;
+        for (int32_t k = 0; k < sc.n_bvh_boxes; k++) {
+            const rtk_aabb& b = sc.bvh_boxes[k];
+            for (double v : {b.xmin, b.xmax, b.ymin, b.ymax, b.zmin, b.zmax})
+                if (std::isfinite(v)) coord = std::max(coord, std::fabs(v));
+        }
+        min_thick = std::ldexp(coord, -20);
+    }
+    auto float_box = [&](double* vals) {
+        for (int a = 0; a < 3; a++) {
+            double& lo = vals[2 * a];
+            double& hi = vals[2 * a + 1];
+            if (!(hi - lo >= min_thick)) {  // (also NaN-safe: an empty or degenerate box is padded like a thin one)
+                const double mid = 0.5 * (lo + hi), half = 0.5 * min_thick;
+                if (std::isfinite(mid)) lo = std::min(lo, mid - half), hi = std::max(hi, mid + half);
+            }
+            float flo = float(lo), fhi = float(hi);
+            if (double(flo) > lo) flo = std::nextafter(flo, -INFINITY);
+            if (double(fhi) < hi) fhi = std::nextafter(fhi, INFINITY);
+            lo = flo;
+            hi = fhi;
+        }
+    };
     for (size_t i = 0; i < prog.ops.size(); i++) {
         const Op& op = prog.ops[i];
         const uint32_t kind = slot_kind(op), payload = op.kind_payload >> 4;
@@ -637,7 +667,8 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
         switch (kind) {
             case OP_BOX: {
                 const rtk_aabb& b = sc.bvh_boxes[payload];
-                const double vals[6] = {b.xmin, b.xmax, b.ymin, b.ymax, b.zmin, b.zmax};
+                double vals[6] = {b.xmin, b.xmax, b.ymin, b.ymax, b.zmin, b.zmax};
+                if constexpr (sizeof(real) == 4) float_box(vals);
                 pack(rec, vals, 6);
                 rec->aux = slot_of_op[op.aux];
                 break;

@@ -275,11 +275,14 @@ def test_two_ranks_on_one_device_equal_one_rank(rt, renderer):
         r.close()
 
 
-def _sums_from_blob(blob, tiles):
+def _sums_from_blob(blob, tiles, elem=8):
+    """(running sums [tiles, 3, 64] as float64, S1, S2) of a checkpoint: `elem`-byte running sums (4 in f32 sessions), then the
+    f64 S1 and S2 planes."""
     body = np.frombuffer(blob, np.uint8, offset=256)
-    acc = np.frombuffer(body[: tiles * 192 * 8].tobytes(), np.float64).reshape(tiles, 3, 64)
-    s1 = np.frombuffer(body[tiles * 192 * 8: tiles * 256 * 8].tobytes(), np.float64).reshape(tiles, 64)
-    s2 = np.frombuffer(body[tiles * 256 * 8: tiles * 320 * 8].tobytes(), np.float64).reshape(tiles, 64)
+    n_acc = tiles * 192 * elem
+    acc = np.frombuffer(body[:n_acc].tobytes(), np.float64 if elem == 8 else np.float32).astype(np.float64).reshape(tiles, 3, 64)
+    s1 = np.frombuffer(body[n_acc: n_acc + tiles * 64 * 8].tobytes(), np.float64).reshape(tiles, 64)
+    s2 = np.frombuffer(body[n_acc + tiles * 64 * 8: n_acc + tiles * 128 * 8].tobytes(), np.float64).reshape(tiles, 64)
     return acc, s1, s2
 
 
