@@ -554,6 +554,59 @@ int rtk_adaptive_tile_samples(rtk_progressive* p, int32_t* h_out);
  * h_tile_spp is left alone.  Version 2: the options and, when h_tile_spp is given, tile_spp[tiles_per_rank]. */
 int rtk_checkpoint_read_adaptive(const void* h_buf, int64_t n, rtk_adaptive_opts* out, int32_t* h_tile_spp);
 
+/* Denoising ------------------------------------------------------------------------
+ * First-hit guide buffers (AOVs): rtk_render_aovs renders, for samples s = 0 .. n_samples-1 of every pixel, the render's primary
+ * ray (get_ray with opts->seed: sample s of the render, bit for bit) and the closest hit of the scene root on interval(0.001, inf)
+ * (Camera.txt:211), a constant medium drawing from the stream of keys (seed, j*W+i, s + 2^31) -- rtk_debug_get_ray then
+ * rtk_debug_closest_hit reproduce every sample.  d_aov[(j*W+i)*8 + k] (float32; sums in the real mode's type in sample order,
+ * each divided by its count once, then rounded to float):
+ *   k 0-2  albedo, mean over the n samples: a miss gives the camera background clamped to [0, 1]; a hit, by material kind:
+ *          lambertian / isotropic texture::value(u, v, p), metal / specular albedo, dielectric (1, 1, 1), diffuse_light
+ *          min(1, texture::value) per channel
+ *   k 3    hit fraction: hits / n (medium hits count)
+ *   k 4-6  the hit record's normal summed over hits (isotropic hits add 0), divided by n
+ *   k 7    depth: the mean over hits of t * |rd|; 0 when no sample hits
+ * Whole images only: n_ranks != 1, n_samples <= 0 or a null buffer give RTK_ERR_INVALID; no scene gives RTK_ERR_NO_SCENE.
+ * rtk_render_aovs is asynchronous on opts->stream; rtk_render_aovs_host blocks (count_work and variant are ignored).
+ *
+ * Denoiser: an edge-avoiding a-trous filter (Dammertz et al. 2010) with the luminance weight of SVGF (Schied et al. 2017),
+ * spatial part only, guided by the AOVs and by the per-pixel variance se^2 of the noise estimate (d_noise, as a progressive
+ * step writes it).  Iteration k = 0 .. iterations-1 takes the 5x5 taps q = p + 2^k (dx, dy), dy outer, dx inner, skipping
+ * taps outside the image, with weight h[dx] h[dy] w_l w_n w_z w_a, h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *   w_l = exp(-|y_p - y_q| / (sigma_l sqrt(max(gv_p, 0)) + 1e-6)), y = (r + g + b) / 3, gv_p = the 3x3 binomial (1 2 1)/4 of
+ *         the variance around p (edges clamped)
+ *   w_n = 1 if both mean normals are 0, 0 if one is, else max(0, cos(n_p, n_q))^sigma_n
+ *   w_z = 1 if either hit fraction is 0, else exp(-|z_p - z_q| / (sigma_z (g_p |o| + 1e-3 z_p) + 1e-6)), g_p = half the
+ *         larger central difference of depth at p (edges clamped), |o| = 2^k sqrt(dx^2 + dy^2)
+ *   w_a = exp(-|a_p - a_q| / sigma_a)
+ * c'_p = sum w c_q / sum w, var'_p = sum w^2 var_q / (sum w)^2.  The filter computes in float32 with no atomics and a fixed tap
+ * order: the same inputs give the same bits.  Its ping-pong buffers are context-owned device memory, grown on demand.
+ *   d_linear  H*W*3 reals of real_mode (read as such, then rounded to float); d_aov as above; d_noise H*W floats (se; required)
+ *   outputs   d_out_linear H*W*3 reals of real_mode and / or d_out_rgb8 H*W*3 bytes (the resolve's gamma / clamp / quantise in
+ *             double); either may alias an input.
+ * Options: a field that is 0 takes its default -- iterations 5 (1..8), sigma_l 4, sigma_n 128, sigma_z 1, sigma_a 0.1; negative
+ * or non-finite sigmas, other iteration counts and reserved != 0 give RTK_ERR_INVALID.  opts may be NULL (all defaults).
+ * rtk_denoise is asynchronous on `stream`; rtk_denoise_host (h_linear doubles, F32 rounded; h_out_linear widened) blocks. */
+typedef struct rtk_denoise_opts {
+    int32_t iterations;
+    float sigma_l, sigma_n, sigma_z, sigma_a;
+    int32_t reserved;   /* 0 */
+} rtk_denoise_opts;
+
+int rtk_render_aovs(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, float* d_aov);
+int rtk_render_aovs_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, float* h_aov);
+int rtk_denoise(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const void* d_linear, const float* d_aov, const float* d_noise,
+                const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8, void* stream);
+int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear, const float* h_aov, const float* h_noise,
+                     const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8);
+/* The session's current preview denoised with its own se (per-tile scale and K in adaptive sessions), on the session's stream.
+ * The AOVs of the session's camera and seed are rendered on first use and kept per aov_samples on the session (not in
+ * checkpoints).  Needs n_ranks == 1 and at least 2 full chunks (RTK_ERR_INVALID otherwise).  The session is not changed: later
+ * steps, checkpoints, noise statistics and the finished image are what they would have been.  The _host form blocks and
+ * returns the linear image as doubles. */
+int rtk_progressive_denoise(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8);
+int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8);
+
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and
  * hit-record code as the render kernel.  Host buffers:

@@ -186,6 +186,18 @@ _host_lib = None
 _hip_lib = None
 
 
+class DenoiseOpts(C.Structure):
+    """rtk_denoise_opts (include/rtk.h): a field left 0 takes its default (iterations 5, sigma_l 4, sigma_n 128, sigma_z 1,
+    sigma_a 0.1)."""
+
+    _fields_ = [("iterations", C.c_int32), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float),
+                ("sigma_a", C.c_float), ("reserved", C.c_int32)]
+
+
+def _denoise_opts(iterations: int = 0, sigma_l: float = 0.0, sigma_n: float = 0.0, sigma_z: float = 0.0, sigma_a: float = 0.0) -> DenoiseOpts:
+    return DenoiseOpts(int(iterations), float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a), 0)
+
+
 def host_lib() -> C.CDLL:
     """librtk_host.so: scene construction + flattening (no GPU needed)."""
     global _host_lib
@@ -291,6 +303,14 @@ def hip_lib() -> C.CDLL:
             lib.rtk_adaptive_status.argtypes = [C.c_void_p, C.POINTER(AdaptiveState)]
             lib.rtk_adaptive_tile_samples.argtypes = [C.c_void_p, C.c_void_p]
             lib.rtk_checkpoint_read_adaptive.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AdaptiveOpts), C.c_void_p]
+            lib.rtk_render_aovs.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_int32, C.c_void_p]
+            lib.rtk_render_aovs_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_int32, C.c_void_p]
+            lib.rtk_denoise.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseOpts),
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rtk_denoise_host.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseOpts),
+                                             C.c_void_p, C.c_void_p]
+            lib.rtk_progressive_denoise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]
+            lib.rtk_progressive_denoise_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -569,6 +589,35 @@ class Renderer:
         self._check(self._lib.rtk_debug_get_ray(self._ctx, real_mode, C.byref(cam), seed, n, ijs.ctypes.data, out.ctypes.data, draws.ctypes.data))
         return out, draws
 
+    def aovs(self, cam: Camera, samples: int = 4, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_render_aovs_host: the denoiser's first-hit guide buffers, float32 (H, W, 8) = albedo(3), hit fraction, mean
+        normal(3), depth over ``samples`` primary rays per pixel (the render's own rays for ``seed``)."""
+        import numpy as np
+
+        out = np.zeros((cam.image_height, cam.image_width, 8), np.float32)
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        self._check(self._lib.rtk_render_aovs_host(self._ctx, C.byref(cam), C.byref(opts), int(samples), out.ctypes.data))
+        return out
+
+    def denoise(self, linear, aov, noise, *, real_mode: int = RTK_REAL_F64, iterations: int = 0, sigma_l: float = 0.0, sigma_n: float = 0.0,
+                sigma_z: float = 0.0, sigma_a: float = 0.0):
+        """rtk_denoise_host: the a-trous filter of ``linear`` (H, W, 3; rounded to float32 first when real_mode is F32) guided
+        by ``aov`` (H, W, 8) and the per-pixel standard error ``noise`` (H, W).  Options left 0 take their defaults.
+        Returns (linear float64 (H, W, 3), rgb8 (H, W, 3))."""
+        import numpy as np
+
+        linear = np.ascontiguousarray(linear, np.float64)
+        aov = np.ascontiguousarray(aov, np.float32)
+        noise = np.ascontiguousarray(noise, np.float32)
+        h, w = linear.shape[:2]
+        if linear.shape != (h, w, 3) or aov.shape != (h, w, 8) or noise.shape != (h, w):
+            raise ValueError(f"denoise: shapes {linear.shape}, {aov.shape}, {noise.shape} do not describe one (H, W) image")
+        out, rgb8 = np.zeros((h, w, 3)), np.zeros((h, w, 3), np.uint8)
+        opts = _denoise_opts(iterations, sigma_l, sigma_n, sigma_z, sigma_a)
+        self._check(self._lib.rtk_denoise_host(self._ctx, w, h, real_mode, linear.ctypes.data, aov.ctypes.data, noise.ctypes.data, C.byref(opts),
+                                               out.ctypes.data, rgb8.ctypes.data))
+        return out, rgb8
+
     def progressive(self, cam: Camera, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
                     stream: int = 0, rel_target: float | None = None, min_samples: int | None = None) -> "Progressive":
         """rtk_progressive_create: a session that renders the frame of ``cam`` (samples_per_pixel = the target) in steps.
@@ -691,6 +740,17 @@ class Progressive:
         keep = tiles < tx * ty
         grid[tiles[keep]] = spp[keep]
         return np.repeat(np.repeat(grid.reshape(ty, tx), 8, 0), 8, 1)[: self.height, : self.width].copy()
+
+    def denoised(self, aov_samples: int = 4, **opts):
+        """rtk_progressive_denoise_host: the current preview denoised with the session's own noise estimate (needs two full
+        chunks; one rank).  ``opts``: iterations, sigma_l, sigma_n, sigma_z, sigma_a (0 = default).  The session is not
+        changed.  Returns (linear float64 (H, W, 3), rgb8 (H, W, 3))."""
+        import numpy as np
+
+        out, rgb8 = np.zeros((self.height, self.width, 3)), np.zeros((self.height, self.width, 3), np.uint8)
+        o = _denoise_opts(**opts)
+        self._check(self._lib.rtk_progressive_denoise_host(self._h, int(aov_samples), C.byref(o), out.ctypes.data, rgb8.ctypes.data))
+        return out, rgb8
 
     def save(self) -> bytes:
         n = self._lib.rtk_progressive_checkpoint_bytes(self._h)

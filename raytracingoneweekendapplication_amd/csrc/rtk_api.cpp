@@ -989,6 +989,9 @@ struct rtk_ctx {
     hipStream_t progress_stream = nullptr;
     unsigned int* progress_word = nullptr;  // pinned host memory, one word per pass
     bool progress_pending = false;
+    // The denoiser's ping-pong colour / variance buffers (rtk_denoise), grown on demand.
+    void* d_denoise = nullptr;
+    size_t denoise_bytes = 0;
 };
 // Sample chunks per launch: the partial-sum workspace holds up to this many planes [local tile][3][64] at 1920x1080 f64 (+ one
 // for the running sum of a frame that needs several launches): 21 + 1 planes = 1.09 GB, where the 63 chunks of a 1000-spp
@@ -1178,6 +1181,7 @@ int rtk_destroy(rtk_ctx* ctx) {
     if (ctx->tile_counters) (void)hipFree(ctx->tile_counters);
     if (ctx->d_cameras) (void)hipFree(ctx->d_cameras);
     if (ctx->d_partial) (void)hipFree(ctx->d_partial);
+    if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
     if (ctx->d_tile_cost) (void)hipFree(ctx->d_tile_cost);
     if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
     if (ctx->progress_stream) (void)hipStreamDestroy(ctx->progress_stream);
@@ -1734,6 +1738,35 @@ hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst) {
 }
 
 size_t camera_record_bytes() { return kCameraStride; }
+
+template <typename real>
+const SceneView<real>& ctx_view(const rtk_ctx* ctx) {
+    if constexpr (std::is_same_v<real, double>) return ctx->scene64.view;
+    else return ctx->scene32.view;
+}
+template const SceneView<double>& ctx_view<double>(const rtk_ctx*);
+template const SceneView<float>& ctx_view<float>(const rtk_ctx*);
+
+template <typename real>
+CameraRec<real> device_camera(const rtk_camera& cam) { return to_device_camera<real>(cam); }
+template CameraRec<double> device_camera<double>(const rtk_camera&);
+template CameraRec<float> device_camera<float>(const rtk_camera&);
+
+hipError_t denoise_workspace(rtk_ctx* ctx, size_t bytes, void** out) {
+    hipError_t e = hipSuccess;
+    if (bytes > ctx->denoise_bytes) {
+        if (ctx->d_denoise) {
+            if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+            if ((e = hipFree(ctx->d_denoise)) != hipSuccess) return e;
+            ctx->d_denoise = nullptr;
+            ctx->denoise_bytes = 0;
+        }
+        if ((e = hipMalloc(&ctx->d_denoise, bytes)) != hipSuccess) return e;
+        ctx->denoise_bytes = bytes;
+    }
+    *out = ctx->d_denoise;
+    return e;
+}
 
 hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
                          const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial) {

@@ -1,0 +1,333 @@
+// rtk_denoise.hip -- the entry points of the AOV pass (its kernel, rtk_aov_kernel, shares the traversal of rtk_trace.hip) and
+// the variance-guided edge-avoiding a-trous filter of include/rtk.h ("Denoiser"): Dammertz et al. 2010
+// with the luminance weight of SVGF (Schied et al. 2017), spatial part only.  Hand-written HIP for gfx950, wave64.
+//
+// Layout.  Every pixel carries its colour and variance as one float4 {r, g, b, var} (the context's ping-pong buffers) and its
+// guides as the two float4s rtk_render_aovs writes, {albedo, hit fraction} and {mean normal, depth}: a tap is three 16-byte
+// loads.  One lane per pixel, one wave per 8x8 tile (the render's tile convention), four tiles per 256-thread block.  The 5x5
+// taps of a wave cover at most (8 + 4 * step)^2 pixels, which the vector L1 / L2 serve; nothing is staged in LDS.
+//
+// Determinism.  No atomics, a fixed tap order (dy outer, dx inner) and f32 arithmetic throughout: the same inputs give the same
+// bits on every run.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "rtk.h"
+#include "rtk_internal.h"
+#include "rtk_trace.h"
+
+#define RTK_HIP(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+namespace rtk {
+namespace {
+
+#define RTK_DN __device__ __forceinline__
+
+// The resolve's byte conversion (rtk_trace.hip, to_byte; Camera.txt:29-34,77-83), in double.
+RTK_DN uint8_t denoise_byte(double x) {
+    double g = x > 0 ? __builtin_sqrt(x) : 0.0;
+    g = g < 0.000 ? 0.000 : (g > 0.999 ? 0.999 : g);
+    return uint8_t(int(255.999 * g));
+}
+
+struct DenoiseParams {
+    int width, height, tiles_x, n_tiles;
+    float sigma_l, sigma_n, sigma_z, sigma_a;
+};
+
+// Lane -> pixel: wave w of the grid is tile w (row-major over tiles_x), lane l its pixel (l & 7, l >> 3).  False outside.
+RTK_DN bool lane_pixel(const DenoiseParams& P, int& i, int& j) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int tile = int(gid >> 6), pix = int(gid & 63);
+    if (tile >= P.n_tiles) return false;
+    i = (tile % P.tiles_x) * 8 + (pix & 7);
+    j = (tile / P.tiles_x) * 8 + (pix >> 3);
+    return i < P.width && j < P.height;
+}
+
+// {colour, se^2} of the input image, the colour read as `real` and rounded to float.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_denoise_pack_kernel(DenoiseParams P, const real* __restrict__ linear, const float* __restrict__ noise,
+                                                                float4* __restrict__ cv) {
+    int i, j;
+    if (!lane_pixel(P, i, j)) return;
+    const size_t px = size_t(j) * P.width + i;
+    const float se = noise[px];
+    cv[px] = make_float4(float(linear[px * 3]), float(linear[px * 3 + 1]), float(linear[px * 3 + 2]), se * se);
+}
+
+RTK_DN int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+RTK_DN float luminance(float4 c) { return (c.x + c.y + c.z) / 3.0f; }
+
+// One a-trous iteration with taps 2^k apart.  A final iteration (out_cv null) writes the colour as `real` and / or bytes.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_denoise_step_kernel(DenoiseParams P, int step, const float4* __restrict__ cv, const float4* __restrict__ aov,
+                                                                float4* __restrict__ out_cv, real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8) {
+    int i, j;
+    if (!lane_pixel(P, i, j)) return;
+    const int W = P.width, H = P.height;
+    const size_t px = size_t(j) * W + i;
+    const float4 cp = cv[px];
+    const float4 ap = aov[px * 2], gp = aov[px * 2 + 1];  // {albedo, hit}, {normal, depth}
+    // gv_p: 3x3 binomial (1 2 1)/4 x (1 2 1)/4 of the variance, edges clamped
+    const float bw[3] = {0.25f, 0.5f, 0.25f};
+    float gv = 0.0f;
+    for (int b = -1; b <= 1; b++) {
+        const size_t row = size_t(clampi(j + b, 0, H - 1)) * W;
+        for (int a = -1; a <= 1; a++) gv += bw[b + 1] * bw[a + 1] * cv[row + clampi(i + a, 0, W - 1)].w;
+    }
+    // depth gradient: half the larger central difference, edges clamped
+    const float zx = fabsf(aov[(size_t(j) * W + clampi(i + 1, 0, W - 1)) * 2 + 1].w - aov[(size_t(j) * W + clampi(i - 1, 0, W - 1)) * 2 + 1].w);
+    const float zy = fabsf(aov[(size_t(clampi(j + 1, 0, H - 1)) * W + i) * 2 + 1].w - aov[(size_t(clampi(j - 1, 0, H - 1)) * W + i) * 2 + 1].w);
+    const float grad = (zx > zy ? zx : zy) / 2.0f;
+    const float yp = luminance(cp);
+    const float l_den = P.sigma_l * sqrtf(gv > 0.0f ? gv : 0.0f) + 1e-6f;
+    const bool np_zero = gp.x == 0.0f && gp.y == 0.0f && gp.z == 0.0f;
+    const float np_len = sqrtf(gp.x * gp.x + gp.y * gp.y + gp.z * gp.z);
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qj = j + step * dy;
+        if (qj < 0 || qj >= H) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qi = i + step * dx;
+            if (qi < 0 || qi >= W) continue;
+            const size_t q = size_t(qj) * W + qi;
+            const float4 cq = cv[q];
+            const float4 aq = aov[q * 2], gq = aov[q * 2 + 1];
+            const float wl = __expf(-fabsf(yp - luminance(cq)) / l_den);
+            const bool nq_zero = gq.x == 0.0f && gq.y == 0.0f && gq.z == 0.0f;
+            float wn;
+            if (np_zero || nq_zero) {
+                wn = np_zero && nq_zero ? 1.0f : 0.0f;
+            } else {
+                const float c = (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z) / (np_len * sqrtf(gq.x * gq.x + gq.y * gq.y + gq.z * gq.z));
+                wn = c > 0.0f ? __powf(c, P.sigma_n) : 0.0f;
+            }
+            float wz = 1.0f;
+            if (ap.w != 0.0f && aq.w != 0.0f) {
+                const float o = float(step) * sqrtf(float(dx * dx + dy * dy));
+                wz = __expf(-fabsf(gp.w - gq.w) / (P.sigma_z * (grad * o + 1e-3f * gp.w) + 1e-6f));
+            }
+            const float ex = ap.x - aq.x, ey = ap.y - aq.y, ez = ap.z - aq.z;
+            const float wa = __expf(-sqrtf(ex * ex + ey * ey + ez * ez) / P.sigma_a);
+            const float w = h[dx + 2] * h[dy + 2] * wl * wn * wz * wa;
+            sw += w;
+            sr += w * cq.x;
+            sg += w * cq.y;
+            sb += w * cq.z;
+            sv += w * w * cq.w;
+        }
+    }
+    const float r = sr / sw, g = sg / sw, b = sb / sw;
+    if (out_cv) {
+        out_cv[px] = make_float4(r, g, b, sv / (sw * sw));
+        return;
+    }
+    if (out_linear) {
+        out_linear[px * 3] = real(r);
+        out_linear[px * 3 + 1] = real(g);
+        out_linear[px * 3 + 2] = real(b);
+    }
+    if (out_rgb8) {
+        out_rgb8[px * 3] = denoise_byte(double(r));
+        out_rgb8[px * 3 + 1] = denoise_byte(double(g));
+        out_rgb8[px * 3 + 2] = denoise_byte(double(b));
+    }
+}
+
+template <typename real>
+hipError_t launch_denoise(const DenoiseParams& P, int iterations, const void* linear, const float* noise, const float4* aov, float4* ping, float4* pong,
+                          void* out_linear, uint8_t* out_rgb8, hipStream_t stream) {
+    const dim3 grid((P.n_tiles + 3) / 4), block(256);
+    rtk_denoise_pack_kernel<real><<<grid, block, 0, stream>>>(P, static_cast<const real*>(linear), noise, ping);
+    hipError_t e = hipGetLastError();
+    for (int k = 0; k < iterations && e == hipSuccess; k++) {
+        const bool last = k == iterations - 1;
+        rtk_denoise_step_kernel<real><<<grid, block, 0, stream>>>(P, 1 << k, ping, aov, last ? nullptr : pong, last ? static_cast<real*>(out_linear) : nullptr,
+                                                                  last ? out_rgb8 : nullptr);
+        e = hipGetLastError();
+        float4* t = ping;
+        ping = pong;
+        pong = t;
+    }
+    return e;
+}
+
+// The options with defaults for 0 fields; false (and the reason in g_error) when they are out of range.
+bool resolve_opts(const rtk_denoise_opts* in, int& iterations, DenoiseParams& P, const char* who) {
+    rtk_denoise_opts o{};
+    if (in) o = *in;
+    iterations = o.iterations == 0 ? 5 : o.iterations;
+    if (iterations < 1 || iterations > 8) {
+        fail(RTK_ERR_INVALID, "%s: iterations %d out of range (1..8, 0 = 5)", who, o.iterations);
+        return false;
+    }
+    const float s[4] = {o.sigma_l, o.sigma_n, o.sigma_z, o.sigma_a};
+    for (float v : s)
+        if (!(v >= 0.0f) || v > 3.0e38f) {
+            fail(RTK_ERR_INVALID, "%s: sigmas must be finite and >= 0 (0 = default)", who);
+            return false;
+        }
+    if (o.reserved != 0) {
+        fail(RTK_ERR_INVALID, "%s: reserved must be 0", who);
+        return false;
+    }
+    P.sigma_l = o.sigma_l == 0.0f ? 4.0f : o.sigma_l;
+    P.sigma_n = o.sigma_n == 0.0f ? 128.0f : o.sigma_n;
+    P.sigma_z = o.sigma_z == 0.0f ? 1.0f : o.sigma_z;
+    P.sigma_a = o.sigma_a == 0.0f ? 0.1f : o.sigma_a;
+    return true;
+}
+
+}  // namespace
+
+int check_denoise_opts(const rtk_denoise_opts* opts, const char* who) {
+    DenoiseParams P{};
+    int iterations = 0;
+    return resolve_opts(opts, iterations, P, who) ? RTK_OK : RTK_ERR_INVALID;
+}
+
+}  // namespace rtk
+
+using namespace rtk;
+
+extern "C" {
+
+int rtk_render_aovs(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, float* d_aov) {
+    if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_aovs: null argument");
+    uint64_t digest = 0;
+    if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "rtk_render_aovs: no scene uploaded");
+    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->image_width > 65536 || cam->image_height > 65536)
+        return fail(RTK_ERR_INVALID, "rtk_render_aovs: bad camera dimensions");
+    if (opts->n_ranks != 1) return fail(RTK_ERR_INVALID, "rtk_render_aovs: whole images only (n_ranks must be 1, not %d)", opts->n_ranks);
+    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_render_aovs: unknown real_mode %d", opts->real_mode);
+    if (n_samples <= 0) return fail(RTK_ERR_INVALID, "rtk_render_aovs: n_samples must be positive (%d)", n_samples);
+    if (!d_aov) return fail(RTK_ERR_INVALID, "rtk_render_aovs: null output buffer");
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    const hipStream_t st = static_cast<hipStream_t>(opts->stream);
+    const hipError_t e = opts->real_mode == RTK_REAL_F64 ? launch_aov<double>(ctx_view<double>(ctx), device_camera<double>(*cam), opts->seed, n_samples, d_aov, st)
+                                                         : launch_aov<float>(ctx_view<float>(ctx), device_camera<float>(*cam), opts->seed, n_samples, d_aov, st);
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_render_aovs: %s", hipGetErrorString(e));
+    return RTK_OK;
+}
+
+int rtk_render_aovs_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, float* h_aov) {
+    if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_aovs_host: null argument");
+    if (!h_aov) return fail(RTK_ERR_INVALID, "rtk_render_aovs_host: null output buffer");
+    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->image_width > 65536 || cam->image_height > 65536)
+        return fail(RTK_ERR_INVALID, "rtk_render_aovs_host: bad camera dimensions");
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    const size_t n = size_t(cam->image_width) * cam->image_height * 8;
+    float* d_aov = nullptr;
+    RTK_HIP(hipMalloc(reinterpret_cast<void**>(&d_aov), n * sizeof(float)));
+    int rc = rtk_render_aovs(ctx, cam, opts, n_samples, d_aov);
+    if (rc == RTK_OK) {
+        hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
+        if (e == hipSuccess) e = hipMemcpy(h_aov, d_aov, n * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RTK_ERR_HIP, "rtk_render_aovs_host: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(d_aov);
+    return rc;
+}
+
+int rtk_denoise(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const void* d_linear, const float* d_aov, const float* d_noise,
+                const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8, void* stream) {
+    if (!ctx) return fail(RTK_ERR_INVALID, "rtk_denoise: null context");
+    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise: bad image size %dx%d", width, height);
+    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise: unknown real_mode %d", real_mode);
+    if (!d_linear || !d_aov || !d_noise) return fail(RTK_ERR_INVALID, "rtk_denoise: d_linear, d_aov and d_noise are required");
+    if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise: no output");
+    DenoiseParams P{};
+    int iterations = 0;
+    if (!resolve_opts(opts, iterations, P, "rtk_denoise")) return RTK_ERR_INVALID;
+    P.width = width;
+    P.height = height;
+    P.tiles_x = (width + 7) / 8;
+    P.n_tiles = P.tiles_x * ((height + 7) / 8);
+    hipError_t e = hipSetDevice(ctx_device(ctx));
+    void* ws = nullptr;
+    const size_t plane = size_t(width) * height * sizeof(float4);
+    if (e == hipSuccess) e = denoise_workspace(ctx, 2 * plane, &ws);
+    if (e == hipSuccess) {
+        float4* ping = static_cast<float4*>(ws);
+        float4* pong = reinterpret_cast<float4*>(static_cast<char*>(ws) + plane);
+        const auto* aov = reinterpret_cast<const float4*>(d_aov);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        e = real_mode == RTK_REAL_F64 ? launch_denoise<double>(P, iterations, d_linear, d_noise, aov, ping, pong, d_out_linear, d_out_rgb8, st)
+                                      : launch_denoise<float>(P, iterations, d_linear, d_noise, aov, ping, pong, d_out_linear, d_out_rgb8, st);
+    }
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_denoise: %s", hipGetErrorString(e));
+    return RTK_OK;
+}
+
+int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear, const float* h_aov, const float* h_noise,
+                     const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8) {
+    if (!ctx) return fail(RTK_ERR_INVALID, "rtk_denoise_host: null context");
+    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise_host: bad image size %dx%d", width, height);
+    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise_host: unknown real_mode %d", real_mode);
+    if (!h_linear || !h_aov || !h_noise) return fail(RTK_ERR_INVALID, "rtk_denoise_host: h_linear, h_aov and h_noise are required");
+    if (!h_out_linear && !h_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise_host: no output");
+    {
+        DenoiseParams P{};
+        int it = 0;
+        if (!resolve_opts(opts, it, P, "rtk_denoise_host")) return RTK_ERR_INVALID;
+    }
+    hipError_t e = hipSetDevice(ctx_device(ctx));
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_denoise_host: %s", hipGetErrorString(e));
+    const size_t px = size_t(width) * height, elem = real_mode == RTK_REAL_F64 ? 8 : 4;
+    void *d_lin = nullptr, *d_out = nullptr;
+    float *d_aov = nullptr, *d_noise = nullptr;
+    uint8_t* d_rgb8 = nullptr;
+    auto cleanup = [&]() {
+        for (void* d : {d_lin, d_out, static_cast<void*>(d_aov), static_cast<void*>(d_noise), static_cast<void*>(d_rgb8)})
+            if (d) (void)hipFree(d);
+    };
+    std::vector<float> tmp;
+    e = hipMalloc(&d_lin, px * 3 * elem);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_aov), px * 8 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_noise), px * sizeof(float));
+    if (e == hipSuccess && h_out_linear) e = hipMalloc(&d_out, px * 3 * elem);
+    if (e == hipSuccess && h_out_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), px * 3);
+    if (e == hipSuccess) {
+        if (real_mode == RTK_REAL_F64) {
+            e = hipMemcpy(d_lin, h_linear, px * 3 * sizeof(double), hipMemcpyHostToDevice);
+        } else {
+            tmp.resize(px * 3);
+            for (size_t k = 0; k < px * 3; k++) tmp[k] = float(h_linear[k]);
+            e = hipMemcpy(d_lin, tmp.data(), px * 3 * sizeof(float), hipMemcpyHostToDevice);
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpy(d_aov, h_aov, px * 8 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_noise, h_noise, px * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        cleanup();
+        return fail(RTK_ERR_HIP, "rtk_denoise_host: device buffers: %s", hipGetErrorString(e));
+    }
+    int rc = rtk_denoise(ctx, width, height, real_mode, d_lin, d_aov, d_noise, opts, d_out, d_rgb8, nullptr);
+    if (rc != RTK_OK) {
+        cleanup();
+        return rc;
+    }
+    e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess && h_out_linear) {
+        if (real_mode == RTK_REAL_F64) {
+            e = hipMemcpy(h_out_linear, d_out, px * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        } else {
+            e = hipMemcpy(tmp.data(), d_out, px * 3 * sizeof(float), hipMemcpyDeviceToHost);
+            for (size_t k = 0; k < px * 3; k++) h_out_linear[k] = double(tmp[k]);
+        }
+    }
+    if (e == hipSuccess && h_out_rgb8) e = hipMemcpy(h_out_rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_denoise_host: %s", hipGetErrorString(e));
+    return RTK_OK;
+}
+
+}  // extern "C"

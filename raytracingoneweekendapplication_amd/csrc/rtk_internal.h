@@ -47,6 +47,18 @@ hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst);  //
 hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
                          const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial);
 
+// The uploaded scene's device view per arithmetic type, and a camera's device record (for the AOV pass, rtk_denoise.hip).
+template <typename real>
+const SceneView<real>& ctx_view(const rtk_ctx* ctx);
+template <typename real>
+CameraRec<real> device_camera(const rtk_camera& cam);
+
+// The denoiser's ping-pong buffers: context-owned device memory of at least `bytes`, grown on demand (apart from the render's
+// partial-sum workspace).  Growing waits for the device: earlier launches may still read the old buffers.
+hipError_t denoise_workspace(rtk_ctx* ctx, size_t bytes, void** out);
+// RTK_OK, or RTK_ERR_INVALID with the reason in g_error, for rtk_denoise_opts out of range (null = every default).
+int check_denoise_opts(const rtk_denoise_opts* opts, const char* who);
+
 // Block until streams[i] (on ctxs[i]'s device) has drained, i = 0..n-1, feeding ctxs[0]'s progress callback
 // (rtk_set_progress_callback) from the work-item counters of the launches in flight.
 int wait_with_progress(rtk_ctx* const* ctxs, const hipStream_t* streams, int n);

@@ -54,6 +54,11 @@ struct rtk_progressive {
     int32_t* d_tile_spp = nullptr;
     int32_t* d_list = nullptr;          // [n_tiles_local] + the count behind it
     bool list_valid = false;
+    // rtk_progressive_denoise: the AOVs of the session's camera and seed per sample count (never in checkpoints) and the
+    // preview / se it rebuilds from the sums
+    std::vector<std::pair<int, float*>> aovs;
+    void* d_preview = nullptr;          // H*W*3 reals
+    float* d_preview_se = nullptr;      // H*W
     int full_chunks() const { return done / chunk; }  // every chunk before the target's end is full
     size_t n_slots() const { return size_t(tm.n_tiles_local) * 64; }
 };
@@ -93,6 +98,9 @@ void release(rtk_progressive* p) {
                     static_cast<void*>(p->d_order), static_cast<void*>(p->d_stats), static_cast<void*>(p->d_active), static_cast<void*>(p->d_tile_spp),
                     static_cast<void*>(p->d_list)})
         if (d) (void)hipFree(d);
+    for (auto& a : p->aovs) (void)hipFree(a.second);
+    if (p->d_preview) (void)hipFree(p->d_preview);
+    if (p->d_preview_se) (void)hipFree(p->d_preview_se);
     delete p;
 }
 
@@ -584,6 +592,74 @@ int rtk_progressive_destroy(rtk_progressive* p) {
     (void)hipSetDevice(ctx_device(p->ctx));
     (void)hipStreamSynchronize(p->stream);  // launches in flight still read the session's buffers
     release(p);
+    return RTK_OK;
+}
+
+int rtk_progressive_denoise(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8) {
+    int rc = usable(p, "rtk_progressive_denoise");
+    if (rc != RTK_OK) return rc;
+    if (p->n_ranks != 1) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: whole images only (n_ranks must be 1, not %d)", p->n_ranks);
+    if (aov_samples <= 0) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: aov_samples must be positive (%d)", aov_samples);
+    if (p->full_chunks() < 2)
+        return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: the noise estimate needs 2 full chunks in every tile (%d samples done, chunk %d)", p->done, p->chunk);
+    if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: no output");
+    if ((rc = check_denoise_opts(opts, "rtk_progressive_denoise")) != RTK_OK) return rc;
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    const int W = p->cam.image_width, H = p->cam.image_height;
+    const size_t px = size_t(W) * H;
+    float* aov = nullptr;
+    for (auto& a : p->aovs)
+        if (a.first == aov_samples) aov = a.second;
+    if (!aov) {
+        RTK_HIP(hipMalloc(reinterpret_cast<void**>(&aov), px * 8 * sizeof(float)));
+        const rtk_render_opts ro{p->seed, p->real_mode, 0, 1, 0, 0, p->stream};
+        if ((rc = rtk_render_aovs(p->ctx, &p->cam, &ro, aov_samples, aov)) != RTK_OK) {
+            (void)hipFree(aov);
+            return rc;
+        }
+        p->aovs.emplace_back(aov_samples, aov);
+    }
+    if (!p->d_preview) RTK_HIP(hipMalloc(&p->d_preview, px * 3 * p->elem));
+    if (!p->d_preview_se) RTK_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_preview_se), px * sizeof(float)));
+    const int32_t* spp = p->adaptive ? p->d_tile_spp : nullptr;
+    RTK_HIP(p->real_mode == RTK_REAL_F64
+                ? launch_preview<double>(p->d_sum, p->d_s1, p->d_s2, p->tm, W, H, p->chunk, p->done, spp, p->d_preview, p->d_preview_se, p->stream)
+                : launch_preview<float>(p->d_sum, p->d_s1, p->d_s2, p->tm, W, H, p->chunk, p->done, spp, p->d_preview, p->d_preview_se, p->stream));
+    return rtk_denoise(p->ctx, W, H, p->real_mode, p->d_preview, aov, p->d_preview_se, opts, d_out_linear, d_out_rgb8, p->stream);
+}
+
+int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, double* h_linear, uint8_t* h_rgb8) {
+    int rc = usable(p, "rtk_progressive_denoise_host");
+    if (rc != RTK_OK) return rc;
+    if (p->n_ranks != 1) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise_host: whole images only (n_ranks must be 1, not %d)", p->n_ranks);
+    if (!h_linear && !h_rgb8) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise_host: no output");
+    RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
+    const size_t n = size_t(p->cam.image_width) * p->cam.image_height * 3;
+    void* d_linear = nullptr;
+    uint8_t* d_rgb8 = nullptr;
+    hipError_t e = hipSuccess;
+    if (h_linear) e = hipMalloc(&d_linear, n * p->elem);
+    if (e == hipSuccess && h_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), n);
+    if (e == hipSuccess) {
+        rc = rtk_progressive_denoise(p, aov_samples, opts, d_linear, d_rgb8);
+        if (rc == RTK_OK) {
+            e = hipStreamSynchronize(p->stream);
+            if (e == hipSuccess && h_linear) {
+                if (p->real_mode == RTK_REAL_F64) {
+                    e = hipMemcpy(h_linear, d_linear, n * sizeof(double), hipMemcpyDeviceToHost);
+                } else {
+                    std::vector<float> tmp(n);
+                    e = hipMemcpy(tmp.data(), d_linear, n * sizeof(float), hipMemcpyDeviceToHost);
+                    for (size_t k = 0; k < n; k++) h_linear[k] = double(tmp[k]);
+                }
+            }
+            if (e == hipSuccess && h_rgb8) e = hipMemcpy(h_rgb8, d_rgb8, n, hipMemcpyDeviceToHost);
+        }
+    }
+    if (d_linear) (void)hipFree(d_linear);
+    if (d_rgb8) (void)hipFree(d_rgb8);
+    if (rc != RTK_OK) return rc;
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_progressive_denoise_host: %s", hipGetErrorString(e));
     return RTK_OK;
 }
 

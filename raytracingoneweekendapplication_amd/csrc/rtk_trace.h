@@ -74,6 +74,16 @@ hipError_t launch_debug_texture(const SceneView<real>& sc, int n, const int32_t*
 template <typename real>
 hipError_t launch_debug_get_ray(const CameraRec<real>& cam, uint32_t seed, int n, const int32_t* d_ijs, double* d_out, unsigned long long* d_draws, hipStream_t stream);
 
+// Guide buffers of the denoiser: aov[(j * W + i) * 8 + k] over samples 0 .. n_samples - 1 of every pixel (rtk_render_aovs).
+template <typename real>
+hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream);
+
+// A one-rank progressive session's preview and se (row-major) from its running sum and noise sums; tile_spp null = every tile
+// holds `done` samples.  Reads the state only.
+template <typename real>
+hipError_t launch_preview(const void* acc, const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, int done,
+                          const int32_t* tile_spp, void* out_linear, float* out_noise, hipStream_t stream);
+
 template <typename real>
 hipError_t launch_unpermute(const void* gathered, int width, int height, int n_ranks, long long tiles_per_rank, void* out_linear, uint8_t* out_rgb8,
                             hipStream_t stream);

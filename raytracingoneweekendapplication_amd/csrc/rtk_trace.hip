@@ -2295,6 +2295,29 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
     }
 }
 
+// hittable::hit of the scene root on the query interval L.tmin .. L.best_t (set up by begin_segment<true>): the slot program
+// walked one lane at a time, with every record kind and the tie table (inert for reference-order uploads).  L.best_pc /
+// L.best_t hold the winner.  The known-answer entry point and the AOV pass share it.
+template <typename real, bool COUNT>
+RTK_DEV void closest_hit_slots(Lane<real>& L, const SceneView<real>& sc, Counters<COUNT>& cnt) {
+    const Slot<real>* prog = sc.program;
+    auto kind_of = [&](uint32_t pc) -> uint32_t { return prog[pc].kind_payload & 15u; };
+    const TieCtx<true, decltype(kind_of)> tie{sc.tie_rank_slot, kind_of};  // inert (null table) for reference-order uploads
+    for (;;) {
+        const Slot<real>* rec = prog + L.pc;
+        const uint32_t kind = rec->kind_payload & 15u;
+        if (kind == OP_END) break;
+        if (kind == OP_BOX) {
+            if (L.box_kind == OP_BOX) step_box<false, true>(L, *rec, cnt);
+            else step_box<true, true>(L, *rec, cnt);
+        } else if (kind == OP_SPHERE) {
+            step_sphere<true>(L, *rec, cnt, tie);
+        } else {
+            step_other<real, kFeatAll>(L, rec, sc, cnt, tie);
+        }
+    }
+}
+
 // Known-answer entry point (tests): hittable::hit(r, interval(tmin, tmax), rec) of the uploaded scene's
 // root for caller-supplied rays, one lane per ray, lock-step over the traversal program.  Exercises the same
 // step_* / make_surface code as the render kernel.  out[12] = hit, t, p(3), normal(3), front_face, u, v, material.
@@ -2316,22 +2339,8 @@ __global__ __launch_bounds__(256) void rtk_debug_hit_kernel(SceneView<real> sc, 
     begin_segment<true>(L, cnt);
     L.tmin = real(r[7]);
     L.best_t = real(r[8]);
+    closest_hit_slots(L, sc, cnt);
     const Slot<real>* prog = sc.program;
-    auto kind_of = [&](uint32_t pc) -> uint32_t { return prog[pc].kind_payload & 15u; };
-    const TieCtx<true, decltype(kind_of)> tie{sc.tie_rank_slot, kind_of};  // inert (null table) for reference-order uploads
-    for (;;) {
-        const Slot<real>* rec = prog + L.pc;
-        const uint32_t kind = rec->kind_payload & 15u;
-        if (kind == OP_END) break;
-        if (kind == OP_BOX) {
-            if (L.box_kind == OP_BOX) step_box<false, true>(L, *rec, cnt);
-            else step_box<true, true>(L, *rec, cnt);
-        } else if (kind == OP_SPHERE) {
-            step_sphere<true>(L, *rec, cnt, tie);
-        } else {
-            step_other<real, kFeatAll>(L, rec, sc, cnt, tie);
-        }
-    }
     double* o = out + size_t(gid) * 12;
     for (int k = 0; k < 12; k++) o[k] = 0.0;
     o[11] = -1.0;
@@ -2426,6 +2435,70 @@ __global__ __launch_bounds__(256) void rtk_debug_get_ray_kernel(CameraRec<real> 
     o[3] = double(L.rd.x); o[4] = double(L.rd.y); o[5] = double(L.rd.z);
     o[6] = double(L.tm);
     draws[gid] = cnt.c[C_RNG];
+}
+
+// First-hit guide buffers (AOVs) of the denoiser (include/rtk.h, rtk_render_aovs): one lane per pixel, a 256-thread block is
+// four 8x8 tiles (the render's tile convention).  Sample s of pixel (i, j) takes the render's primary ray -- begin_sample with
+// the render's seed, bit for bit -- then re-seeds its stream with keys (seed, pixel, s + 2^31), as rtk_debug_closest_hit does,
+// so a constant medium never draws the render's numbers, and finds world.hit(r, interval(0.001, inf)) (Camera.txt:211) with
+// the known-answer traversal.  Sums run in `real` in sample order and are divided by their count once:
+//   aov[px][0..2] albedo: miss -> background clamped to [0, 1]; lambertian / isotropic -> texture::value; metal / specular ->
+//                 albedo; dielectric -> 1; diffuse_light -> min(1, texture::value)    (mean over n)
+//   aov[px][3]    hits / n (medium hits count)
+//   aov[px][4..6] sum over hits of the record's normal (isotropic hits add 0) / n
+//   aov[px][7]    mean over hits of t * |rd| (0 without hits)
+template <typename real>
+RTK_DEV real clamp01(real x) { return x < real(0) ? real(0) : (x > real(1) ? real(1) : x); }
+
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_aov_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, int n_samples, int tiles_x, int n_tiles,
+                                                       float4* __restrict__ aov) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int tile = int(gid >> 6), pix = int(gid & 63);
+    if (tile >= n_tiles) return;
+    const int i = (tile % tiles_x) * 8 + (pix & 7), j = (tile / tiles_x) * 8 + (pix >> 3);
+    if (i >= cam.width || j >= cam.height) return;
+    Counters<false> cnt;
+    const uint32_t seed_hash = pcg_hash(seed);
+    const uint32_t pixel = uint32_t(j * cam.width + i);
+    const V3<real> zero = mk(real(0), real(0), real(0));
+    V3<real> albedo = zero, normal = zero;
+    real hits = real(0), depth = real(0);
+    for (int s = 0; s < n_samples; s++) {
+        Lane<real> L;
+        L.s = s;
+        L.segs = 0;
+        begin_sample(L, cam, i, j, seed_hash, cnt);
+        L.rng = pcg_hash(pixel + pcg_hash(uint32_t(s) + 0x80000000u + seed_hash));
+        L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
+        L.sv_best_pc = kNoHit;
+        begin_segment<true>(L, cnt);
+        closest_hit_slots(L, sc, cnt);
+        if (L.best_pc == kNoHit) {
+            albedo = albedo + mk(clamp01(cam.background[0]), clamp01(cam.background[1]), clamp01(cam.background[2]));
+            continue;
+        }
+        Surface<real> sf;
+        make_surface<real, kFeatAll>(sc.program, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
+        const MaterialRec<real>& m = sc.materials[sf.material];
+        V3<real> a = mk(real(1), real(1), real(1));  // dielectric
+        if (m.kind == RTK_MAT_LAMBERTIAN || m.kind == RTK_MAT_ISOTROPIC) {
+            a = material_color<real, kFeatAll>(sc, m, sf.u, sf.v, sf.p, cnt);
+        } else if (m.kind == RTK_MAT_METAL || m.kind == RTK_MAT_SPECULAR) {
+            a = ld3(m.albedo);
+        } else if (m.kind == RTK_MAT_DIFFUSE_LIGHT) {
+            const V3<real> e = material_color<real, kFeatAll>(sc, m, sf.u, sf.v, sf.p, cnt);
+            a = mk(e.x > real(1) ? real(1) : e.x, e.y > real(1) ? real(1) : e.y, e.z > real(1) ? real(1) : e.z);
+        }
+        albedo = albedo + a;
+        hits = hits + real(1);
+        if (m.kind != RTK_MAT_ISOTROPIC) normal = normal + sf.normal;
+        depth = depth + L.best_t * rt_sqrt(length_squared(L.rd));
+    }
+    const real n = real(n_samples);
+    float4* o = aov + (size_t(j) * cam.width + i) * 2;
+    o[0] = make_float4(float(albedo.x / n), float(albedo.y / n), float(albedo.z / n), float(hits / n));
+    o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(depth / hits) : 0.0f);
 }
 
 // Tile order for the NEXT frame: local tiles sorted by the cost measured in this frame, most expensive first
@@ -2620,6 +2693,29 @@ __global__ __launch_bounds__(256) void rtk_accumulate_kernel(const real* __restr
         }
         if (out_noise) out_noise[px] = float(se);
     }
+}
+
+// A progressive session's current preview, rebuilt from its state without changing it (rtk_progressive_denoise): the
+// accumulate kernels' outputs -- the running sum scaled by 1 / the tile's sample count (samples_done, or tile_spp[t] of an
+// adaptive session) and se over that count's full chunks -- row-major, for one rank that renders the whole image.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_preview_kernel(const real* __restrict__ acc, const double* __restrict__ s1, const double* __restrict__ s2,
+                                                           TileMap tmap, int width, int height, int chunk_size, int done, const int32_t* __restrict__ tile_spp,
+                                                           real* __restrict__ out_linear, float* __restrict__ out_noise) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int pix = int(gid & 63);
+    const long long tile = gid >> 6;
+    if (tile >= tmap.n_tiles_local) return;
+    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
+    if (i >= width || j >= height) return;
+    const int spp = tile_spp ? tile_spp[tile] : done;
+    const real* a = acc + size_t(tile) * 192 + pix;
+    const V3<real> sum = scale(real(1.0 / double(spp)), mk(a[0], a[64], a[128]));
+    const size_t px = size_t(j) * width + i;
+    out_linear[px * 3] = sum.x;
+    out_linear[px * 3 + 1] = sum.y;
+    out_linear[px * 3 + 2] = sum.z;
+    out_noise[px] = float(noise_se(s1[size_t(tile) * 64 + pix], s2[size_t(tile) * 64 + pix], spp / chunk_size));
 }
 
 // Frame noise statistics, deterministic (no float atomics): every block reduces its pixels' (se, max se, se / max(mean, 1e-3))
@@ -3333,6 +3429,25 @@ hipError_t launch_debug_get_ray(const CameraRec<real>& cam, uint32_t seed, int n
 }
 template hipError_t launch_debug_get_ray<double>(const CameraRec<double>&, uint32_t, int, const int32_t*, double*, unsigned long long*, hipStream_t);
 template hipError_t launch_debug_get_ray<float>(const CameraRec<float>&, uint32_t, int, const int32_t*, double*, unsigned long long*, hipStream_t);
+
+template <typename real>
+hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream) {
+    const int tiles_x = (cam.width + 7) / 8, n_tiles = tiles_x * ((cam.height + 7) / 8);
+    rtk_aov_kernel<real><<<dim3((n_tiles + 3) / 4), dim3(256), 0, stream>>>(sc, cam, seed, n_samples, tiles_x, n_tiles, reinterpret_cast<float4*>(d_aov));
+    return hipGetLastError();
+}
+template hipError_t launch_aov<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, float*, hipStream_t);
+template hipError_t launch_aov<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, int, float*, hipStream_t);
+
+template <typename real>
+hipError_t launch_preview(const void* acc, const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, int done,
+                          const int32_t* tile_spp, void* out_linear, float* out_noise, hipStream_t stream) {
+    rtk_preview_kernel<real><<<dim3((tmap.n_tiles_local + 3) / 4), dim3(256), 0, stream>>>(static_cast<const real*>(acc), s1, s2, tmap, width, height, chunk_size,
+                                                                                          done, tile_spp, static_cast<real*>(out_linear), out_noise);
+    return hipGetLastError();
+}
+template hipError_t launch_preview<double>(const void*, const double*, const double*, const TileMap&, int, int, int, int, const int32_t*, void*, float*, hipStream_t);
+template hipError_t launch_preview<float>(const void*, const double*, const double*, const TileMap&, int, int, int, int, const int32_t*, void*, float*, hipStream_t);
 
 template <typename real>
 hipError_t launch_unpermute(const void* gathered, int width, int height, int n_ranks, long long tiles_per_rank, void* out_linear, uint8_t* out_rgb8,

@@ -156,6 +156,12 @@ public:
     int last_samples_done = 0;         // ... the samples per pixel in the image it wrote ...
     rtk_noise_stats last_noise{};      // ... and the noise estimate after its last step (valid = 0 before two full chunks)
     rtk_adaptive_state last_adaptive{};  // ... and the tiles' state after it (without adaptive_target every tile is active)
+    // Denoising (rtk_progressive_denoise): denoise_image_name set -> render() also writes the denoised image there as PNG,
+    // guided by aov_samples first-hit samples per pixel.  Without progressive_step the frame is rendered as ONE progressive step
+    // of the whole target, which is bit-identical to the one-shot frame (image_name is unchanged); the noise estimate needs
+    // two full chunks, so a target below that fails with a message.
+    const char* denoise_image_name = nullptr;
+    int aov_samples = 4;
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -277,7 +283,8 @@ public:
         opts.rank = 0;
         opts.n_ranks = 1;
         rtk_ctx* ctx = rtk_multi_ctx(multi, 0);
-        if (rc == RTK_OK && checkpoint_file) {
+        const bool stepped = progressive_step > 0;  // (otherwise one step of the whole target, for denoise_image_name)
+        if (rc == RTK_OK && stepped && checkpoint_file) {
             std::vector<unsigned char> blob;
             if (FILE* f = std::fopen(checkpoint_file, "rb")) {
                 unsigned char buf[65536];
@@ -295,7 +302,7 @@ public:
         }
         if (rc == RTK_OK && !p) {
             rc = rtk_progressive_create(ctx, &cam, &opts, &p);
-            if (rc == RTK_OK && adaptive_target > 0) {
+            if (rc == RTK_OK && stepped && adaptive_target > 0) {
                 rtk_adaptive_opts ad{};
                 ad.rel_target = adaptive_target;
                 ad.min_samples = adaptive_min_samples > 0 ? adaptive_min_samples : 2 * rtk_progressive_chunk_size(p);
@@ -304,10 +311,11 @@ public:
         }
         if (rc == RTK_OK) {
             const int chunk = rtk_progressive_chunk_size(p);
-            const int step = (progressive_step + chunk - 1) / chunk * chunk;
+            const int step = stepped ? (progressive_step + chunk - 1) / chunk * chunk : cam.samples_per_pixel;
             const int start = rtk_progressive_samples_done(p);
             rgb8->assign(size_t(cam.image_width) * cam.image_height * 3, 0);
-            std::vector<unsigned char> blob(checkpoint_file ? size_t(rtk_progressive_checkpoint_bytes(p)) : 0);
+            const char* checkpoint = stepped ? checkpoint_file : nullptr;
+            std::vector<unsigned char> blob(checkpoint ? size_t(rtk_progressive_checkpoint_bytes(p)) : 0);
             auto t0 = std::chrono::steady_clock::now();
             for (int done = start; rc == RTK_OK && done < cam.samples_per_pixel;) {
                 rc = rtk_progressive_step_host(p, std::min(step, cam.samples_per_pixel - done), nullptr, rgb8->data(), nullptr, nullptr);
@@ -315,21 +323,26 @@ public:
                 done = rtk_progressive_samples_done(p);
                 last_samples_done = done;
                 last_samples_rendered = done - start;
-                if (checkpoint_file && (rc = rtk_progressive_save(p, blob.data(), int64_t(blob.size()))) == RTK_OK) {
+                if (checkpoint && (rc = rtk_progressive_save(p, blob.data(), int64_t(blob.size()))) == RTK_OK) {
                     const std::string tmp = std::string(checkpoint_file) + ".tmp";  // replace the old checkpoint only once the new one is whole
                     FILE* f = std::fopen(tmp.c_str(), "wb");
                     const bool ok = f && std::fwrite(blob.data(), 1, blob.size(), f) == blob.size();
                     if (f) std::fclose(f);
                     if (!ok || std::rename(tmp.c_str(), checkpoint_file) != 0) std::cerr << "camera::render: cannot write " << checkpoint_file << std::endl;
                 }
-                if (rc == RTK_OK && write_previews && write_image) rtk::write_png(image_name, cam.image_width, cam.image_height, rgb8->data());
+                if (rc == RTK_OK && stepped && write_previews && write_image) rtk::write_png(image_name, cam.image_width, cam.image_height, rgb8->data());
                 if (rc == RTK_OK && (noise_target > 0 || done >= cam.samples_per_pixel)) rc = rtk_progressive_noise(p, &last_noise);
                 if (rc == RTK_OK) rc = rtk_adaptive_status(p, &last_adaptive);
-                if (rc == RTK_OK && noise_target > 0 && last_noise.valid && last_noise.mean_rel_se <= noise_target) break;
-                if (rc == RTK_OK && adaptive_target > 0 && last_adaptive.active_tiles == 0) break;  // every tile retired
+                if (rc == RTK_OK && stepped && noise_target > 0 && last_noise.valid && last_noise.mean_rel_se <= noise_target) break;
+                if (rc == RTK_OK && stepped && adaptive_target > 0 && last_adaptive.active_tiles == 0) break;  // every tile retired
                 if (show_progress) print_progress(done, cam.samples_per_pixel, nullptr);
             }
             last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (rc == RTK_OK && denoise_image_name) {
+                std::vector<uint8_t> den(rgb8->size());
+                rc = rtk_progressive_denoise_host(p, aov_samples, nullptr, nullptr, den.data());
+                if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
+            }
         }
         if (p) rtk_progressive_destroy(p);
         rtk_multi_destroy(multi);
@@ -345,7 +358,7 @@ public:
     // Camera.txt:54.  Blocking; borrows world and lights for the call.
     void render(const hittable& world, std::vector<point_light>& lights) {
         std::vector<uint8_t> rgb8;
-        int rc = progressive_step > 0 ? render_progressive(world, lights, &rgb8) : render_to(world, lights, nullptr, &rgb8);
+        int rc = progressive_step > 0 || denoise_image_name ? render_progressive(world, lights, &rgb8) : render_to(world, lights, nullptr, &rgb8);
         if (rc != RTK_OK) {
             std::cerr << "camera::render failed: " << rtk_last_error() << std::endl;
             return;
