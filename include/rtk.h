@@ -583,7 +583,8 @@ int rtk_checkpoint_read_adaptive(const void* h_buf, int64_t n, rtk_adaptive_opts
  * order: the same inputs give the same bits.  Its ping-pong buffers are context-owned device memory, grown on demand.
  *   d_linear  H*W*3 reals of real_mode (read as such, then rounded to float); d_aov as above; d_noise H*W floats (se; required)
  *   outputs   d_out_linear H*W*3 reals of real_mode and / or d_out_rgb8 H*W*3 bytes (the resolve's gamma / clamp / quantise in
- *             double); either may alias an input.
+ *             double); either may alias d_linear or d_noise (read once, before the first iteration), but not d_aov: the last
+ *             iteration reads the neighbours' guides from d_aov while it writes the outputs.
  * Options: a field that is 0 takes its default -- iterations 5 (1..8), sigma_l 4, sigma_n 128, sigma_z 1, sigma_a 0.1; negative
  * or non-finite sigmas, other iteration counts and reserved != 0 give RTK_ERR_INVALID.  opts may be NULL (all defaults).
  * rtk_denoise is asynchronous on `stream`; rtk_denoise_host (h_linear doubles, F32 rounded; h_out_linear widened) blocks. */

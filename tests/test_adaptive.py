@@ -1,7 +1,8 @@
 """Tile-adaptive sampling of progressive sessions (rtk_progressive_set_adaptive): a tile retires once the largest relative standard
 error of its pixels is low enough; every pixel of a tile then equals a one-shot render at that tile's own sample count, bit for bit.
 
-CPU tests: the API's declarations and exports, version-2 checkpoints (built field by field here) and argument checks.
+CPU tests: the API's declarations and exports, version-2 checkpoints (built field by field here), argument checks and the
+rel_target picker of the large cases.
 GPU tests (-m gpu): everything that renders."""
 import ctypes as C
 import os
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import EARTH, ROOT
+from tests.test_progressive import _tile_image
 
 ENTRY_POINTS = ("rtk_progressive_set_adaptive", "rtk_adaptive_status", "rtk_adaptive_tile_samples", "rtk_checkpoint_read_adaptive")
 
@@ -170,14 +172,15 @@ def _small_scenes():
 
 
 def _uniform_metrics(renderer, cam, real_mode, step):
-    """A non-adaptive session stepped to the target: per step end s, every tile's retire metric from the checkpoint's exact S1 / S2."""
+    """A non-adaptive session stepped to the target in steps of `step` (the last one may be shorter): per step end s, every tile's
+    retire metric from the checkpoint's exact S1 / S2."""
     w, h, target = cam.image_width, cam.image_height, cam.samples_per_pixel
     tiles = _tiles(w, h, 1)
     inside = _inside(w, h, tiles)
     p = renderer.progressive(cam, real_mode=real_mode)
     metrics = {}
     while p.samples_done < target:
-        p.step(step)
+        p.step(min(step, target - p.samples_done))
         s = p.samples_done
         if s // 8 >= 2:
             s1, s2 = _sums_from_blob(p.save(), tiles, real_mode)
@@ -232,6 +235,52 @@ def _pick_rel_target(metrics, min_samples, target):
     return best
 
 
+def _median_rel_target(metrics, min_samples, target, share=0.1):
+    """_pick_rel_target for thousands of tiles, one replay per try: the midpoint between the two adjacent distinct metrics at
+    min_samples nearest their median.  At least `share` of the tiles must retire early and as many reach the target; tiles
+    above the median may still retire at a later step, so where too few would reach the target the next tries take lower
+    quantiles instead of the median."""
+    values = np.unique(metrics[min_samples])
+    assert len(values) >= 2, "every tile has the same metric"
+    tries = []
+    for q in (0.5, 0.4, 0.3, 0.2):
+        k = int(np.clip(np.searchsorted(values, np.quantile(metrics[min_samples], q)), 1, len(values) - 1))
+        lo, hi = values[k - 1], values[k]
+        if hi - lo <= 1e-6 * hi:
+            continue
+        rel_target = float(lo + hi) / 2
+        spp, _ = _expected_spp(metrics, rel_target, min_samples, target)
+        early, full = int((spp < target).sum()), int((spp == target).sum())
+        if min(early, full) >= share * len(spp):
+            return rel_target
+        tries.append((q, rel_target, early, full))
+    raise AssertionError(("no rel_target near the median splits the tiles", tries))
+
+
+def test_median_rel_target_on_synthetic_metrics():
+    rng = np.random.default_rng(9)
+    n = 5001
+    m16 = rng.random(n)
+    metrics = {16: m16, 24: m16 * 0.95, 32: m16 * 0.9, 40: m16 * 0.85}
+    rel = _median_rel_target(metrics, 16, 48)
+    below = np.sort(m16)[n // 2 - 1:n // 2 + 2]
+    assert below[0] < rel < below[2] and np.sum(m16 <= rel) in (n // 2, n // 2 + 1)
+    spp, near = _expected_spp(metrics, rel, 16, 48)
+    # the replay: a tile retires at the first step end whose metric meets rel_target
+    want = np.full(n, 48)
+    for s in (40, 32, 24, 16):
+        want[metrics[s] <= rel] = s
+    assert np.array_equal(spp, want) and not near.any()
+    # the slow picker agrees with the rule on a small draw; a constant metric is refused; so is a split under the share
+    small = {16: m16[:40], 24: m16[:40] * 0.8}
+    assert 0 < np.sum(_expected_spp(small, _pick_rel_target(small, 16, 32), 16, 32)[0] < 32) < 40
+    with pytest.raises(AssertionError):
+        _median_rel_target({16: np.full(100, 0.5), 24: np.full(100, 0.4)}, 16, 32)
+    skew = np.where(np.arange(100) < 95, 0.0, 1.0) + np.arange(100) * 1e-3
+    with pytest.raises(AssertionError):
+        _median_rel_target({16: skew, 24: skew * 0.99}, 16, 32, share=0.6)
+
+
 def _unreachable(rt, renderer, real_mode=0):
     """A small scene whose every tile's metric stays above 0 (a flat background tile -- every sample alike -- has metric 0 and
     retires under any rel_target), and half its smallest metric: (scene, cam, name, w, h, target, depth, rel_target).  The
@@ -247,19 +296,41 @@ def _unreachable(rt, renderer, real_mode=0):
     raise AssertionError("every small scene has a flat tile")
 
 
+def _adaptive_cases(case):
+    """(scene, width, height, target, depth, min_samples, step) of test_every_tile_equals_a_one_shot_render_at_its_own_count.
+    ragged: 43 x 33 = 1 419 tiles -- two 1 024-position windows of the compaction kernel, a partial last row and column and
+    n_tiles % 4 == 3.  full_hd: 32 400 tiles, target 512 in 8-sample chunks, so a 192-sample step is 24 chunk planes, two launches
+    (21 per launch); tiles retire at 192 and 384, and the second step renders the active tiles only, in two launches."""
+    if case == "small":
+        return [(name, w, h, target, depth, 16, 8) for name, w, h, target, depth in _small_scenes()]
+    if case == "ragged":
+        return [("book1_final", 340, 260, 64, 8, 16, 8)]
+    assert case == "full_hd"
+    return [("book1_final", 1920, 1080, 512, 8, 192, 192)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("real_mode", [0, 1])
-def test_every_tile_equals_a_one_shot_render_at_its_own_count(rt, renderer, real_mode):
+@pytest.mark.parametrize("real_mode,case", [(0, "small"), (1, "small"), (0, "ragged"), (1, "ragged"), (0, "full_hd")],
+                         ids=["0", "1", "ragged-f64", "ragged-f32", "full_hd-f64"])
+def test_every_tile_equals_a_one_shot_render_at_its_own_count(rt, renderer, real_mode, case):
     """The invariant, plus: retire decisions agree with the rule replayed in numpy on a uniform session's exact noise sums, the step
     work counters add up to the tile map, and the noise statistics use each tile's own K."""
-    for name, w, h, target, depth in _small_scenes():
+    for name, w, h, target, depth, min_samples, step in _adaptive_cases(case):
         scene = rt.Scene.build(name, rt.SCENE_SEED, EARTH)
         renderer.upload(scene)
         cam = scene.camera(w, h, target, depth)
-        min_samples = 16
-        metrics = _uniform_metrics(renderer, cam, real_mode, 8)
-        rel_target = _pick_rel_target(metrics, min_samples, target)
-        p, linear, rgb8, noise, counters, actives = _run_adaptive(renderer, cam, real_mode, rel_target, min_samples, 8, count=True)
+        if case == "full_hd":
+            launches = rt.hip_lib().rtk_frame_launches(C.byref(scene.camera(w, h, step, depth)), C.byref(rt.RenderOpts(rt.RENDER_SEED, 0, 0, 1, 0, 0, None)))
+            probe = renderer.progressive(cam)
+            assert launches >= 2 and probe.chunk_size == 8, launches
+            probe.close()
+        metrics = _uniform_metrics(renderer, cam, real_mode, step)
+        if case == "small":
+            rel_target = _pick_rel_target(metrics, min_samples, target)
+        else:
+            assert _tiles(w, h, 1) > 1024
+            rel_target = _median_rel_target(metrics, min_samples, target)
+        p, linear, rgb8, noise, counters, actives = _run_adaptive(renderer, cam, real_mode, rel_target, min_samples, step, count=True)
         spp = p.tile_samples()
         expected, near = _expected_spp(metrics, rel_target, min_samples, target)
         assert np.array_equal(spp[~near], expected[~near]), name
@@ -284,14 +355,7 @@ def test_every_tile_equals_a_one_shot_render_at_its_own_count(rt, renderer, real
         k = (spp // 8)[:, None].astype(np.float64)
         se, rel = _rel(s1, s2, k)
         inside = _inside(w, h, len(spp))
-        tx = (w + 7) // 8
-        se_img = np.zeros((h, w))
-        for t in range(len(spp)):
-            for lane in range(64):
-                i, j = (t % tx) * 8 + (lane & 7), (t // tx) * 8 + (lane >> 3)
-                if i < w and j < h:
-                    se_img[j, i] = se[t, lane]
-        np.testing.assert_allclose(noise, se_img.astype(np.float32), rtol=1e-6, atol=0)
+        np.testing.assert_allclose(noise, _tile_image(se, w, h).astype(np.float32), rtol=1e-6, atol=0)
         stats = p.noise()
         np.testing.assert_allclose(stats["mean_se"], se[inside].mean(), rtol=1e-9)
         np.testing.assert_allclose(stats["max_se"], se[inside].max(), rtol=1e-12)
@@ -385,6 +449,44 @@ def test_resume_in_a_fresh_context_equals_an_uninterrupted_run(rt, tmp_path):
         linear, rgb8, noise = q.step(8)
     assert np.array_equal(linear, whole) and np.array_equal(rgb8, whole8) and np.array_equal(noise, whole_noise)
     assert np.array_equal(q.tile_samples(), whole_spp)
+    q.close()
+    r2.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
+def test_resume_above_1024_tiles_equals_an_uninterrupted_run(rt, real_mode):
+    """Case "ragged" of test_every_tile_equals_a_one_shot_render_at_its_own_count, saved at 32 samples: the resumed session
+    recomputes its retired tiles (rtk_adaptive_restore_kernel) and compacts 1 419 tiles in two windows with no learned order."""
+    name, w, h, target, depth, min_samples, step = _adaptive_cases("ragged")[0]
+    scene = rt.Scene.build(name, rt.SCENE_SEED, EARTH)
+    cam = scene.camera(w, h, target, depth)
+    r = rt.Renderer(0)
+    r.upload(scene)
+    rel_target = _median_rel_target(_uniform_metrics(r, cam, real_mode, step), min_samples, target)
+    p, whole, whole8, whole_noise, _, _ = _run_adaptive(r, cam, real_mode, rel_target, min_samples, step)
+    whole_spp, whole_blob, whole_stats = p.tile_samples(), p.save(), p.noise()
+    p.close()
+    p = r.progressive(cam, real_mode=real_mode, rel_target=rel_target, min_samples=min_samples)
+    while p.samples_done < 32:
+        p.step(step)
+    mid_spp = p.tile_samples()
+    active = p.adaptive_status()["active_tiles"]
+    # retired tiles, and tiles still at 32 samples in both 1 024-tile windows (a resumed session compacts in tile order)
+    assert (mid_spp < 32).any() and (mid_spp[:1024] == 32).any() and (mid_spp[1024:] == 32).any() and active > 0, (np.unique(mid_spp), active)
+    blob = p.save()
+    p.close()
+    r.close()
+
+    r2 = rt.Renderer(0)
+    r2.upload(scene)
+    q = r2.resume(cam, blob, real_mode=real_mode)
+    assert np.array_equal(q.tile_samples(), mid_spp) and q.adaptive_status()["active_tiles"] == active
+    while q.samples_done < target:
+        linear, rgb8, noise = q.step(step)
+    assert np.array_equal(linear, whole) and np.array_equal(rgb8, whole8) and np.array_equal(noise, whole_noise)
+    assert np.array_equal(q.tile_samples(), whole_spp) and q.noise() == whole_stats
+    assert q.save() == whole_blob
     q.close()
     r2.close()
 

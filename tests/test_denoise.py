@@ -2,9 +2,10 @@
 
 CPU tests: the entry points are declared and exported; the numpy restatement of the filter below keeps a constant image
 constant and gives the weights of a hand-computed 3x3 case.
-GPU tests (-m gpu): AOVs equal the composition of the known-answer entry points bit for bit; the filter matches the numpy
-restatement; it lowers the error against a 1024-spp frame; nothing else changes (renders, sessions, checkpoints); refusals write
-nothing; the C++ camera writes the same images."""
+GPU tests (-m gpu): AOVs equal the composition of the known-answer entry points bit for bit, at ragged sizes at every pixel; the
+filter matches the numpy restatement; it lowers the error against a 1024-spp frame; nothing else changes (renders, sessions,
+checkpoints); denoised previews of adaptive sessions are the step's own output denoised; one output, aliased outputs, a torch
+stream and a reused workspace give the same bits; refusals write nothing; the C++ camera writes the same images."""
 import ctypes as C
 import json
 import os
@@ -267,17 +268,73 @@ def test_aovs_equal_the_known_answer_composition(rt, renderer, scenes, case, ord
     got1 = a1.reshape(-1, 8)[px]
     assert np.array_equal(got1, comp[:, 0].astype(np.float32)), np.argwhere(got1 != comp[:, 0].astype(np.float32))[:5]
     # four samples: in-order `real` sums, each divided by its count once
-    sums = np.zeros((len(px), 8), real)
-    for s in range(4):
+    want = _aov_of_samples(comp, real)
+    got4 = a4.reshape(-1, 8)[px]
+    assert np.array_equal(got4, want), np.argwhere(got4 != want)[:5]
+    assert (a4[..., 3] > 0).any()
+
+
+def _aov_of_samples(comp, real):
+    """What rtk_render_aovs writes for per-sample compositions comp [pixels, n, 8]: in-order `real` sums, each divided by its
+    count once (depth by the hits), rounded to float."""
+    sums = np.zeros((comp.shape[0], 8), real)
+    for s in range(comp.shape[1]):
         sums = sums + comp[:, s]
     hits = sums[:, 3]
-    want = np.zeros((len(px), 8), real)
-    want[:, 0:7] = sums[:, 0:7] / real(4)
+    want = np.zeros_like(sums)
+    want[:, 0:7] = sums[:, 0:7] / real(comp.shape[1])
     with np.errstate(invalid="ignore", divide="ignore"):
         want[:, 7] = np.where(hits > 0, sums[:, 7] / np.where(hits > 0, hits, real(1)), real(0))
-    got4 = a4.reshape(-1, 8)[px]
-    assert np.array_equal(got4, want.astype(np.float32)), np.argwhere(got4 != want.astype(np.float32))[:5]
-    assert (a4[..., 3] > 0).any()
+    return want.astype(np.float32)
+
+
+def _check_every_pixel(rt, renderer, scene, cam, n, real_mode, seed=7):
+    """rtk_render_aovs of n samples against the composition at every pixel of the image; returns the AOVs."""
+    w, h = cam.image_width, cam.image_height
+    got = renderer.aovs(cam, n, seed=seed, real_mode=real_mode)
+    ijs = np.array([[p % w, p // w, s] for p in range(w * h) for s in range(n)], np.int32)
+    comp = _compose(rt, renderer, scene, cam, seed, real_mode, ijs).reshape(w * h, n, 8)
+    want = _aov_of_samples(comp, np.float64 if real_mode == 0 else np.float32).reshape(h, w, 8)
+    assert np.array_equal(got, want), (w, h, n, np.argwhere(got != want)[:5])
+    return got
+
+
+# (width, height) with partial 8x8 tiles: a single pixel, 1-pixel columns and rows, both edges partial
+RAGGED = [(1, 1), (1, 37), (37, 1), (13, 7), (65, 9)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
+@pytest.mark.parametrize("name", ["material_zoo", "cornell_smoke", "book2_final"])
+def test_aovs_at_ragged_and_degenerate_sizes(rt, renderer, scenes, name, real_mode):
+    """Textures, media and motion blur at image sizes whose last tile row and column are partial, every pixel checked, for one
+    sample and for a count that is not a power of two."""
+    scene = scenes(name)
+    renderer.upload(scene)
+    hit = 0
+    for w, h in RAGGED:
+        for n in (1, 5):
+            hit += int((_check_every_pixel(rt, renderer, scene, scene.camera(w, h, 8, 6), n, real_mode)[..., 3] > 0).sum())
+    assert hit > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
+def test_aov_background_is_clamped_per_channel(rt, renderer, scenes, real_mode):
+    """Every library scene's background lies inside [0, 1]; a camera with one component above 1 and one below 0 checks the
+    clamp of a miss channel by channel."""
+    scene = scenes("book1_final")                                 # the sky fills the top of the frame
+    renderer.upload(scene)
+    misses = 0
+    for w, h in ((65, 9), (13, 7)):
+        cam = scene.camera(w, h, 8, 6)
+        cam.background = rt.Vec3(1.75, -0.5, 0.25)
+        for n in (1, 5):
+            a = _check_every_pixel(rt, renderer, scene, cam, n, real_mode)
+            sky = a[..., 3] == 0
+            assert np.array_equal(a[sky][:, 0:3], np.broadcast_to(np.float32([1.0, 0.0, 0.25]), (int(sky.sum()), 3)))
+            misses += int(sky.sum())
+    assert misses > 0
 
 
 def _c3_preview(rt, renderer, scenes, w=200, h=200, spp=32, real_mode=0):
@@ -293,20 +350,22 @@ def _c3_preview(rt, renderer, scenes, w=200, h=200, spp=32, real_mode=0):
 @pytest.mark.gpu
 @pytest.mark.parametrize("opts", [{"iterations": 1}, {}, {"iterations": 8}, {"iterations": 3, "sigma_l": 2.0, "sigma_n": 32.0, "sigma_z": 0.5, "sigma_a": 0.3}],
                          ids=["it1", "defaults", "it8", "sigmas"])
-@pytest.mark.parametrize("source", ["synthetic", "c3"])
+@pytest.mark.parametrize("source", ["synthetic", "c3", "ragged"])
 def test_filter_matches_the_numpy_reference(rt, renderer, scenes, source, opts):
     if source == "synthetic":
         renderer.upload(scenes("cornell_box"))
-        linear, aov, noise = _synthetic()
+        cases = [_synthetic()]
+    elif source == "ragged":                                      # partial tiles; at 8 iterations the taps 128 apart overshoot both sides
+        cases = [_synthetic(h, w) for w, h in RAGGED + [(100, 75)]]
     else:
-        linear, aov, noise = _c3_preview(rt, renderer, scenes)
-    modes = [0, 1] if source == "synthetic" else [0]
-    for real_mode in modes:
+        cases = [_c3_preview(rt, renderer, scenes)]
+    modes = [0] if source == "c3" else [0, 1]
+    for (linear, aov, noise), real_mode in [(c, m) for c in cases for m in modes]:
         out, rgb8 = renderer.denoise(linear, aov, noise, real_mode=real_mode, **opts)
         full = dict(DEFAULTS, **opts)
         ref = reference_denoise(linear, aov, noise, **full)
         rel = (np.abs(out - ref) / np.maximum(1.0, np.abs(ref))).max()
-        assert rel <= 1e-4, (real_mode, rel)
+        assert rel <= 1e-4, (real_mode, out.shape, rel)
         if real_mode == 1:
             assert np.array_equal(out, out.astype(np.float32).astype(np.float64))
         # bytes: the resolve's conversion of the float colour
@@ -394,6 +453,111 @@ def test_denoised_previews_leave_the_session_alone(rt, renderer, scenes, real_mo
     assert np.array_equal(fa, one) and np.array_equal(fa8, one8) and np.array_equal(fb, one)
     a.close()
     b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
+def test_denoised_previews_of_adaptive_and_partial_chunk_sessions(rt, renderer, scenes, real_mode):
+    """rtk_preview_kernel rebuilds the step's preview from the sums: each tile scaled by its own count and se over its own K in an
+    adaptive session (1 419 tiles, retired and active ones side by side), and a last step that ends inside a chunk."""
+    from tests.test_adaptive import _adaptive_cases, _median_rel_target, _uniform_metrics
+
+    name, w, h, target, depth, min_samples, step = _adaptive_cases("ragged")[0]
+    scene = scenes(name)
+    renderer.upload(scene)
+    cam = scene.camera(w, h, target, depth)
+    aov = renderer.aovs(cam, 4, real_mode=real_mode)
+    rel_target = _median_rel_target(_uniform_metrics(renderer, cam, real_mode, step), min_samples, target)
+    p = renderer.progressive(cam, real_mode=real_mode, rel_target=rel_target, min_samples=min_samples)
+    mixed = 0
+    while p.samples_done < target:
+        linear, _, noise = p.step(step)
+        spp = p.tile_samples()
+        if not ((spp < p.samples_done).any() and (spp == p.samples_done).any()):
+            continue
+        mixed += 1
+        before = p.save()
+        den, den8 = p.denoised()
+        want, want8 = renderer.denoise(linear, aov, noise, real_mode=real_mode)
+        assert np.array_equal(den, want) and np.array_equal(den8, want8), p.samples_done
+        assert p.save() == before
+    assert mixed >= 2
+    p.close()
+    # a plain session whose last step ends at the target with a partial chunk: 36 samples are 4 full chunks and 4 samples
+    cam = scene.camera(w, h, 36, depth)
+    p = renderer.progressive(cam, real_mode=real_mode)
+    for n in (8, 8, 8, 8, 4):
+        linear, _, noise = p.step(n)
+    assert p.samples_done == 36 and p.chunk_size == 8 and p.noise()["full_chunks"] == 4
+    before = p.save()
+    den, den8 = p.denoised()
+    want, want8 = renderer.denoise(linear, aov, noise, real_mode=real_mode)
+    assert np.array_equal(den, want) and np.array_equal(den8, want8)
+    assert p.save() == before
+    p.close()
+
+
+@pytest.mark.gpu
+def test_filter_matches_the_numpy_reference_on_a_c2_preview(rt, renderer):
+    """C2's scene and camera (fast order) at 960x540 -- the float64 numpy reference takes about 20 s there, four times that at
+    1920x1080: a 32-spp preview, 4-sample AOVs, the default options."""
+    scene = rt.Scene.build("book1_final", rt.SCENE_SEED)
+    cam = scene.camera(960, 540, 100, 0)
+    assert renderer.upload_fast(scene, cam.center)["exact"]
+    p = renderer.progressive(cam)
+    linear, _, noise = p.step(32)
+    p.close()
+    aov = renderer.aovs(cam, 4)
+    out, rgb8 = renderer.denoise(linear, aov, noise)
+    ref = reference_denoise(linear, aov, noise)
+    rel = (np.abs(out - ref) / np.maximum(1.0, np.abs(ref))).max()
+    assert rel <= 1e-4, rel
+    assert np.array_equal(rgb8, _to_byte(out.astype(np.float32).astype(np.float64)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
+def test_denoise_entry_point_paths(rt, renderer, real_mode):
+    """One output at a time; the device entry point on a torch stream with the colour written over d_linear and the bytes over
+    d_noise (include/rtk.h: the outputs may alias d_linear or d_noise); the context's workspace grown and then reused."""
+    import torch
+
+    lib = rt.hip_lib()
+    h, w = 75, 100
+    linear, aov, noise = _synthetic(h, w)
+    lin = np.ascontiguousarray(linear)
+    both, both8 = renderer.denoise(linear, aov, noise, real_mode=real_mode)
+    opts = rt.DenoiseOpts(0, 0, 0, 0, 0, 0)
+    args = (renderer._ctx, w, h, real_mode, lin.ctypes.data, aov.ctypes.data, noise.ctypes.data, C.byref(opts))
+    only = np.full((h, w, 3), -3.0)
+    assert lib.rtk_denoise_host(*args, only.ctypes.data, None) == 0
+    only8 = np.full((h, w, 3), 77, np.uint8)
+    assert lib.rtk_denoise_host(*args, None, only8.ctypes.data) == 0
+    assert np.array_equal(only, both) and np.array_equal(only8, both8)
+
+    dev = torch.device("cuda", renderer.device)
+    d_lin = torch.from_numpy(lin).to(dev, torch.float64 if real_mode == 0 else torch.float32)
+    d_aov, d_noise = torch.from_numpy(aov).to(dev), torch.from_numpy(noise).to(dev)
+    sep_lin, sep8 = torch.full_like(d_lin, -3.0), torch.full((h, w, 3), 77, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize(dev)
+    ptrs = (d_lin.data_ptr(), d_aov.data_ptr(), d_noise.data_ptr())
+    assert lib.rtk_denoise(renderer._ctx, w, h, real_mode, *ptrs, C.byref(opts), sep_lin.data_ptr(), sep8.data_ptr(), stream.cuda_stream) == 0
+    assert lib.rtk_denoise(renderer._ctx, w, h, real_mode, *ptrs, C.byref(opts), d_lin.data_ptr(), d_noise.data_ptr(), stream.cuda_stream) == 0
+    stream.synchronize()
+    assert np.array_equal(sep_lin.double().cpu().numpy(), both) and np.array_equal(sep8.cpu().numpy(), both8)
+    assert torch.equal(d_lin, sep_lin)
+    assert torch.equal(d_noise.view(torch.uint8).flatten()[: h * w * 3].view(h, w, 3), sep8)
+
+    one = rt.Renderer(renderer.device)                             # a context of its own: its workspace starts empty
+    for w, h in ((13, 7), (340, 260), (13, 7)):
+        inputs = _synthetic(h, w)
+        got, got8 = one.denoise(*inputs, real_mode=real_mode)
+        fresh = rt.Renderer(renderer.device)
+        want, want8 = fresh.denoise(*inputs, real_mode=real_mode)
+        fresh.close()
+        assert np.array_equal(got, want) and np.array_equal(got8, want8), (w, h)
+    one.close()
 
 
 @pytest.mark.gpu

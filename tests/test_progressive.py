@@ -2,7 +2,8 @@
 running sums is the one-shot frame bit for bit; previews equal short one-shot renders; checkpoints resume to the same image and
 are refused when anything the image depends on differs; the batch-means noise estimate matches a numpy restatement.
 
-CPU tests: the checkpoint format (parsed from a blob built field by field here) and the exported entry points.
+CPU tests: the checkpoint format (parsed from a blob built field by field here), the exported entry points and the tile-to-image
+helper of the numpy checks.
 GPU tests (-m gpu): everything that renders."""
 import ctypes as C
 import hashlib
@@ -287,7 +288,14 @@ def _sums_from_blob(blob, tiles, elem=8):
 
 
 def _tile_image(a, w, h):
-    """[tiles, 64] of one rank of one -> (h, w)."""
+    """[tiles, 64] of one rank of one -> (h, w): tile t = (row ty, column tx), lane = 8 * pixel row + pixel column."""
+    tx, ty = (w + 7) // 8, (h + 7) // 8
+    a = np.asarray(a)
+    return np.ascontiguousarray(a[: tx * ty].reshape(ty, tx, 8, 8).transpose(0, 2, 1, 3).reshape(ty * 8, tx * 8)[:h, :w])
+
+
+def _tile_image_loop(a, w, h):
+    """_tile_image written out pixel by pixel (the CPU test's yardstick)."""
     tx = (w + 7) // 8
     out = np.zeros((h, w), a.dtype)
     for t in range(a.shape[0]):
@@ -296,6 +304,17 @@ def _tile_image(a, w, h):
             if i < w and j < h:
                 out[j, i] = a[t, lane]
     return out
+
+
+def test_tile_image_equals_the_pixel_loop():
+    rng = np.random.default_rng(2)
+    for w, h in ((128, 128), (16, 16), (96, 56), (64, 64), (96, 54), (64, 40), (84, 50), (120, 64), (1, 1), (13, 7), (1, 37), (37, 1), (65, 9)):
+        a = rng.random((_tiles(w, h, 1), 64))
+        got = _tile_image(a, w, h)
+        assert got.shape == (h, w) and got.dtype == a.dtype
+        assert np.array_equal(got, _tile_image_loop(a, w, h)), (w, h)
+        f = a.astype(np.float32)
+        assert np.array_equal(_tile_image(f, w, h), _tile_image_loop(f, w, h)) and _tile_image(f, w, h).dtype == np.float32
 
 
 @pytest.mark.gpu
@@ -352,6 +371,45 @@ def test_noise_estimate_matches_numpy(rt, renderer):
     # a second identical run: bit-identical statistics
     _, noise2, stats2, _, _, _ = run()
     assert stats2 == stats and np.array_equal(noise2, noise)
+
+
+def _check_noise_against_the_sums(p, noise, w, h):
+    """The step's per-pixel se plane and p.noise() against numpy from the checkpoint's own S1 / S2 (one rank, K full chunks)."""
+    k = p.samples_done // p.chunk_size
+    _, s1, s2 = _sums_from_blob(p.save(), _tiles(w, h, 1), 8 if p.real_mode == 0 else 4)
+    m = s1 / k
+    se = np.sqrt(np.maximum(0.0, (s2 - k * m * m) / (k - 1)) / k)
+    se_img = _tile_image(se, w, h)
+    rel_img = _tile_image(se / np.maximum(m, 1e-3), w, h)
+    np.testing.assert_allclose(noise, se_img.astype(np.float32), rtol=1e-6, atol=0)
+    st = p.noise()
+    assert st["valid"] == 1 and st["full_chunks"] == k and st["samples_done"] == p.samples_done
+    np.testing.assert_allclose(st["mean_se"], se_img.mean(), rtol=1e-9)
+    np.testing.assert_allclose(st["max_se"], se_img.max(), rtol=1e-12)
+    np.testing.assert_allclose(st["mean_rel_se"], rel_img.mean(), rtol=1e-9)
+    return st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [("book1_final", 48, 16, 0), ("book1_final", 48, 16, 1), ("cornell_box", 1000, 160, 0)],
+                         ids=["c2-f64", "c2-f32", "c3-f64"])
+def test_noise_estimate_at_full_size_matches_numpy(rt, renderer, tmp_path, case):
+    """Full-size frames: 1920x1080 is 32 400 tiles, 8 100 block partials of the noise statistics (8-sample chunks); 800x800 is
+    2 500 partials of 16-sample chunks.  rtk_noise_final_kernel reduces them in strided slices of 256."""
+    name, target, step, real_mode = case
+    scene, cam = _full_size(rt, renderer, tmp_path, name)
+    cam = scene.camera(cam.image_width, cam.image_height, target, cam.max_depth)
+    w, h = cam.image_width, cam.image_height
+    partials = (_tiles(w, h, 1) * 64 + 255) // 256
+    assert partials > 2 * 256, partials
+    p = renderer.progressive(cam, real_mode=real_mode)
+    assert p.chunk_size == (8 if target <= 512 else 16)
+    means = []
+    for _ in range(2 if name == "cornell_box" else 3):
+        _, _, noise = p.step(step)
+        means.append(_check_noise_against_the_sums(p, noise, w, h)["mean_se"])
+    assert means == sorted(means, reverse=True) and means[-1] > 0    # more chunks, less noise
+    p.close()
 
 
 @pytest.mark.gpu
