@@ -299,20 +299,14 @@ inline float round_up(double x) {
     return double(f) < x ? std::nextafterf(f, INFINITY) : f;
 }
 
-// How far an f32 culling box is grown beyond its outward-rounded bounds.  RTK_SIGNED_SLAB: the ray carries the error of
-// its own origin term (a bracket of o/d, rtk_trace.hip begin_culling32), so a box answers only for the product b * rcp(d)
+// How far an f32 culling box is grown beyond its outward-rounded bounds.  The ray carries the error of its own origin
+// term (a bracket of o/d, rtk_trace.hip begin_culling32), so a box answers only for the product b * rcp(d)
 // -- float(d) 2^-24, v_rcp_f32 one ulp, the fused multiply-add's final rounding 2^-24 of it: < 2^-22 relative -- i.e. a
-// plane displaced by < 2^-22 |b|; grown by 2^-21 of the box's largest coordinate (twice that).  Otherwise: the scene-wide
-// margin the caller computed (2^-19 x extent).
-static double box_margin(const rtk_aabb& b, double scene_margin) {
-#if RTK_SIGNED_SLAB
-    (void)scene_margin;
+// plane displaced by < 2^-22 |b|; grown by 2^-21 of the box's largest coordinate (twice that).
+static double box_margin(const rtk_aabb& b) {
     double big = 0.0;
     for (double v : {b.xmin, b.xmax, b.ymin, b.ymax, b.zmin, b.zmax}) big = std::max(big, std::fabs(v));
     return std::ldexp(big, -21) + 1e-300;
-#else
-    return scene_margin;
-#endif
 }
 
 // The MIXED program of rtk_device_layout.h for a sphere-only scene whose boxes carry rtk_scene_optimize's margin:
@@ -346,8 +340,6 @@ static void build_mixed_program(const rtk_scene_desc& sc, const Program& prog, d
         }
     }
     extent = double(round_up(extent * 1.0000001));
-    const double margin = std::ldexp(extent, -19);  // (A/B on C2: a margin 128 times smaller renders 0.7 % faster -- nothing to gain)
-    (void)margin;
     units.assign(unit_of_op.back(), MixedHead{});
     std::memset(units.data(), 0, units.size() * sizeof(MixedHead));
     rank_of_unit.assign(unit_of_op.back(), 0u);
@@ -360,7 +352,6 @@ static void build_mixed_program(const rtk_scene_desc& sc, const Program& prog, d
         rank_of_unit[unit_of_op[i]] = prog.ranks[i];
         if (kind == OP_BOX) {
             const rtk_aabb& b = sc.bvh_boxes[payload];
-#if RTK_CH_BOX
             // Centre / half-extent form.  The kernel computes, per axis, tc = fma(c, inv, -oi), near = fma(-h, |inv|, tc),
             // far = fma(h, |inv|, tc) with inv = v_rcp_f32(float(d)) (relative error <= 2^-24 + 2^-23) and oi = float(o) * inv
             // (<= 2^-24 + that + 2^-24).  Against the exact planes (c -/+ h - o) / d of the stored box the computed ones are off
@@ -378,13 +369,7 @@ static void build_mixed_program(const rtk_scene_desc& sc, const Program& prog, d
                 rec->set_f(ax, cf);
                 rec->set_f(3 + ax, round_up(grown * (1.0 + 1e-7)));
             }
-#else
-            const double m = box_margin(b, margin);
-            rec->set_f(0, round_down(b.xmin - m)); rec->set_f(1, round_up(b.xmax + m));
-            rec->set_f(2, round_down(b.ymin - m)); rec->set_f(3, round_up(b.ymax + m));
-            rec->set_f(4, round_down(b.zmin - m)); rec->set_f(5, round_up(b.zmax + m));
-#endif
-            rec->aux = unit_of_op[op.aux] * ((RTK_CH_BOX && RTK_CH_BYTE_PC) ? uint32_t(sizeof(MixedHead)) : 1u);  // RTK_CH_BOX: the kernel's pcs count bytes
+            rec->aux = unit_of_op[op.aux] * uint32_t(sizeof(MixedHead));  // the kernel's pcs count bytes
         } else if (kind == OP_SPHERE || kind == OP_SPHERE_MOVING) {
             const rtk_sphere& s = sc.spheres[payload];
             rec->set_d(0, s.center0.x); rec->set_d(1, s.center0.y); rec->set_d(2, s.center0.z);
@@ -442,10 +427,10 @@ static double scene_extent(const rtk_scene_desc& sc, double eye_extent) {
 // COMPACT programs of the mesh family hold centre / half-extent box records (the rule of rtk_trace.hip kCompactChStatic)
 static bool compact_ch_family(const Program& prog) {
     const uint32_t scene = prog.features & ~uint32_t(F_FMA_BOX | F_MATTE);
-    return RTK_CH_COMPACT && scene != kFeatLean && (scene & ~kFeatQuadBox) != 0 && (scene & ~kFeatMesh) == 0;
+    return scene != kFeatLean && (scene & ~kFeatQuadBox) != 0 && (scene & ~kFeatMesh) == 0;
 }
 
-static void write_compact_record(const rtk_scene_desc& sc, const Program& prog, size_t i, uint32_t kind, Unit16* dst, double margin,
+static void write_compact_record(const rtk_scene_desc& sc, const Program& prog, size_t i, uint32_t kind, Unit16* dst,
                                  const std::vector<uint32_t>& unit_of_link, bool ch_boxes = false) {
     const Op& op = prog.ops[i];
     const uint32_t payload = op.kind_payload >> 4;
@@ -471,7 +456,7 @@ static void write_compact_record(const rtk_scene_desc& sc, const Program& prog, 
                 head->set_f(3 + ax, round_up(grown * (1.0 + 1e-7)));
             }
             } else {
-            const double m = box_margin(b, margin);
+            const double m = box_margin(b);
             head->set_f(0, round_down(b.xmin - m)); head->set_f(1, round_up(b.xmax + m));
             head->set_f(2, round_down(b.ymin - m)); head->set_f(3, round_up(b.ymax + m));
             head->set_f(4, round_down(b.zmin - m)); head->set_f(5, round_up(b.zmax + m));
@@ -539,11 +524,10 @@ static void build_compact_program(const rtk_scene_desc& sc, const Program& prog,
     std::vector<uint32_t> unit_of_op(prog.ops.size() + 1, 0);
     for (size_t i = 0; i < prog.ops.size(); i++) unit_of_op[i + 1] = unit_of_op[i] + uint32_t(compact_units(compact_kind_of(sc, prog.ops[i])));
     const double extent = double(round_up(scene_extent(sc, eye_extent) * 1.0000001));
-    const double margin = std::ldexp(extent, -19);
     units.assign(unit_of_op.back(), Unit16{{0u, 0u, 0u, 0u}});
     rank_of_unit.assign(unit_of_op.back(), 0u);
     for (size_t i = 0; i < prog.ops.size(); i++) {
-        write_compact_record(sc, prog, i, compact_kind_of(sc, prog.ops[i]), &units[unit_of_op[i]], margin, unit_of_op, compact_ch_family(prog));
+        write_compact_record(sc, prog, i, compact_kind_of(sc, prog.ops[i]), &units[unit_of_op[i]], unit_of_op, compact_ch_family(prog));
         rank_of_unit[unit_of_op[i]] = prog.ranks[i];
     }
     extent_out = float(extent);
@@ -555,7 +539,7 @@ static void build_compact_program(const rtk_scene_desc& sc, const Program& prog,
 // count; aux = first unit of the run in `cold`}.  A run ends where the kind changes, at 255 primitives, and in front of any
 // record some box or medium links to (so that every link target is the start of a record of the hot program).
 // rank_of_id[unit of a hot record, or hot.size() + unit of a cold one] = the primitive's reference rank.
-static void build_hot_cold_program(const rtk_scene_desc& sc, const Program& prog, double eye_extent, std::vector<Unit16>& hot, std::vector<Unit16>& cold,
+static void build_hot_cold_program(const rtk_scene_desc& sc, const Program& prog, std::vector<Unit16>& hot, std::vector<Unit16>& cold,
                                    std::vector<uint32_t>& rank_of_id) {
     const size_t n = prog.ops.size();
     std::vector<uint32_t> kind(n);
@@ -586,14 +570,12 @@ static void build_hot_cold_program(const rtk_scene_desc& sc, const Program& prog
         i = j;
     }
     hot_unit[n] = n_hot;
-    const double extent = double(round_up(scene_extent(sc, eye_extent) * 1.0000001));
-    const double margin = std::ldexp(extent, -19);
     hot.assign(n_hot, Unit16{{0u, 0u, 0u, 0u}});
     cold.assign(std::max<uint32_t>(n_cold, 1u), Unit16{{0u, 0u, 0u, 0u}});
     rank_of_id.assign(size_t(n_hot) + cold.size(), 0u);
     for (size_t i = 0; i < n; i++) {
         if (!is_cold(i)) {
-            write_compact_record(sc, prog, i, kind[i], &hot[hot_unit[i]], margin, hot_unit);
+            write_compact_record(sc, prog, i, kind[i], &hot[hot_unit[i]], hot_unit);
             rank_of_id[hot_unit[i]] = prog.ranks[i];
             continue;
         }
@@ -602,7 +584,7 @@ static void build_hot_cold_program(const rtk_scene_desc& sc, const Program& prog
             run->kind_payload = make_op(kind[i], run_len[i]);
             run->aux = cold_unit[i];
         }
-        write_compact_record(sc, prog, i, kind[i], &cold[cold_unit[i]], margin, hot_unit);
+        write_compact_record(sc, prog, i, kind[i], &cold[cold_unit[i]], hot_unit);
         rank_of_id[size_t(n_hot) + cold_unit[i]] = prog.ranks[i];
     }
 }
@@ -905,7 +887,7 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
             if ((prog.features & ~kFeatQuadBox) != 0 && (prog.features & ~kFeatMesh) != 0) {
                 std::vector<Unit16> hot, cold;
                 std::vector<uint32_t> ranks_by_id;
-                build_hot_cold_program(sc, prog, eye_extent, hot, cold, ranks_by_id);
+                build_hot_cold_program(sc, prog, hot, cold, ranks_by_id);
                 if (getenv("RTK_DEBUG")) fprintf(stderr, "[rtk] COMPACT program %zu B; hot part %zu B, cold part %zu B\n", units.size() * 16, hot.size() * 16, cold.size() * 16);
                 if (hot.size() * sizeof(Unit16) + mats.size() * sizeof(MaterialRec<real>) + 64 <= size_t(kLdsBytesPerCU) && hot.size() < (size_t(1) << 24)) {
                     if ((rc = out.upload(hot, &out.view.program_hot)) != RTK_OK) return rc;
@@ -1328,9 +1310,7 @@ static int upload_scene(rtk_ctx* ctx, const rtk_scene_desc* scene, UploadOrder o
     for (int32_t i = 0; i < scene->n_materials; i++)
         if (scene->materials[i].kind != RTK_MAT_LAMBERTIAN && scene->materials[i].kind != RTK_MAT_DIFFUSE_LIGHT) matte = false;
     if (matte) hierarchy_flags |= F_MATTE;
-#ifndef RTK_NO_SPHERE_MEDIA_ONLY   // (A/B builds)
     if ((prog.features & F_MEDIA) != 0 && !prog.has_media_bracket) hierarchy_flags |= F_SPHERE_MEDIA_ONLY;
-#endif
 
     RTK_HIP(hipSetDevice(ctx->device));
     ctx->has_scene = false;
@@ -1706,7 +1686,7 @@ size_t hot_program_lds_bytes(const rtk_scene_desc* scene) {
         if (compile_scene(scene, prog) != RTK_OK) return 0;
         std::vector<Unit16> hot, cold;
         std::vector<uint32_t> ranks;
-        build_hot_cold_program(*scene, prog, 0.0, hot, cold, ranks);
+        build_hot_cold_program(*scene, prog, hot, cold, ranks);
         return hot.size() * sizeof(Unit16) + size_t(scene->n_materials) * sizeof(MaterialRec<double>);
     } catch (const std::bad_alloc&) {
         return 0;

@@ -29,7 +29,7 @@ namespace {
 
 #define RTK_DN __device__ __forceinline__
 
-// The resolve's byte conversion (rtk_trace.hip, to_byte; Camera.txt:29-34,77-83), in double.
+// The resolve's byte conversion (rtk_device_math.h, to_byte; Camera.txt:29-34,77-83), in double.
 RTK_DN uint8_t denoise_byte(double x) {
     double g = x > 0 ? __builtin_sqrt(x) : 0.0;
     g = g < 0.000 ? 0.000 : (g > 0.999 ? 0.999 : g);

@@ -30,37 +30,19 @@
 #include <stdint.h>
 #include <hip/hip_vector_types.h>
 
-// f32 culling boxes (MIXED / COMPACT programs): 1 = the sign-selected slab test with a per-ray bracket of o/d, boxes grown by
-// 2^-21 of their OWN coordinates; 0 = the min/max form, boxes grown by 2^-19 of the largest coordinate in the scene.  Shared
-// by the kernels (rtk_trace.hip) and the program builders (rtk_api.cpp); A/B builds pass -DRTK_SIGNED_SLAB=0.
-#ifndef RTK_SIGNED_SLAB
-#define RTK_SIGNED_SLAB 1
-#endif
-
-// MIXED program (sphere-only scenes): 1 = a box record holds centre and half-extent, f[0..2] = c, f[3..5] = h, and the slab test
-// is near = (c/d - o/d) - h/|d|, far = (c/d - o/d) + h/|d| -- nine fused multiply-adds (|1/d| is a free source modifier)
-// instead of six selects and six multiply-adds; the half-extent carries the whole float error budget (rtk_api.cpp).
-#ifndef RTK_CH_BOX
-#define RTK_CH_BOX 1
-#endif
-
-// ... (RTK_CH_SCALED) with the ray parameter scaled per ray so that the current interval's end maps to 1: the two interval
-// clamps of the slab test become the free [0, 1] output clamp of v_max3 / v_min3 (rtk_trace.hip slab_test32_chs)
-#ifndef RTK_CH_SCALED
-#define RTK_CH_SCALED 1
-#endif
-// ... and (RTK_CH_BYTE_PC) that kernel's program counters and box links count bytes instead of 32-byte units
-#ifndef RTK_CH_BYTE_PC
-#define RTK_CH_BYTE_PC 1
-#endif
-
-// COMPACT program: 1 = centre / half-extent records for the programs of the mesh family (triangles + spheres) as well; the
-// origin's share of the float error stays with the RAY, as one slack term for all three axes (rtk_trace.hip
-// slab_test32_che), so a box is grown by 2^-21 of its own coordinates only -- nine fused multiply-adds, a subtraction and a
-// compare against -2 x slack.  The other families keep the sign-selected test (measured, see rtk_trace.hip).
-#ifndef RTK_CH_COMPACT
-#define RTK_CH_COMPACT 1
-#endif
+// f32 culling boxes (MIXED / COMPACT programs), as the kernels (rtk_trace.hip) and the program builders (rtk_api.cpp) agree on them:
+//  * the sign-selected slab test with a per-ray bracket of o/d; boxes grown by 2^-21 of their OWN coordinates (the min/max
+//    form it replaced needed 2^-19 of the largest coordinate in the scene);
+//  * MIXED program (sphere-only scenes): a box record holds centre and half-extent, f[0..2] = c, f[3..5] = h, and the slab test
+//    is near = (c/d - o/d) - h/|d|, far = (c/d - o/d) + h/|d| -- nine fused multiply-adds (|1/d| is a free source modifier)
+//    instead of six selects and six multiply-adds; the half-extent carries the whole float error budget (rtk_api.cpp).  The
+//    ray parameter is scaled per ray so that the current interval's end maps to 1: the two interval clamps of the slab test
+//    become the free [0, 1] output clamp of v_max3 / v_min3 (rtk_trace.hip slab_test32_chs).  That kernel's program counters
+//    and box links count bytes instead of 32-byte units;
+//  * COMPACT program: centre / half-extent records for the programs of the mesh family (triangles + spheres) as well; the
+//    origin's share of the float error stays with the RAY, as one slack term for all three axes (rtk_trace.hip
+//    slab_test32_che), so a box is grown by 2^-21 of its own coordinates only -- nine fused multiply-adds, a subtraction and a
+//    compare against -2 x slack.  The other families keep the sign-selected test (measured, see rtk_trace.hip).
 
 namespace rtk {
 
@@ -116,9 +98,8 @@ inline constexpr int slots_of(uint32_t kind) {
 
 // The MIXED traversal program (F_F32_BOX): records are sequences of 32-byte units, pc counts units.  The first unit of
 // every record carries the header at bytes 24..31, so the kind of the record at pc is always one 8-byte read away:
-//   OP_BOX            1 unit : f[0..5] = xmin,xmax,ymin,ymax,zmin,zmax as floats, rounded OUTWARD and grown (see
-//                              rtk_api.cpp) -- or, RTK_CH_BOX, centre(3) and half-extent(3), the half-extent rounded up
-//                              and grown; aux = pc to continue at when the slab test fails
+//   OP_BOX            1 unit : f[0..5] = centre(3) and half-extent(3) as floats, the half-extent rounded up and grown
+//                              (see rtk_api.cpp); aux = pc (in bytes) to continue at when the slab test fails
 //   OP_SPHERE         2 units: d[0..2] = centre (f64); unit 1 = radius, 1/radius (f64)
 //   OP_SPHERE_MOVING  3 units: as OP_SPHERE; unit 1 also holds dx, dy; unit 2 holds dz (centre2 - centre1)
 //   OP_END            1 unit
@@ -269,7 +250,7 @@ struct SceneView {  // device pointers, passed to the kernel by value
     // the reference order) -- same `extent` rule, applied to the object-space origin under instance transforms
     const Unit16* program_compact;
     int32_t n_units16;
-    int32_t compact_ch;  // 1 = program_compact's box records are centre / half-extent (RTK_CH_COMPACT: the mesh family's programs)
+    int32_t compact_ch;  // 1 = program_compact's box records are centre / half-extent (the mesh family's programs)
     // ... and, for COMPACT programs too large for LDS, the same program in two parts (F_LDS_BOXES | F_F32_BOX kernels): the
     // hot part -- staged in LDS -- holds every record except quads and triangles, with one two-unit record {kind, count;
     // aux = first unit in program_cold} per run of them; program_cold holds those primitives' usual records.  A hit on a

@@ -1,4 +1,6 @@
-// rtk_trace.h -- launch entry points of rtk_trace.hip for the C-ABI layer.
+// rtk_trace.h -- launch entry points of the device code for the C-ABI layer: the render, debug and AOV kernels of
+// rtk_trace.hip and the frame-assembly kernels of rtk_frame.hip (tile order, resolve, accumulate, preview, noise statistics,
+// adaptive state, un-permute).
 #ifndef RTK_TRACE_H
 #define RTK_TRACE_H
 
@@ -56,7 +58,7 @@ hipError_t launch_adaptive_restore(const double* s1, const double* s2, const Til
                                    int done, bool retire_ok, double rel_target, int32_t* active, hipStream_t stream);
 // list = the positions of `order` (identity when null; n entries) whose tile is active, in order; *count = their number.
 hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, int n, int32_t* list, int32_t* count, hipStream_t stream);
-// launch_noise_stats with per-tile K = tile_spp[t] / chunk_size.
+// launch_noise_stats with per-tile K = tile_spp[t] / chunk_size (the same kernel, given tile_spp).
 hipError_t launch_noise_stats_adaptive(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
                                        double* partials, double* out3, hipStream_t stream);
 

@@ -20,6 +20,9 @@
 // keeps only (t, winning op); position, normal and uv are computed once per
 // segment from the winning primitive, which gives the same values because they
 // are pure functions of (ray, t, primitive).
+//
+// Frame assembly -- partial sums -> images and progressive-session state -- is rtk_frame.hip; the two files share
+// rtk_device_math.h (V3, mk, operator+, scale, to_byte) and nothing else.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -28,24 +31,17 @@
 
 #include "rtk.h"
 #include "rtk_device_layout.h"
+#include "rtk_device_math.h"
 #include "rtk_trace.h"
 
 namespace rtk {
 
 // ------------------------------------------------------------------ math -----
-template <typename real>
-struct V3 {
-    real x, y, z;
-};
-#define RTK_DEV __device__ __forceinline__
-
-template <typename real> RTK_DEV V3<real> mk(real a, real b, real c) { return V3<real>{a, b, c}; }
+// (V3, RTK_DEV, mk, operator+ and scale: rtk_device_math.h)
 template <typename real> RTK_DEV V3<real> ld3(const real* p) { return V3<real>{p[0], p[1], p[2]}; }
 template <typename real> RTK_DEV V3<real> operator-(V3<real> a) { return V3<real>{-a.x, -a.y, -a.z}; }
-template <typename real> RTK_DEV V3<real> operator+(V3<real> a, V3<real> b) { return V3<real>{a.x + b.x, a.y + b.y, a.z + b.z}; }
 template <typename real> RTK_DEV V3<real> operator-(V3<real> a, V3<real> b) { return V3<real>{a.x - b.x, a.y - b.y, a.z - b.z}; }
 template <typename real> RTK_DEV V3<real> operator*(V3<real> a, V3<real> b) { return V3<real>{a.x * b.x, a.y * b.y, a.z * b.z}; }
-template <typename real> RTK_DEV V3<real> scale(real t, V3<real> a) { return V3<real>{t * a.x, t * a.y, t * a.z}; }
 template <typename real> RTK_DEV V3<real> divide(V3<real> a, real t) { return scale(real(1) / t, a); }  // vec3.h:91-93
 template <typename real> RTK_DEV real dot(V3<real> a, V3<real> b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 template <typename real> RTK_DEV V3<real> cross(V3<real> a, V3<real> b) {
@@ -77,31 +73,13 @@ RTK_DEV double rt_atan2(double y, double x) { return atan2(y, x); }
 RTK_DEV float rt_atan2(float y, float x) { return atan2f(y, x); }
 
 template <typename real> RTK_DEV real real_inf() { return real(__builtin_huge_val()); }
-// Round 3: libm-heavy f64 code kept OUT OF LINE, one macro each (see sphere_uv below for the reasoning and the first two).
+// Round 3: libm-heavy f64 code kept OUT OF LINE (see sphere_uv below for the reasoning and the first two).
 // Measured and left inline: perlin::noise (43.7 vs 34.0 ms) and texture::value as a whole (864 B of scratch).
-#ifndef RTK_COLD_POW
-#define RTK_COLD_POW 1   // pow (the specular material): C5 38.87 -> 38.25 ms at 32 spp
-#endif
-#ifndef RTK_COLD_LOG
-#define RTK_COLD_LOG 1   // log (constant_medium's scatter distance, twice per segment in book 2): 38.87 -> 35.72; both: 33.98
-#endif
-#ifndef RTK_COLD_PERLIN
-#define RTK_COLD_PERLIN 0
-#endif
-#ifndef RTK_COLD_TEX
-#define RTK_COLD_TEX 0
-#endif
 #define RTK_NOINLINE __device__ __attribute__((noinline))
-#if RTK_COLD_POW
+// pow (the specular material): C5 38.87 -> 38.25 ms at 32 spp
 template <typename real> RTK_NOINLINE real call_pow(real x, real y) { return rt_pow(x, y); }
-#else
-template <typename real> RTK_DEV real call_pow(real x, real y) { return rt_pow(x, y); }
-#endif
-#if RTK_COLD_LOG
+// log (constant_medium's scatter distance, twice per segment in book 2): 38.87 -> 35.72; both: 33.98
 template <typename real> RTK_NOINLINE real call_log(real x) { return rt_log(x); }
-#else
-template <typename real> RTK_DEV real call_log(real x) { return rt_log(x); }
-#endif
 
 // v_min/v_max as single instructions.  __builtin_fmin/fmax are IEEE minnum/maxnum, for which the
 // compiler first canonicalises every operand it cannot prove quiet (an extra v_max x,x per use).
@@ -198,9 +176,6 @@ RTK_DEV V3<real> random_unit_vector(uint32_t& s, Counters<COUNT>& cnt) {
 
 // ------------------------------------------------------------------ rays ------
 // Object-space ray for a chain of instance transforms (hittable.h:46-49,101-116).
-#ifndef RTK_CHAIN_PREFETCH
-#define RTK_CHAIN_PREFETCH 1
-#endif
 template <uint32_t FEAT>
 constexpr bool kChainPrefetch = (FEAT & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_LDS_BOXES)) == kFeatAll || (FEAT & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE)) == kFeatQuadBox;
 // The constants of the first two steps of a chain are requested together, in front of the branches that pick them: walking
@@ -229,7 +204,7 @@ RTK_DEV void apply_chain(const ChainRec<real>* __restrict__ chains, uint32_t cha
         }
     };
     int first = 0;
-    if constexpr (PREFETCH && RTK_CHAIN_PREFETCH) {
+    if constexpr (PREFETCH) {
         const int r0 = ch.is_rotate[0], r1 = ch.is_rotate[1];
         const real a0 = ch.a[0], b0 = ch.b[0], c0 = ch.c[0], a1 = ch.a[1], b1 = ch.b[1], c1 = ch.c[1];
         if (n > 0) step(r0, a0, b0, c0);
@@ -253,7 +228,7 @@ RTK_DEV void unapply_chain(const ChainRec<real>* __restrict__ chains, uint32_t c
             p = p + mk(a, b, c);
         }
     };
-    if constexpr (PREFETCH && RTK_CHAIN_PREFETCH) {
+    if constexpr (PREFETCH) {
         const int r0 = ch.is_rotate[0], r1 = ch.is_rotate[1];
         const real a0 = ch.a[0], b0 = ch.b[0], c0 = ch.c[0], a1 = ch.a[1], b1 = ch.b[1], c1 = ch.c[1];
         for (int k = count - 1; k >= 2; k--) step(ch.is_rotate[k], ch.a[k], ch.b[k], ch.c[k]);
@@ -479,11 +454,9 @@ struct Lane {
     // F_F32_BOX kernels: the ray as the f32 culling boxes see it -- 1/d and o/d in float, the query interval rounded
     // outward.  inv and oi above are dead there.
     V3<float> inv32, oi32;
-#if RTK_SIGNED_SLAB
     V3<float> oi32_lo;  // oi32 holds the UPPER bracket of o/d, this the lower one (see begin_culling32)
-#endif
     float tmin32, tmax32;
-    V3<float> inv32s, oi32s; // lean MIXED kernel (RTK_CH_SCALED): inv32 and oi32 times 1 / (end of the current interval), see rescale32
+    V3<float> inv32s, oi32s; // lean MIXED kernel: inv32 and oi32 times 1 / (end of the current interval), see rescale32
     float m2slack32;         // COMPACT kernels with centre / half-extent boxes: -2 x the ray's slack (slab_test32_che)
     real a, inv_a, tm;       // d.d (sphere.h:35, hoisted likewise) and 1/(d.d) for divide_by; ray time
     real tmin, best_t;       // current query interval: (tmin, closest so far)
@@ -533,7 +506,6 @@ RTK_DEV void begin_culling32(Lane<real>& L, V3<real> o, V3<real> d, float extent
     const V3<float> d32 = V3<float>{float(d.x), float(d.y), float(d.z)};
     L.inv32 = V3<float>{__builtin_amdgcn_rcpf(d32.x), __builtin_amdgcn_rcpf(d32.y), __builtin_amdgcn_rcpf(d32.z)};
     L.oi32 = V3<float>{float(o.x) * L.inv32.x, float(o.y) * L.inv32.y, float(o.z) * L.inv32.z};
-#if RTK_SIGNED_SLAB
     if constexpr (CH >= 2) {
         // centre / half-extent boxes that carry only their own share: the origin's -- o/d off by < (2.5 + 1) 2^-23 |o/d| per
         // axis, the two final roundings of the test included -- becomes ONE slack for all axes, 2^-20 of the largest |o/d|
@@ -551,11 +523,10 @@ RTK_DEV void begin_culling32(Lane<real>& L, V3<real> o, V3<real> d, float extent
         L.oi32_lo = V3<float>{L.oi32.x - e.x, L.oi32.y - e.y, L.oi32.z - e.z};
         L.oi32 = V3<float>{L.oi32.x + e.x, L.oi32.y + e.y, L.oi32.z + e.z};
     }
-#endif
-    // (RTK_CH_SCALED, lean MIXED kernel: the constants are multiplied once more by 1 / (end of the interval) <= 1, down to
+    // (lean MIXED kernel: the constants are multiplied once more by 1 / (end of the interval) <= 1, down to
     // 2^-42 / extent -- direction components within 2^-40 .. 2^40 keep every product a normal float; anything else takes
     // the exact path like a zero component does)
-    const float big = (CH == 1 && RTK_CH_SCALED) ? 1.0e12f : 3.0e38f, tiny = (CH == 1 && RTK_CH_SCALED) ? 1.0e-12f : 1.0e-30f;
+    const float big = CH == 1 ? 1.0e12f : 3.0e38f, tiny = CH == 1 ? 1.0e-12f : 1.0e-30f;
     const bool ok = __builtin_fabsf(L.inv32.x) < big && __builtin_fabsf(L.inv32.y) < big && __builtin_fabsf(L.inv32.z) < big &&
                     __builtin_fabsf(d32.x) < big && __builtin_fabsf(d32.y) < big && __builtin_fabsf(d32.z) < big &&
                     __builtin_fabsf(d32.x) > tiny && __builtin_fabsf(d32.y) > tiny && __builtin_fabsf(d32.z) > tiny &&
@@ -579,7 +550,7 @@ RTK_DEV void begin_segment(Lane<real>& L, Counters<COUNT>& cnt, float extent = 0
     if constexpr (MIXED) {
         begin_culling32<CH>(L, L.ro, L.rd, extent);
         sync_interval32(L);
-        if constexpr (CH == 1 && RTK_CH_SCALED) rescale32(L, extent);
+        if constexpr (CH == 1) rescale32(L, extent);
     } else {
         L.inv = mk(real(1) / L.rd.x, real(1) / L.rd.y, real(1) / L.rd.z);
         L.box_kind = regular_direction(L.inv) ? uint32_t(OP_BOX) : kIrregularBox;
@@ -607,7 +578,7 @@ struct NoTie {
     RTK_DEV bool inclusive_wins(uint32_t, uint32_t) const { return true; }
 };
 
-// RTK_CH_SCALED (lean MIXED kernel): the box test works in t' = t * s with s = 1 / (end of the current interval), so that
+// The lean MIXED kernel's box test works in t' = t * s with s = 1 / (end of the current interval), so that
 // the interval is [~0, 1] and its two clamps are the output clamp of v_max3 / v_min3.  The end is tmax32 or, while there is
 // no hit yet, a bound no hit can exceed: origin and every box lie in [-extent, extent]^3, so a hit has
 // t <= 2 sqrt(3) extent / |d| <= 4 extent |1/d_x|.  s is rounded DOWN (v_rcp_f32 is good to an ulp; times 1 - 2^-22), so 1
@@ -669,21 +640,9 @@ RTK_DEV void hit_tri(Lane<real>& L, const Rec* __restrict__ rec, uint32_t units,
 }
 
 // ---- F_F32_BOX: the steps on the MIXED / COMPACT programs (rtk_device_layout.h) -------------------------------
-// Conservative slab test in float: the same min/max structure as slab_test_fma on bounds that were rounded outward
-// and grown for exactly this arithmetic.  v_max3/v_min3 fold the reduction.
-RTK_DEV bool slab_test32(const MixedHead& b, V3<float> oi, V3<float> inv, float tmin, float tmax) {
-    const float t0x = __builtin_fmaf(b.f(0), inv.x, -oi.x), t1x = __builtin_fmaf(b.f(1), inv.x, -oi.x);
-    const float t0y = __builtin_fmaf(b.f(2), inv.y, -oi.y), t1y = __builtin_fmaf(b.f(3), inv.y, -oi.y);
-    const float t0z = __builtin_fmaf(b.f(4), inv.z, -oi.z), t1z = __builtin_fmaf(b.f(5), inv.z, -oi.z);
-    const float nx = raw_min(t0x, t1x), fx = raw_max(t0x, t1x);
-    const float ny = raw_min(t0y, t1y), fy = raw_max(t0y, t1y);
-    const float nz = raw_min(t0z, t1z), fz = raw_max(t0z, t1z);
-    const float near = raw_max(raw_max3(nx, ny, nz), tmin);
-    const float far = raw_min(raw_min3(fx, fy, fz), tmax);
-    return far >= near;  // >= : a tie is let through (conservative)
-}
+// Conservative slab tests in float, on bounds that were rounded outward and grown for exactly this arithmetic; v_max3 / v_min3
+// fold the reduction and a tie is let through (>=).
 // UNITS = length of a box record: 1 in the MIXED program (32-byte units), 2 in the COMPACT one (16-byte units)
-#if RTK_SIGNED_SLAB
 // The sign-selected form: which bound of an axis is the near plane depends only on the sign of that direction component,
 // known per ray -- three wave-level masks (SGPR pairs, taken once at the loop's entry: no lane changes its ray inside it)
 // pick it with six v_cndmask instead of six min/max, so near and far planes can use the two ends of the o/d bracket:
@@ -710,31 +669,13 @@ RTK_DEV void step_box32(Lane<real>& L, const MixedHead& rec, Counters<COUNT>& cn
     const bool hit = slab_test32_signed(rec, L.oi32, L.oi32_lo, L.inv32, L.tmin32, L.tmax32, m);
     L.pc = hit ? L.pc + UNITS : rec.aux;
 }
-#else
-struct SignMasks {};
-template <uint32_t UNITS = 1, typename real, bool COUNT>
-RTK_DEV void step_box32(Lane<real>& L, const MixedHead& rec, Counters<COUNT>& cnt, const SignMasks&) {
-    cnt.inc(C_BOX);
-    const bool hit = slab_test32(rec, L.oi32, L.inv32, L.tmin32, L.tmax32);
-    L.pc = hit ? L.pc + UNITS : rec.aux;
-}
-#endif
 // The lean MIXED kernel's program counters count BYTES (a unit is 32 of them) when its boxes are centre / half-extent
 // records: the box step then needs no shift to turn its pc into an LDS address -- box step 19 -> 18 instructions.
-constexpr uint32_t kChPcUnit = RTK_CH_BYTE_PC ? 32u : 1u;
-// RTK_CH_BOX (MIXED program): the box as centre c = f[0..2] and half-extent h = f[3..5]; per axis
+constexpr uint32_t kChPcUnit = 32u;
+// MIXED program: the box as centre c = f[0..2] and half-extent h = f[3..5]; per axis
 // tc = c/d - o/d, near = tc - h/|d|, far = tc + h/|d| -- which plane is the near one never has to be asked.  The
 // half-extent was grown for exactly this arithmetic (rtk_api.cpp build_mixed_program), so the test is conservative.
-RTK_DEV bool slab_test32_ch(const MixedHead& b, V3<float> oi, V3<float> inv, float tmin, float tmax) {
-    const float tcx = __builtin_fmaf(b.f(0), inv.x, -oi.x), tcy = __builtin_fmaf(b.f(1), inv.y, -oi.y), tcz = __builtin_fmaf(b.f(2), inv.z, -oi.z);
-    const float ax = __builtin_fabsf(inv.x), ay = __builtin_fabsf(inv.y), az = __builtin_fabsf(inv.z);  // source modifiers, no instructions
-    const float nx = __builtin_fmaf(-b.f(3), ax, tcx), fx = __builtin_fmaf(b.f(3), ax, tcx);
-    const float ny = __builtin_fmaf(-b.f(4), ay, tcy), fy = __builtin_fmaf(b.f(4), ay, tcy);
-    const float nz = __builtin_fmaf(-b.f(5), az, tcz), fz = __builtin_fmaf(b.f(5), az, tcz);
-    const float near = raw_max(raw_max3(nx, ny, nz), tmin);
-    const float far = raw_min(raw_min3(fx, fy, fz), tmax);
-    return far >= near;
-}
+// (|1/d| is a source modifier: no instructions.)
 // ... with the ray's slack (COMPACT programs): the planes may each be off by `slack` = -m2slack / 2 in t, so the box is
 // passed when min(far, tmax) - max(near, tmin) >= -2 slack -- at the interval's ends a touch more permissive than
 // clamping the widened planes, never less.
@@ -776,11 +717,7 @@ RTK_DEV bool slab_test32_chs(const MixedHead& b, V3<float> oi, V3<float> inv) {
 template <typename real, bool COUNT>
 RTK_DEV void step_box32_ch(Lane<real>& L, const MixedHead& rec, Counters<COUNT>& cnt) {
     cnt.inc(C_BOX);
-#if RTK_CH_SCALED
     const bool hit = slab_test32_chs(rec, L.oi32s, L.inv32s);
-#else
-    const bool hit = slab_test32_ch(rec, L.oi32, L.inv32, L.tmin32, L.tmax32);
-#endif
     L.pc = hit ? L.pc + kChPcUnit : rec.aux;  // (pcs of this kernel count bytes, and so does the link)
 }
 // A box of those programs for a ray the float test must not judge (zero / out-of-range direction component, origin
@@ -789,7 +726,7 @@ template <bool XF = false, uint32_t UNITS = 1, uint32_t PCU = 1, typename real, 
 RTK_DEV void step_box_mixed_exact(Lane<real>& L, const MixedHead& rec, Counters<COUNT>& cnt, bool compact_ch = false) {
     cnt.inc(C_BOX);
     Slot<real> b;
-    if ((RTK_CH_BOX && UNITS == 1) || (UNITS == 2 && compact_ch)) {  // centre / half-extent records (the MIXED program; COMPACT programs of the mesh family)
+    if (UNITS == 1 || (UNITS == 2 && compact_ch)) {  // centre / half-extent records (the MIXED program; COMPACT programs of the mesh family)
         for (int k = 0; k < 3; k++) {
             b.v[2 * k] = real(rec.f(k)) - real(rec.f(3 + k));
             b.v[2 * k + 1] = real(rec.f(k)) + real(rec.f(3 + k));
@@ -806,7 +743,7 @@ RTK_DEV void step_box_mixed_exact(Lane<real>& L, const MixedHead& rec, Counters<
 template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie>
 RTK_DEV void step_sphere_mixed(Lane<real>& L, const MixedHead& head, const MixedHead* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie, float extent) {
     const double radius = reinterpret_cast<const double*>(rec + 1)[0];
-    hit_sphere<false, true, RTK_CH_BOX && RTK_CH_SCALED>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), real(radius), 2u * PCU, cnt, tie, extent);
+    hit_sphere<false, true, true>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), real(radius), 2u * PCU, cnt, tie, extent);
 }
 // ... and on a COMPACT record (3 units): the head (centre) is usually in registers already, the radius follows it.
 template <bool XF, typename real, bool COUNT, typename Tie>
@@ -822,7 +759,7 @@ RTK_DEV void step_other_mixed(Lane<real>& L, const MixedHead* __restrict__ rec, 
     } else if (kind == OP_SPHERE_MOVING) {
         const double* cont = reinterpret_cast<const double*>(rec + 1);
         const V3<real> cc = mk(real(rec->d(0)), real(rec->d(1)), real(rec->d(2))) + scale(L.tm, mk(real(cont[2]), real(cont[3]), real(cont[4])));
-        hit_sphere<false, true, RTK_CH_BOX && RTK_CH_SCALED>(L, cc, real(cont[0]), 3u * PCU, cnt, tie, extent);
+        hit_sphere<false, true, true>(L, cc, real(cont[0]), 3u * PCU, cnt, tie, extent);
     } else {
         L.pc += uint32_t(mixed_units(kind)) * PCU;  // unreachable for a validated sphere-only program
     }
@@ -843,16 +780,16 @@ RTK_DEV void step_sphere(Lane<real>& L, const Slot<real>& rec, Counters<COUNT>& 
     hit_sphere<XF, false>(L, mk(rec.v[0], rec.v[1], rec.v[2]), rec.v[3], 1u, cnt, tie);
 }
 
-// Which COMPACT programs hold centre / half-extent box records (RTK_CH_COMPACT): those of the mesh family -- the same rule
+// Which COMPACT programs hold centre / half-extent box records: those of the mesh family -- the same rule
 // in rtk_api.cpp, which also sets SceneView::compact_ch for the counting kernel, the one kernel that serves every family.
 // (Measured: C4 62.3 -> 59.7 ms; the Cornell box and book 2, thin axis-aligned quads at coordinates in the hundreds
 // and thousands, lose 2-4 % to the all-axes slack and keep the sign-selected test with its per-axis bracket.)
 template <uint32_t FEAT>
-constexpr bool kCompactChStatic = RTK_CH_COMPACT && (FEAT & F_F32_BOX) != 0 && (FEAT & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE | F_LDS_BOXES)) == kFeatMesh;
+constexpr bool kCompactChStatic = (FEAT & F_F32_BOX) != 0 && (FEAT & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE | F_LDS_BOXES)) == kFeatMesh;
 template <uint32_t FEAT, bool COUNT, typename real>
 RTK_DEV bool compact_ch_records(const SceneView<real>& sc) {
     if constexpr (kCompactChStatic<FEAT>) return true;
-    else if constexpr (RTK_CH_COMPACT && COUNT) return sc.compact_ch != 0;
+    else if constexpr (COUNT) return sc.compact_ch != 0;
     else return false;
 }
 // Every other record kind (moving sphere, quad, triangle, chain switch, the three medium ops, a box met by a ray the
@@ -967,13 +904,8 @@ RTK_DEV void step_other(Lane<real>& L, const Rec* __restrict__ rec, const SceneV
 
 // ------------------------------------------------------------------ textures --
 // perlin::noise (perlin.h:14-37,72-89).
-#if RTK_COLD_PERLIN
-#define RTK_PERLIN_FN RTK_NOINLINE
-#else
-#define RTK_PERLIN_FN RTK_DEV
-#endif
 template <typename real, bool COUNT>
-RTK_PERLIN_FN real perlin_noise(const PerlinRec<real>& pn, V3<real> p, Counters<COUNT>& cnt) {
+RTK_DEV real perlin_noise(const PerlinRec<real>& pn, V3<real> p, Counters<COUNT>& cnt) {
     cnt.inc(C_NOISE);
     const real fx = rt_floor(p.x), fy = rt_floor(p.y), fz = rt_floor(p.z);
     const real u = p.x - fx, v = p.y - fy, w = p.z - fz;
@@ -1001,29 +933,13 @@ RTK_PERLIN_FN real perlin_noise(const PerlinRec<real>& pn, V3<real> p, Counters<
 // (acos, atan2, sin: long polynomial expansions) that few lanes ever reach; inlined into the shade step they sit on top of
 // everything live there and account for most of the full-feature kernel's scratch (compile-only ablation,
 // tools/kernel_resources.py: without the two 248 VGPRs and no scratch at the 2-wave bound, with them 256 + 292 B).  Kept OUT
-// OF LINE (RTK_COLD_UV / RTK_COLD_NOISE) a call saves and restores around itself on the cold path only: 248 VGPRs + 32 B at
+// OF LINE a call saves and restores around itself on the cold path only: 248 VGPRs + 32 B at
 // two waves per SIMD, 168 + 352 B at three (it was 168 + 640 B) -- and three waves then win: C5 at 32 spp 42.05 ms (inline,
 // 2 waves) -> 40.5 (out of line, 2 waves) -> 38.85 (out of line, 3 waves); out of line at 3 waves with only the uv function
 // moved: 47.3.  Same image.  (Moving more -- pow, perlin::turb, the image lookup, get_lighting, the media's log -- was
 // measured too and lost: 43.0-46.7 ms at three waves.)
-#ifndef RTK_COLD_UV
-#define RTK_COLD_UV 1
-#endif
-#ifndef RTK_COLD_NOISE
-#define RTK_COLD_NOISE 1
-#endif
-#if RTK_COLD_UV
-#define RTK_UV_FN __device__ __attribute__((noinline))
-#else
-#define RTK_UV_FN RTK_DEV
-#endif
-#if RTK_COLD_NOISE
-#define RTK_NOISE_FN __device__ __attribute__((noinline))
-#else
-#define RTK_NOISE_FN RTK_DEV
-#endif
 template <typename real>
-RTK_UV_FN void sphere_uv(real ox, real oy, real oz, real* __restrict__ uv) {  // sphere.h:67-73 on the outward unit normal
+RTK_NOINLINE void sphere_uv(real ox, real oy, real oz, real* __restrict__ uv) {  // sphere.h:67-73 on the outward unit normal
     const real pi = real(3.1415926535897932385);
     const real theta = rt_acos(-oy);
     const real phi = rt_atan2(-oz, ox) + pi;
@@ -1031,16 +947,11 @@ RTK_UV_FN void sphere_uv(real ox, real oy, real oz, real* __restrict__ uv) {  //
     uv[1] = theta / pi;
 }
 template <typename real>
-RTK_NOISE_FN real noise_tail(real arg) { return real(1) + rt_sin(arg); }  // texture.h:115: 1 + sin(scale * p.z + 10 * turb)
+RTK_NOINLINE real noise_tail(real arg) { return real(1) + rt_sin(arg); }  // texture.h:115: 1 + sin(scale * p.z + 10 * turb)
 
 // texture::value (texture.h:20-120); checker nesting is followed iteratively.
-#if RTK_COLD_TEX
-#define RTK_TEX_FN RTK_NOINLINE
-#else
-#define RTK_TEX_FN RTK_DEV
-#endif
 template <typename real, bool COUNT>
-RTK_TEX_FN V3<real> texture_value(const SceneView<real>& sc, int tex, real u, real v, V3<real> p, Counters<COUNT>& cnt) {
+RTK_DEV V3<real> texture_value(const SceneView<real>& sc, int tex, real u, real v, V3<real> p, Counters<COUNT>& cnt) {
     for (;;) {
         const TextureRec<real>& t = sc.textures[tex];
         if (t.kind == RTK_TEX_SOLID) return ld3(t.color);
@@ -1145,17 +1056,9 @@ RTK_DEV void make_surface_mixed(const MixedHead* __restrict__ prog, uint32_t bes
 
 
 // The barycentrics of the winning triangle for its UVs (triangle.h:96-110): triangle::hit once more on the winner, with an
-// open interval.  RTK_COLD_TRI_UV keeps it out of line (A/B: the mesh kernels at four waves per SIMD).
-#ifndef RTK_COLD_TRI_UV
-#define RTK_COLD_TRI_UV 0
-#endif
-#if RTK_COLD_TRI_UV
-#define RTK_TRI_UV_FN RTK_NOINLINE
-#else
-#define RTK_TRI_UV_FN RTK_DEV
-#endif
+// open interval.  Inline (keeping it out of line was tried on the mesh kernels at four waves per SIMD and not kept).
 template <typename real, typename Rec>
-RTK_TRI_UV_FN void tri_barycentrics(const Rec* __restrict__ rec, real ox, real oy, real oz, real dx, real dy, real dz, float* fa, float* fb, float* fg) {
+RTK_DEV void tri_barycentrics(const Rec* __restrict__ rec, real ox, real oy, real oz, real dx, real dy, real dz, float* fa, float* fb, float* fg) {
     real tt;
     float a = 0, b = 0, g = 0;
     tri_test(rec, mk(ox, oy, oz), mk(dx, dy, dz), -real_inf<real>(), real_inf<real>(), tt, a, b, g);
@@ -1407,12 +1310,6 @@ RTK_DEV bool shade(Lane<real>& L, const ProgT* __restrict__ hit_rec, const Scene
     return shade_surface<real, FEAT>(L, sf, sc, mats, cnt RTK_SHADE_PROF_ARG);
 }
 
-RTK_DEV uint8_t to_byte(double x) {  // Camera.txt:29-34,77-83
-    double g = x > 0 ? __builtin_sqrt(x) : 0.0;
-    g = g < 0.000 ? 0.000 : (g > 0.999 ? 0.999 : g);
-    return uint8_t(int(255.999 * g));
-}
-
 // ------------------------------------------------------------------ kernel ----
 // Persistent waves + a wave-level ballot scheduler.
 //
@@ -1527,20 +1424,13 @@ RTK_DEV void store_partial(real* __restrict__ partial, int item, int pix, V3<rea
     base[128] = sum.z;
 }
 
-#ifndef RTK_SPLIT_MATERIALS_IN_LDS
-#define RTK_SPLIT_MATERIALS_IN_LDS 1
-#endif
-#ifndef RTK_THREADS_ALL_F64
-#define RTK_THREADS_ALL_F64 768   // workgroup bound of the full-feature f64 kernels: 3 waves per SIMD, 168 VGPRs (A/B builds: 512 = 2 waves, 1024 = 4)
-#endif
 // Workgroup-size bound = register budget: 1024 threads -> 4 waves per SIMD, 128 VGPRs; 768 -> 3 waves, 168 VGPRs;
 // 512 -> 2 waves, 256 VGPRs.  Measured on C2 (lean f64 kernel): 2 waves 93.8 ms, 3 waves 73.5 ms, 4 waves 68.5 ms
 // per frame (the 4-wave build spills a few values in the shade path).  Same-box A/B for the other f64 kernels
 // (tools/ab/run_ab.sh): quad/box subset on C3 43.3 ms at 4 waves vs 48.7 at 3; mesh subset on C4 no difference;
 // the full-feature kernel, which needs far more registers (~560 B/lane of spills at 168), is fastest at 2 waves.
-#ifndef RTK_THREADS_MESH_F64
-#define RTK_THREADS_MESH_F64 1024   // workgroup bound of the f64 mesh kernels: 4 waves per SIMD, 128 VGPRs (C4 60.1 -> 53.0 ms; 768 = 3 waves)
-#endif
+constexpr int kThreadsAllF64 = 768;    // workgroup bound of the full-feature f64 kernels: 3 waves per SIMD, 168 VGPRs (measured against 512 = 2 waves and 1024 = 4)
+constexpr int kThreadsMeshF64 = 1024;  // workgroup bound of the f64 mesh kernels: 4 waves per SIMD, 128 VGPRs (C4 60.1 -> 53.0 ms; 768 = 3 waves)
 // (round 3) the f64 mesh kernels run at four waves per SIMD when the whole program is staged in LDS (C4 60.1 -> 53.0 ms, 44 B of
 // scratch); with the program, or all but its boxes, in memory a fourth wave only adds pressure on L2 (C4, program in global
 // memory: 23.2 ms at three waves, 33.6 at four), so those keep 768 threads.
@@ -1552,8 +1442,8 @@ constexpr int max_threads_of(uint32_t feat, bool in_lds) {
     // come from memory (program in global memory 25.5 vs 29.1 ms at three; slot program with its boxes in LDS 25.6 vs 29.0).
     const bool hot_cold = (feat & F_LDS_BOXES) != 0 && (feat & F_F32_BOX) != 0;
     if (sizeof(real) == 8)
-        return scene_feat == kFeatAll ? ((in_lds || hot_cold) ? RTK_THREADS_ALL_F64 : 512)
-                                      : ((scene_feat == kFeatLean || scene_feat == kFeatQuadBox) ? 1024 : (in_lds ? RTK_THREADS_MESH_F64 : 768));
+        return scene_feat == kFeatAll ? ((in_lds || hot_cold) ? kThreadsAllF64 : 512)
+                                      : ((scene_feat == kFeatLean || scene_feat == kFeatQuadBox) ? 1024 : (in_lds ? kThreadsMeshF64 : 768));
     return 768;
 }
 template <typename real, uint32_t FEAT, bool IN_LDS>
@@ -1561,23 +1451,43 @@ constexpr int max_threads() {
     return max_threads_of<real>(FEAT, IN_LDS);
 }
 
+// Wave priorities (s_setprio) by scheduler phase.  The SIMD's instruction arbiter serves the higher priority first (then the
+// older wave); waves inside a traversal loop -- short dependent chains, an LDS round trip per step -- lose issue slots to
+// waves that are in a shade step (long independent runs of arithmetic) exactly when a stall costs them most.  Measured on
+// C2 (tools/ab, same box): no priorities 21.93-22.09 ms; box loop 1 / 2 / 3: 21.55 / 21.53 / 21.52; box 2 + sphere loop 1:
+// 21.45-21.49 (kept); raising the shade step instead: 22.5.
+constexpr int kBoxLoopPrio = 2, kSphereLoopPrio = 1, kPrimLoopPrio = 1;  // (prim: the quad and triangle loops)
+// Box steps per trip around the box loop's scalar checks.  Measured per kernel (tools/ab): the MIXED sphere kernel
+// (long runs of cheap box steps) 27.8 / 26.3 / 25.5 / 24.8 / 24.6 ms at 1 / 2 / 4 / 6 / 8; the reference-order
+// kernels lose with any unrolling (C2 53.2 -> 54.8 at 4; C4 62.6 -> 64.2), the full-feature kernel gains 1 % at 2;
+// the fused-slab sphere kernels (f32 mode, f64 fallback) behave like the MIXED one (f32: 20.6 -> 18.8 ms at 8).
+constexpr int kUnrollMixed = 8;
+// the boxes-in-LDS kernels: C4 49.9 / 48.2 / 47.8 / 49.7 ms at 1 / 2 / 4 / 8 (64 spp), C5 +0.8 % at 4
+constexpr int kUnrollSplit = 4;
+// the subset kernels, now that their primitive tests ride inside the loop: quad/box (C3) 30.5 / 29.4 / 30.7 ms at
+// 1 / 2 / 4; mesh with the program in LDS (C4 f32) 28.8 / 25.5 / 25.3
+constexpr int kUnrollQuadBox = 2, kUnrollMesh = 4, kUnrollCompactQuadBox = 2, kUnrollCompactMesh = 4;
+// the lean kernel with the exact slab test (sphere scenes in the reference order): C2 50.7 / 50.0 / 52.0 ms at 1 / 2 / 4
+constexpr int kUnrollLean = 2;
+constexpr int kUnrollCold = 4;  // the hot/cold full-feature kernel: C5 45.8 / 42.9 / 42.2 / 42.5 / 42.8 ms at 1 / 2 / 4 / 6 / 8
+// Lanes of a wave that must sit on a triangle / quad record for those tests to ride along inside the box loop (the
+// measurements are beside the two blocks).
+constexpr int kTriRide = 16, kQuadRide = 16;
+#ifndef RTK_DEV_MASK_OFF
+#define RTK_DEV_MASK_OFF 0u   // register-pressure experiments (tools/kernel_resources.py): feature bits compiled out of every kernel
+#endif
+
 template <typename real, uint32_t FEAT_ALL, bool COUNT, bool IN_LDS>
 __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_render_kernel(SceneView<real> sc, const CameraRec<real>* __restrict__ cam_ptr, TileMap tmap, uint32_t seed,
                                                           real* __restrict__ partial, unsigned long long* __restrict__ counters,
                                                           unsigned int* __restrict__ tile_counter, const int32_t* __restrict__ tile_order,
                                                           unsigned int* __restrict__ tile_cost, uint32_t diag) {
     extern __shared__ __align__(16) unsigned char lds_program[];
-#ifndef RTK_CH_LDS_ABS
-#define RTK_CH_LDS_ABS 1
-#endif
-    if constexpr (RTK_CH_BOX && RTK_CH_BYTE_PC && RTK_CH_LDS_ABS && IN_LDS) {
+    if constexpr (IN_LDS) {
         // (lean MIXED kernel: byte pcs are used as LDS addresses, see rec_at) -- render nothing rather than garbage otherwise
         typedef const unsigned char __attribute__((address_space(3))) * lds_bytes_t;
         if (uint32_t(size_t((lds_bytes_t)lds_program)) != 0u) return;
     }
-#ifndef RTK_DEV_MASK_OFF
-#define RTK_DEV_MASK_OFF 0u   // register-pressure experiments (tools/kernel_resources.py): feature bits compiled out of every kernel
-#endif
     constexpr bool BRACKET = (FEAT_ALL & F_SPHERE_MEDIA_ONLY) == 0;  // generic media (OP_MED_BEGIN / MID / END) may occur in the program
     // (measured and not done: also compiling get_lighting and the radiance registers out of the restricted variant -- 80 instead
     // of 96 B of scratch, and C5 34.6 instead of 32.0 ms at 32 spp)
@@ -1592,9 +1502,9 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
     // program (COLD): the whole "hot" program -- f32 culling boxes, spheres, every rare record -- in which each run of quads
     // or triangles is ONE two-unit record {kind, count, first unit in the cold array}; the quads and triangles themselves
     // ("cold": 144 / 80 bytes each, tested a few times per sample) stay in memory (SceneView::program_cold).
-    constexpr bool CH = RTK_CH_BOX && MIXED && !COMPACT;  // the MIXED program's boxes are centre / half-extent records
+    constexpr bool CH = MIXED && !COMPACT;  // the MIXED program's boxes are centre / half-extent records
     constexpr bool CHE = COMPACT && kCompactChStatic<FEAT>;  // ... and so are the COMPACT programs' of the mesh family, with a per-ray slack
-    constexpr bool CHE_RT = RTK_CH_COMPACT && COMPACT && COUNT && !CHE;  // the counting kernel on any family's COMPACT program: asks the scene
+    constexpr bool CHE_RT = COMPACT && COUNT && !CHE;  // the counting kernel on any family's COMPACT program: asks the scene
     [[maybe_unused]] const bool che_rt = CHE_RT && sc.compact_ch != 0;
     constexpr int kCulling = CH ? 1 : (CHE ? 2 : (CHE_RT ? 3 : 0));
     constexpr bool SPLIT = LDS_PART && !COMPACT;
@@ -1651,7 +1561,6 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
         for (int k = threadIdx.x; k < n_kind_words; k += blockDim.x) kdst[k] = kind_words[k];
         uint2* rdst = reinterpret_cast<uint2*>(lds_program + box_bytes + ((size_t(n_kind_words) * 4 + 7) & ~size_t(7)));
         for (int k = threadIdx.x; k < n_rank_words; k += blockDim.x) rdst[k] = box_rank[k];
-#if RTK_SPLIT_MATERIALS_IN_LDS
         // ... and the material table behind them when the launcher found room (tmap.mats_lds_offset > 0): every shade step reads it
         if (tmap.mats_lds_offset > 0) {
             const int n_mat16 = sc.n_materials * int(sizeof(MaterialRec<real>) / 16);
@@ -1660,7 +1569,6 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
             for (int k = threadIdx.x; k < n_mat16; k += blockDim.x) mdst[k] = msrc[k];
             mats = reinterpret_cast<const MaterialRec<real>*>(lds_program + tmap.mats_lds_offset);
         }
-#endif
         if constexpr ((FEAT & F_TEXTURE) != 0) {  // the Perlin tables too, when the launcher found room (tmap.perlin_lds_offset > 0)
             if (tmap.perlin_lds_offset > 0) {
                 const int n16 = sc.n_perlins * int(sizeof(PerlinRec<real>) / 16);
@@ -1681,13 +1589,13 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
     constexpr uint32_t kPcUnit = CH ? kChPcUnit : 1u;  // what one unit of the program adds to a pc (CH: pcs count bytes)
     // the record that starts at pc
     auto rec_at = [&](uint32_t pc) -> const ProgRec* {
-        if constexpr (CH && RTK_CH_BYTE_PC && IN_LDS && RTK_CH_LDS_ABS) {
+        if constexpr (CH && IN_LDS) {
             // The staged program starts at LDS address 0 -- this kernel declares no static LDS, so its dynamic segment does
             // (checked when the kernel starts, and on the code object by tests/test_abi_and_host.py) -- hence a byte pc IS
             // the LDS address: the box step's next read needs no address arithmetic at all (C2 19.35 -> 18.96 ms).
             typedef const unsigned char __attribute__((address_space(3))) * lds_bytes_t;
             return reinterpret_cast<const ProgRec*>((const unsigned char*)(lds_bytes_t)(size_t)pc);
-        } else if constexpr (CH && RTK_CH_BYTE_PC) return reinterpret_cast<const ProgRec*>(reinterpret_cast<const unsigned char*>(prog) + pc);
+        } else if constexpr (CH) return reinterpret_cast<const ProgRec*>(reinterpret_cast<const unsigned char*>(prog) + pc);
         else return prog + pc;
     };
     auto head_at = [&](uint32_t pc) -> CurRec {
@@ -1708,7 +1616,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
         } else {
             const BoxRec<real> b = lds_boxes[at];
             Slot<real> s;
-#pragma unroll
+            #pragma unroll
             for (int k = 0; k < 6; k++) s.v[k] = b.v[k];
             s.kind_payload = OP_BOX;
             s.aux = b.aux;
@@ -1727,28 +1635,8 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
     // exact ties between primitives are resolved by the reference's ranks in the kernels that run re-grouped hierarchies
     // (the quad/box subset kernel serves the fast order without a flag of its own)
     // f64 kernels only: the float kernels are not bit-exact against the reference anyway, and the lean one has no register to spare
-// Wave priorities (s_setprio) by scheduler phase.  The SIMD's instruction arbiter serves the higher priority first (then the
-// older wave); waves inside a traversal loop -- short dependent chains, an LDS round trip per step -- lose issue slots to
-// waves that are in a shade step (long independent runs of arithmetic) exactly when a stall costs them most.  Measured on
-// C2 (tools/ab, same box): no priorities 21.93-22.09 ms; box loop 1 / 2 / 3: 21.55 / 21.53 / 21.52; box 2 + sphere loop 1:
-// 21.45-21.49 (kept); raising the shade step instead: 22.5.
-#ifndef RTK_AB_BOX_PRIO
-#define RTK_AB_BOX_PRIO 2
-#endif
-#ifndef RTK_AB_PRIM_PRIO
-#define RTK_AB_PRIM_PRIO 1   // quad and triangle loops
-#endif
-#ifndef RTK_AB_SPH_PRIO
-#define RTK_AB_SPH_PRIO 1
-#endif
-#ifndef RTK_AB_SHADE_PRIO
-#define RTK_AB_SHADE_PRIO 0
-#endif
-#ifndef RTK_AB_NO_TIE
-#define RTK_AB_NO_TIE 0   // tools/ab: what the tie rule costs
-#endif
-    constexpr bool TIE = !RTK_AB_NO_TIE && sizeof(real) == 8 && ((FEAT & (F_FMA_BOX | F_F32_BOX)) != 0 || (FEAT & ~uint32_t(F_MATTE)) == kFeatQuadBox);
-    const TieCtx<TIE, decltype(kind_of_hit)> tie{TIE ? (COLD ? sc.tie_rank_hot : (MIXED ? sc.tie_rank : sc.tie_rank_slot)) : nullptr, kind_of_hit, (CH && RTK_CH_BYTE_PC) ? 5u : 0u};
+    constexpr bool TIE = sizeof(real) == 8 && ((FEAT & (F_FMA_BOX | F_F32_BOX)) != 0 || (FEAT & ~uint32_t(F_MATTE)) == kFeatQuadBox);
+    const TieCtx<TIE, decltype(kind_of_hit)> tie{TIE ? (COLD ? sc.tie_rank_hot : (MIXED ? sc.tie_rank : sc.tie_rank_slot)) : nullptr, kind_of_hit, CH ? 5u : 0u};
     // The hand-out order of the tiles (learned from the previous frame) is staged behind the program when the host
     // found room for it (tmap.order_in_lds): a lookup per work item from LDS instead of a cold global load.
     if constexpr ((FEAT & F_XFORM) != 0 && (IN_LDS || LDS_PART)) {
@@ -1823,17 +1711,12 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
             const MixedHead run = head_at(hot);
             const uint32_t at = run.aux + sub * units;
             L.pc = uint32_t(n_records) + at;
-#ifndef RTK_COLD_QUAD_PREFETCH
-#define RTK_COLD_QUAD_PREFETCH 1
-#endif
-            if constexpr (QUAD && RTK_COLD_QUAD_PREFETCH) {
+            if constexpr (QUAD) {
                 QuadRegs regs;
                 const double* __restrict__ src = reinterpret_cast<const double*>(cold + at);
-#pragma unroll
+                #pragma unroll
                 for (int e = 0; e < 18; e++) regs.q[e] = src[e];
                 hit_quad<XF, MIXED>(L, &regs, 0u, cnt, tie);
-            } else if constexpr (QUAD) {
-                hit_quad<XF, MIXED>(L, reinterpret_cast<const ProgRec*>(cold + at), 0u, cnt, tie);
             } else {
                 hit_tri<XF, MIXED>(L, reinterpret_cast<const ProgRec*>(cold + at), 0u, cnt, tie);
             }
@@ -1957,42 +1840,11 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
             const int eighths = sel == 0 ? (kFamily == kFeatMesh ? 3 : 2) : sel;  // mesh subset: 3/8 (C4 42.4 -> 41.1 ms)  // measured on C2 (votes now cost ~2 box steps, spheres ride along): 2/8 of the starters 30.9 ms, 3/8 31.8, 4/8 32.4
             const int frac = (n_box * eighths) >> 3;
             const int keep = frac > 8 ? frac : 8;
-            // Box steps per trip around the loop's scalar checks.  Measured per kernel (tools/ab): the MIXED sphere kernel
-            // (long runs of cheap box steps) 27.8 / 26.3 / 25.5 / 24.8 / 24.6 ms at 1 / 2 / 4 / 6 / 8; the reference-order
-            // kernels lose with any unrolling (C2 53.2 -> 54.8 at 4; C4 62.6 -> 64.2), the full-feature kernel gains 1 % at 2;
-            // the fused-slab sphere kernels (f32 mode, f64 fallback) behave like the MIXED one (f32: 20.6 -> 18.8 ms at 8).
-#ifndef RTK_UNROLL_MIXED
-#define RTK_UNROLL_MIXED 8
-#endif
-                        // the boxes-in-LDS kernels: C4 49.9 / 48.2 / 47.8 / 49.7 ms at 1 / 2 / 4 / 8 (64 spp), C5 +0.8 % at 4
-            // the subset kernels, now that their primitive tests ride inside the loop: quad/box (C3) 30.5 / 29.4 / 30.7 ms at
-            // 1 / 2 / 4; mesh with the program in LDS (C4 f32) 28.8 / 25.5 / 25.3
-            // the lean kernel with the exact slab test (sphere scenes in the reference order): C2 50.7 / 50.0 / 52.0 ms at 1 / 2 / 4
-#ifndef RTK_UNROLL_LEAN
-#define RTK_UNROLL_LEAN 2
-#endif
-#ifndef RTK_UNROLL_QUADBOX
-#define RTK_UNROLL_QUADBOX 2
-#endif
-#ifndef RTK_UNROLL_MESH
-#define RTK_UNROLL_MESH 4
-#endif
-#ifndef RTK_UNROLL_SPLIT
-#define RTK_UNROLL_SPLIT 4
-#endif
-#ifndef RTK_UNROLL_COMPACT_QUADBOX
-#define RTK_UNROLL_COMPACT_QUADBOX 2
-#endif
-#ifndef RTK_UNROLL_COMPACT_MESH
-#define RTK_UNROLL_COMPACT_MESH 4
-#endif
-#ifndef RTK_UNROLL_COLD
-#define RTK_UNROLL_COLD 4   // the hot/cold full-feature kernel: C5 45.8 / 42.9 / 42.2 / 42.5 / 42.8 ms at 1 / 2 / 4 / 6 / 8
-#endif
-            constexpr int kBoxUnroll = COLD ? RTK_UNROLL_COLD : (SPLIT && RTK_UNROLL_SPLIT > 0) ? RTK_UNROLL_SPLIT
-                                       : (((MIXED && !COMPACT) || FEAT == (kFeatLean | uint32_t(F_FMA_BOX))) ? RTK_UNROLL_MIXED
-                                          : (kFamily == kFeatAll ? 2 : (kFamily == kFeatQuadBox ? (COMPACT ? RTK_UNROLL_COMPACT_QUADBOX : RTK_UNROLL_QUADBOX)
-                                                                       : (kFamily == kFeatMesh ? (COMPACT ? RTK_UNROLL_COMPACT_MESH : RTK_UNROLL_MESH) : RTK_UNROLL_LEAN))));
+            // box steps per trip around the loop's scalar checks: the per-family table above the kernel
+            constexpr int kBoxUnroll = COLD ? kUnrollCold : SPLIT ? kUnrollSplit
+                                       : (((MIXED && !COMPACT) || FEAT == (kFeatLean | uint32_t(F_FMA_BOX))) ? kUnrollMixed
+                                          : (kFamily == kFeatAll ? 2 : (kFamily == kFeatQuadBox ? (COMPACT ? kUnrollCompactQuadBox : kUnrollQuadBox)
+                                                                       : (kFamily == kFeatMesh ? (COMPACT ? kUnrollCompactMesh : kUnrollMesh) : kUnrollLean))));
             CurRec cur;  // the record at L.pc (its first 32 bytes in the MIXED / COMPACT layouts), held in registers: one LDS round trip per step
             uint32_t k = kind;
             // the record at L.pc -> cur, its kind -> k.  SPLIT: the kind comes from the LDS nibble table and only boxes are
@@ -2016,16 +1868,12 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
             const uint32_t box_kind = L.box_kind;  // a lane with an irregular ray matches nothing here: it never steps in this loop
             int remaining;
             [[maybe_unused]] SignMasks signs;
-#if RTK_SIGNED_SLAB
             if constexpr (MIXED && !CH && !CHE) {  // per-lane direction signs as wave masks; rays do not change inside this loop
                 signs.x = __ballot(L.inv32.x < 0.0f);
                 signs.y = __ballot(L.inv32.y < 0.0f);
                 signs.z = __ballot(L.inv32.z < 0.0f);
             }
-#endif
-#if RTK_AB_BOX_PRIO
-            __builtin_amdgcn_s_setprio(RTK_AB_BOX_PRIO);
-#endif
+            __builtin_amdgcn_s_setprio(kBoxLoopPrio);
             // Sphere tests ride along: whenever `sphere_min` lanes of the wave sit on a sphere record, they are
             // stepped here, inside the box loop, instead of waiting for the loop to drain and a vote to pick
             // them (a vote round costs about two box steps).  Those lanes then return to box records, which
@@ -2043,7 +1891,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                     fetch();
                     L.kind = k;
                 }
-#pragma unroll
+                #pragma unroll
                 for (int extra = 1; extra < kBoxUnroll; extra++) {
                     // further box steps before the loop's scalar checks (vote / sphere / exit): the checks are a
                     // dependent v_cmp -> s_bcnt1 -> s_cmp -> branch chain per step, and the kernel is latency-bound
@@ -2071,19 +1919,10 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                     }
                     RTK_PROF_MARK(2, 1, n_ride)
                 }
-#ifndef RTK_TRI_RIDE
-#define RTK_TRI_RIDE 16
-#endif
-#ifndef RTK_TRI_RIDE_ALL
-#define RTK_TRI_RIDE_ALL 1
-#endif
-#ifndef RTK_QUAD_RIDE
-#define RTK_QUAD_RIDE 16
-#endif
-                if constexpr ((FEAT & F_TRI) != 0 && (SPLIT || RTK_TRI_RIDE_ALL) && RTK_TRI_RIDE > 0) {
+                if constexpr ((FEAT & F_TRI) != 0) {
                     // triangle tests ride along as well (mesh scenes: a bvh leaf is a box and one or two triangles):
                     // C4 47.8 -> 42.5 ms at 16 lanes (8: 42.8, 24: 43.6)
-                    if (popcount64(__ballot(k == OP_TRI)) >= RTK_TRI_RIDE) {
+                    if (popcount64(__ballot(k == OP_TRI)) >= kTriRide) {
                         if (k == OP_TRI) {
                             if constexpr (COLD) {
                                 cold_step(std::false_type{}, k);
@@ -2098,8 +1937,8 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                 }
                 // ... and quad tests in the quad/box subset kernels (C3 31.9 -> 30.4 ms at 16 lanes, 30.8 at 24); the
                 // full-feature kernel has no registers for it (C5 298 -> 316 ms)
-                if constexpr ((FEAT & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE)) == kFeatQuadBox && RTK_QUAD_RIDE > 0) {
-                    if (popcount64(__ballot(k == OP_QUAD)) >= RTK_QUAD_RIDE) {
+                if constexpr ((FEAT & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE)) == kFeatQuadBox) {
+                    if (popcount64(__ballot(k == OP_QUAD)) >= kQuadRide) {
                         if (k == OP_QUAD) {
                             hit_quad<XF, MIXED>(L, prog + L.pc, kQuadUnits, cnt, tie);
                             fetch();
@@ -2110,9 +1949,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                 remaining = popcount64(__ballot(k == box_kind));
                 RTK_PROF_MARK(1, 1, remaining)
             } while (remaining >= keep);
-#if RTK_AB_BOX_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
         } else if (pick == W_SPHERE) {
             // A bvh leaf usually holds two spheres in a row: same amortisation, half the starters.
             const int ssel = int(diag >> 11) & 7;  // tools/: same for the sphere loop (0 = default)
@@ -2121,9 +1958,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
             CurRec cur = head_at(L.pc);
             uint32_t k = kind;
             int remaining;
-#if RTK_AB_SPH_PRIO
-            __builtin_amdgcn_s_setprio(RTK_AB_SPH_PRIO);
-#endif
+            __builtin_amdgcn_s_setprio(kSphereLoopPrio);
             do {
                 if (k == OP_SPHERE) {
                     if constexpr (COMPACT) step_sphere_compact<XF>(L, cur, prog + L.pc, cnt, tie);
@@ -2141,18 +1976,14 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                 remaining = popcount64(__ballot(k == OP_SPHERE));
                 RTK_PROF_MARK(2, 1, remaining)
             } while (remaining >= keep);
-#if RTK_AB_SPH_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
         } else if ((FEAT & F_QUAD) && pick == W_QUAD) {
           if constexpr ((FEAT & F_QUAD) != 0) {
             // quad::hit.  A box() is six quads in a row (quad.h:86-108): stay while at least half the starters do.
             const int keep = (n_quad >> 1) > 8 ? (n_quad >> 1) : 8;
             uint32_t k = kind;
             int remaining;
-#if RTK_AB_PRIM_PRIO
-            __builtin_amdgcn_s_setprio(RTK_AB_PRIM_PRIO);
-#endif
+            __builtin_amdgcn_s_setprio(kPrimLoopPrio);
             do {
                 if (k == OP_QUAD) {
                     if constexpr (COLD) {
@@ -2166,9 +1997,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                 remaining = popcount64(__ballot(k == OP_QUAD));
                 RTK_PROF_MARK(5, 1, remaining)
             } while (remaining >= keep);
-#if RTK_AB_PRIM_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
           }
         } else if ((FEAT & F_TRI) && pick == W_TRI) {
           if constexpr ((FEAT & F_TRI) != 0) {
@@ -2176,9 +2005,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
             const int keep = (n_tri >> 1) > 8 ? (n_tri >> 1) : 8;
             uint32_t k = kind;
             int remaining;
-#if RTK_AB_PRIM_PRIO
-            __builtin_amdgcn_s_setprio(RTK_AB_PRIM_PRIO);
-#endif
+            __builtin_amdgcn_s_setprio(kPrimLoopPrio);
             do {
                 if (k == OP_TRI) {
                     if constexpr (COLD) {
@@ -2192,9 +2019,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                 remaining = popcount64(__ballot(k == OP_TRI));
                 RTK_PROF_MARK(5, 1, remaining)
             } while (remaining >= keep);
-#if RTK_AB_PRIM_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
           }
         } else if (pick == W_SHADE) {
             // 1. the body of ray_color for the lanes whose segment ended; a finished (pixel, chunk) is written out
@@ -2202,9 +2027,6 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
             // 4 - 16 of them had gathered -- C5 34.1 - 34.3 vs 31.9 ms at 32 spp for every threshold: the textures are 9 % of that
             // frame (tools/knockout.py), the gathering saved none of it and the extra ballot and spills cost 7 %.)
             bool finished = false, next_sample = false, alive = false;
-#if RTK_AB_SHADE_PRIO
-            __builtin_amdgcn_s_setprio(RTK_AB_SHADE_PRIO);
-#endif
             RTK_PROF_MARK(8, 1, 0)   // profile build: from the vote to here (marks sit outside divergent code: the profile registers are lane 0's)
             if (kind == OP_END) {
                 alive = true;
@@ -2263,9 +2085,6 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
                 else L.pc = end_pc;
                 L.kind = kind_of(L.pc);
             }
-#if RTK_AB_SHADE_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
             RTK_PROF_MARK(7, 1, popcount64(__ballot(alive)))
         } else {
             // (A short loop here -- stay while at least half of the starters still sit on a rare record: book 2's two media are
@@ -2286,7 +2105,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
     }
     RTK_PROF_FLUSH
     if constexpr (COUNT) {
-#pragma unroll
+        #pragma unroll
         for (int k = 0; k < C_COUNT; k++) {
             unsigned long long v = cnt.c[k];
             for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -2501,534 +2320,6 @@ __global__ __launch_bounds__(256) void rtk_aov_kernel(SceneView<real> sc, Camera
     o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(depth / hits) : 0.0f);
 }
 
-// Tile order for the NEXT frame: local tiles sorted by the cost measured in this frame, most expensive first
-// (64 buckets on a scale relative to the maximum: a counting sort, one workgroup).  A frame cannot end before its
-// slowest sample -- a 50-bounce path inside a glass sphere is one sequential ~2-3 ms chain on one lane -- so the
-// expensive tiles must START early; otherwise every GPU idles ~2.5 ms at the end of its share of the frame.
-// Clears the cost array for the next measurement.
-__global__ __launch_bounds__(1024) void rtk_tile_order_kernel(unsigned int* __restrict__ cost, int n, int32_t* __restrict__ order) {
-    __shared__ unsigned int s_max;
-    __shared__ unsigned int s_count[64], s_base[64];
-    const int tid = threadIdx.x;
-    if (tid == 0) s_max = 0;
-    if (tid < 64) s_count[tid] = 0;
-    __syncthreads();
-    unsigned int local_max = 0;
-    for (int k = tid; k < n; k += 1024) local_max = cost[k] > local_max ? cost[k] : local_max;
-    atomicMax(&s_max, local_max);
-    __syncthreads();
-    const unsigned long long top = (unsigned long long)s_max + 1ull;
-    for (int k = tid; k < n; k += 1024) atomicAdd(&s_count[63 - int((unsigned long long)cost[k] * 64ull / top)], 1u);  // bucket 0 = most expensive
-    __syncthreads();
-    if (tid == 0) {
-        unsigned int run = 0;
-        for (int b = 0; b < 64; b++) {
-            s_base[b] = run;
-            run += s_count[b];
-        }
-    }
-    __syncthreads();
-    for (int k = tid; k < n; k += 1024) {
-        const int b = 63 - int((unsigned long long)cost[k] * 64ull / top);
-        order[atomicAdd(&s_base[b], 1u)] = k;
-    }
-    __syncthreads();
-    for (int k = tid; k < n; k += 1024) cost[k] = 0;
-}
-
-hipError_t launch_tile_order(unsigned int* cost, int n, int32_t* order, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    rtk_tile_order_kernel<<<dim3(1), dim3(1024), 0, stream>>>(cost, n, order);
-    return hipGetLastError();
-}
-
-// Partial sums -> pixels.  For every pixel of this rank: add its chunks in index
-// order, scale by 1/spp (Camera.txt:74) and write either the row-major image
-// (+ gamma/clamp/quantised bytes, Camera.txt:77-89) or this rank's compact tile
-// buffer.  One thread per (local tile, pixel).
-// A frame with more sample chunks than the workspace has planes (kMaxPlanesPerPass) is rendered in several passes over
-// consecutive chunk ranges; `acc` [local tile][3][64] carries the running sum from pass to pass.  The additions happen in the
-// same order as in one pass over all chunks -- c0, + c1, + c2, ... -- so the image does not depend on the number of passes.
-template <typename real>
-__global__ __launch_bounds__(256) void rtk_resolve_kernel(const real* __restrict__ partial, TileMap tmap, int width, int height, real samples_scale,
-                                                           real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8, real* __restrict__ acc, int first_pass,
-                                                           int last_pass) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int pix = int(gid & 63);
-    const long long local_tile = gid >> 6;
-    if (local_tile >= tmap.n_tiles_local) return;
-    const long long tile = local_tile * tmap.n_ranks + tmap.rank;
-    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
-    const bool inside = tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height;
-    V3<real> sum = mk(real(0), real(0), real(0));
-    if (inside) {
-        const real* src = partial + size_t(local_tile) * 192 + pix;
-        const size_t chunk_stride = size_t(tmap.n_tiles_local) * 192;
-        int c = 0;
-        if (first_pass) {
-            sum = mk(src[0], src[64], src[128]);
-            c = 1;
-        } else {
-            const real* a = acc + size_t(local_tile) * 192 + pix;
-            sum = mk(a[0], a[64], a[128]);
-        }
-        for (; c < tmap.n_chunks; c++) {
-            const real* q = src + size_t(c) * chunk_stride;
-            sum = sum + mk(q[0], q[64], q[128]);
-        }
-        if (!last_pass) {
-            real* a = acc + size_t(local_tile) * 192 + pix;
-            a[0] = sum.x;
-            a[64] = sum.y;
-            a[128] = sum.z;
-        }
-        sum = scale(samples_scale, sum);
-    }
-    if (!last_pass) return;
-    if (tmap.compact) {
-        if (out_linear) {
-            real* base = out_linear + size_t(local_tile) * 192 + pix;
-            base[0] = sum.x;
-            base[64] = sum.y;
-            base[128] = sum.z;
-        }
-    } else if (inside) {
-        const size_t idx = (size_t(j) * width + i) * 3;
-        if (out_linear) {
-            out_linear[idx] = sum.x;
-            out_linear[idx + 1] = sum.y;
-            out_linear[idx + 2] = sum.z;
-        }
-        if (out_rgb8) {
-            out_rgb8[idx] = to_byte(double(sum.x));
-            out_rgb8[idx + 1] = to_byte(double(sum.y));
-            out_rgb8[idx + 2] = to_byte(double(sum.z));
-        }
-    }
-}
-
-// Progressive sessions (rtk_progressive_*): a step renders an absolute range of sample chunks into the partial-sum planes and
-// this kernel folds them into the session's own running sum [local tile][3][64] -- the additions of rtk_resolve_kernel, in the
-// same order (c0, + c1, + c2, ...), so a frame rendered in steps is the one-shot frame bit for bit.  `init` = plane 0 is the
-// session's first chunk: it becomes the sum (0.0 + (-0.0) would not be -0.0).  Every FULL chunk (chunk_size samples; a final
-// partial chunk goes into the image only) also feeds the batch-means noise sums S1 = sum y_k, S2 = sum y_k^2 with
-// y_k = (s.x + s.y + s.z) / (3 c) in double.  On the step's last launch (`scale_out` != 0) the preview is written like the
-// resolve's output: scaled by 1 / samples_done, row-major linear + bytes or the compact tile buffer, plus the per-pixel
-// standard error (float, row-major or [local tile][64]) when out_noise is given.  One thread per (local tile, pixel).
-RTK_DEV double noise_se(double s1, double s2, int k) {  // batch means over k >= 2 chunk means: standard error of the pixel mean
-    if (k < 2) return 0.0;
-    const double m = s1 / double(k);
-    double v = (s2 - double(k) * m * m) / double(k - 1);
-    v = v > 0.0 ? v : 0.0;
-    return __builtin_sqrt(v / double(k));
-}
-
-template <typename real>
-__global__ __launch_bounds__(256) void rtk_accumulate_kernel(const real* __restrict__ partial, TileMap tmap, int width, int height, int chunk_size, int init,
-                                                              real* __restrict__ acc, double* __restrict__ s1, double* __restrict__ s2, int scale_out,
-                                                              real samples_scale, int k_full, real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8,
-                                                              float* __restrict__ out_noise) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int pix = int(gid & 63);
-    const long long local_tile = gid >> 6;
-    if (local_tile >= tmap.n_tiles_local) return;
-    const long long tile = local_tile * tmap.n_ranks + tmap.rank;
-    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
-    const bool inside = tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height;
-    V3<real> sum = mk(real(0), real(0), real(0));
-    double se = 0.0;
-    if (inside) {
-        const real* src = partial + size_t(local_tile) * 192 + pix;
-        const size_t chunk_stride = size_t(tmap.n_tiles_local) * 192;
-        real* a = acc + size_t(local_tile) * 192 + pix;
-        double* p1 = s1 + size_t(local_tile) * 64 + pix;
-        double* p2 = s2 + size_t(local_tile) * 64 + pix;
-        double n1 = *p1, n2 = *p2;
-        const double three_c = 3.0 * double(chunk_size);
-        int c = 0;
-        if (init) {
-            sum = mk(src[0], src[64], src[128]);
-            c = 1;
-        } else {
-            sum = mk(a[0], a[64], a[128]);
-        }
-        for (int k = 0; k < tmap.n_chunks; k++) {
-            const real* q = src + size_t(k) * chunk_stride;
-            const V3<real> part = mk(q[0], q[64], q[128]);
-            if (k >= c) sum = sum + part;
-            if (tmap.chunk_start[k + 1] - tmap.chunk_start[k] == chunk_size) {
-                const double y = ((double(part.x) + double(part.y)) + double(part.z)) / three_c;
-                n1 = n1 + y;
-                n2 = n2 + y * y;
-            }
-        }
-        a[0] = sum.x;
-        a[64] = sum.y;
-        a[128] = sum.z;
-        *p1 = n1;
-        *p2 = n2;
-        sum = scale(samples_scale, sum);
-        se = noise_se(n1, n2, k_full);
-    }
-    if (!scale_out) return;
-    if (tmap.compact) {
-        if (out_linear) {
-            real* base = out_linear + size_t(local_tile) * 192 + pix;
-            base[0] = sum.x;
-            base[64] = sum.y;
-            base[128] = sum.z;
-        }
-        if (out_noise) out_noise[size_t(local_tile) * 64 + pix] = float(se);
-    } else if (inside) {
-        const size_t px = size_t(j) * width + i, idx = px * 3;
-        if (out_linear) {
-            out_linear[idx] = sum.x;
-            out_linear[idx + 1] = sum.y;
-            out_linear[idx + 2] = sum.z;
-        }
-        if (out_rgb8) {
-            out_rgb8[idx] = to_byte(double(sum.x));
-            out_rgb8[idx + 1] = to_byte(double(sum.y));
-            out_rgb8[idx + 2] = to_byte(double(sum.z));
-        }
-        if (out_noise) out_noise[px] = float(se);
-    }
-}
-
-// A progressive session's current preview, rebuilt from its state without changing it (rtk_progressive_denoise): the
-// accumulate kernels' outputs -- the running sum scaled by 1 / the tile's sample count (samples_done, or tile_spp[t] of an
-// adaptive session) and se over that count's full chunks -- row-major, for one rank that renders the whole image.
-template <typename real>
-__global__ __launch_bounds__(256) void rtk_preview_kernel(const real* __restrict__ acc, const double* __restrict__ s1, const double* __restrict__ s2,
-                                                           TileMap tmap, int width, int height, int chunk_size, int done, const int32_t* __restrict__ tile_spp,
-                                                           real* __restrict__ out_linear, float* __restrict__ out_noise) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int pix = int(gid & 63);
-    const long long tile = gid >> 6;
-    if (tile >= tmap.n_tiles_local) return;
-    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
-    if (i >= width || j >= height) return;
-    const int spp = tile_spp ? tile_spp[tile] : done;
-    const real* a = acc + size_t(tile) * 192 + pix;
-    const V3<real> sum = scale(real(1.0 / double(spp)), mk(a[0], a[64], a[128]));
-    const size_t px = size_t(j) * width + i;
-    out_linear[px * 3] = sum.x;
-    out_linear[px * 3 + 1] = sum.y;
-    out_linear[px * 3 + 2] = sum.z;
-    out_noise[px] = float(noise_se(s1[size_t(tile) * 64 + pix], s2[size_t(tile) * 64 + pix], spp / chunk_size));
-}
-
-// Frame noise statistics, deterministic (no float atomics): every block reduces its pixels' (se, max se, se / max(mean, 1e-3))
-// -- a wave64 butterfly, then the four waves in a fixed order -- into partials[block][3]; one single-block kernel reduces the
-// partials in a fixed tree.  The same inputs give the same bits on every run.
-RTK_DEV void wave_reduce3(double& a, double& b, double& c) {
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off);
-        const double bo = __shfl_xor(b, off);
-        b = bo > b ? bo : b;
-        c += __shfl_xor(c, off);
-    }
-}
-
-__global__ __launch_bounds__(256) void rtk_noise_partial_kernel(const double* __restrict__ s1, const double* __restrict__ s2, TileMap tmap, int width, int height,
-                                                                 int k_full, double* __restrict__ partials) {
-    __shared__ double s_w[4][3];
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int pix = int(gid & 63);
-    const long long local_tile = gid >> 6;
-    double se = 0.0, rel = 0.0;
-    if (local_tile < tmap.n_tiles_local) {
-        const long long tile = local_tile * tmap.n_ranks + tmap.rank;
-        const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
-        if (tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height && k_full >= 2) {
-            const double n1 = s1[size_t(local_tile) * 64 + pix], n2 = s2[size_t(local_tile) * 64 + pix];
-            se = noise_se(n1, n2, k_full);
-            const double m = n1 / double(k_full);
-            rel = se / (m > 1e-3 ? m : 1e-3);
-        }
-    }
-    double sum_se = se, max_se = se, sum_rel = rel;
-    wave_reduce3(sum_se, max_se, sum_rel);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_w[wave][0] = sum_se;
-        s_w[wave][1] = max_se;
-        s_w[wave][2] = sum_rel;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double a = (s_w[0][0] + s_w[1][0]) + (s_w[2][0] + s_w[3][0]);
-        const double b01 = s_w[0][1] > s_w[1][1] ? s_w[0][1] : s_w[1][1], b23 = s_w[2][1] > s_w[3][1] ? s_w[2][1] : s_w[3][1];
-        const double c = (s_w[0][2] + s_w[1][2]) + (s_w[2][2] + s_w[3][2]);
-        partials[size_t(blockIdx.x) * 3] = a;
-        partials[size_t(blockIdx.x) * 3 + 1] = b01 > b23 ? b01 : b23;
-        partials[size_t(blockIdx.x) * 3 + 2] = c;
-    }
-}
-
-__global__ __launch_bounds__(256) void rtk_noise_final_kernel(const double* __restrict__ partials, int n, double* __restrict__ out) {
-    __shared__ double s_v[3][256];
-    const int t = threadIdx.x;
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int k = t; k < n; k += 256) {  // each thread walks its strided slice in index order
-        a += partials[size_t(k) * 3];
-        b = partials[size_t(k) * 3 + 1] > b ? partials[size_t(k) * 3 + 1] : b;
-        c += partials[size_t(k) * 3 + 2];
-    }
-    s_v[0][t] = a;
-    s_v[1][t] = b;
-    s_v[2][t] = c;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {  // fixed pairwise tree
-        if (t < half) {
-            s_v[0][t] = s_v[0][t] + s_v[0][t + half];
-            s_v[1][t] = s_v[1][t + half] > s_v[1][t] ? s_v[1][t + half] : s_v[1][t];
-            s_v[2][t] = s_v[2][t] + s_v[2][t + half];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        out[0] = s_v[0][0];
-        out[1] = s_v[1][0];
-        out[2] = s_v[2][0];
-    }
-}
-
-// Adaptive progressive sessions (include/rtk.h, "Tile-adaptive sampling"): every local tile is active (it holds the session's
-// samples_done samples) or retired (it keeps tile_spp[t] samples for good).  A step renders the active tiles only -- the render
-// kernel hands out the compacted list `tile_order` up to the device word `active_count` -- and the kernels below keep the
-// per-tile state.  The retire metric of a tile is the maximum over its in-image pixels of se / max(m, 1e-3) over K chunks.
-RTK_DEV double noise_rel(double se, double s1, int k) {
-    const double m = s1 / double(k);
-    return se / (m > 1e-3 ? m : 1e-3);
-}
-
-RTK_DEV double wave_max(double v) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// rtk_accumulate_kernel with per-tile state: folds this launch's planes only into the tiles that were active in it (the same
-// additions in the same order) and leaves retired tiles' sums and S1 / S2 alone.  On the step's last launch (`last`) it writes
-// the preview -- each tile scaled by 1 / its own sample count, se over its own K -- and fuses the retire test: one wave64 per
-// tile (a 256-thread block is 4 tiles), the wave max of the metric through __shfl_xor, lane 0 writes the tile's new state.
-template <typename real>
-__global__ __launch_bounds__(256) void rtk_accumulate_adaptive_kernel(const real* __restrict__ partial, TileMap tmap, int width, int height, int chunk_size,
-                                                                       int init, real* __restrict__ acc, double* __restrict__ s1, double* __restrict__ s2,
-                                                                       int32_t* __restrict__ active, int32_t* __restrict__ tile_spp, int last, int s_end,
-                                                                       int retire_ok, double rel_target, real samples_scale, real* __restrict__ out_linear,
-                                                                       uint8_t* __restrict__ out_rgb8, float* __restrict__ out_noise) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int pix = int(gid & 63);
-    const long long local_tile = gid >> 6;
-    if (local_tile >= tmap.n_tiles_local) return;  // (wave-uniform: one wave is one tile)
-    const long long tile = local_tile * tmap.n_ranks + tmap.rank;
-    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
-    const bool inside = tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height;
-    const bool is_active = active[local_tile] != 0;
-    V3<real> sum = mk(real(0), real(0), real(0));
-    double n1 = 0.0, n2 = 0.0;
-    real* a = acc + size_t(local_tile) * 192 + pix;
-    double* p1 = s1 + size_t(local_tile) * 64 + pix;
-    double* p2 = s2 + size_t(local_tile) * 64 + pix;
-    if (inside && is_active) {
-        const real* src = partial + size_t(local_tile) * 192 + pix;
-        const size_t chunk_stride = size_t(tmap.n_tiles_local) * 192;
-        n1 = *p1;
-        n2 = *p2;
-        const double three_c = 3.0 * double(chunk_size);
-        int c = 0;
-        if (init) {
-            sum = mk(src[0], src[64], src[128]);
-            c = 1;
-        } else {
-            sum = mk(a[0], a[64], a[128]);
-        }
-        for (int k = 0; k < tmap.n_chunks; k++) {
-            const real* q = src + size_t(k) * chunk_stride;
-            const V3<real> part = mk(q[0], q[64], q[128]);
-            if (k >= c) sum = sum + part;
-            if (tmap.chunk_start[k + 1] - tmap.chunk_start[k] == chunk_size) {
-                const double y = ((double(part.x) + double(part.y)) + double(part.z)) / three_c;
-                n1 = n1 + y;
-                n2 = n2 + y * y;
-            }
-        }
-        a[0] = sum.x;
-        a[64] = sum.y;
-        a[128] = sum.z;
-        *p1 = n1;
-        *p2 = n2;
-    } else if (inside && last) {
-        sum = mk(a[0], a[64], a[128]);
-        n1 = *p1;
-        n2 = *p2;
-    }
-    if (!last) return;
-    const int spp = is_active ? s_end : tile_spp[local_tile];
-    const int k_full = spp / chunk_size;
-    double se = 0.0, rel = 0.0;
-    if (inside) {
-        sum = scale(is_active ? samples_scale : real(1.0 / double(spp)), sum);
-        se = noise_se(n1, n2, k_full);
-        if (k_full >= 2) rel = noise_rel(se, n1, k_full);
-    }
-    if (is_active) {  // the retire test: wave-uniform branch, every lane of the tile takes part in the reduction
-        const double metric = wave_max(rel);
-        if (pix == 0) {
-            tile_spp[local_tile] = s_end;
-            if (retire_ok && metric <= rel_target) active[local_tile] = 0;
-        }
-    }
-    if (tmap.compact) {
-        if (out_linear) {
-            real* base = out_linear + size_t(local_tile) * 192 + pix;
-            base[0] = sum.x;
-            base[64] = sum.y;
-            base[128] = sum.z;
-        }
-        if (out_noise) out_noise[size_t(local_tile) * 64 + pix] = float(se);
-    } else if (inside) {
-        const size_t px = size_t(j) * width + i, idx = px * 3;
-        if (out_linear) {
-            out_linear[idx] = sum.x;
-            out_linear[idx + 1] = sum.y;
-            out_linear[idx + 2] = sum.z;
-        }
-        if (out_rgb8) {
-            out_rgb8[idx] = to_byte(double(sum.x));
-            out_rgb8[idx + 1] = to_byte(double(sum.y));
-            out_rgb8[idx + 2] = to_byte(double(sum.z));
-        }
-        if (out_noise) out_noise[px] = float(se);
-    }
-}
-
-// Resume of an adaptive checkpoint: the retired state is not stored, it is recomputed -- a tile is active when it holds
-// samples_done samples and the retire test of the step that ended there (the same metric, from the same S1 / S2) did not
-// retire it.  One wave64 per tile, as in the accumulate pass.
-__global__ __launch_bounds__(256) void rtk_adaptive_restore_kernel(const double* __restrict__ s1, const double* __restrict__ s2, TileMap tmap, int width,
-                                                                    int height, int chunk_size, const int32_t* __restrict__ tile_spp, int done,
-                                                                    int retire_ok, double rel_target, int32_t* __restrict__ active) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int pix = int(gid & 63);
-    const long long local_tile = gid >> 6;
-    if (local_tile >= tmap.n_tiles_local) return;
-    const long long tile = local_tile * tmap.n_ranks + tmap.rank;
-    const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
-    const bool in_tiles = tile < (long long)tmap.tiles_x * tmap.tiles_y;
-    const int k_full = done / chunk_size;
-    double rel = 0.0;
-    if (in_tiles && i < width && j < height && k_full >= 2) {
-        const double n1 = s1[size_t(local_tile) * 64 + pix], n2 = s2[size_t(local_tile) * 64 + pix];
-        rel = noise_rel(noise_se(n1, n2, k_full), n1, k_full);
-    }
-    const double metric = wave_max(rel);
-    if (pix == 0) active[local_tile] = (in_tiles && tile_spp[local_tile] == done && !(retire_ok && metric <= rel_target)) ? 1 : 0;
-}
-
-// The next step's hand-out list: a stable filter of `order` (identity when null) keeping the active tiles, and its length.
-// One block walks the positions 1024 at a time: a 64-bit ballot per wave, the waves' counts summed in wave order -- the same
-// list on every run.
-__global__ __launch_bounds__(1024) void rtk_adaptive_compact_kernel(const int32_t* __restrict__ active, const int32_t* __restrict__ order, int n,
-                                                                     int32_t* __restrict__ list, int32_t* __restrict__ count) {
-    __shared__ int s_wave[16];
-    __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int pos = base + tid;
-        int t = 0;
-        bool keep = false;
-        if (pos < n) {
-            t = order ? order[pos] : pos;
-            keep = active[t] != 0;
-        }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        __syncthreads();
-        int at = s_base;
-        for (int w = 0; w < wave; w++) at += s_wave[w];
-        if (keep) list[at + __popcll(m & ((1ull << lane) - 1ull))] = t;
-        __syncthreads();
-        if (tid == 0) {
-            int total = 0;
-            for (int w = 0; w < 16; w++) total += s_wave[w];
-            s_base += total;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) *count = s_base;
-}
-
-// rtk_noise_partial_kernel with per-tile K = tile_spp[t] / chunk_size (feeds rtk_noise_final_kernel).
-__global__ __launch_bounds__(256) void rtk_noise_partial_adaptive_kernel(const double* __restrict__ s1, const double* __restrict__ s2, TileMap tmap, int width,
-                                                                          int height, int chunk_size, const int32_t* __restrict__ tile_spp,
-                                                                          double* __restrict__ partials) {
-    __shared__ double s_w[4][3];
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int pix = int(gid & 63);
-    const long long local_tile = gid >> 6;
-    double se = 0.0, rel = 0.0;
-    if (local_tile < tmap.n_tiles_local) {
-        const long long tile = local_tile * tmap.n_ranks + tmap.rank;
-        const int i = int(tile % tmap.tiles_x) * 8 + (pix & 7), j = int(tile / tmap.tiles_x) * 8 + (pix >> 3);
-        const int k_full = tile_spp[local_tile] / chunk_size;
-        if (tile < (long long)tmap.tiles_x * tmap.tiles_y && i < width && j < height && k_full >= 2) {
-            const double n1 = s1[size_t(local_tile) * 64 + pix], n2 = s2[size_t(local_tile) * 64 + pix];
-            se = noise_se(n1, n2, k_full);
-            rel = noise_rel(se, n1, k_full);
-        }
-    }
-    double sum_se = se, max_se = se, sum_rel = rel;
-    wave_reduce3(sum_se, max_se, sum_rel);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_w[wave][0] = sum_se;
-        s_w[wave][1] = max_se;
-        s_w[wave][2] = sum_rel;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double a = (s_w[0][0] + s_w[1][0]) + (s_w[2][0] + s_w[3][0]);
-        const double b01 = s_w[0][1] > s_w[1][1] ? s_w[0][1] : s_w[1][1], b23 = s_w[2][1] > s_w[3][1] ? s_w[2][1] : s_w[3][1];
-        const double c = (s_w[0][2] + s_w[1][2]) + (s_w[2][2] + s_w[3][2]);
-        partials[size_t(blockIdx.x) * 3] = a;
-        partials[size_t(blockIdx.x) * 3 + 1] = b01 > b23 ? b01 : b23;
-        partials[size_t(blockIdx.x) * 3 + 2] = c;
-    }
-}
-
-// Gathered compact tiles -> row-major image (+ bytes).  One thread per pixel slot.
-template <typename real>
-__global__ __launch_bounds__(256) void rtk_unpermute_kernel(const real* __restrict__ gathered, int width, int height, int tiles_x, int n_tiles, int n_ranks,
-                                                             long long tiles_per_rank, real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int lane = int(gid & 63);
-    const long long tile = gid >> 6;
-    if (tile >= n_tiles) return;
-    const int i = int(tile % tiles_x) * 8 + (lane & 7), j = int(tile / tiles_x) * 8 + (lane >> 3);
-    if (i >= width || j >= height) return;
-    const long long rank = tile % n_ranks, local_tile = tile / n_ranks;
-    const real* src = gathered + (rank * tiles_per_rank + local_tile) * 192 + lane;
-    const real r = src[0], g = src[64], b = src[128];
-    const size_t idx = (size_t(j) * width + i) * 3;
-    if (out_linear) {
-        out_linear[idx] = r;
-        out_linear[idx + 1] = g;
-        out_linear[idx + 2] = b;
-    }
-    if (out_rgb8) {
-        out_rgb8[idx] = to_byte(double(r));
-        out_rgb8[idx + 1] = to_byte(double(g));
-        out_rgb8[idx + 2] = to_byte(double(b));
-    }
-}
-
 // ------------------------------------------------------------------ launchers --
 
 // Geometry of a persistent launch: waves per workgroup and workgroups per CU so
@@ -3098,30 +2389,24 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
     if constexpr ((FEAT & F_LDS_BOXES) != 0) {  // boxes-in-LDS kernels: the material table too, if it is small and there is room
         const size_t mat_bytes = size_t(sc.n_materials) * sizeof(MaterialRec<real>);
         const size_t at = (lds + 15) & ~size_t(15);
-        if (!is_compact(FEAT) /* (COLD kernels always stage it, right behind the hot program) */ && RTK_SPLIT_MATERIALS_IN_LDS && mat_bytes <= 16 * 1024 &&
+        if (!is_compact(FEAT) /* (COLD kernels always stage it, right behind the hot program) */ && mat_bytes <= 16 * 1024 &&
             at + mat_bytes + 64 <= size_t(kLdsBytesPerCU)) {
             tm.mats_lds_offset = int32_t(at);
             lds = at + mat_bytes;
         }
-#ifndef RTK_SPLIT_PERLIN_IN_LDS
-#define RTK_SPLIT_PERLIN_IN_LDS 1
-#endif
         // ... and the Perlin tables (book-2's noise sphere: 7.8 % of the C5 frame went into perlin::turb's dependent gathers from memory)
         const size_t perlin_bytes = size_t(sc.n_perlins) * sizeof(PerlinRec<real>);
         const size_t pat = (lds + 15) & ~size_t(15);
-        if (RTK_SPLIT_PERLIN_IN_LDS && (FEAT & F_TEXTURE) != 0 && perlin_bytes > 0 && pat + perlin_bytes + 64 <= size_t(kLdsBytesPerCU)) {
+        if ((FEAT & F_TEXTURE) != 0 && perlin_bytes > 0 && pat + perlin_bytes + 64 <= size_t(kLdsBytesPerCU)) {
             tm.perlin_lds_offset = int32_t(pat);
             lds = pat + perlin_bytes;
         }
     }
-#ifndef RTK_CHAINS_IN_LDS
-#define RTK_CHAINS_IN_LDS 1
-#endif
     tm.chains_lds_offset = 0;
     if constexpr ((FEAT & F_XFORM) != 0 && (IN_LDS || (FEAT & F_LDS_BOXES) != 0)) {
         const size_t chain_bytes = size_t(sc.n_chains) * sizeof(ChainRec<real>);
         const size_t cat = (lds + 15) & ~size_t(15);
-        if (RTK_CHAINS_IN_LDS && sc.n_chains > 1 && chain_bytes <= 8192 && cat + chain_bytes + 64 <= size_t(kLdsBytesPerCU)) {
+        if (sc.n_chains > 1 && chain_bytes <= 8192 && cat + chain_bytes + 64 <= size_t(kLdsBytesPerCU)) {
             tm.chains_lds_offset = int32_t(cat);
             lds = cat + chain_bytes;
         }
@@ -3260,6 +2545,10 @@ hipError_t launch_render(const SceneView<real>& sc, const CameraRec<real>* cam, 
     const KernelChoice k = choose_kernel(sc, features, count, allow_lds, diag);
 #define RTK_LAUNCH_CASE(F) \
     case F: return launch_feat<real, F>(k, sc, cam, tmap, seed, diag, partial, counters, tile_counter, tile_order, tile_cost, stream);
+#define RTK_LAUNCH_CASE_F64(F) \
+    case F:                      \
+        if constexpr (sizeof(real) == 8) return launch_feat<real, F>(k, sc, cam, tmap, seed, diag, partial, counters, tile_counter, tile_order, tile_cost, stream); \
+        break;
     switch (k.feat & ~uint32_t(F_LDS_BOXES | F_SPHERE_MEDIA_ONLY)) {
 #if !defined(RTK_DEV_ONLY_ALL)   // tools/kernel_resources.py -DRTK_DEV_ONLY_ALL: only the full-feature family (quick register experiments)
         RTK_LAUNCH_CASE(kFeatLean)
@@ -3270,10 +2559,6 @@ hipError_t launch_render(const SceneView<real>& sc, const CameraRec<real>* cam, 
         RTK_LAUNCH_CASE(kFeatMesh | F_FMA_BOX)
         RTK_LAUNCH_CASE(kFeatMesh | F_MATTE)
         RTK_LAUNCH_CASE(kFeatMesh | F_FMA_BOX | F_MATTE)
-#define RTK_LAUNCH_CASE_F64(F) \
-    case F:                      \
-        if constexpr (sizeof(real) == 8) return launch_feat<real, F>(k, sc, cam, tmap, seed, diag, partial, counters, tile_counter, tile_order, tile_cost, stream); \
-        break;
         RTK_LAUNCH_CASE_F64(kFeatLean | F_F32_BOX)
         RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_F32_BOX)
         RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_MATTE | F_F32_BOX)
@@ -3282,12 +2567,6 @@ hipError_t launch_render(const SceneView<real>& sc, const CameraRec<real>* cam, 
 #endif
         RTK_LAUNCH_CASE(kFeatAll)
         RTK_LAUNCH_CASE(kFeatAll | F_FMA_BOX)
-#ifndef RTK_LAUNCH_CASE_F64
-#define RTK_LAUNCH_CASE_F64(F) \
-    case F:                      \
-        if constexpr (sizeof(real) == 8) return launch_feat<real, F>(k, sc, cam, tmap, seed, diag, partial, counters, tile_counter, tile_order, tile_cost, stream); \
-        break;
-#endif
         RTK_LAUNCH_CASE_F64(kFeatAll | F_F32_BOX)
 #undef RTK_LAUNCH_CASE_F64
     }
@@ -3308,89 +2587,6 @@ const char* render_kernel_name(const SceneView<real>& sc, uint32_t features, boo
 }
 template const char* render_kernel_name<double>(const SceneView<double>&, uint32_t, bool, bool, uint32_t);
 template const char* render_kernel_name<float>(const SceneView<float>&, uint32_t, bool, bool, uint32_t);
-
-template <typename real>
-hipError_t launch_resolve(const void* partial, const TileMap& tmap, int width, int height, double samples_scale, void* out_linear, uint8_t* out_rgb8,
-                          void* acc, bool first_pass, bool last_pass, hipStream_t stream) {
-    const long long slots = (long long)tmap.n_tiles_local * 64;
-    if (slots <= 0) return hipSuccess;
-    rtk_resolve_kernel<real><<<dim3(int((slots + 255) / 256)), dim3(256), 0, stream>>>(static_cast<const real*>(partial), tmap, width, height,
-                                                                                      real(samples_scale), static_cast<real*>(out_linear), out_rgb8,
-                                                                                      static_cast<real*>(acc), first_pass ? 1 : 0, last_pass ? 1 : 0);
-    return hipGetLastError();
-}
-template hipError_t launch_resolve<double>(const void*, const TileMap&, int, int, double, void*, uint8_t*, void*, bool, bool, hipStream_t);
-template hipError_t launch_resolve<float>(const void*, const TileMap&, int, int, double, void*, uint8_t*, void*, bool, bool, hipStream_t);
-
-template <typename real>
-hipError_t launch_accumulate(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, bool init, void* acc, double* s1, double* s2,
-                             bool write_out, double samples_scale, int k_full, void* out_linear, uint8_t* out_rgb8, float* out_noise, hipStream_t stream) {
-    const long long slots = (long long)tmap.n_tiles_local * 64;
-    if (slots <= 0) return hipSuccess;
-    rtk_accumulate_kernel<real><<<dim3(int((slots + 255) / 256)), dim3(256), 0, stream>>>(
-        static_cast<const real*>(partial), tmap, width, height, chunk_size, init ? 1 : 0, static_cast<real*>(acc), s1, s2, write_out ? 1 : 0,
-        real(samples_scale), k_full, static_cast<real*>(out_linear), out_rgb8, out_noise);
-    return hipGetLastError();
-}
-template hipError_t launch_accumulate<double>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, bool, double, int, void*, uint8_t*,
-                                              float*, hipStream_t);
-template hipError_t launch_accumulate<float>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, bool, double, int, void*, uint8_t*,
-                                             float*, hipStream_t);
-
-int noise_partial_blocks(const TileMap& tmap) { return int(((long long)tmap.n_tiles_local * 64 + 255) / 256); }
-
-hipError_t launch_noise_stats(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int k_full, double* partials, double* out3,
-                              hipStream_t stream) {
-    const int blocks = noise_partial_blocks(tmap);
-    if (blocks <= 0) return hipErrorInvalidValue;
-    rtk_noise_partial_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(s1, s2, tmap, width, height, k_full, partials);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    rtk_noise_final_kernel<<<dim3(1), dim3(256), 0, stream>>>(partials, blocks, out3);
-    return hipGetLastError();
-}
-
-template <typename real>
-hipError_t launch_accumulate_adaptive(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, bool init, void* acc, double* s1,
-                                      double* s2, int32_t* active, int32_t* tile_spp, bool last, int s_end, bool retire_ok, double rel_target,
-                                      void* out_linear, uint8_t* out_rgb8, float* out_noise, hipStream_t stream) {
-    const long long slots = (long long)tmap.n_tiles_local * 64;
-    if (slots <= 0) return hipSuccess;
-    rtk_accumulate_adaptive_kernel<real><<<dim3(int((slots + 255) / 256)), dim3(256), 0, stream>>>(
-        static_cast<const real*>(partial), tmap, width, height, chunk_size, init ? 1 : 0, static_cast<real*>(acc), s1, s2, active, tile_spp, last ? 1 : 0,
-        s_end, retire_ok ? 1 : 0, rel_target, real(1.0 / double(s_end)), static_cast<real*>(out_linear), out_rgb8, out_noise);
-    return hipGetLastError();
-}
-template hipError_t launch_accumulate_adaptive<double>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, int32_t*, int32_t*, bool, int,
-                                                       bool, double, void*, uint8_t*, float*, hipStream_t);
-template hipError_t launch_accumulate_adaptive<float>(const void*, const TileMap&, int, int, int, bool, void*, double*, double*, int32_t*, int32_t*, bool, int,
-                                                      bool, double, void*, uint8_t*, float*, hipStream_t);
-
-hipError_t launch_adaptive_restore(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
-                                   int done, bool retire_ok, double rel_target, int32_t* active, hipStream_t stream) {
-    const long long slots = (long long)tmap.n_tiles_local * 64;
-    if (slots <= 0) return hipSuccess;
-    rtk_adaptive_restore_kernel<<<dim3(int((slots + 255) / 256)), dim3(256), 0, stream>>>(s1, s2, tmap, width, height, chunk_size, tile_spp, done,
-                                                                                         retire_ok ? 1 : 0, rel_target, active);
-    return hipGetLastError();
-}
-
-hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, int n, int32_t* list, int32_t* count, hipStream_t stream) {
-    if (n <= 0) return hipErrorInvalidValue;
-    rtk_adaptive_compact_kernel<<<dim3(1), dim3(1024), 0, stream>>>(active, order, n, list, count);
-    return hipGetLastError();
-}
-
-hipError_t launch_noise_stats_adaptive(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
-                                       double* partials, double* out3, hipStream_t stream) {
-    const int blocks = noise_partial_blocks(tmap);
-    if (blocks <= 0) return hipErrorInvalidValue;
-    rtk_noise_partial_adaptive_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(s1, s2, tmap, width, height, chunk_size, tile_spp, partials);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    rtk_noise_final_kernel<<<dim3(1), dim3(256), 0, stream>>>(partials, blocks, out3);
-    return hipGetLastError();
-}
 
 template <typename real>
 hipError_t launch_debug_hit(const SceneView<real>& sc, int n, const double* d_rays, const uint32_t* d_keys, double* d_out, unsigned long long* d_draws,
@@ -3438,29 +2634,6 @@ hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uin
 }
 template hipError_t launch_aov<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, float*, hipStream_t);
 template hipError_t launch_aov<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, int, float*, hipStream_t);
-
-template <typename real>
-hipError_t launch_preview(const void* acc, const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, int done,
-                          const int32_t* tile_spp, void* out_linear, float* out_noise, hipStream_t stream) {
-    rtk_preview_kernel<real><<<dim3((tmap.n_tiles_local + 3) / 4), dim3(256), 0, stream>>>(static_cast<const real*>(acc), s1, s2, tmap, width, height, chunk_size,
-                                                                                          done, tile_spp, static_cast<real*>(out_linear), out_noise);
-    return hipGetLastError();
-}
-template hipError_t launch_preview<double>(const void*, const double*, const double*, const TileMap&, int, int, int, int, const int32_t*, void*, float*, hipStream_t);
-template hipError_t launch_preview<float>(const void*, const double*, const double*, const TileMap&, int, int, int, int, const int32_t*, void*, float*, hipStream_t);
-
-template <typename real>
-hipError_t launch_unpermute(const void* gathered, int width, int height, int n_ranks, long long tiles_per_rank, void* out_linear, uint8_t* out_rgb8,
-                            hipStream_t stream) {
-    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
-    const long long slots = (long long)tiles_x * tiles_y * 64;
-    const int blocks = int((slots + 255) / 256);
-    rtk_unpermute_kernel<real><<<dim3(blocks), dim3(256), 0, stream>>>(static_cast<const real*>(gathered), width, height, tiles_x, tiles_x * tiles_y, n_ranks,
-                                                                       tiles_per_rank, static_cast<real*>(out_linear), out_rgb8);
-    return hipGetLastError();
-}
-template hipError_t launch_unpermute<double>(const void*, int, int, int, long long, void*, uint8_t*, hipStream_t);
-template hipError_t launch_unpermute<float>(const void*, int, int, int, long long, void*, uint8_t*, hipStream_t);
 
 #ifdef RTK_ISA_PROBES
 // Instruction-cost probes (tools/isa_costs.py; never part of the product build): one kernel per unit of work of the lean

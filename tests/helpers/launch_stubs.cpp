@@ -1,4 +1,4 @@
-// Link-time stand-ins for the launch entry points of csrc/rtk_trace.hip, so that csrc/rtk_api.cpp can be linked into
+// Link-time stand-ins for the launch entry points of csrc/rtk_trace.hip and csrc/rtk_frame.hip, so that csrc/rtk_api.cpp can be linked into
 // the CPU sanitizer harness (tests/helpers/parser_harness.cpp) without device code.  Test infrastructure only; the
 // harness calls host-only entry points (rtk_scene_validate, rtk_scene_optimize) and never reaches these.
 #include "rtk_trace.h"

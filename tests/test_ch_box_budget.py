@@ -1,5 +1,5 @@
 """CPU check of the error budget behind the centre / half-extent culling boxes of the MIXED program (DESIGN.md 4a,
-rtk_api.cpp build_mixed_program, rtk_trace.hip slab_test32_ch / slab_test32_chs / rescale32).
+rtk_api.cpp build_mixed_program, rtk_trace.hip slab_test32_chs / rescale32).
 
 The float test only decides which primitives get tested, so it must be CONSERVATIVE: whenever aabb::hit (aabb.h:61-85) in
 double passes a ray through the reference's box within (tmin, tmax), the float test on the grown record must pass it too.
@@ -26,7 +26,7 @@ def round_up32(x):
 
 
 def build_record(lo, hi, extent):
-    """rtk_api.cpp build_mixed_program, RTK_CH_BOX: float centre, half-extent from that centre grown by
+    """rtk_api.cpp build_mixed_program: float centre, half-extent from that centre grown by
     2^-21 (|c| + h) + 2^-20 extent, rounded up."""
     c = 0.5 * (lo + hi)
     cf = c.astype(F)

@@ -18,7 +18,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "raytracingoneweekendapplication_amd", "csrc")
+sys.path.insert(0, ROOT)
+from __graft_entry__ import hip_build_command  # noqa: E402
 PROBES = ["EMPTY", "BOX", "SPHERE", "SEGMENT", "SAMPLE", "MISS", "LAMBERTIAN", "METAL", "DIELECTRIC", "PARTIAL"]  # enum ProbeKind order
 TRANS = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_log_", "v_exp_", "v_sin_", "v_cos_")
 # nominal issue cost of a wave64 instruction in SIMD cycles per class, used when no measurement is at hand
@@ -63,9 +64,8 @@ def count_kernel(lines):
 def derive(extra_flags=()):
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "probes.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-S", "--cuda-device-only",
-                               "-DRTK_ISA_PROBES", "-DRTK_DEV_ONLY_ALL", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, *extra_flags,
-                               os.path.join(CSRC, "rtk_trace.hip"), "-o", out], stderr=subprocess.DEVNULL)
+        subprocess.check_call(hip_build_command(out, ["-DRTK_ISA_PROBES", "-DRTK_DEV_ONLY_ALL", *extra_flags], sources=("rtk_trace.hip",),
+                                                mode=("-S", "--cuda-device-only")), stderr=subprocess.DEVNULL)
         text = open(out).read().split("\n")
     kernels = {}
     name = None

@@ -10,10 +10,11 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-csrc = os.path.join(ROOT, "raytracingoneweekendapplication_amd", "csrc")
+sys.path.insert(0, ROOT)
+from __graft_entry__ import hip_build_command
+
 with tempfile.TemporaryDirectory() as tmp:
-    p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + csrc, os.path.join(csrc, "rtk_trace.hip"), "-o", os.path.join(tmp, "t.o"), "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:],
+    p = subprocess.run(hip_build_command(os.path.join(tmp, "t.o"), ["-Rpass-analysis=kernel-resource-usage", *sys.argv[1:]], sources=("rtk_trace.hip",), mode=("-c",)),
                        capture_output=True, text=True)
 if p.returncode != 0:
     sys.exit(p.stderr[-4000:])
