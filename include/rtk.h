@@ -353,7 +353,31 @@ int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks);
  *                  [tiles_per_rank][3][64] reals; d_rgb8 must be NULL (bytes
  *                  are produced by rtk_tiles_unpermute on the gathering rank).
  * d_counters (device, sizeof(rtk_work_counters), zeroed by the caller) is
- * required iff opts->count_work != 0. */
+ * required iff opts->count_work != 0.
+ *
+ * Streams (this holds for every entry point that is "asynchronous on" a stream:
+ * rtk_render_device, rtk_tiles_unpermute, rtk_progressive_step, rtk_render_aovs,
+ * rtk_denoise, rtk_progressive_denoise):
+ *   - all work of a call -- kernels, memsets, the upload of the camera record --
+ *     is enqueued on the stream it is given and on no other; the call reads its
+ *     host arguments (cam, opts) before it returns and never waits for the
+ *     device, except to grow a workspace the first time a larger frame is seen.
+ *   - a context is driven from ONE stream at a time: its launches share the
+ *     partial-sum workspace, the tile order and the per-launch rings, and what
+ *     orders them is that stream.  Sessions of the context count: a session
+ *     steps on the stream it was created with.
+ *   - moving a context (or a session and the one-shot renders between its steps)
+ *     to another stream needs an event the new stream waits for, or a host wait.
+ *     Two streams on one context without such ordering are a data race.
+ *   - any number of frames may be in flight on the stream; the rings behind a
+ *     launch (work-item counters, camera records) are reused in stream order.
+ *   - rtk_progressive_create, rtk_progressive_set_adaptive and
+ *     rtk_progressive_resume may be called while the stream is busy: they touch
+ *     only the session's own, new memory.  create and set_adaptive set it up on
+ *     the session's stream and do not wait for it; resume copies the caller's
+ *     checkpoint with blocking calls, which may wait for work queued ahead of
+ *     them on the device, and for an adaptive checkpoint waits for the stream.
+ *   - for overlap use two contexts on two streams. */
 int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts,
                       void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters);
 

@@ -1708,15 +1708,6 @@ int frame_chunk_size(int spp) { return chunk_size_for(spp, 0); }
 
 int chunks_per_launch(size_t plane_bytes) { return planes_per_pass_for(plane_bytes, 0); }
 
-hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst) {
-    if (real_mode == RTK_REAL_F64) {
-        const CameraRec<double> rec = to_device_camera<double>(cam);
-        return hipMemcpy(d_dst, &rec, sizeof rec, hipMemcpyHostToDevice);
-    }
-    const CameraRec<float> rec = to_device_camera<float>(cam);
-    return hipMemcpy(d_dst, &rec, sizeof rec, hipMemcpyHostToDevice);
-}
-
 size_t camera_record_bytes() { return kCameraStride; }
 
 template <typename real>

@@ -512,4 +512,38 @@ hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ session set-up --
+// A session is set up on ITS stream by kernels and asynchronous memsets: a blocking call on the NULL stream can be queued
+// behind another stream's backlog (streams share the hardware queues), and rtk_progressive_create would then wait for the
+// very stream it is documented not to wait for.  The camera record travels as a kernel argument, so no host memory has to
+// outlive the call.
+struct RecordWords {
+    unsigned int w[64];
+};
+__global__ __launch_bounds__(64) void rtk_store_record_kernel(RecordWords rec, unsigned int n_words, unsigned int* __restrict__ dst) {
+    if (threadIdx.x < n_words) dst[threadIdx.x] = rec.w[threadIdx.x];
+}
+
+hipError_t launch_store_record(const void* h_record, size_t bytes, void* d_dst, hipStream_t stream) {
+    RecordWords rec{};
+    if (bytes > sizeof rec || bytes % sizeof(unsigned int) != 0) return hipErrorInvalidValue;
+    __builtin_memcpy(rec.w, h_record, bytes);
+    rtk_store_record_kernel<<<dim3(1), dim3(64), 0, stream>>>(rec, static_cast<unsigned int>(bytes / sizeof(unsigned int)), static_cast<unsigned int*>(d_dst));
+    return hipGetLastError();
+}
+
+// A fresh adaptive session: every tile of the rank that lies in the image is active, and none holds a sample.
+__global__ __launch_bounds__(256) void rtk_adaptive_init_kernel(TileMap tmap, int32_t* __restrict__ active, int32_t* __restrict__ tile_spp) {
+    const long long lt = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (lt >= tmap.n_tiles_local) return;
+    active[lt] = lt * tmap.n_ranks + tmap.rank < (long long)tmap.tiles_x * tmap.tiles_y ? 1 : 0;
+    tile_spp[lt] = 0;
+}
+
+hipError_t launch_adaptive_init(const TileMap& tmap, int32_t* active, int32_t* tile_spp, hipStream_t stream) {
+    if (tmap.n_tiles_local <= 0) return hipSuccess;
+    rtk_adaptive_init_kernel<<<dim3((tmap.n_tiles_local + 255) / 256), dim3(256), 0, stream>>>(tmap, active, tile_spp);
+    return hipGetLastError();
+}
+
 }  // namespace rtk

@@ -42,7 +42,6 @@ int ctx_scene(const rtk_ctx* ctx, uint64_t* digest);  // 1 when a scene is uploa
 int frame_chunk_size(int spp);                        // the one-shot frame's chunk size (variant 0)
 int chunks_per_launch(size_t plane_bytes);            // ... and chunk planes per launch
 size_t camera_record_bytes();
-hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst);  // the kernel's camera record, blocking copy
 // One render launch over tp's chunks into the context's partial-sum workspace (grown to workspace_bytes; *partial = it).
 hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
                          const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial);

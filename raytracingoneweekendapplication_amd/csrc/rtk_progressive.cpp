@@ -104,8 +104,22 @@ void release(rtk_progressive* p) {
     delete p;
 }
 
-// Argument checks and device state of a new session (sums zeroed).
-int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, rtk_progressive** out) {
+// The kernel's camera record, stored on `stream` from a kernel argument (no host wait, no host memory that outlives the call).
+static_assert(sizeof(CameraRec<double>) % 4 == 0 && sizeof(CameraRec<float>) % 4 == 0, "launch_store_record stores 4-byte words");
+hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst, hipStream_t stream) {
+    if (real_mode == RTK_REAL_F64) {
+        const CameraRec<double> rec = device_camera<double>(cam);
+        return launch_store_record(&rec, sizeof rec, d_dst, stream);
+    }
+    const CameraRec<float> rec = device_camera<float>(cam);
+    return launch_store_record(&rec, sizeof rec, d_dst, stream);
+}
+
+// Argument checks and device state of a new session.  The state is set up ON THE SESSION'S STREAM, by asynchronous memsets and
+// a kernel that stores the camera record: nothing here blocks, so a session can be created while its stream is busy without
+// waiting for it (a blocking call on the NULL stream may be queued behind any stream's backlog).  zero_sums = false: the
+// caller fills the sums itself (resume; a memset on the stream would run after its blocking copies).
+int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, rtk_progressive** out, bool zero_sums = true) {
     if (!ctx || !cam || !opts || !out) return fail(RTK_ERR_INVALID, "%s: null argument", who);
     *out = nullptr;
     uint64_t digest = 0;
@@ -143,11 +157,11 @@ int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opt
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_order), size_t(tm.n_tiles_local) * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_stats), (size_t(noise_partial_blocks(tm)) + 1) * 3 * sizeof(double));
     // zeroed sums: a checkpoint holds defined bytes for the pixels outside the image too
-    if (e == hipSuccess) e = hipMemset(p->d_sum, 0, slots * 3 * p->elem);
-    if (e == hipSuccess) e = hipMemset(p->d_s1, 0, slots * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(p->d_s2, 0, slots * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(p->d_cost, 0, size_t(tm.n_tiles_local) * sizeof(unsigned int));
-    if (e == hipSuccess) e = upload_camera(*cam, p->real_mode, p->d_cam);
+    if (e == hipSuccess && zero_sums) e = hipMemsetAsync(p->d_sum, 0, slots * 3 * p->elem, p->stream);
+    if (e == hipSuccess && zero_sums) e = hipMemsetAsync(p->d_s1, 0, slots * sizeof(double), p->stream);
+    if (e == hipSuccess && zero_sums) e = hipMemsetAsync(p->d_s2, 0, slots * sizeof(double), p->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_cost, 0, size_t(tm.n_tiles_local) * sizeof(unsigned int), p->stream);
+    if (e == hipSuccess) e = upload_camera(*cam, p->real_mode, p->d_cam, p->stream);
     if (e != hipSuccess) {
         release(p);
         return fail(RTK_ERR_HIP, "%s: device allocation failed: %s", who, hipGetErrorString(e));
@@ -156,13 +170,21 @@ int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opt
     return RTK_OK;
 }
 
-// Device state of an adaptive session: every in-image tile active with 0 samples (tile_spp = h_spp when given: resume).
+// Device state of an adaptive session: every in-image tile active with 0 samples, set up on the session's stream without a
+// blocking call (rtk_progressive_set_adaptive) -- or tile_spp = h_spp when given (resume, which copies the caller's
+// checkpoint with blocking calls anyway).
 hipError_t make_adaptive(rtk_progressive* p, const int32_t* h_spp) {
     const size_t n = size_t(p->tm.n_tiles_local);
     hipError_t e = hipSuccess;
     if (!p->d_active) e = hipMalloc(reinterpret_cast<void**>(&p->d_active), n * sizeof(int32_t));
     if (e == hipSuccess && !p->d_tile_spp) e = hipMalloc(reinterpret_cast<void**>(&p->d_tile_spp), n * sizeof(int32_t));
     if (e == hipSuccess && !p->d_list) e = hipMalloc(reinterpret_cast<void**>(&p->d_list), (n + 1) * sizeof(int32_t));
+    p->list_valid = false;
+    if (!h_spp) {
+        if (e == hipSuccess) e = hipMemsetAsync(p->d_list, 0, (n + 1) * sizeof(int32_t), p->stream);
+        if (e == hipSuccess) e = launch_adaptive_init(p->tm, p->d_active, p->d_tile_spp, p->stream);
+        return e;
+    }
     if (e == hipSuccess) e = hipMemset(p->d_list, 0, (n + 1) * sizeof(int32_t));
     std::vector<int32_t> active(n), spp(n, 0);
     for (size_t lt = 0; lt < n; lt++) active[lt] = tile_pixels(p->cam.image_width, p->cam.image_height, p->rank, p->n_ranks, int64_t(lt)) > 0 ? 1 : 0;
@@ -506,7 +528,7 @@ int rtk_progressive_resume(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render
         return fail(RTK_ERR_INVALID, "rtk_progressive_resume: the checkpoint was made on another scene or visiting order (digest %016llx, uploaded %016llx)",
                     (unsigned long long)info.scene_digest, (unsigned long long)digest);
     rtk_progressive* p = nullptr;
-    if ((rc = make_session(ctx, cam, opts, "rtk_progressive_resume", &p)) != RTK_OK) return rc;
+    if ((rc = make_session(ctx, cam, opts, "rtk_progressive_resume", &p, /*zero_sums=*/false)) != RTK_OK) return rc;  // the copies below fill every sum
     const size_t slots = p->n_slots();
     const unsigned char* at = b + kCheckpointHeader;
     hipError_t e = hipMemcpy(p->d_sum, at, slots * 3 * p->elem, hipMemcpyHostToDevice);

@@ -58,6 +58,10 @@ hipError_t launch_adaptive_restore(const double* s1, const double* s2, const Til
                                    int done, bool retire_ok, double rel_target, int32_t* active, hipStream_t stream);
 // list = the positions of `order` (identity when null; n entries) whose tile is active, in order; *count = their number.
 hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, int n, int32_t* list, int32_t* count, hipStream_t stream);
+// Session set-up on the session's stream: a record of up to 256 bytes (a multiple of 4) stored from a kernel argument; the
+// state of a fresh adaptive session (in-image tiles active, no samples).
+hipError_t launch_store_record(const void* h_record, size_t bytes, void* d_dst, hipStream_t stream);
+hipError_t launch_adaptive_init(const TileMap& tmap, int32_t* active, int32_t* tile_spp, hipStream_t stream);
 // launch_noise_stats with per-tile K = tile_spp[t] / chunk_size (the same kernel, given tile_spp).
 hipError_t launch_noise_stats_adaptive(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
                                        double* partials, double* out3, hipStream_t stream);
