@@ -357,7 +357,7 @@ int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks);
  *
  * Streams (this holds for every entry point that is "asynchronous on" a stream:
  * rtk_render_device, rtk_tiles_unpermute, rtk_progressive_step, rtk_render_aovs,
- * rtk_denoise, rtk_progressive_denoise):
+ * rtk_denoise, rtk_progressive_denoise, rtk_render_guides, rtk_denoise_guided, rtk_progressive_denoise_guided):
  *   - all work of a call -- kernels, memsets, the upload of the camera record --
  *     is enqueued on the stream it is given and on no other; the call reads its
  *     host arguments (cam, opts) before it returns and never waits for the
@@ -631,6 +631,56 @@ int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_m
  * returns the linear image as doubles. */
 int rtk_progressive_denoise(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8);
 int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8);
+
+/* Guides that follow mirrors ---------------------------------------------------------
+ * First-hit guides give everything seen in a mirror one albedo, one smooth normal and one smooth depth.  rtk_render_guides
+ * writes 16 floats per pixel, d_guides[(j*W+i)*16 + k]:
+ *   k 0-7   set 1: exactly what rtk_render_aovs writes for the same camera, seed, real mode and n_samples (bit-identical)
+ *   k 8-10  seen albedo, mean over the n samples      k 11     end-hit fraction
+ *   k 12-14 end normal summed over end hits, / n      k 15     mean over end hits of the path length
+ * Per sample s of pixel (i, j), in the real mode's type:  ray_0 = the render's primary ray, T = (1, 1, 1), len = 0;  for
+ * b = 0, 1, ...: hit_b = the closest hit of ray_b on interval(0.001, inf), a constant medium drawing from the stream of keys
+ * (seed, j*W+i, 2^31 + ((2b) << 20) + s) (b = 0 is rtk_render_aovs' key).  A miss adds T * clamp01(background) to the seen
+ * albedo and ends the sample without an end hit.  Otherwise len += t_b |rd_b|; the hit material is FOLLOWED when
+ * (follow & RTK_GUIDE_FOLLOW_MIRROR and it is a metal with fuzz 0) or (follow & RTK_GUIDE_FOLLOW_DIELECTRIC and it is a
+ * dielectric).  A followed hit with b < max_bounces runs material::scatter (as rtk_debug_scatter does) with the stream of keys
+ * (seed, j*W+i, 2^31 + ((2b+1) << 20) + s); if it scatters, T = T * attenuation, ray_{b+1} = the scattered ray (time kept)
+ * and the chain goes on.  Every other hit is the END HIT: seen albedo += T * (rtk_render_aovs' albedo rule at hit_b), end
+ * normal += the record's normal (isotropic: 0), path length += len.  Sums run in sample order and are divided once (k 15 by
+ * the end hits), then rounded to float.  Where nothing is followed, k 8-15 equal k 0-7 bit for bit.
+ * Options (NULL = defaults): follow 0 = RTK_GUIDE_FOLLOW_MIRROR, other bits RTK_ERR_INVALID (glass is followed by the
+ * render's own reflect / refract lottery: noisy at few samples, hence opt-in); max_bounces 0 = 4, else 1..8.
+ * n_samples 1 .. 2^20.  Otherwise the rules of rtk_render_aovs: whole images only, asynchronous on opts->stream, _host blocks.
+ *
+ * rtk_denoise_guided is rtk_denoise's iteration (taps, h, tap order, w_l, variance propagation, output conversion) with
+ *   w_n = min(w_n of set 1, w_n of set 2), w_z = min(w_z of set 1, w_z of set 2) -- each w_z with its own set's hit fraction,
+ *   depth and depth gradient (k 3 / 7 and k 11 / 15) -- and w_a on the SEEN albedo (k 8-10).
+ * With set 2 == set 1 every weight is rtk_denoise's and the output is bit-identical to it.
+ * flags & RTK_DENOISE_DEMODULATE: the filter runs on irradiance.  Before the first iteration A = max(seen albedo, 0.02) per
+ * channel, c' = c / A, var' = var / ((A.x + A.y + A.z) / 3)^2; w_a = 1 (sigma_a is ignored); after the last iteration
+ * out = c' * A, then the usual conversion.  It keeps textures sharp where the guide albedo matches the colour (a textured wall:
+ * the error falls by half) and loses where few-pixel objects give a 4-sample albedo that does not (book1_final): off by default.
+ * Other flag bits give RTK_ERR_INVALID.  Outputs may alias d_linear or d_noise but not d_guides. */
+#define RTK_GUIDE_FOLLOW_MIRROR 1
+#define RTK_GUIDE_FOLLOW_DIELECTRIC 2
+#define RTK_DENOISE_DEMODULATE 1
+typedef struct rtk_guide_opts {
+    int32_t follow;       /* RTK_GUIDE_FOLLOW_* bits; 0 = RTK_GUIDE_FOLLOW_MIRROR */
+    int32_t max_bounces;  /* 0 = 4, else 1..8 */
+} rtk_guide_opts;
+
+int rtk_render_guides(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* d_guides);
+int rtk_render_guides_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* h_guides);
+int rtk_denoise_guided(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const void* d_linear, const float* d_guides, const float* d_noise,
+                       const rtk_denoise_opts* opts, int32_t flags, void* d_out_linear, uint8_t* d_out_rgb8, void* stream);
+int rtk_denoise_guided_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear, const float* h_guides,
+                            const float* h_noise, const rtk_denoise_opts* opts, int32_t flags, double* h_out_linear, uint8_t* h_out_rgb8);
+/* rtk_progressive_denoise with followed guides: the guides of the session's camera and seed are rendered on first use and kept
+ * per (aov_samples, follow, max_bounces) on the session (not in checkpoints); the session is otherwise unchanged. */
+int rtk_progressive_denoise_guided(rtk_progressive* p, int32_t aov_samples, const rtk_guide_opts* gopts, const rtk_denoise_opts* opts, int32_t flags,
+                                   void* d_out_linear, uint8_t* d_out_rgb8);
+int rtk_progressive_denoise_guided_host(rtk_progressive* p, int32_t aov_samples, const rtk_guide_opts* gopts, const rtk_denoise_opts* opts, int32_t flags,
+                                        double* h_out_linear, uint8_t* h_out_rgb8);
 
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and

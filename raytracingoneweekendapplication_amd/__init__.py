@@ -198,6 +198,17 @@ def _denoise_opts(iterations: int = 0, sigma_l: float = 0.0, sigma_n: float = 0.
     return DenoiseOpts(int(iterations), float(sigma_l), float(sigma_n), float(sigma_z), float(sigma_a), 0)
 
 
+class GuideOpts(C.Structure):
+    """rtk_guide_opts (include/rtk.h): follow = GUIDE_FOLLOW_* bits (0 = mirrors), max_bounces 1..8 (0 = 4)."""
+
+    _fields_ = [("follow", C.c_int32), ("max_bounces", C.c_int32)]
+
+
+GUIDE_FOLLOW_MIRROR = 1
+GUIDE_FOLLOW_DIELECTRIC = 2
+DENOISE_DEMODULATE = 1
+
+
 def host_lib() -> C.CDLL:
     """librtk_host.so: scene construction + flattening (no GPU needed)."""
     global _host_lib
@@ -311,6 +322,16 @@ def hip_lib() -> C.CDLL:
                                              C.c_void_p, C.c_void_p]
             lib.rtk_progressive_denoise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]
             lib.rtk_progressive_denoise_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]
+            lib.rtk_render_guides.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_int32, C.POINTER(GuideOpts), C.c_void_p]
+            lib.rtk_render_guides_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_int32, C.POINTER(GuideOpts), C.c_void_p]
+            lib.rtk_denoise_guided.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseOpts),
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rtk_denoise_guided_host.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(DenoiseOpts), C.c_int32, C.c_void_p, C.c_void_p]
+            lib.rtk_progressive_denoise_guided.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GuideOpts), C.POINTER(DenoiseOpts), C.c_int32, C.c_void_p,
+                                                           C.c_void_p]
+            lib.rtk_progressive_denoise_guided_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GuideOpts), C.POINTER(DenoiseOpts), C.c_int32, C.c_void_p,
+                                                                C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -618,6 +639,39 @@ class Renderer:
                                                out.ctypes.data, rgb8.ctypes.data))
         return out, rgb8
 
+    def guides(self, cam: Camera, samples: int = 4, *, follow: int = GUIDE_FOLLOW_MIRROR, max_bounces: int = 0, seed: int = RENDER_SEED,
+               real_mode: int = RTK_REAL_F64):
+        """rtk_render_guides_host: the guide buffers that follow mirrors (``follow`` = GUIDE_FOLLOW_* bits, at most ``max_bounces``
+        followed hits per sample, 0 = 4), float32 (H, W, 16): [..., :8] are ``aovs``' values; [..., 8:16] the seen albedo(3), end-hit
+        fraction, end normal(3) and path length of the surface a mirror shows."""
+        import numpy as np
+
+        out = np.zeros((cam.image_height, cam.image_width, 16), np.float32)
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        gopts = GuideOpts(int(follow), int(max_bounces))
+        self._check(self._lib.rtk_render_guides_host(self._ctx, C.byref(cam), C.byref(opts), int(samples), C.byref(gopts), out.ctypes.data))
+        return out
+
+    def denoise_guided(self, linear, guides, noise, *, demodulate: bool = False, real_mode: int = RTK_REAL_F64, iterations: int = 0,
+                       sigma_l: float = 0.0, sigma_n: float = 0.0, sigma_z: float = 0.0, sigma_a: float = 0.0):
+        """rtk_denoise_guided_host: ``denoise`` guided by ``guides`` (H, W, 16) -- normal and depth weights are the smaller of the
+        first-hit and the seen surface's, the albedo weight is taken on the seen albedo.  ``demodulate`` filters colour / albedo
+        instead (no albedo weight) and multiplies the albedo back.  Returns (linear float64 (H, W, 3), rgb8 (H, W, 3))."""
+        import numpy as np
+
+        linear = np.ascontiguousarray(linear, np.float64)
+        guides = np.ascontiguousarray(guides, np.float32)
+        noise = np.ascontiguousarray(noise, np.float32)
+        h, w = linear.shape[:2]
+        if linear.shape != (h, w, 3) or guides.shape != (h, w, 16) or noise.shape != (h, w):
+            raise ValueError(f"denoise_guided: shapes {linear.shape}, {guides.shape}, {noise.shape} do not describe one (H, W) image")
+        out, rgb8 = np.zeros((h, w, 3)), np.zeros((h, w, 3), np.uint8)
+        opts = _denoise_opts(iterations, sigma_l, sigma_n, sigma_z, sigma_a)
+        flags = DENOISE_DEMODULATE if demodulate else 0
+        self._check(self._lib.rtk_denoise_guided_host(self._ctx, w, h, real_mode, linear.ctypes.data, guides.ctypes.data, noise.ctypes.data,
+                                                      C.byref(opts), flags, out.ctypes.data, rgb8.ctypes.data))
+        return out, rgb8
+
     def progressive(self, cam: Camera, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
                     stream: int = 0, rel_target: float | None = None, min_samples: int | None = None) -> "Progressive":
         """rtk_progressive_create: a session that renders the frame of ``cam`` (samples_per_pixel = the target) in steps.
@@ -750,6 +804,18 @@ class Progressive:
         out, rgb8 = np.zeros((self.height, self.width, 3)), np.zeros((self.height, self.width, 3), np.uint8)
         o = _denoise_opts(**opts)
         self._check(self._lib.rtk_progressive_denoise_host(self._h, int(aov_samples), C.byref(o), out.ctypes.data, rgb8.ctypes.data))
+        return out, rgb8
+
+    def denoised_guided(self, aov_samples: int = 4, *, follow: int = GUIDE_FOLLOW_MIRROR, max_bounces: int = 0, demodulate: bool = False, **opts):
+        """rtk_progressive_denoise_guided_host: ``denoised`` with the guides of ``Renderer.guides`` (kept on the session per
+        aov_samples, follow and max_bounces) and, with ``demodulate``, on colour / albedo.  The session is not changed."""
+        import numpy as np
+
+        out, rgb8 = np.zeros((self.height, self.width, 3)), np.zeros((self.height, self.width, 3), np.uint8)
+        o = _denoise_opts(**opts)
+        g = GuideOpts(int(follow), int(max_bounces))
+        self._check(self._lib.rtk_progressive_denoise_guided_host(self._h, int(aov_samples), C.byref(g), C.byref(o), DENOISE_DEMODULATE if demodulate else 0,
+                                                                  out.ctypes.data, rgb8.ctypes.data))
         return out, rgb8
 
     def save(self) -> bytes:

@@ -1,6 +1,7 @@
-// rtk_denoise.hip -- the entry points of the AOV pass (its kernel, rtk_aov_kernel, shares the traversal of rtk_trace.hip) and
-// the variance-guided edge-avoiding a-trous filter of include/rtk.h ("Denoiser"): Dammertz et al. 2010
-// with the luminance weight of SVGF (Schied et al. 2017), spatial part only.  Hand-written HIP for gfx950, wave64.
+// rtk_denoise.hip -- the entry points of the AOV and guide passes (their kernels, rtk_aov_kernel and rtk_guide_kernel, share the
+// traversal of rtk_trace.hip) and the variance-guided edge-avoiding a-trous filter of include/rtk.h ("Denoiser"): Dammertz et
+// al. 2010 with the luminance weight of SVGF (Schied et al. 2017), spatial part only, and its guided form ("Guides that follow
+// mirrors": two sets of guides, optional albedo demodulation).  Hand-written HIP for gfx950, wave64.
 //
 // Layout.  Every pixel carries its colour and variance as one float4 {r, g, b, var} (the context's ping-pong buffers) and its
 // guides as the two float4s rtk_render_aovs writes, {albedo, hit fraction} and {mean normal, depth}: a tap is three 16-byte
@@ -160,6 +161,148 @@ hipError_t launch_denoise(const DenoiseParams& P, int iterations, const void* li
     return e;
 }
 
+// ---- the guided filter (rtk_denoise_guided): guides are the four float4s rtk_render_guides writes per pixel, {first albedo,
+// hit}, {normal, depth}, {seen albedo, end hit}, {end normal, path length}.  A tap reads the colour, the last three and the
+// first one's hit fraction (a 4-byte load): 4 x 16 B + 4 B.  The weights are the expressions of rtk_denoise_step_kernel, once
+// per set, so guides whose second set equals the first give that kernel's bits.
+
+// Depth gradient of guide float4 `slot` (1 = first hit, 3 = end hit): half the larger central difference, edges clamped.
+RTK_DN float guide_depth_gradient(const float4* __restrict__ g, int slot, int i, int j, int W, int H) {
+    const float zx = fabsf(g[(size_t(j) * W + clampi(i + 1, 0, W - 1)) * 4 + slot].w - g[(size_t(j) * W + clampi(i - 1, 0, W - 1)) * 4 + slot].w);
+    const float zy = fabsf(g[(size_t(clampi(j + 1, 0, H - 1)) * W + i) * 4 + slot].w - g[(size_t(clampi(j - 1, 0, H - 1)) * W + i) * 4 + slot].w);
+    return (zx > zy ? zx : zy) / 2.0f;
+}
+
+RTK_DN bool zero3(float4 v) { return v.x == 0.0f && v.y == 0.0f && v.z == 0.0f; }
+
+RTK_DN float normal_weight(float4 gp, bool np_zero, float np_len, float4 gq, float sigma_n) {
+    const bool nq_zero = zero3(gq);
+    if (np_zero || nq_zero) return np_zero && nq_zero ? 1.0f : 0.0f;
+    const float c = (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z) / (np_len * sqrtf(gq.x * gq.x + gq.y * gq.y + gq.z * gq.z));
+    return c > 0.0f ? __powf(c, sigma_n) : 0.0f;
+}
+
+RTK_DN float depth_weight(float hit_p, float hit_q, float zp, float zq, float grad, float o, float sigma_z) {
+    if (hit_p == 0.0f || hit_q == 0.0f) return 1.0f;
+    return __expf(-fabsf(zp - zq) / (sigma_z * (grad * o + 1e-3f * zp) + 1e-6f));
+}
+
+// The albedo a demodulating filter divides by and multiplies back: max(seen albedo, 0.02) per channel.
+RTK_DN float4 demodulation_albedo(float4 seen) {
+    return make_float4(seen.x > 0.02f ? seen.x : 0.02f, seen.y > 0.02f ? seen.y : 0.02f, seen.z > 0.02f ? seen.z : 0.02f, 0.0f);
+}
+
+// rtk_denoise_pack_kernel, and with DEMOD the division by the albedo: c' = c / A, var' = var / mean(A)^2.
+template <typename real, bool DEMOD>
+__global__ __launch_bounds__(256) void rtk_denoise_guided_pack_kernel(DenoiseParams P, const real* __restrict__ linear, const float* __restrict__ noise,
+                                                                       const float4* __restrict__ guides, float4* __restrict__ cv) {
+    int i, j;
+    if (!lane_pixel(P, i, j)) return;
+    const size_t px = size_t(j) * P.width + i;
+    const float se = noise[px];
+    float4 c = make_float4(float(linear[px * 3]), float(linear[px * 3 + 1]), float(linear[px * 3 + 2]), se * se);
+    if constexpr (DEMOD) {
+        const float4 A = demodulation_albedo(guides[px * 4 + 2]);
+        const float m = (A.x + A.y + A.z) / 3.0f;
+        c = make_float4(c.x / A.x, c.y / A.y, c.z / A.z, c.w / (m * m));
+    }
+    cv[px] = c;
+}
+
+// One guided a-trous iteration with taps 2^k apart (rtk_denoise_step_kernel's conventions).
+template <typename real, bool DEMOD>
+__global__ __launch_bounds__(256) void rtk_denoise_guided_step_kernel(DenoiseParams P, int step, const float4* __restrict__ cv, const float4* __restrict__ guides,
+                                                                       float4* __restrict__ out_cv, real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8) {
+    int i, j;
+    if (!lane_pixel(P, i, j)) return;
+    const int W = P.width, H = P.height;
+    const size_t px = size_t(j) * W + i;
+    const float4 cp = cv[px];
+    const float hit1_p = guides[px * 4].w;
+    const float4 g1p = guides[px * 4 + 1], ap = guides[px * 4 + 2], g2p = guides[px * 4 + 3];  // {normal, depth}, {seen albedo, end hit}, {end normal, length}
+    const float bw[3] = {0.25f, 0.5f, 0.25f};
+    float gv = 0.0f;
+    for (int b = -1; b <= 1; b++) {
+        const size_t row = size_t(clampi(j + b, 0, H - 1)) * W;
+        for (int a = -1; a <= 1; a++) gv += bw[b + 1] * bw[a + 1] * cv[row + clampi(i + a, 0, W - 1)].w;
+    }
+    const float grad1 = guide_depth_gradient(guides, 1, i, j, W, H), grad2 = guide_depth_gradient(guides, 3, i, j, W, H);
+    const float yp = luminance(cp);
+    const float l_den = P.sigma_l * sqrtf(gv > 0.0f ? gv : 0.0f) + 1e-6f;
+    const bool n1p_zero = zero3(g1p), n2p_zero = zero3(g2p);
+    const float n1p_len = sqrtf(g1p.x * g1p.x + g1p.y * g1p.y + g1p.z * g1p.z), n2p_len = sqrtf(g2p.x * g2p.x + g2p.y * g2p.y + g2p.z * g2p.z);
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qj = j + step * dy;
+        if (qj < 0 || qj >= H) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qi = i + step * dx;
+            if (qi < 0 || qi >= W) continue;
+            const size_t q = size_t(qj) * W + qi;
+            const float4 cq = cv[q];
+            const float hit1_q = guides[q * 4].w;
+            const float4 g1q = guides[q * 4 + 1], aq = guides[q * 4 + 2], g2q = guides[q * 4 + 3];
+            const float wl = __expf(-fabsf(yp - luminance(cq)) / l_den);
+            const float wn1 = normal_weight(g1p, n1p_zero, n1p_len, g1q, P.sigma_n), wn2 = normal_weight(g2p, n2p_zero, n2p_len, g2q, P.sigma_n);
+            const float wn = wn1 < wn2 ? wn1 : wn2;
+            const float o = float(step) * sqrtf(float(dx * dx + dy * dy));
+            const float wz1 = depth_weight(hit1_p, hit1_q, g1p.w, g1q.w, grad1, o, P.sigma_z), wz2 = depth_weight(ap.w, aq.w, g2p.w, g2q.w, grad2, o, P.sigma_z);
+            const float wz = wz1 < wz2 ? wz1 : wz2;
+            float wa = 1.0f;
+            if constexpr (!DEMOD) {
+                const float ex = ap.x - aq.x, ey = ap.y - aq.y, ez = ap.z - aq.z;
+                wa = __expf(-sqrtf(ex * ex + ey * ey + ez * ez) / P.sigma_a);
+            }
+            const float w = h[dx + 2] * h[dy + 2] * wl * wn * wz * wa;
+            sw += w;
+            sr += w * cq.x;
+            sg += w * cq.y;
+            sb += w * cq.z;
+            sv += w * w * cq.w;
+        }
+    }
+    float r = sr / sw, g = sg / sw, b = sb / sw;
+    if (out_cv) {
+        out_cv[px] = make_float4(r, g, b, sv / (sw * sw));
+        return;
+    }
+    if constexpr (DEMOD) {
+        const float4 A = demodulation_albedo(ap);
+        r *= A.x;
+        g *= A.y;
+        b *= A.z;
+    }
+    if (out_linear) {
+        out_linear[px * 3] = real(r);
+        out_linear[px * 3 + 1] = real(g);
+        out_linear[px * 3 + 2] = real(b);
+    }
+    if (out_rgb8) {
+        out_rgb8[px * 3] = denoise_byte(double(r));
+        out_rgb8[px * 3 + 1] = denoise_byte(double(g));
+        out_rgb8[px * 3 + 2] = denoise_byte(double(b));
+    }
+}
+
+template <typename real, bool DEMOD>
+hipError_t launch_denoise_guided(const DenoiseParams& P, int iterations, const void* linear, const float* noise, const float4* guides, float4* ping, float4* pong,
+                                 void* out_linear, uint8_t* out_rgb8, hipStream_t stream) {
+    const dim3 grid((P.n_tiles + 3) / 4), block(256);
+    rtk_denoise_guided_pack_kernel<real, DEMOD><<<grid, block, 0, stream>>>(P, static_cast<const real*>(linear), noise, guides, ping);
+    hipError_t e = hipGetLastError();
+    for (int k = 0; k < iterations && e == hipSuccess; k++) {
+        const bool last = k == iterations - 1;
+        rtk_denoise_guided_step_kernel<real, DEMOD><<<grid, block, 0, stream>>>(P, 1 << k, ping, guides, last ? nullptr : pong,
+                                                                                last ? static_cast<real*>(out_linear) : nullptr, last ? out_rgb8 : nullptr);
+        e = hipGetLastError();
+        float4* t = ping;
+        ping = pong;
+        pong = t;
+    }
+    return e;
+}
+
 // The options with defaults for 0 fields; false (and the reason in g_error) when they are out of range.
 bool resolve_opts(const rtk_denoise_opts* in, int& iterations, DenoiseParams& P, const char* who) {
     rtk_denoise_opts o{};
@@ -192,6 +335,21 @@ int check_denoise_opts(const rtk_denoise_opts* opts, const char* who) {
     DenoiseParams P{};
     int iterations = 0;
     return resolve_opts(opts, iterations, P, who) ? RTK_OK : RTK_ERR_INVALID;
+}
+
+int resolve_guide_opts(const rtk_guide_opts* gopts, int* follow, int* max_bounces, const char* who) {
+    rtk_guide_opts o{};
+    if (gopts) o = *gopts;
+    if (o.follow & ~(RTK_GUIDE_FOLLOW_MIRROR | RTK_GUIDE_FOLLOW_DIELECTRIC)) return fail(RTK_ERR_INVALID, "%s: unknown follow bits 0x%x", who, unsigned(o.follow));
+    if (o.max_bounces < 0 || o.max_bounces > 8) return fail(RTK_ERR_INVALID, "%s: max_bounces %d out of range (1..8, 0 = 4)", who, o.max_bounces);
+    *follow = o.follow == 0 ? RTK_GUIDE_FOLLOW_MIRROR : o.follow;
+    *max_bounces = o.max_bounces == 0 ? 4 : o.max_bounces;
+    return RTK_OK;
+}
+
+int check_denoise_flags(int32_t flags, const char* who) {
+    if (flags & ~RTK_DENOISE_DEMODULATE) return fail(RTK_ERR_INVALID, "%s: unknown flags 0x%x", who, unsigned(flags));
+    return RTK_OK;
 }
 
 }  // namespace rtk
@@ -267,20 +425,108 @@ int rtk_denoise(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, 
     return RTK_OK;
 }
 
-int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear, const float* h_aov, const float* h_noise,
-                     const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8) {
-    if (!ctx) return fail(RTK_ERR_INVALID, "rtk_denoise_host: null context");
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise_host: bad image size %dx%d", width, height);
-    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise_host: unknown real_mode %d", real_mode);
-    if (!h_linear || !h_aov || !h_noise) return fail(RTK_ERR_INVALID, "rtk_denoise_host: h_linear, h_aov and h_noise are required");
-    if (!h_out_linear && !h_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise_host: no output");
+// Argument checks of rtk_render_guides / _host that need no device (options first: they need no context either).
+static int check_guide_args(const char* who, rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts,
+                            const float* out, int* follow, int* max_bounces) {
+    int rc = resolve_guide_opts(gopts, follow, max_bounces, who);
+    if (rc != RTK_OK) return rc;
+    if (n_samples <= 0 || n_samples > (1 << 20)) return fail(RTK_ERR_INVALID, "%s: n_samples must be 1 .. 2^20 (%d)", who, n_samples);
+    if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "%s: null argument", who);
+    if (!out) return fail(RTK_ERR_INVALID, "%s: null output buffer", who);
+    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->image_width > 65536 || cam->image_height > 65536)
+        return fail(RTK_ERR_INVALID, "%s: bad camera dimensions", who);
+    if (opts->n_ranks != 1) return fail(RTK_ERR_INVALID, "%s: whole images only (n_ranks must be 1, not %d)", who, opts->n_ranks);
+    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, opts->real_mode);
+    return RTK_OK;
+}
+
+int rtk_render_guides(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* d_guides) {
+    int follow = 0, max_bounces = 0;
+    const int rc = check_guide_args("rtk_render_guides", ctx, cam, opts, n_samples, gopts, d_guides, &follow, &max_bounces);
+    if (rc != RTK_OK) return rc;
+    uint64_t digest = 0;
+    if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "rtk_render_guides: no scene uploaded");
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    const hipStream_t st = static_cast<hipStream_t>(opts->stream);
+    const hipError_t e = opts->real_mode == RTK_REAL_F64
+                             ? launch_guides<double>(ctx_view<double>(ctx), device_camera<double>(*cam), opts->seed, n_samples, follow, max_bounces, d_guides, st)
+                             : launch_guides<float>(ctx_view<float>(ctx), device_camera<float>(*cam), opts->seed, n_samples, follow, max_bounces, d_guides, st);
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_render_guides: %s", hipGetErrorString(e));
+    return RTK_OK;
+}
+
+int rtk_render_guides_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* h_guides) {
+    int follow = 0, max_bounces = 0;
+    int rc = check_guide_args("rtk_render_guides_host", ctx, cam, opts, n_samples, gopts, h_guides, &follow, &max_bounces);
+    if (rc != RTK_OK) return rc;
+    uint64_t digest = 0;
+    if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "rtk_render_guides_host: no scene uploaded");
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    const size_t n = size_t(cam->image_width) * cam->image_height * 16;
+    float* d_guides = nullptr;
+    RTK_HIP(hipMalloc(reinterpret_cast<void**>(&d_guides), n * sizeof(float)));
+    rc = rtk_render_guides(ctx, cam, opts, n_samples, gopts, d_guides);
+    if (rc == RTK_OK) {
+        hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
+        if (e == hipSuccess) e = hipMemcpy(h_guides, d_guides, n * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RTK_ERR_HIP, "rtk_render_guides_host: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(d_guides);
+    return rc;
+}
+
+int rtk_denoise_guided(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const void* d_linear, const float* d_guides, const float* d_noise,
+                       const rtk_denoise_opts* opts, int32_t flags, void* d_out_linear, uint8_t* d_out_rgb8, void* stream) {
+    if (check_denoise_flags(flags, "rtk_denoise_guided") != RTK_OK) return RTK_ERR_INVALID;
+    DenoiseParams P{};
+    int iterations = 0;
+    if (!resolve_opts(opts, iterations, P, "rtk_denoise_guided")) return RTK_ERR_INVALID;
+    if (!ctx) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: null context");
+    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: bad image size %dx%d", width, height);
+    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: unknown real_mode %d", real_mode);
+    if (!d_linear || !d_guides || !d_noise) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: d_linear, d_guides and d_noise are required");
+    if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: no output");
+    P.width = width;
+    P.height = height;
+    P.tiles_x = (width + 7) / 8;
+    P.n_tiles = P.tiles_x * ((height + 7) / 8);
+    hipError_t e = hipSetDevice(ctx_device(ctx));
+    void* ws = nullptr;
+    const size_t plane = size_t(width) * height * sizeof(float4);
+    if (e == hipSuccess) e = denoise_workspace(ctx, 2 * plane, &ws);
+    if (e == hipSuccess) {
+        float4* ping = static_cast<float4*>(ws);
+        float4* pong = reinterpret_cast<float4*>(static_cast<char*>(ws) + plane);
+        const auto* guides = reinterpret_cast<const float4*>(d_guides);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        const bool demod = (flags & RTK_DENOISE_DEMODULATE) != 0, f64 = real_mode == RTK_REAL_F64;
+        if (demod)
+            e = f64 ? launch_denoise_guided<double, true>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st)
+                    : launch_denoise_guided<float, true>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st);
+        else
+            e = f64 ? launch_denoise_guided<double, false>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st)
+                    : launch_denoise_guided<float, false>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st);
+    }
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_denoise_guided: %s", hipGetErrorString(e));
+    return RTK_OK;
+}
+
+// rtk_denoise_host (guide_floats 8) and rtk_denoise_guided_host (16): device copies of the inputs, the asynchronous entry point
+// on the null stream, the outputs copied back.
+static int denoise_host(const char* who, int guide_floats, int32_t flags, rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear,
+                        const float* h_aov, const float* h_noise, const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8) {
+    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
+    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
+    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, real_mode);
+    if (!h_linear || !h_aov || !h_noise) return fail(RTK_ERR_INVALID, "%s: h_linear, %s and h_noise are required", who, guide_floats == 8 ? "h_aov" : "h_guides");
+    if (!h_out_linear && !h_out_rgb8) return fail(RTK_ERR_INVALID, "%s: no output", who);
     {
         DenoiseParams P{};
         int it = 0;
-        if (!resolve_opts(opts, it, P, "rtk_denoise_host")) return RTK_ERR_INVALID;
+        if (!resolve_opts(opts, it, P, who)) return RTK_ERR_INVALID;
     }
     hipError_t e = hipSetDevice(ctx_device(ctx));
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_denoise_host: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     const size_t px = size_t(width) * height, elem = real_mode == RTK_REAL_F64 ? 8 : 4;
     void *d_lin = nullptr, *d_out = nullptr;
     float *d_aov = nullptr, *d_noise = nullptr;
@@ -291,7 +537,7 @@ int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_m
     };
     std::vector<float> tmp;
     e = hipMalloc(&d_lin, px * 3 * elem);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_aov), px * 8 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_aov), px * guide_floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_noise), px * sizeof(float));
     if (e == hipSuccess && h_out_linear) e = hipMalloc(&d_out, px * 3 * elem);
     if (e == hipSuccess && h_out_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), px * 3);
@@ -304,13 +550,14 @@ int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_m
             e = hipMemcpy(d_lin, tmp.data(), px * 3 * sizeof(float), hipMemcpyHostToDevice);
         }
     }
-    if (e == hipSuccess) e = hipMemcpy(d_aov, h_aov, px * 8 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_aov, h_aov, px * guide_floats * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_noise, h_noise, px * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         cleanup();
-        return fail(RTK_ERR_HIP, "rtk_denoise_host: device buffers: %s", hipGetErrorString(e));
+        return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
     }
-    int rc = rtk_denoise(ctx, width, height, real_mode, d_lin, d_aov, d_noise, opts, d_out, d_rgb8, nullptr);
+    int rc = guide_floats == 8 ? rtk_denoise(ctx, width, height, real_mode, d_lin, d_aov, d_noise, opts, d_out, d_rgb8, nullptr)
+                               : rtk_denoise_guided(ctx, width, height, real_mode, d_lin, d_aov, d_noise, opts, flags, d_out, d_rgb8, nullptr);
     if (rc != RTK_OK) {
         cleanup();
         return rc;
@@ -326,8 +573,19 @@ int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_m
     }
     if (e == hipSuccess && h_out_rgb8) e = hipMemcpy(h_out_rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost);
     cleanup();
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_denoise_host: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
+}
+
+int rtk_denoise_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear, const float* h_aov, const float* h_noise,
+                     const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8) {
+    return denoise_host("rtk_denoise_host", 8, 0, ctx, width, height, real_mode, h_linear, h_aov, h_noise, opts, h_out_linear, h_out_rgb8);
+}
+
+int rtk_denoise_guided_host(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear, const float* h_guides,
+                            const float* h_noise, const rtk_denoise_opts* opts, int32_t flags, double* h_out_linear, uint8_t* h_out_rgb8) {
+    if (check_denoise_flags(flags, "rtk_denoise_guided_host") != RTK_OK || check_denoise_opts(opts, "rtk_denoise_guided_host") != RTK_OK) return RTK_ERR_INVALID;
+    return denoise_host("rtk_denoise_guided_host", 16, flags, ctx, width, height, real_mode, h_linear, h_guides, h_noise, opts, h_out_linear, h_out_rgb8);
 }
 
 }  // extern "C"

@@ -57,6 +57,9 @@ CameraRec<real> device_camera(const rtk_camera& cam);
 hipError_t denoise_workspace(rtk_ctx* ctx, size_t bytes, void** out);
 // RTK_OK, or RTK_ERR_INVALID with the reason in g_error, for rtk_denoise_opts out of range (null = every default).
 int check_denoise_opts(const rtk_denoise_opts* opts, const char* who);
+// The same for rtk_guide_opts (null = every default) and the guided filter's flags; *follow / *max_bounces = the resolved options.
+int resolve_guide_opts(const rtk_guide_opts* gopts, int* follow, int* max_bounces, const char* who);
+int check_denoise_flags(int32_t flags, const char* who);
 
 // Block until streams[i] (on ctxs[i]'s device) has drained, i = 0..n-1, feeding ctxs[0]'s progress callback
 // (rtk_set_progress_callback) from the work-item counters of the launches in flight.

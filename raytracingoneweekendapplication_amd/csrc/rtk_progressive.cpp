@@ -57,6 +57,9 @@ struct rtk_progressive {
     // rtk_progressive_denoise: the AOVs of the session's camera and seed per sample count (never in checkpoints) and the
     // preview / se it rebuilds from the sums
     std::vector<std::pair<int, float*>> aovs;
+    // rtk_progressive_denoise_guided: the guides of rtk_render_guides per resolved option set
+    struct GuideSet { int samples, follow, max_bounces; float* d; };
+    std::vector<GuideSet> guides;
     void* d_preview = nullptr;          // H*W*3 reals
     float* d_preview_se = nullptr;      // H*W
     int full_chunks() const { return done / chunk; }  // every chunk before the target's end is full
@@ -99,6 +102,7 @@ void release(rtk_progressive* p) {
                     static_cast<void*>(p->d_list)})
         if (d) (void)hipFree(d);
     for (auto& a : p->aovs) (void)hipFree(a.second);
+    for (auto& g : p->guides) (void)hipFree(g.d);
     if (p->d_preview) (void)hipFree(p->d_preview);
     if (p->d_preview_se) (void)hipFree(p->d_preview_se);
     delete p;
@@ -617,29 +621,49 @@ int rtk_progressive_destroy(rtk_progressive* p) {
     return RTK_OK;
 }
 
-int rtk_progressive_denoise(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8) {
-    int rc = usable(p, "rtk_progressive_denoise");
-    if (rc != RTK_OK) return rc;
-    if (p->n_ranks != 1) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: whole images only (n_ranks must be 1, not %d)", p->n_ranks);
-    if (aov_samples <= 0) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: aov_samples must be positive (%d)", aov_samples);
+// rtk_progressive_denoise (guided false: first-hit AOVs, rtk_denoise) and rtk_progressive_denoise_guided (the guides of
+// rtk_render_guides, rtk_denoise_guided): argument checks, the guides from the session's cache, the preview rebuilt, the filter.
+static int progressive_denoise(const char* who, bool guided, rtk_progressive* p, int32_t aov_samples, const rtk_guide_opts* gopts, const rtk_denoise_opts* opts,
+                               int32_t flags, void* d_out_linear, uint8_t* d_out_rgb8) {
+    int follow = 0, max_bounces = 0;
+    int rc = RTK_OK;
+    if (guided && ((rc = resolve_guide_opts(gopts, &follow, &max_bounces, who)) != RTK_OK || (rc = check_denoise_flags(flags, who)) != RTK_OK)) return rc;
+    if (guided && (rc = check_denoise_opts(opts, who)) != RTK_OK) return rc;
+    if ((rc = usable(p, who)) != RTK_OK) return rc;
+    if (p->n_ranks != 1) return fail(RTK_ERR_INVALID, "%s: whole images only (n_ranks must be 1, not %d)", who, p->n_ranks);
+    if (aov_samples <= 0 || (guided && aov_samples > (1 << 20))) return fail(RTK_ERR_INVALID, "%s: aov_samples must be positive (%d)", who, aov_samples);
     if (p->full_chunks() < 2)
-        return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: the noise estimate needs 2 full chunks in every tile (%d samples done, chunk %d)", p->done, p->chunk);
-    if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise: no output");
-    if ((rc = check_denoise_opts(opts, "rtk_progressive_denoise")) != RTK_OK) return rc;
+        return fail(RTK_ERR_INVALID, "%s: the noise estimate needs 2 full chunks in every tile (%d samples done, chunk %d)", who, p->done, p->chunk);
+    if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "%s: no output", who);
+    if (!guided && (rc = check_denoise_opts(opts, who)) != RTK_OK) return rc;
     RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
     const int W = p->cam.image_width, H = p->cam.image_height;
     const size_t px = size_t(W) * H;
     float* aov = nullptr;
-    for (auto& a : p->aovs)
-        if (a.first == aov_samples) aov = a.second;
-    if (!aov) {
-        RTK_HIP(hipMalloc(reinterpret_cast<void**>(&aov), px * 8 * sizeof(float)));
-        const rtk_render_opts ro{p->seed, p->real_mode, 0, 1, 0, 0, p->stream};
-        if ((rc = rtk_render_aovs(p->ctx, &p->cam, &ro, aov_samples, aov)) != RTK_OK) {
-            (void)hipFree(aov);
-            return rc;
+    const rtk_render_opts ro{p->seed, p->real_mode, 0, 1, 0, 0, p->stream};
+    if (guided) {
+        for (auto& g : p->guides)
+            if (g.samples == aov_samples && g.follow == follow && g.max_bounces == max_bounces) aov = g.d;
+        if (!aov) {
+            RTK_HIP(hipMalloc(reinterpret_cast<void**>(&aov), px * 16 * sizeof(float)));
+            const rtk_guide_opts go{follow, max_bounces};
+            if ((rc = rtk_render_guides(p->ctx, &p->cam, &ro, aov_samples, &go, aov)) != RTK_OK) {
+                (void)hipFree(aov);
+                return rc;
+            }
+            p->guides.push_back({aov_samples, follow, max_bounces, aov});
         }
-        p->aovs.emplace_back(aov_samples, aov);
+    } else {
+        for (auto& a : p->aovs)
+            if (a.first == aov_samples) aov = a.second;
+        if (!aov) {
+            RTK_HIP(hipMalloc(reinterpret_cast<void**>(&aov), px * 8 * sizeof(float)));
+            if ((rc = rtk_render_aovs(p->ctx, &p->cam, &ro, aov_samples, aov)) != RTK_OK) {
+                (void)hipFree(aov);
+                return rc;
+            }
+            p->aovs.emplace_back(aov_samples, aov);
+        }
     }
     if (!p->d_preview) RTK_HIP(hipMalloc(&p->d_preview, px * 3 * p->elem));
     if (!p->d_preview_se) RTK_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_preview_se), px * sizeof(float)));
@@ -647,14 +671,19 @@ int rtk_progressive_denoise(rtk_progressive* p, int32_t aov_samples, const rtk_d
     RTK_HIP(p->real_mode == RTK_REAL_F64
                 ? launch_preview<double>(p->d_sum, p->d_s1, p->d_s2, p->tm, W, H, p->chunk, p->done, spp, p->d_preview, p->d_preview_se, p->stream)
                 : launch_preview<float>(p->d_sum, p->d_s1, p->d_s2, p->tm, W, H, p->chunk, p->done, spp, p->d_preview, p->d_preview_se, p->stream));
-    return rtk_denoise(p->ctx, W, H, p->real_mode, p->d_preview, aov, p->d_preview_se, opts, d_out_linear, d_out_rgb8, p->stream);
+    return guided ? rtk_denoise_guided(p->ctx, W, H, p->real_mode, p->d_preview, aov, p->d_preview_se, opts, flags, d_out_linear, d_out_rgb8, p->stream)
+                  : rtk_denoise(p->ctx, W, H, p->real_mode, p->d_preview, aov, p->d_preview_se, opts, d_out_linear, d_out_rgb8, p->stream);
 }
 
-int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, double* h_linear, uint8_t* h_rgb8) {
-    int rc = usable(p, "rtk_progressive_denoise_host");
-    if (rc != RTK_OK) return rc;
-    if (p->n_ranks != 1) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise_host: whole images only (n_ranks must be 1, not %d)", p->n_ranks);
-    if (!h_linear && !h_rgb8) return fail(RTK_ERR_INVALID, "rtk_progressive_denoise_host: no output");
+static int progressive_denoise_host(const char* who, bool guided, rtk_progressive* p, int32_t aov_samples, const rtk_guide_opts* gopts,
+                                    const rtk_denoise_opts* opts, int32_t flags, double* h_linear, uint8_t* h_rgb8) {
+    int follow = 0, max_bounces = 0;
+    int rc = RTK_OK;
+    if (guided && ((rc = resolve_guide_opts(gopts, &follow, &max_bounces, who)) != RTK_OK || (rc = check_denoise_flags(flags, who)) != RTK_OK)) return rc;
+    if (guided && (rc = check_denoise_opts(opts, who)) != RTK_OK) return rc;
+    if ((rc = usable(p, who)) != RTK_OK) return rc;
+    if (p->n_ranks != 1) return fail(RTK_ERR_INVALID, "%s: whole images only (n_ranks must be 1, not %d)", who, p->n_ranks);
+    if (!h_linear && !h_rgb8) return fail(RTK_ERR_INVALID, "%s: no output", who);
     RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
     const size_t n = size_t(p->cam.image_width) * p->cam.image_height * 3;
     void* d_linear = nullptr;
@@ -663,7 +692,7 @@ int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const 
     if (h_linear) e = hipMalloc(&d_linear, n * p->elem);
     if (e == hipSuccess && h_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), n);
     if (e == hipSuccess) {
-        rc = rtk_progressive_denoise(p, aov_samples, opts, d_linear, d_rgb8);
+        rc = guided ? rtk_progressive_denoise_guided(p, aov_samples, gopts, opts, flags, d_linear, d_rgb8) : rtk_progressive_denoise(p, aov_samples, opts, d_linear, d_rgb8);
         if (rc == RTK_OK) {
             e = hipStreamSynchronize(p->stream);
             if (e == hipSuccess && h_linear) {
@@ -681,8 +710,26 @@ int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const 
     if (d_linear) (void)hipFree(d_linear);
     if (d_rgb8) (void)hipFree(d_rgb8);
     if (rc != RTK_OK) return rc;
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_progressive_denoise_host: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
+}
+
+int rtk_progressive_denoise(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8) {
+    return progressive_denoise("rtk_progressive_denoise", false, p, aov_samples, nullptr, opts, 0, d_out_linear, d_out_rgb8);
+}
+
+int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, double* h_linear, uint8_t* h_rgb8) {
+    return progressive_denoise_host("rtk_progressive_denoise_host", false, p, aov_samples, nullptr, opts, 0, h_linear, h_rgb8);
+}
+
+int rtk_progressive_denoise_guided(rtk_progressive* p, int32_t aov_samples, const rtk_guide_opts* gopts, const rtk_denoise_opts* opts, int32_t flags,
+                                   void* d_out_linear, uint8_t* d_out_rgb8) {
+    return progressive_denoise("rtk_progressive_denoise_guided", true, p, aov_samples, gopts, opts, flags, d_out_linear, d_out_rgb8);
+}
+
+int rtk_progressive_denoise_guided_host(rtk_progressive* p, int32_t aov_samples, const rtk_guide_opts* gopts, const rtk_denoise_opts* opts, int32_t flags,
+                                        double* h_out_linear, uint8_t* h_out_rgb8) {
+    return progressive_denoise_host("rtk_progressive_denoise_guided_host", true, p, aov_samples, gopts, opts, flags, h_out_linear, h_out_rgb8);
 }
 
 }  // extern "C"

@@ -84,6 +84,12 @@ hipError_t launch_debug_get_ray(const CameraRec<real>& cam, uint32_t seed, int n
 template <typename real>
 hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream);
 
+// The same with the surface seen through followed mirrors / glass: guides[(j * W + i) * 16 + k], k 0-7 = launch_aov's values
+// (rtk_render_guides).  follow = RTK_GUIDE_FOLLOW_* bits, max_bounces 1..8 (both resolved by the caller).
+template <typename real>
+hipError_t launch_guides(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, int follow, int max_bounces, float* d_guides,
+                         hipStream_t stream);
+
 // A one-rank progressive session's preview and se (row-major) from its running sum and noise sums; tile_spp null = every tile
 // holds `done` samples.  Reads the state only.
 template <typename real>

@@ -2320,6 +2320,95 @@ __global__ __launch_bounds__(256) void rtk_aov_kernel(SceneView<real> sc, Camera
     o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(depth / hits) : 0.0f);
 }
 
+// Mirror-following guide buffers of the denoiser (include/rtk.h, rtk_render_guides): rtk_aov_kernel's lane-per-pixel layout and
+// first-hit sums (guides[px][0..7], the same expressions in the same order: bit-identical), plus the surface a chain of followed
+// specular hits ends on.  Segment b of sample s re-seeds its stream with keys (seed, pixel, 2^31 + (2b << 20) + s) for the
+// closest hit -- b = 0 is rtk_aov_kernel's key -- and (seed, pixel, 2^31 + ((2b + 1) << 20) + s) for material::scatter, which is
+// shade_surface without point lights as rtk_debug_scatter runs it, compiled for the two followed kinds alone (FORCE_KIND: no
+// texture code in the chain).  L.throughput carries T.  A followed hit at b == max_bounces, or one that does not scatter, ends
+// the chain by the first-hit rule.
+//   guides[px][8..10]  seen albedo: T * (albedo rule of the end hit, or the clamped background), mean over n
+//   guides[px][11]     end hits / n
+//   guides[px][12..14] sum over end hits of the record's normal (isotropic: 0) / n
+//   guides[px][15]     mean over end hits of the path length sum_b t_b |rd_b| (0 without end hits)
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_guide_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, int n_samples, int follow, int max_bounces,
+                                                         int tiles_x, int n_tiles, float4* __restrict__ guides) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int tile = int(gid >> 6), pix = int(gid & 63);
+    if (tile >= n_tiles) return;
+    const int i = (tile % tiles_x) * 8 + (pix & 7), j = (tile / tiles_x) * 8 + (pix >> 3);
+    if (i >= cam.width || j >= cam.height) return;
+    sc.n_lights = 0;  // get_lighting (Camera.txt:228) belongs to ray_color, not to scatter()
+    Counters<false> cnt;
+    const uint32_t seed_hash = pcg_hash(seed);
+    const uint32_t pixel = uint32_t(j * cam.width + i);
+    const V3<real> zero = mk(real(0), real(0), real(0));
+    V3<real> albedo = zero, normal = zero, seen = zero, end_normal = zero;
+    real hits = real(0), depth = real(0), end_hits = real(0), end_len = real(0);
+    for (int s = 0; s < n_samples; s++) {
+        Lane<real> L;
+        L.s = s;
+        L.segs = 0;
+        begin_sample(L, cam, i, j, seed_hash, cnt);
+        L.depth = 1 << 20;  // (the chain is capped by max_bounces, not by the camera's max_depth)
+        real len = real(0);
+        for (int b = 0;; b++) {
+            const uint32_t key = 0x80000000u + (uint32_t(2 * b) << 20) + uint32_t(s);
+            L.rng = pcg_hash(pixel + pcg_hash(key + seed_hash));
+            L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
+            L.sv_best_pc = kNoHit;
+            begin_segment<true>(L, cnt);
+            closest_hit_slots(L, sc, cnt);
+            if (L.best_pc == kNoHit) {
+                const V3<real> bg = mk(clamp01(cam.background[0]), clamp01(cam.background[1]), clamp01(cam.background[2]));
+                if (b == 0) albedo = albedo + bg;
+                seen = seen + L.throughput * bg;
+                break;
+            }
+            Surface<real> sf;
+            make_surface<real, kFeatAll>(sc.program, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
+            const MaterialRec<real>& m = sc.materials[sf.material];
+            const int mkind = m.kind;
+            const real seg = L.best_t * rt_sqrt(length_squared(L.rd));
+            len = len + seg;
+            V3<real> a = mk(real(1), real(1), real(1));  // dielectric
+            if (mkind == RTK_MAT_LAMBERTIAN || mkind == RTK_MAT_ISOTROPIC || mkind == RTK_MAT_DIFFUSE_LIGHT) {
+                a = material_color<real, kFeatAll>(sc, m, sf.u, sf.v, sf.p, cnt);
+                if (mkind == RTK_MAT_DIFFUSE_LIGHT) a = mk(a.x > real(1) ? real(1) : a.x, a.y > real(1) ? real(1) : a.y, a.z > real(1) ? real(1) : a.z);
+            } else if (mkind == RTK_MAT_METAL || mkind == RTK_MAT_SPECULAR) {
+                a = ld3(m.albedo);
+            }
+            const V3<real> nrm = mkind != RTK_MAT_ISOTROPIC ? sf.normal : zero;
+            if (b == 0) {
+                albedo = albedo + a;
+                hits = hits + real(1);
+                normal = normal + nrm;
+                depth = depth + seg;
+            }
+            const bool mirror = (follow & RTK_GUIDE_FOLLOW_MIRROR) && mkind == RTK_MAT_METAL && m.param == real(0);
+            const bool glass = (follow & RTK_GUIDE_FOLLOW_DIELECTRIC) && mkind == RTK_MAT_DIELECTRIC;
+            if ((mirror || glass) && b < max_bounces) {
+                L.rng = pcg_hash(pixel + pcg_hash(key + (1u << 20) + seed_hash));
+                const bool ended = mirror ? shade_surface<real, kFeatAll, RTK_MAT_METAL>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG)
+                                          : shade_surface<real, kFeatAll, RTK_MAT_DIELECTRIC>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG);
+                if (!ended) continue;  // L.ro / L.rd = the scattered ray, L.throughput = T * attenuation, L.tm kept
+            }
+            seen = seen + L.throughput * a;
+            end_normal = end_normal + nrm;
+            end_hits = end_hits + real(1);
+            end_len = end_len + len;
+            break;
+        }
+    }
+    const real n = real(n_samples);
+    float4* o = guides + (size_t(j) * cam.width + i) * 4;
+    o[0] = make_float4(float(albedo.x / n), float(albedo.y / n), float(albedo.z / n), float(hits / n));
+    o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(depth / hits) : 0.0f);
+    o[2] = make_float4(float(seen.x / n), float(seen.y / n), float(seen.z / n), float(end_hits / n));
+    o[3] = make_float4(float(end_normal.x / n), float(end_normal.y / n), float(end_normal.z / n), end_hits > real(0) ? float(end_len / end_hits) : 0.0f);
+}
+
 // ------------------------------------------------------------------ launchers --
 
 // Geometry of a persistent launch: waves per workgroup and workgroups per CU so
@@ -2634,6 +2723,17 @@ hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uin
 }
 template hipError_t launch_aov<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, float*, hipStream_t);
 template hipError_t launch_aov<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, int, float*, hipStream_t);
+
+template <typename real>
+hipError_t launch_guides(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, int follow, int max_bounces, float* d_guides,
+                         hipStream_t stream) {
+    const int tiles_x = (cam.width + 7) / 8, n_tiles = tiles_x * ((cam.height + 7) / 8);
+    rtk_guide_kernel<real><<<dim3((n_tiles + 3) / 4), dim3(256), 0, stream>>>(sc, cam, seed, n_samples, follow, max_bounces, tiles_x, n_tiles,
+                                                                               reinterpret_cast<float4*>(d_guides));
+    return hipGetLastError();
+}
+template hipError_t launch_guides<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, int, int, float*, hipStream_t);
+template hipError_t launch_guides<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, int, int, int, float*, hipStream_t);
 
 #ifdef RTK_ISA_PROBES
 // Instruction-cost probes (tools/isa_costs.py; never part of the product build): one kernel per unit of work of the lean

@@ -160,8 +160,13 @@ public:
     // guided by aov_samples first-hit samples per pixel.  Without progressive_step the frame is rendered as ONE progressive step
     // of the whole target, which is bit-identical to the one-shot frame (image_name is unchanged); the noise estimate needs
     // two full chunks, so a target below that fails with a message.
+    // denoise_follow: RTK_GUIDE_FOLLOW_* bits -> the guides follow mirrors (and glass) to the surface they show
+    // (rtk_progressive_denoise_guided); 0 = the first-hit path above.  denoise_demodulate filters colour / albedo (it takes the
+    // guided path; with denoise_follow 0 it follows mirrors).
     const char* denoise_image_name = nullptr;
     int aov_samples = 4;
+    int denoise_follow = 0;
+    bool denoise_demodulate = false;
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -340,7 +345,12 @@ public:
             last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             if (rc == RTK_OK && denoise_image_name) {
                 std::vector<uint8_t> den(rgb8->size());
-                rc = rtk_progressive_denoise_host(p, aov_samples, nullptr, nullptr, den.data());
+                if (denoise_follow != 0 || denoise_demodulate) {
+                    const rtk_guide_opts go{denoise_follow, 0};
+                    rc = rtk_progressive_denoise_guided_host(p, aov_samples, &go, nullptr, denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, nullptr, den.data());
+                } else {
+                    rc = rtk_progressive_denoise_host(p, aov_samples, nullptr, nullptr, den.data());
+                }
                 if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
             }
         }
