@@ -2623,7 +2623,10 @@ static hipError_t launch_feat(const KernelChoice& k, const SceneView<real>& sc, 
         if (k.feat & F_LDS_BOXES) RTK_GO(FEAT | uint32_t(F_LDS_BOXES), false, false);  // (slot programs only: see choose_kernel)
     }
     if (k.in_lds) RTK_GO(FEAT, false, true);
-    RTK_GO(FEAT, false, false);
+    // a COMPACT program outside the hot/cold form is always staged whole (choose_kernel keeps it only when it fits LDS, and
+    // `fits` is computed from the same byte count): no all-in-memory instantiation of those kernels
+    if constexpr ((FEAT & F_F32_BOX) != 0 && (FEAT & ~uint32_t(F_F32_BOX | F_MATTE)) != kFeatLean) return hipErrorInvalidValue;
+    else RTK_GO(FEAT, false, false);
 #undef RTK_GO
 }
 
@@ -2642,12 +2645,12 @@ hipError_t launch_render(const SceneView<real>& sc, const CameraRec<real>* cam, 
 #if !defined(RTK_DEV_ONLY_ALL)   // tools/kernel_resources.py -DRTK_DEV_ONLY_ALL: only the full-feature family (quick register experiments)
         RTK_LAUNCH_CASE(kFeatLean)
         RTK_LAUNCH_CASE(kFeatQuadBox)
-        RTK_LAUNCH_CASE(kFeatQuadBox | F_MATTE)
+        RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_MATTE)  // (choose_kernel strips F_MATTE from the f32 kernels: the matte variants pay off in f64 only)
         RTK_LAUNCH_CASE(kFeatMesh)
         RTK_LAUNCH_CASE(kFeatLean | F_FMA_BOX)
         RTK_LAUNCH_CASE(kFeatMesh | F_FMA_BOX)
-        RTK_LAUNCH_CASE(kFeatMesh | F_MATTE)
-        RTK_LAUNCH_CASE(kFeatMesh | F_FMA_BOX | F_MATTE)
+        RTK_LAUNCH_CASE_F64(kFeatMesh | F_MATTE)
+        RTK_LAUNCH_CASE_F64(kFeatMesh | F_FMA_BOX | F_MATTE)
         RTK_LAUNCH_CASE_F64(kFeatLean | F_F32_BOX)
         RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_F32_BOX)
         RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_MATTE | F_F32_BOX)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import EARTH, GOLDEN, ROOT
+from tests.kernel_matrix import kernel_static_lds
 from tests.scene_cases import IMAGE_CASES, SCENE_SEED, scene_file
 
 
@@ -37,30 +38,42 @@ def test_kernels_are_built_for_gfx950_only(rt):
 def test_render_kernels_declare_no_static_lds(rt, tmp_path):
     """The lean MIXED kernel uses its byte program counters as LDS addresses (rtk_trace.hip rec_at): the staged program must
     start at LDS address 0, i.e. the kernels' static LDS size in the code object's metadata must be 0."""
-    import shutil
-    import subprocess
-
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not all(os.path.exists(t) for t in tools):
+    sizes = kernel_static_lds(rt.HIP_LIB_PATH, tmp_path)
+    if sizes is None:
         pytest.skip("ROCm LLVM binary tools not present")
-    fat, dev = str(tmp_path / "fat.bin"), str(tmp_path / "dev.co")
-    subprocess.check_call([tools[0], f"--dump-section=.hip_fatbin={fat}", rt.HIP_LIB_PATH, str(tmp_path / "copy.so")])
-    subprocess.check_call([tools[1], "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={dev}", "--unbundle"])
-    notes = subprocess.check_output([tools[2], "--notes", dev], text=True)
-    sizes = {}
-    fixed = None
-    for line in notes.splitlines():
-        m = re.search(r"\.group_segment_fixed_size:\s*(\d+)", line)
-        if m:
-            fixed = int(m.group(1))
-        m = re.search(r"\.name:\s*(\S+)", line)
-        if m and fixed is not None:
-            sizes[m.group(1)] = fixed
-            fixed = None
     render = {k: v for k, v in sizes.items() if "rtk_render_kernel" in k}
     assert len(render) >= 20, sorted(sizes)[:5]
     assert all(v == 0 for v in render.values()), {k: v for k, v in render.items() if v}
+
+
+def test_every_compiled_render_kernel_is_accounted_for(rt, tmp_path):
+    """The rtk_render_kernel instantiations in librtk_hip.so == the ones the rows of tests/kernel_matrix.py select (each launched and
+    checked on the device by tests/test_kernel_matrix.py) + the ones listed there as unreachable, with the reason.  An instantiation
+    added to rtk_trace.hip without a row fails here; so does a row taken away."""
+    from tests import kernel_matrix as km
+
+    sizes = kernel_static_lds(rt.HIP_LIB_PATH, tmp_path)
+    if sizes is None:
+        pytest.skip("ROCm LLVM binary tools not present")
+    compiled = km.compiled_instantiations(sizes)
+    assert len(compiled) == len(set(compiled)) == sum("rtk_render_kernel" in name for name in sizes)   # every symbol parsed
+    expected = {}
+    for row in km.ROWS:
+        assert row.expect[0] == row.real and row.expect[2] == row.count, row
+        if row.expect in expected:
+            assert row.note, f"{km.row_id(row)} expects {row.expect} like {km.row_id(expected[row.expect])} and gives no reason"
+        else:
+            assert not row.note, f"{km.row_id(row)}: a reason for a duplicate on the first row that expects {row.expect}"
+            expected[row.expect] = row
+    for row in km.ROWS:   # an f32 F_LDS_BOXES row is checked against its all-in-memory twin: the twin (a duplicate tuple) must be there
+        if row.real == km.F32 and row.expect[1] & 1024:
+            twin = row._replace(variant=row.variant | km.V_NO_LDS_BOXES, expect=(row.real, row.expect[1] & ~1024, False, False))
+            assert any(r[:6] == twin[:6] for r in km.ROWS), f"{km.row_id(row)} has no row at variant | V_NO_LDS_BOXES"
+    assert all(isinstance(why, str) and why.strip() for why in km.UNREACHABLE.values())
+    assert not set(expected) & set(km.UNREACHABLE), sorted(set(expected) & set(km.UNREACHABLE))
+    accounted = set(expected) | set(km.UNREACHABLE)
+    assert set(compiled) == accounted, {"compiled, in no row": sorted(set(compiled) - accounted), "in the table, not compiled": sorted(accounted - set(compiled))}
+    assert len({km.row_id(r) for r in km.ROWS}) == len(km.ROWS)
 
 
 def test_product_fails_loudly_without_a_device(rt):
