@@ -357,7 +357,8 @@ int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks);
  *
  * Streams (this holds for every entry point that is "asynchronous on" a stream:
  * rtk_render_device, rtk_tiles_unpermute, rtk_progressive_step, rtk_render_aovs,
- * rtk_denoise, rtk_progressive_denoise, rtk_render_guides, rtk_denoise_guided, rtk_progressive_denoise_guided):
+ * rtk_denoise, rtk_progressive_denoise, rtk_render_guides, rtk_denoise_guided, rtk_progressive_denoise_guided,
+ * rtk_temporal_accumulate):
  *   - all work of a call -- kernels, memsets, the upload of the camera record --
  *     is enqueued on the stream it is given and on no other; the call reads its
  *     host arguments (cam, opts) before it returns and never waits for the
@@ -594,8 +595,8 @@ int rtk_checkpoint_read_adaptive(const void* h_buf, int64_t n, rtk_adaptive_opts
  * rtk_render_aovs is asynchronous on opts->stream; rtk_render_aovs_host blocks (count_work and variant are ignored).
  *
  * Denoiser: an edge-avoiding a-trous filter (Dammertz et al. 2010) with the luminance weight of SVGF (Schied et al. 2017),
- * spatial part only, guided by the AOVs and by the per-pixel variance se^2 of the noise estimate (d_noise, as a progressive
- * step writes it).  Iteration k = 0 .. iterations-1 takes the 5x5 taps q = p + 2^k (dx, dy), dy outer, dx inner, skipping
+ * spatial part (the temporal part is "Temporal accumulation" below), guided by the AOVs and by the per-pixel variance se^2
+ * of the noise estimate (d_noise, as a progressive step writes it).  Iteration k = 0 .. iterations-1 takes the 5x5 taps q = p + 2^k (dx, dy), dy outer, dx inner, skipping
  * taps outside the image, with weight h[dx] h[dy] w_l w_n w_z w_a, h = (1/16, 1/4, 3/8, 1/4, 1/16):
  *   w_l = exp(-|y_p - y_q| / (sigma_l sqrt(max(gv_p, 0)) + 1e-6)), y = (r + g + b) / 3, gv_p = the 3x3 binomial (1 2 1)/4 of
  *         the variance around p (edges clamped)
@@ -681,6 +682,71 @@ int rtk_progressive_denoise_guided(rtk_progressive* p, int32_t aov_samples, cons
                                    void* d_out_linear, uint8_t* d_out_rgb8);
 int rtk_progressive_denoise_guided_host(rtk_progressive* p, int32_t aov_samples, const rtk_guide_opts* gopts, const rtk_denoise_opts* opts, int32_t flags,
                                         double* h_out_linear, uint8_t* h_out_rgb8);
+
+/* Temporal accumulation ---------------------------------------------------------------
+ * The temporal half of SVGF (Schied et al. 2017): an rtk_temporal object carries the frames of a MOVING camera along.  Per frame
+ * the caller renders a noisy frame with its se (a progressive step of at least two full chunks), the guides of the same camera
+ * (rtk_render_guides) and calls rtk_temporal_accumulate; the object reprojects the frame it returned last time into the new
+ * camera, rejects history that belongs to another surface, blends, and carries the variance along, so rtk_denoise_guided on the
+ * outputs keeps working on honest numbers.  The object owns its history (ping-pong, 52 bytes per pixel each) in device memory,
+ * apart from the render workspace and the denoiser's buffers; it is bound to the stream given at creation (the stream rules of
+ * rtk_render_device: every launch goes there, the call reads cam / opts before it returns and never waits for the device;
+ * create and reset do not touch the device's queues at all).
+ *   d_linear  H*W*3 reals of real_mode (read as such, then rounded to float); d_guides H*W*16 floats from rtk_render_guides of
+ *             `cam`; d_noise H*W floats (se; required)
+ *   outputs   d_out_linear H*W*3 reals of real_mode, d_out_noise H*W floats, d_out_rgb8 H*W*3 bytes, d_out_history H*W floats;
+ *             any may be NULL; they may alias d_linear / d_noise (a pixel's inputs are read before its outputs are written and
+ *             the taps read the object's own memory), but not d_guides.  Whole images only.
+ * The rule, per pixel (i, j) with colour c (float), se and guides g[0..15]; primes mark the previous frame's values:
+ *   1. Start of a history: the first frame after create / reset, and any pixel whose first-hit fraction g[3] == 0 (the
+ *      background is a constant): out = c, var_out = se^2, n_out = 1.
+ *   2. Reprojection, in double for both real modes: d = pixel00_loc + i du + j dv - center, P = center + g[7] d / |d|,
+ *      q = P - center', (u, v, w) = M'^-1 q with M'^-1 = rtk_temporal_reproject_matrix(previous camera), computed once per frame
+ *      on the host.  w <= 0: no history (a start).  x = u / w, y = v / w, z_exp = |q|.
+ *   3. Taps (x0 + a, y0 + b), a, b in {0, 1}, b outer: x0 = floor(x), fx = x - x0 (the same in y), bilinear weight
+ *      omega = (a ? fx : 1 - fx)(b ? fy : 1 - fy) rounded to float.  A tap is valid iff it lies in the image, its g'[3] > 0,
+ *      |g'[7] - z_exp| <= depth_tol z_exp (in double), the normals g[4..6] and g'[4..6] are both zero or neither is and their
+ *      cosine >= normal_cos, and -- with RTK_TEMPORAL_CHECK_ALBEDO -- max over channels |g[8..10] - g'[8..10]| <= albedo_tol.
+ *   4. Over the valid taps Omega = sum omega; Omega < 1e-3 is a start.  Otherwise c_h = sum omega c' / Omega,
+ *      var_h = sum omega^2 var' / Omega^2, n_h = sum omega n' / Omega, n_out = min(n_h + 1, max_history), alpha = 1 / n_out,
+ *      out = (1 - alpha) c_h + alpha c, var_out = (1 - alpha)^2 var_h + alpha^2 se^2.  c', var' and n' are the previous frame's
+ *      OUTPUTS as float32: the history is what was returned, before any spatial filter.
+ *   5. d_out_linear = out, d_out_noise = sqrt(var_out), d_out_history = n_out, d_out_rgb8 = the resolve's gamma / clamp /
+ *      quantise of out, in double.  Colour arithmetic is float32, no atomics, a fixed tap order: the same inputs give the same
+ *      bits.
+ * Options (NULL = defaults; a 0 field takes its default): max_history 32 (1..1024), depth_tol 0.02, normal_cos 0.9, albedo_tol
+ * 0.25.  RTK_ERR_INVALID, with nothing written and the history and frame count untouched: a camera whose size is not the
+ * object's, negative or non-finite tolerances, normal_cos > 1, unknown flags, reserved != 0, max_history out of range, a null
+ * object, camera or input.  Options are checked first (they need no object).
+ * Limits: geometry is taken as static -- moving spheres are time-averaged within every frame and accumulate like anything else;
+ * what a mirror shows is reprojected with the mirror's own surface: the opt-in check on the SEEN albedo is the available guard
+ * and max_history bounds the lag.
+ * rtk_temporal_accumulate is asynchronous on the object's stream; the _host form (h_linear / h_out_linear doubles, F32 rounded /
+ * widened) blocks.  rtk_temporal_reset makes the next frame start a new history.  rtk_temporal_frames = frames accumulated since
+ * create / reset (negative rtk_status for a null object). */
+#define RTK_TEMPORAL_CHECK_ALBEDO 1
+typedef struct rtk_temporal rtk_temporal;
+typedef struct rtk_temporal_opts {
+    int32_t max_history;   /* 0 = 32; else 1..1024 */
+    float depth_tol;       /* 0 = 0.02 */
+    float normal_cos;      /* 0 = 0.9  */
+    float albedo_tol;      /* 0 = 0.25; used only with RTK_TEMPORAL_CHECK_ALBEDO */
+    int32_t flags;         /* RTK_TEMPORAL_CHECK_ALBEDO; other bits RTK_ERR_INVALID */
+    int32_t reserved;      /* 0 */
+} rtk_temporal_opts;
+
+int rtk_temporal_create(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, void* stream, rtk_temporal** out);
+int rtk_temporal_accumulate(rtk_temporal* t, const rtk_camera* cam, const void* d_linear, const float* d_guides, const float* d_noise,
+                            const rtk_temporal_opts* opts, void* d_out_linear, float* d_out_noise, uint8_t* d_out_rgb8, float* d_out_history);
+int rtk_temporal_accumulate_host(rtk_temporal* t, const rtk_camera* cam, const double* h_linear, const float* h_guides, const float* h_noise,
+                                 const rtk_temporal_opts* opts, double* h_out_linear, float* h_out_noise, uint8_t* h_out_rgb8, float* h_out_history);
+int rtk_temporal_reset(rtk_temporal* t);
+int rtk_temporal_frames(const rtk_temporal* t);
+int rtk_temporal_destroy(rtk_temporal* t);
+/* Host-only, no device: out[0..8] = the inverse (row-major) of the matrix whose COLUMNS are pixel_delta_u, pixel_delta_v and
+ * pixel00_loc - center; out[9..11] = center.  A point center + q is seen at pixel (u / w, v / w), (u, v, w) = out[0..8] q, when
+ * w > 0.  RTK_ERR_INVALID for a singular camera. */
+int rtk_temporal_reproject_matrix(const rtk_camera* cam, double out[12]);
 
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and

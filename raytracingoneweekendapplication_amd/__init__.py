@@ -207,6 +207,19 @@ class GuideOpts(C.Structure):
 GUIDE_FOLLOW_MIRROR = 1
 GUIDE_FOLLOW_DIELECTRIC = 2
 DENOISE_DEMODULATE = 1
+TEMPORAL_CHECK_ALBEDO = 1
+
+
+class TemporalOpts(C.Structure):
+    """rtk_temporal_opts (include/rtk.h): a field left 0 takes its default (max_history 32, depth_tol 0.02, normal_cos 0.9,
+    albedo_tol 0.25); flags = TEMPORAL_CHECK_ALBEDO or 0."""
+
+    _fields_ = [("max_history", C.c_int32), ("depth_tol", C.c_float), ("normal_cos", C.c_float), ("albedo_tol", C.c_float),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def _temporal_opts(max_history: int = 0, depth_tol: float = 0.0, normal_cos: float = 0.0, albedo_tol: float = 0.0, check_albedo: bool = False) -> TemporalOpts:
+    return TemporalOpts(int(max_history), float(depth_tol), float(normal_cos), float(albedo_tol), TEMPORAL_CHECK_ALBEDO if check_albedo else 0, 0)
 
 
 def host_lib() -> C.CDLL:
@@ -332,6 +345,14 @@ def hip_lib() -> C.CDLL:
                                                            C.c_void_p]
             lib.rtk_progressive_denoise_guided_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GuideOpts), C.POINTER(DenoiseOpts), C.c_int32, C.c_void_p,
                                                                 C.c_void_p]
+            lib.rtk_temporal_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+            lib.rtk_temporal_accumulate.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalOpts), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rtk_temporal_accumulate_host.argtypes = lib.rtk_temporal_accumulate.argtypes
+            lib.rtk_temporal_reset.argtypes = [C.c_void_p]
+            lib.rtk_temporal_frames.argtypes = [C.c_void_p]
+            lib.rtk_temporal_destroy.argtypes = [C.c_void_p]
+            lib.rtk_temporal_reproject_matrix.argtypes = [C.POINTER(Camera), C.POINTER(C.c_double)]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -672,6 +693,13 @@ class Renderer:
                                                       C.byref(opts), flags, out.ctypes.data, rgb8.ctypes.data))
         return out, rgb8
 
+    def temporal(self, width: int, height: int, real_mode: int = RTK_REAL_F64, stream: int = 0) -> "Temporal":
+        """rtk_temporal_create: an object that carries the frames of a moving camera along (``Temporal.accumulate``), bound to
+        ``stream``."""
+        h = C.c_void_p()
+        self._check(self._lib.rtk_temporal_create(self._ctx, int(width), int(height), real_mode, stream or None, C.byref(h)))
+        return Temporal(self, h, int(width), int(height), real_mode)
+
     def progressive(self, cam: Camera, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
                     stream: int = 0, rel_target: float | None = None, min_samples: int | None = None) -> "Progressive":
         """rtk_progressive_create: a session that renders the frame of ``cam`` (samples_per_pixel = the target) in steps.
@@ -836,6 +864,85 @@ class Progressive:
             self.close()
         except Exception:
             pass
+
+
+class Temporal:
+    """Temporal accumulation (rtk_temporal): per frame, the history -- the frame returned last time -- is reprojected into the new
+    camera, history of another surface is rejected, and colour, variance and history length are blended (include/rtk.h has the
+    rule).  Feed ``accumulate`` a noisy frame with its se and the guides of the same camera; its outputs are inputs of
+    ``Renderer.denoise_guided``."""
+
+    def __init__(self, renderer: Renderer, handle: C.c_void_p, width: int, height: int, real_mode: int):
+        self._r = renderer      # keeps the context alive
+        self._lib = renderer._lib
+        self._h = handle
+        self.width, self.height, self.real_mode = width, height, real_mode
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise RtkError(rc, self._lib.rtk_last_error().decode())
+
+    @property
+    def frames(self) -> int:
+        """Frames accumulated since creation / ``reset``."""
+        n = self._lib.rtk_temporal_frames(self._h)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def accumulate(self, cam: Camera, linear, guides, noise, **opts):
+        """rtk_temporal_accumulate_host: ``linear`` (H, W, 3), ``guides`` (H, W, 16) of ``cam``, ``noise`` (H, W) se.  ``opts``:
+        max_history, depth_tol, normal_cos, albedo_tol (0 = default), check_albedo.  Returns (linear float64 (H, W, 3), noise
+        float32 (H, W), rgb8 (H, W, 3), history float32 (H, W))."""
+        import numpy as np
+
+        h, w = self.height, self.width
+        linear = np.ascontiguousarray(linear, np.float64)
+        guides = np.ascontiguousarray(guides, np.float32)
+        noise = np.ascontiguousarray(noise, np.float32)
+        if linear.shape != (h, w, 3) or guides.shape != (h, w, 16) or noise.shape != (h, w):
+            raise ValueError(f"accumulate: shapes {linear.shape}, {guides.shape}, {noise.shape} do not describe one ({h}, {w}) image")
+        out, out_noise = np.zeros((h, w, 3)), np.zeros((h, w), np.float32)
+        rgb8, history = np.zeros((h, w, 3), np.uint8), np.zeros((h, w), np.float32)
+        o = _temporal_opts(**opts)
+        self._check(self._lib.rtk_temporal_accumulate_host(self._h, C.byref(cam), linear.ctypes.data, guides.ctypes.data, noise.ctypes.data, C.byref(o),
+                                                           out.ctypes.data, out_noise.ctypes.data, rgb8.ctypes.data, history.ctypes.data))
+        return out, out_noise, rgb8, history
+
+    def accumulate_device(self, cam: Camera, d_linear: int, d_guides: int, d_noise: int, d_out_linear: int = 0, d_out_noise: int = 0, d_out_rgb8: int = 0,
+                          d_out_history: int = 0, **opts) -> None:
+        """rtk_temporal_accumulate with raw device pointers (any output may be 0); asynchronous on the object's stream."""
+        o = _temporal_opts(**opts)
+        self._check(self._lib.rtk_temporal_accumulate(self._h, C.byref(cam), d_linear or None, d_guides or None, d_noise or None, C.byref(o),
+                                                      d_out_linear or None, d_out_noise or None, d_out_rgb8 or None, d_out_history or None))
+
+    def reset(self) -> None:
+        """The next frame starts a new history."""
+        self._check(self._lib.rtk_temporal_reset(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.rtk_temporal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def temporal_reproject_matrix(cam: Camera):
+    """rtk_temporal_reproject_matrix (host-only, no GPU): float64 [12] = the row-major inverse of [pixel_delta_u | pixel_delta_v |
+    pixel00_loc - center], then center.  Raises RtkError for a singular camera."""
+    import numpy as np
+
+    lib = hip_lib()
+    out = (C.c_double * 12)()
+    rc = lib.rtk_temporal_reproject_matrix(C.byref(cam), out)
+    if rc != 0:
+        raise RtkError(rc, lib.rtk_last_error().decode())
+    return np.array(out[:], np.float64)
 
 
 def checkpoint_info(blob: bytes) -> dict:

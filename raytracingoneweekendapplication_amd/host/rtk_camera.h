@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -167,6 +168,18 @@ public:
     int aov_samples = 4;
     int denoise_follow = 0;
     bool denoise_demodulate = false;
+    // Temporal accumulation (rtk_temporal_*; one device, as progressive rendering).  temporal_history > 0: successive render()
+    // calls on this camera object (and its copies) keep one rtk_temporal -- created on the first call; recreated, with a warning,
+    // when the image size, real mode or device changes -- and each call
+    //   1. renders its frame as one progressive step with seed `seed + frames accumulated so far` (samples_per_pixel must give
+    //      two full chunks for the noise estimate, else render() warns and renders without history),
+    //   2. renders the guides of this camera (aov_samples, denoise_follow; the same seed),
+    //   3. accumulates with max_history = temporal_history and writes the ACCUMULATED frame to image_name,
+    //   4. with denoise_image_name set, writes the guided filter of the accumulated colour and se there (denoise_demodulate).
+    // Move lookfrom / lookat between calls; geometry is taken as static.  0 (default): nothing changes, bit for bit.
+    int temporal_history = 0;
+    int last_temporal_frames = 0;      // set by render(): frames in the history the image was written from (0: no history used)
+    void temporal_reset() { if (temporal_) temporal_->reset(); }  // the next render() starts a new history
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -359,6 +372,73 @@ public:
         return rc;
     }
 
+    // render() with temporal_history > 0 (see the member).  RTK_OK with *used = false: too few samples for a noise estimate, the
+    // caller renders without history.
+    int render_temporal(const hittable& world, const std::vector<point_light>& lights, std::vector<uint8_t>* rgb8, bool* used) {
+        *used = false;
+        last_temporal_frames = 0;
+        rtk::scene_builder sb;
+        rtk_scene_desc desc = rtk::flatten(world, lights, sb);
+        rtk_camera cam = derive();
+        const int dev = devices.empty() ? device : devices[0];
+        if (temporal_ && (temporal_->width != cam.image_width || temporal_->height != cam.image_height || temporal_->real_mode != real_mode || temporal_->device != dev)) {
+            std::cerr << "camera::render: image size, real mode or device changed; the temporal history starts over" << std::endl;
+            temporal_.reset();
+        }
+        if (!temporal_) {
+            auto st = std::make_shared<temporal_state>();
+            int rc = rtk_init_multi(1, &dev, RTK_GATHER_PEER, &st->multi);
+            if (rc == RTK_OK) rc = rtk_temporal_create(rtk_multi_ctx(st->multi, 0), cam.image_width, cam.image_height, real_mode, nullptr, &st->temporal);
+            if (rc != RTK_OK) return rc;
+            st->width = cam.image_width;
+            st->height = cam.image_height;
+            st->real_mode = real_mode;
+            st->device = dev;
+            temporal_ = st;
+        }
+        rtk_ctx* ctx = rtk_multi_ctx(temporal_->multi, 0);
+        int rc = upload(temporal_->multi, desc, cam);
+        if (rc != RTK_OK) return rc;
+        rtk_render_opts opts{};
+        opts.seed = seed + uint32_t(rtk_temporal_frames(temporal_->temporal));
+        opts.real_mode = real_mode;
+        opts.rank = 0;
+        opts.n_ranks = 1;
+        rtk_progressive* p = nullptr;
+        rc = rtk_progressive_create(ctx, &cam, &opts, &p);
+        if (rc != RTK_OK) return rc;
+        if (cam.samples_per_pixel < 2 * rtk_progressive_chunk_size(p)) {
+            std::cerr << "camera::render: temporal_history needs samples_per_pixel >= " << 2 * rtk_progressive_chunk_size(p)
+                      << " (two full chunks for the noise estimate); rendering without history" << std::endl;
+            rtk_progressive_destroy(p);
+            return RTK_OK;
+        }
+        const size_t px = size_t(cam.image_width) * cam.image_height;
+        std::vector<double> linear(px * 3);
+        std::vector<float> noise(px), guides(px * 16);
+        rgb8->assign(px * 3, 0);
+        auto t0 = std::chrono::steady_clock::now();
+        rc = rtk_progressive_step_host(p, cam.samples_per_pixel, linear.data(), nullptr, noise.data(), nullptr);
+        rtk_progressive_destroy(p);
+        const rtk_guide_opts go{denoise_follow, 0};
+        if (rc == RTK_OK) rc = rtk_render_guides_host(ctx, &cam, &opts, aov_samples, &go, guides.data());
+        rtk_temporal_opts to{};
+        to.max_history = temporal_history;
+        if (rc == RTK_OK) rc = rtk_temporal_accumulate_host(temporal_->temporal, &cam, linear.data(), guides.data(), noise.data(), &to, linear.data(), noise.data(),
+                                                            rgb8->data(), nullptr);
+        last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc != RTK_OK) return rc;
+        *used = true;
+        last_temporal_frames = rtk_temporal_frames(temporal_->temporal);
+        if (denoise_image_name) {
+            std::vector<uint8_t> den(px * 3);
+            rc = rtk_denoise_guided_host(ctx, cam.image_width, cam.image_height, real_mode, linear.data(), guides.data(), noise.data(), nullptr,
+                                         denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, nullptr, den.data());
+            if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
+        }
+        return rc;
+    }
+
     // Camera.txt:102-106: "\rPercent Rendered: N% " on stderr.
     static void print_progress(int64_t done, int64_t total, void*) {
         const float percent = total > 0 ? 100.0f * float(done) / float(total) : 100.0f;
@@ -368,7 +448,10 @@ public:
     // Camera.txt:54.  Blocking; borrows world and lights for the call.
     void render(const hittable& world, std::vector<point_light>& lights) {
         std::vector<uint8_t> rgb8;
-        int rc = progressive_step > 0 || denoise_image_name ? render_progressive(world, lights, &rgb8) : render_to(world, lights, nullptr, &rgb8);
+        bool temporal = false;
+        int rc = temporal_history > 0 ? render_temporal(world, lights, &rgb8, &temporal) : RTK_OK;
+        if (rc == RTK_OK && !temporal)
+            rc = progressive_step > 0 || denoise_image_name ? render_progressive(world, lights, &rgb8) : render_to(world, lights, nullptr, &rgb8);
         if (rc != RTK_OK) {
             std::cerr << "camera::render failed: " << rtk_last_error() << std::endl;
             return;
@@ -379,6 +462,24 @@ public:
                   << msamples / (last_render_ms / 1000.0) << " Msamples/s)" << std::endl;
         if (write_image) rtk::write_png(image_name, cam.image_width, cam.image_height, rgb8.data());
     }
+
+private:
+    // What temporal_history keeps between render() calls: the context the history lives on and the history.  Copies of the
+    // camera share it.
+    struct temporal_state {
+        rtk_multi* multi = nullptr;
+        rtk_temporal* temporal = nullptr;
+        int width = 0, height = 0, real_mode = 0, device = 0;
+        void reset() { if (temporal) rtk_temporal_reset(temporal); }
+        temporal_state() = default;
+        temporal_state(const temporal_state&) = delete;
+        temporal_state& operator=(const temporal_state&) = delete;
+        ~temporal_state() {
+            if (temporal) rtk_temporal_destroy(temporal);
+            if (multi) rtk_multi_destroy(multi);
+        }
+    };
+    std::shared_ptr<temporal_state> temporal_;
 };
 
 #endif  // RTK_CAMERA_H
