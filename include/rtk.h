@@ -748,6 +748,70 @@ int rtk_temporal_destroy(rtk_temporal* t);
  * w > 0.  RTK_ERR_INVALID for a singular camera. */
 int rtk_temporal_reproject_matrix(const rtk_camera* cam, double out[12]);
 
+/* Guided upsampling -------------------------------------------------------------------
+ * Joint-bilateral upsampling (Kopf et al. 2007): the noisy frame is rendered at 1/f of the width and height -- with f^2 times the
+ * samples per pixel for the same budget, or the same samples in 1/f^2 of the time -- the guides at both resolutions
+ * (rtk_render_guides costs a fraction of a frame), and rtk_upsample rebuilds the full-resolution frame from the low-resolution
+ * colour, steered by both guide sets: edges, normals, depth and -- demodulated -- textures come back at full resolution.
+ *
+ * rtk_upsample_camera (host-only, no device): the low camera of `full` for factor f = 2..4.  With W, H the full size:
+ * image_width = ceil(W / f), image_height = ceil(H / f), pixel_delta_u / v = f * full's, pixel00_loc = full.pixel00_loc +
+ * ((f - 1) / 2)(du + dv), in double; every other field is copied.  The centre of low pixel (I, J) is then the mean of the centres
+ * of full pixels fI .. fI+f-1 by fJ .. fJ+f-1, and the low pixel's sample square is exactly those f x f full pixels' squares.
+ * RTK_ERR_INVALID, with out_low untouched, for a null pointer, a factor outside 2..4 or a camera with non-positive size.
+ *
+ * rtk_upsample, with W x H = full's size, LW x LH = the low camera's:
+ *   d_low_linear  LH*LW*3 reals of real_mode (read as such, then rounded to float); d_low_noise LH*LW floats (se);
+ *                 d_low_guides LH*LW*16 floats from rtk_render_guides of the low camera; d_guides H*W*16 floats from
+ *                 rtk_render_guides of `full`.  All four are required.
+ *   outputs       d_out_linear H*W*3 reals of real_mode, d_out_noise H*W floats, d_out_rgb8 H*W*3 bytes, d_out_support H*W
+ *                 floats; any may be NULL, not all.  They may not alias an input.  Whole images only.
+ * The rule, per full pixel (i, j) with guides g[0..15]; a low pixel has guides G[0..15], colour c (float) and standard error se:
+ *   1. Position, in integers: n = 2i - (f - 1), x0 = floor(n / 2f), fx = float(n - 2f x0) / float(2f); the same in j for y0, fy.
+ *      Taps (x0 + a, y0 + b), a, b in {0, 1}, b outer; a tap outside the low image is skipped.  Bilinear weight
+ *      beta = (a ? fx : 1 - fx)(b ? fy : 1 - fy) in float.  The taps inside the image always carry sum beta >= 0.39: no pixel
+ *      is without taps.
+ *   2. Weight w = w_n w_z w_a with rtk_denoise_guided's expressions, p = the full pixel, q = the tap:
+ *      w_n = min over the two guide sets (k 4-6 / k 12-14) of: 1 if both normals are 0, 0 if one is, else max(0, cos)^sigma_n;
+ *      w_z = min over the two sets (hit fraction k 3 / 11, depth k 7 / 15) of: 1 if either hit fraction is 0, else
+ *            exp(-|z_p - z_q| / (sigma_z (grad_p o + 1e-3 z_p) + 1e-6)), grad_p = half the larger central difference of the
+ *            FULL-resolution depth at p (edges clamped), o = f sqrt((fx - a)^2 + (fy - b)^2), the tap's distance in full pixels;
+ *      w_a = exp(-|g[8..10] - G[8..10]| / sigma_a) (Euclidean), or 1 with RTK_UPSAMPLE_DEMODULATE.
+ *   3. Blend: omega = beta (w + 1e-3); Omega = sum omega; out = sum omega c_q / Omega; var_out = sum omega^2 se_q^2 / Omega^2;
+ *      support = sum beta w / sum beta, the share of the bilinear weight the guides accepted.  The floor 1e-3 makes a pixel
+ *      whose taps are all rejected fall back smoothly to the (edge-renormalised) bilinear interpolation; there is no threshold.
+ *      A caller can re-render pixels with low support.
+ *   4. RTK_UPSAMPLE_DEMODULATE: per tap A_q = max(G[8..10], 0.02) per channel, c_q <- c_q / A_q, se_q^2 <- se_q^2 /
+ *      ((A_q.x + A_q.y + A_q.z) / 3)^2; after the blend out <- out * A_p, var_out <- var_out * mean(A_p)^2, A_p from g[8..10].
+ *   5. d_out_linear = out, d_out_noise = sqrt(var_out), d_out_support = support, d_out_rgb8 = the resolve's gamma / clamp /
+ *      quantise of out, in double.  Arithmetic is float32, no atomics, a fixed tap order: the same inputs give the same bits.
+ *      Neighbouring output pixels share taps: d_out_noise is a per-pixel marginal, the errors of neighbours are correlated.
+ * Options (NULL = defaults; a 0 field takes its default): factor 2 (2..4), sigma_n 128, sigma_z 1, sigma_a 0.1 (the denoiser's).
+ * RTK_ERR_INVALID, with nothing written: a factor outside 2..4, unknown flags, reserved != 0, negative or non-finite sigmas
+ * (these are checked first and need no context or device), a null context, camera or input, all outputs null, a camera with
+ * non-positive size, an unknown real_mode.
+ * rtk_upsample is asynchronous on `stream` under the stream rules of rtk_render_device: its one launch goes there, `full` and
+ * opts are read before it returns, it allocates nothing, uses no context workspace and never waits for the device.
+ * rtk_upsample_host (h_low_linear / h_out_linear doubles, F32 rounded / widened) blocks.
+ * Limits: geometry thinner than a low pixel's footprint may be missed by every low sample that could colour it; a low pixel that
+ * straddles the border of an emitter has a colour no full pixel has, and only w_a tells a light from the wall it lies in (none
+ * with RTK_UPSAMPLE_DEMODULATE); a 4-sample albedo at a texture edge demodulates with a value the colour does not have; what a
+ * mirror shows is steered by the second guide set only as far as the guides follow it (rtk_guide_opts), as for the filter. */
+#define RTK_UPSAMPLE_DEMODULATE 1
+typedef struct rtk_upsample_opts {
+    int32_t factor;        /* 0 = 2; else 2..4 */
+    float sigma_n, sigma_z, sigma_a;   /* 0 = the denoiser's defaults: 128, 1, 0.1 */
+    int32_t flags;         /* RTK_UPSAMPLE_DEMODULATE; other bits RTK_ERR_INVALID */
+    int32_t reserved;      /* 0 */
+} rtk_upsample_opts;
+
+int rtk_upsample_camera(const rtk_camera* full, int32_t factor, rtk_camera* out_low);
+int rtk_upsample(rtk_ctx* ctx, const rtk_camera* full, int32_t real_mode, const void* d_low_linear, const float* d_low_noise, const float* d_low_guides,
+                 const float* d_guides, const rtk_upsample_opts* opts, void* d_out_linear, float* d_out_noise, uint8_t* d_out_rgb8, float* d_out_support,
+                 void* stream);
+int rtk_upsample_host(rtk_ctx* ctx, const rtk_camera* full, int32_t real_mode, const double* h_low_linear, const float* h_low_noise, const float* h_low_guides,
+                      const float* h_guides, const rtk_upsample_opts* opts, double* h_out_linear, float* h_out_noise, uint8_t* h_out_rgb8, float* h_out_support);
+
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and
  * hit-record code as the render kernel.  Host buffers:

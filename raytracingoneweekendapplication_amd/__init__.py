@@ -208,6 +208,7 @@ GUIDE_FOLLOW_MIRROR = 1
 GUIDE_FOLLOW_DIELECTRIC = 2
 DENOISE_DEMODULATE = 1
 TEMPORAL_CHECK_ALBEDO = 1
+UPSAMPLE_DEMODULATE = 1
 
 
 class TemporalOpts(C.Structure):
@@ -220,6 +221,18 @@ class TemporalOpts(C.Structure):
 
 def _temporal_opts(max_history: int = 0, depth_tol: float = 0.0, normal_cos: float = 0.0, albedo_tol: float = 0.0, check_albedo: bool = False) -> TemporalOpts:
     return TemporalOpts(int(max_history), float(depth_tol), float(normal_cos), float(albedo_tol), TEMPORAL_CHECK_ALBEDO if check_albedo else 0, 0)
+
+
+class UpsampleOpts(C.Structure):
+    """rtk_upsample_opts (include/rtk.h): a field left 0 takes its default (factor 2, sigma_n 128, sigma_z 1, sigma_a 0.1);
+    flags = UPSAMPLE_DEMODULATE or 0."""
+
+    _fields_ = [("factor", C.c_int32), ("sigma_n", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def _upsample_opts(factor: int = 2, demodulate: bool = False, sigma_n: float = 0.0, sigma_z: float = 0.0, sigma_a: float = 0.0) -> UpsampleOpts:
+    return UpsampleOpts(int(factor), float(sigma_n), float(sigma_z), float(sigma_a), UPSAMPLE_DEMODULATE if demodulate else 0, 0)
 
 
 def host_lib() -> C.CDLL:
@@ -353,6 +366,10 @@ def hip_lib() -> C.CDLL:
             lib.rtk_temporal_frames.argtypes = [C.c_void_p]
             lib.rtk_temporal_destroy.argtypes = [C.c_void_p]
             lib.rtk_temporal_reproject_matrix.argtypes = [C.POINTER(Camera), C.POINTER(C.c_double)]
+            lib.rtk_upsample_camera.argtypes = [C.POINTER(Camera), C.c_int32, C.POINTER(Camera)]
+            lib.rtk_upsample.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpsampleOpts),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rtk_upsample_host.argtypes = lib.rtk_upsample.argtypes[:-1]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -693,6 +710,40 @@ class Renderer:
                                                       C.byref(opts), flags, out.ctypes.data, rgb8.ctypes.data))
         return out, rgb8
 
+    def upsample(self, full_cam: Camera, low_linear, low_noise, low_guides, guides, *, factor: int = 2, demodulate: bool = False,
+                 real_mode: int = RTK_REAL_F64, sigma_n: float = 0.0, sigma_z: float = 0.0, sigma_a: float = 0.0):
+        """rtk_upsample_host: the frame of ``upsample_camera(full_cam, factor)`` -- ``low_linear`` (LH, LW, 3), its se ``low_noise``
+        (LH, LW) and its guides ``low_guides`` (LH, LW, 16) -- rebuilt at ``full_cam``'s size, steered by ``guides`` (H, W, 16) of
+        ``full_cam``.  ``demodulate`` interpolates colour / seen albedo and multiplies the full-resolution albedo back.  Returns
+        (linear float64 (H, W, 3), se float32 (H, W), rgb8 (H, W, 3), support float32 (H, W))."""
+        import numpy as np
+
+        h, w = full_cam.image_height, full_cam.image_width
+        f = int(factor) or 2
+        lh, lw = -(-h // f), -(-w // f)
+        low_linear = np.ascontiguousarray(low_linear, np.float64)
+        low_noise = np.ascontiguousarray(low_noise, np.float32)
+        low_guides = np.ascontiguousarray(low_guides, np.float32)
+        guides = np.ascontiguousarray(guides, np.float32)
+        if low_linear.shape != (lh, lw, 3) or low_noise.shape != (lh, lw) or low_guides.shape != (lh, lw, 16) or guides.shape != (h, w, 16):
+            raise ValueError(f"upsample: shapes {low_linear.shape}, {low_noise.shape}, {low_guides.shape}, {guides.shape} do not describe a "
+                             f"({lh}, {lw}) image and the guides of a ({h}, {w}) one")
+        out, out_noise = np.zeros((h, w, 3)), np.zeros((h, w), np.float32)
+        rgb8, support = np.zeros((h, w, 3), np.uint8), np.zeros((h, w), np.float32)
+        o = _upsample_opts(factor, demodulate, sigma_n, sigma_z, sigma_a)
+        self._check(self._lib.rtk_upsample_host(self._ctx, C.byref(full_cam), real_mode, low_linear.ctypes.data, low_noise.ctypes.data, low_guides.ctypes.data,
+                                                guides.ctypes.data, C.byref(o), out.ctypes.data, out_noise.ctypes.data, rgb8.ctypes.data, support.ctypes.data))
+        return out, out_noise, rgb8, support
+
+    def upsample_device(self, full_cam: Camera, d_low_linear: int, d_low_noise: int, d_low_guides: int, d_guides: int, d_out_linear: int = 0,
+                        d_out_noise: int = 0, d_out_rgb8: int = 0, d_out_support: int = 0, *, real_mode: int = RTK_REAL_F64, stream: int = 0, **opts) -> None:
+        """rtk_upsample with raw device pointers (any output may be 0, not all); asynchronous on ``stream``.  ``opts``: factor,
+        demodulate, sigma_n, sigma_z, sigma_a."""
+        o = _upsample_opts(**opts)
+        self._check(self._lib.rtk_upsample(self._ctx, C.byref(full_cam), real_mode, d_low_linear or None, d_low_noise or None, d_low_guides or None,
+                                           d_guides or None, C.byref(o), d_out_linear or None, d_out_noise or None, d_out_rgb8 or None, d_out_support or None,
+                                           stream or None))
+
     def temporal(self, width: int, height: int, real_mode: int = RTK_REAL_F64, stream: int = 0) -> "Temporal":
         """rtk_temporal_create: an object that carries the frames of a moving camera along (``Temporal.accumulate``), bound to
         ``stream``."""
@@ -943,6 +994,17 @@ def temporal_reproject_matrix(cam: Camera):
     if rc != 0:
         raise RtkError(rc, lib.rtk_last_error().decode())
     return np.array(out[:], np.float64)
+
+
+def upsample_camera(cam: Camera, factor: int = 2) -> Camera:
+    """rtk_upsample_camera (host-only, no GPU): the camera that renders ``cam``'s view at 1 / ``factor`` of the width and height
+    (rounded up), each of its pixels covering ``factor`` x ``factor`` of ``cam``'s.  Raises RtkError for a factor outside 2..4."""
+    lib = hip_lib()
+    low = Camera()
+    rc = lib.rtk_upsample_camera(C.byref(cam), int(factor), C.byref(low))
+    if rc != 0:
+        raise RtkError(rc, lib.rtk_last_error().decode())
+    return low
 
 
 def checkpoint_info(blob: bytes) -> dict:

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "rtk.h"
+#include "rtk_guide_weights.h"
 #include "rtk_internal.h"
 #include "rtk_trace.h"
 
@@ -29,13 +30,6 @@ namespace rtk {
 namespace {
 
 #define RTK_DN __device__ __forceinline__
-
-// The resolve's byte conversion (rtk_device_math.h, to_byte; Camera.txt:29-34,77-83), in double.
-RTK_DN uint8_t denoise_byte(double x) {
-    double g = x > 0 ? __builtin_sqrt(x) : 0.0;
-    g = g < 0.000 ? 0.000 : (g > 0.999 ? 0.999 : g);
-    return uint8_t(int(255.999 * g));
-}
 
 struct DenoiseParams {
     int width, height, tiles_x, n_tiles;
@@ -63,7 +57,6 @@ __global__ __launch_bounds__(256) void rtk_denoise_pack_kernel(DenoiseParams P, 
     cv[px] = make_float4(float(linear[px * 3]), float(linear[px * 3 + 1]), float(linear[px * 3 + 2]), se * se);
 }
 
-RTK_DN int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 RTK_DN float luminance(float4 c) { return (c.x + c.y + c.z) / 3.0f; }
 
 // One a-trous iteration with taps 2^k apart.  A final iteration (out_cv null) writes the colour as `real` and / or bytes.
@@ -137,9 +130,9 @@ __global__ __launch_bounds__(256) void rtk_denoise_step_kernel(DenoiseParams P, 
         out_linear[px * 3 + 2] = real(b);
     }
     if (out_rgb8) {
-        out_rgb8[px * 3] = denoise_byte(double(r));
-        out_rgb8[px * 3 + 1] = denoise_byte(double(g));
-        out_rgb8[px * 3 + 2] = denoise_byte(double(b));
+        out_rgb8[px * 3] = guide_byte(double(r));
+        out_rgb8[px * 3 + 1] = guide_byte(double(g));
+        out_rgb8[px * 3 + 2] = guide_byte(double(b));
     }
 }
 
@@ -166,31 +159,8 @@ hipError_t launch_denoise(const DenoiseParams& P, int iterations, const void* li
 // first one's hit fraction (a 4-byte load): 4 x 16 B + 4 B.  The weights are the expressions of rtk_denoise_step_kernel, once
 // per set, so guides whose second set equals the first give that kernel's bits.
 
-// Depth gradient of guide float4 `slot` (1 = first hit, 3 = end hit): half the larger central difference, edges clamped.
-RTK_DN float guide_depth_gradient(const float4* __restrict__ g, int slot, int i, int j, int W, int H) {
-    const float zx = fabsf(g[(size_t(j) * W + clampi(i + 1, 0, W - 1)) * 4 + slot].w - g[(size_t(j) * W + clampi(i - 1, 0, W - 1)) * 4 + slot].w);
-    const float zy = fabsf(g[(size_t(clampi(j + 1, 0, H - 1)) * W + i) * 4 + slot].w - g[(size_t(clampi(j - 1, 0, H - 1)) * W + i) * 4 + slot].w);
-    return (zx > zy ? zx : zy) / 2.0f;
-}
-
-RTK_DN bool zero3(float4 v) { return v.x == 0.0f && v.y == 0.0f && v.z == 0.0f; }
-
-RTK_DN float normal_weight(float4 gp, bool np_zero, float np_len, float4 gq, float sigma_n) {
-    const bool nq_zero = zero3(gq);
-    if (np_zero || nq_zero) return np_zero && nq_zero ? 1.0f : 0.0f;
-    const float c = (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z) / (np_len * sqrtf(gq.x * gq.x + gq.y * gq.y + gq.z * gq.z));
-    return c > 0.0f ? __powf(c, sigma_n) : 0.0f;
-}
-
-RTK_DN float depth_weight(float hit_p, float hit_q, float zp, float zq, float grad, float o, float sigma_z) {
-    if (hit_p == 0.0f || hit_q == 0.0f) return 1.0f;
-    return __expf(-fabsf(zp - zq) / (sigma_z * (grad * o + 1e-3f * zp) + 1e-6f));
-}
-
-// The albedo a demodulating filter divides by and multiplies back: max(seen albedo, 0.02) per channel.
-RTK_DN float4 demodulation_albedo(float4 seen) {
-    return make_float4(seen.x > 0.02f ? seen.x : 0.02f, seen.y > 0.02f ? seen.y : 0.02f, seen.z > 0.02f ? seen.z : 0.02f, 0.0f);
-}
+// The weights (guide_depth_gradient, normal_weight, depth_weight, demodulation_albedo) are rtk_guide_weights.h's, shared with
+// the upsampling pass.
 
 // rtk_denoise_pack_kernel, and with DEMOD the division by the albedo: c' = c / A, var' = var / mean(A)^2.
 template <typename real, bool DEMOD>
@@ -279,9 +249,9 @@ __global__ __launch_bounds__(256) void rtk_denoise_guided_step_kernel(DenoisePar
         out_linear[px * 3 + 2] = real(b);
     }
     if (out_rgb8) {
-        out_rgb8[px * 3] = denoise_byte(double(r));
-        out_rgb8[px * 3 + 1] = denoise_byte(double(g));
-        out_rgb8[px * 3 + 2] = denoise_byte(double(b));
+        out_rgb8[px * 3] = guide_byte(double(r));
+        out_rgb8[px * 3 + 1] = guide_byte(double(g));
+        out_rgb8[px * 3 + 2] = guide_byte(double(b));
     }
 }
 

@@ -180,6 +180,18 @@ public:
     int temporal_history = 0;
     int last_temporal_frames = 0;      // set by render(): frames in the history the image was written from (0: no history used)
     void temporal_reset() { if (temporal_) temporal_->reset(); }  // the next render() starts a new history
+    // Guided upsampling (rtk_upsample; one device, as progressive rendering).  render_scale = 2..4: render()
+    //   1. derives the low camera (rtk_upsample_camera: 1 / render_scale of the width and height, rounded up) and renders it as one
+    //      progressive step of the whole target -- samples_per_pixel samples per LOW pixel, render_scale^2 times fewer rays;
+    //      samples_per_pixel must give two full chunks for the noise estimate, else render() warns and renders at full resolution,
+    //   2. renders the guides of both cameras (aov_samples, denoise_follow; the same seed),
+    //   3. rebuilds the full-resolution frame with rtk_upsample (upsample_demodulate: on colour / seen albedo, which brings textures
+    //      back at full resolution) and writes it to image_name.
+    // With temporal_history > 0 the upsampled colour and se are what is accumulated; with denoise_image_name set the guided filter
+    // runs on the result at full resolution.  1 (default): nothing changes, bit for bit.
+    int render_scale = 1;
+    bool upsample_demodulate = false;
+    bool last_render_upsampled = false;  // set by render(): the image was rebuilt from a low-resolution frame
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -372,15 +384,9 @@ public:
         return rc;
     }
 
-    // render() with temporal_history > 0 (see the member).  RTK_OK with *used = false: too few samples for a noise estimate, the
-    // caller renders without history.
-    int render_temporal(const hittable& world, const std::vector<point_light>& lights, std::vector<uint8_t>* rgb8, bool* used) {
-        *used = false;
-        last_temporal_frames = 0;
-        rtk::scene_builder sb;
-        rtk_scene_desc desc = rtk::flatten(world, lights, sb);
-        rtk_camera cam = derive();
-        const int dev = devices.empty() ? device : devices[0];
+    // The rtk_temporal that temporal_history keeps between render() calls, for this image size, real mode and device: created on
+    // first use, recreated (with a warning) when one of them changed.
+    int temporal_context(const rtk_camera& cam, int dev) {
         if (temporal_ && (temporal_->width != cam.image_width || temporal_->height != cam.image_height || temporal_->real_mode != real_mode || temporal_->device != dev)) {
             std::cerr << "camera::render: image size, real mode or device changed; the temporal history starts over" << std::endl;
             temporal_.reset();
@@ -396,8 +402,22 @@ public:
             st->device = dev;
             temporal_ = st;
         }
+        return RTK_OK;
+    }
+
+    // render() with temporal_history > 0 (see the member).  RTK_OK with *used = false: too few samples for a noise estimate, the
+    // caller renders without history.
+    int render_temporal(const hittable& world, const std::vector<point_light>& lights, std::vector<uint8_t>* rgb8, bool* used) {
+        *used = false;
+        last_temporal_frames = 0;
+        rtk::scene_builder sb;
+        rtk_scene_desc desc = rtk::flatten(world, lights, sb);
+        rtk_camera cam = derive();
+        const int dev = devices.empty() ? device : devices[0];
+        int rc = temporal_context(cam, dev);
+        if (rc != RTK_OK) return rc;
         rtk_ctx* ctx = rtk_multi_ctx(temporal_->multi, 0);
-        int rc = upload(temporal_->multi, desc, cam);
+        rc = upload(temporal_->multi, desc, cam);
         if (rc != RTK_OK) return rc;
         rtk_render_opts opts{};
         opts.seed = seed + uint32_t(rtk_temporal_frames(temporal_->temporal));
@@ -439,6 +459,74 @@ public:
         return rc;
     }
 
+    // render() with render_scale > 1 (see the member).  RTK_OK with *used = false: render_scale out of range or too few samples
+    // for a noise estimate, the caller renders plainly.
+    int render_scaled(const hittable& world, const std::vector<point_light>& lights, std::vector<uint8_t>* rgb8, bool* used) {
+        *used = false;
+        last_temporal_frames = 0;
+        rtk_camera cam = derive(), low;
+        if (rtk_upsample_camera(&cam, render_scale, &low) != RTK_OK) {
+            std::cerr << "camera::render: render_scale must be 1..4 (" << render_scale << "); rendering at full resolution" << std::endl;
+            return RTK_OK;
+        }
+        rtk::scene_builder sb;
+        rtk_scene_desc desc = rtk::flatten(world, lights, sb);
+        const int dev = devices.empty() ? device : devices[0];
+        const bool temporal = temporal_history > 0;
+        rtk_multi* own = nullptr;  // without a history the context lives for this call
+        int rc = temporal ? temporal_context(cam, dev) : rtk_init_multi(1, &dev, RTK_GATHER_PEER, &own);
+        if (rc != RTK_OK) return rc;
+        rtk_multi* multi = temporal ? temporal_->multi : own;
+        rtk_ctx* ctx = rtk_multi_ctx(multi, 0);
+        rtk_render_opts opts{};
+        opts.seed = seed + (temporal ? uint32_t(rtk_temporal_frames(temporal_->temporal)) : 0u);
+        opts.real_mode = real_mode;
+        opts.rank = 0;
+        opts.n_ranks = 1;
+        rtk_progressive* p = nullptr;
+        rc = upload(multi, desc, cam);
+        if (rc == RTK_OK) rc = rtk_progressive_create(ctx, &low, &opts, &p);
+        if (rc == RTK_OK && low.samples_per_pixel < 2 * rtk_progressive_chunk_size(p)) {
+            std::cerr << "camera::render: render_scale needs samples_per_pixel >= " << 2 * rtk_progressive_chunk_size(p)
+                      << " (two full chunks for the noise estimate); rendering at full resolution" << std::endl;
+            rtk_progressive_destroy(p);
+            if (own) rtk_multi_destroy(own);
+            return RTK_OK;
+        }
+        const size_t px = size_t(cam.image_width) * cam.image_height, lpx = size_t(low.image_width) * low.image_height;
+        std::vector<double> linear(px * 3), low_linear(lpx * 3);
+        std::vector<float> noise(px), guides(px * 16), low_noise(lpx), low_guides(lpx * 16);
+        rgb8->assign(px * 3, 0);
+        auto t0 = std::chrono::steady_clock::now();
+        if (rc == RTK_OK) rc = rtk_progressive_step_host(p, low.samples_per_pixel, low_linear.data(), nullptr, low_noise.data(), nullptr);
+        if (p) rtk_progressive_destroy(p);
+        const rtk_guide_opts go{denoise_follow, 0};
+        if (rc == RTK_OK) rc = rtk_render_guides_host(ctx, &low, &opts, aov_samples, &go, low_guides.data());
+        if (rc == RTK_OK) rc = rtk_render_guides_host(ctx, &cam, &opts, aov_samples, &go, guides.data());
+        rtk_upsample_opts uo{};
+        uo.factor = render_scale;
+        uo.flags = upsample_demodulate ? RTK_UPSAMPLE_DEMODULATE : 0;
+        if (rc == RTK_OK) rc = rtk_upsample_host(ctx, &cam, real_mode, low_linear.data(), low_noise.data(), low_guides.data(), guides.data(), &uo, linear.data(),
+                                                 noise.data(), rgb8->data(), nullptr);
+        if (rc == RTK_OK && temporal) {  // the upsampled colour and se are what is accumulated
+            rtk_temporal_opts to{};
+            to.max_history = temporal_history;
+            rc = rtk_temporal_accumulate_host(temporal_->temporal, &cam, linear.data(), guides.data(), noise.data(), &to, linear.data(), noise.data(), rgb8->data(),
+                                              nullptr);
+            if (rc == RTK_OK) last_temporal_frames = rtk_temporal_frames(temporal_->temporal);
+        }
+        last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc == RTK_OK && denoise_image_name) {
+            std::vector<uint8_t> den(px * 3);
+            rc = rtk_denoise_guided_host(ctx, cam.image_width, cam.image_height, real_mode, linear.data(), guides.data(), noise.data(), nullptr,
+                                         denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, nullptr, den.data());
+            if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
+        }
+        if (own) rtk_multi_destroy(own);
+        *used = rc == RTK_OK;
+        return rc;
+    }
+
     // Camera.txt:102-106: "\rPercent Rendered: N% " on stderr.
     static void print_progress(int64_t done, int64_t total, void*) {
         const float percent = total > 0 ? 100.0f * float(done) / float(total) : 100.0f;
@@ -448,9 +536,12 @@ public:
     // Camera.txt:54.  Blocking; borrows world and lights for the call.
     void render(const hittable& world, std::vector<point_light>& lights) {
         std::vector<uint8_t> rgb8;
-        bool temporal = false;
-        int rc = temporal_history > 0 ? render_temporal(world, lights, &rgb8, &temporal) : RTK_OK;
-        if (rc == RTK_OK && !temporal)
+        bool temporal = false, scaled = false;
+        last_render_upsampled = false;
+        int rc = render_scale != 1 ? render_scaled(world, lights, &rgb8, &scaled) : RTK_OK;
+        last_render_upsampled = scaled;
+        if (rc == RTK_OK && !scaled && temporal_history > 0) rc = render_temporal(world, lights, &rgb8, &temporal);
+        if (rc == RTK_OK && !temporal && !scaled)
             rc = progressive_step > 0 || denoise_image_name ? render_progressive(world, lights, &rgb8) : render_to(world, lights, nullptr, &rgb8);
         if (rc != RTK_OK) {
             std::cerr << "camera::render failed: " << rtk_last_error() << std::endl;
