@@ -374,6 +374,38 @@ def test_filter_matches_the_numpy_reference(rt, renderer, scenes, source, opts):
         assert np.array_equal(again, out) and np.array_equal(again8, rgb8)
 
 
+RICH_OPTIONS = [{"iterations": 1}, {}, {"iterations": 8}, {"iterations": 3, "sigma_l": 2.0, "sigma_n": 32.0, "sigma_z": 0.5, "sigma_a": 0.3}]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("opts", RICH_OPTIONS, ids=["it1", "defaults", "it8", "sigmas"])
+@pytest.mark.parametrize("source", ["rich", "ragged"])
+def test_filter_matches_the_numpy_reference_on_rich_inputs(rt, renderer, scenes, source, opts):
+    """The same comparison on inputs that show every term of the rule (tests/rule_inputs.py, tests/test_rule_sensitivity.py):
+    neighbours' cosines where cos^sigma_n is neither 0 nor 1, normals of length 0.3 .. 1, fractional hit fractions, albedo
+    distances around sigma_a -- in both real modes.  Worst relative error on an MI355X: DESIGN.md, "What the post-processing
+    tests can see"."""
+    from tests.rule_inputs import rich_filter_case
+
+    renderer.upload(scenes("cornell_box"))
+    sizes = [(64, 48)] if source == "rich" else RAGGED + [(100, 75)]
+    full = dict(DEFAULTS, **opts)
+    for w, h in sizes:
+        linear, g, noise = rich_filter_case(h, w)
+        aov = np.ascontiguousarray(g[..., 0:8])
+        ref = reference_denoise(linear, aov, noise, **full)      # one reference for both modes: the filter rounds its input to float
+        for real_mode in (0, 1):
+            out, rgb8 = renderer.denoise(linear, aov, noise, real_mode=real_mode, **opts)
+            rel = (np.abs(out - ref) / np.maximum(1.0, np.abs(ref))).max()
+            print("rich", opts, real_mode, out.shape, "rel", rel)
+            assert rel <= 1e-4, (real_mode, out.shape, rel)
+            if real_mode == 1:
+                assert np.array_equal(out, out.astype(np.float32).astype(np.float64))
+            assert np.array_equal(rgb8, _to_byte(out.astype(np.float32).astype(np.float64)))
+            again, again8 = renderer.denoise(linear, aov, noise, real_mode=real_mode, **opts)
+            assert np.array_equal(again, out) and np.array_equal(again8, rgb8)
+
+
 # (width, height, bound on the MSE ratio denoised / noisy over the image, the same over edge pixels).  The bounds are the
 # measured ratios + 15 % ("Denoiser"): book1_final 0.603 / 1.291 -- at 480x270 its small spheres make a third of the
 # pixels edges, where the filter is WORSE than the noisy preview -- and cornell_box 0.114 / 0.142.

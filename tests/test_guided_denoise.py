@@ -18,7 +18,7 @@ import pytest
 
 from tests.conftest import EARTH, ROOT
 from tests.desc_builder import (MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC, MAT_LAMBERTIAN, MAT_METAL, MAT_SPECULAR, DescBuilder, SceneDesc)
-from tests.test_denoise import (BINOMIAL3, DEFAULTS, H5, RAGGED, _aov_of_samples, _clamped, _read_png, _shift, _synthetic, _to_byte, reference_denoise)
+from tests.test_denoise import (BINOMIAL3, DEFAULTS, H5, RAGGED, RICH_OPTIONS, _aov_of_samples, _clamped, _read_png, _shift, _synthetic, _to_byte, reference_denoise)
 
 ENTRY_POINTS = ("rtk_render_guides", "rtk_render_guides_host", "rtk_denoise_guided", "rtk_denoise_guided_host", "rtk_progressive_denoise_guided",
                 "rtk_progressive_denoise_guided_host")
@@ -26,8 +26,16 @@ MIRROR, DIELECTRIC = 1, 2
 
 
 # ------------------------------------------------------------------------------------------------------ numpy reference --
-def reference_denoise_guided(linear, guides, noise, demodulate=False, iterations=5, sigma_l=4.0, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1):
-    """include/rtk.h, rtk_denoise_guided, in float64 (reference_denoise's conventions)."""
+# Deliberate one-term deviations from the rule: what a subtly wrong kernel would compute.  tests/test_rule_sensitivity.py shows
+# that the device comparison's inputs tell each of them from the rule; none is ever run against the device.
+VARIANTS = ("cos_without_lengths", "no_z_term", "gradient_min", "hit_below_1", "wn_set1_only", "wz_set1_only", "wz2_with_hit1", "wz2_with_grad1",
+            "wa_first_albedo", "gv_centre", "variance_w", "floor_0", "variance_per_channel")
+
+
+def reference_denoise_guided(linear, guides, noise, demodulate=False, iterations=5, sigma_l=4.0, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1, variant=None):
+    """include/rtk.h, rtk_denoise_guided, in float64 (reference_denoise's conventions).  variant: one of VARIANTS, a deliberately
+    wrong rule."""
+    assert variant is None or variant in VARIANTS, variant
     c = np.asarray(linear, np.float32).astype(np.float64)
     se = np.asarray(noise, np.float32)
     var = (se * se).astype(np.float64)
@@ -35,15 +43,26 @@ def reference_denoise_guided(linear, guides, noise, demodulate=False, iterations
     seen = g[..., 8:11]
     sets = []
     for hit, nrm, z in ((g[..., 3], g[..., 4:7], g[..., 7]), (g[..., 11], g[..., 12:15], g[..., 15])):
-        grad = np.maximum(np.abs(_clamped(z, 0, 1) - _clamped(z, 0, -1)), np.abs(_clamped(z, 1, 0) - _clamped(z, -1, 0))) / 2
+        zx, zy = np.abs(_clamped(z, 0, 1) - _clamped(z, 0, -1)), np.abs(_clamped(z, 1, 0) - _clamped(z, -1, 0))
+        grad = (np.minimum(zx, zy) if variant == "gradient_min" else np.maximum(zx, zy)) / 2
         sets.append((hit, nrm, z, grad, np.all(nrm == 0, axis=-1), np.sqrt((nrm * nrm).sum(-1))))
+    if variant == "wz2_with_hit1":
+        sets[1] = (sets[0][0],) + sets[1][1:]
+    if variant == "wz2_with_grad1":
+        sets[1] = sets[1][:3] + (sets[0][3],) + sets[1][4:]
+    floor = 0.0 if variant == "floor_0" else 0.02
     if demodulate:
-        A = np.maximum(seen, 0.02)
-        c = c / A
-        var = var / ((A[..., 0] + A[..., 1] + A[..., 2]) / 3) ** 2
+        A = np.maximum(seen, floor)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c = c / A
+            var = (var[..., None] / A ** 2).mean(-1) if variant == "variance_per_channel" else var / ((A[..., 0] + A[..., 1] + A[..., 2]) / 3) ** 2
+    wa_of = g[..., 0:3] if variant == "wa_first_albedo" else seen
+    z_term = 0.0 if variant == "no_z_term" else 1e-3
     for k in range(iterations):
         step = 2 ** k
         gv = sum(BINOMIAL3[b + 1] * BINOMIAL3[a + 1] * _clamped(var, b, a) for b in (-1, 0, 1) for a in (-1, 0, 1))
+        if variant == "gv_centre":
+            gv = var
         y = (c[..., 0] + c[..., 1] + c[..., 2]) / 3
         lden = sigma_l * np.sqrt(np.maximum(gv, 0)) + 1e-6
         sw, sc, sv = np.zeros(y.shape), np.zeros(c.shape), np.zeros(y.shape)
@@ -63,22 +82,26 @@ def reference_denoise_guided(linear, guides, noise, demodulate=False, iterations
                     nqzero = np.all(nq == 0, axis=-1)
                     with np.errstate(invalid="ignore", divide="ignore"):
                         cos = (nrm * nq).sum(-1) / (nlen * np.sqrt((nq * nq).sum(-1)))
+                        if variant == "cos_without_lengths":
+                            cos = (nrm * nq).sum(-1)
                         wn_s = np.where(nzero & nqzero, 1.0, np.where(nzero | nqzero, 0.0, np.maximum(0.0, np.nan_to_num(cos)) ** sigma_n))
-                    wz_s = np.where((hit == 0) | (hq == 0), 1.0, np.exp(-np.abs(z - zq) / (sigma_z * (grad * o + 1e-3 * z) + 1e-6)))
-                    wn = wn_s if wn is None else np.minimum(wn, wn_s)
-                    wz = wz_s if wz is None else np.minimum(wz, wz_s)
+                        wz_s = np.exp(-np.abs(z - zq) / (sigma_z * (grad * o + z_term * z) + 1e-6))
+                    wz_s = np.where(((hit < 1) | (hq < 1)) if variant == "hit_below_1" else ((hit == 0) | (hq == 0)), 1.0, wz_s)
+                    wn = wn_s if wn is None else (wn if variant == "wn_set1_only" else np.minimum(wn, wn_s))
+                    wz = wz_s if wz is None else (wz if variant == "wz_set1_only" else np.minimum(wz, wz_s))
                 if demodulate:
                     wa = 1.0
                 else:
-                    aq, _ = _shift(seen, oy, ox)
-                    wa = np.exp(-np.sqrt(((seen - aq) ** 2).sum(-1)) / sigma_a)
+                    aq, _ = _shift(wa_of, oy, ox)
+                    wa = np.exp(-np.sqrt(((wa_of - aq) ** 2).sum(-1)) / sigma_a)
                 w = np.where(valid, H5[dx + 2] * H5[dy + 2] * wl * wn * wz * wa, 0.0)
                 sw += w
                 sc += w[..., None] * cq
-                sv += w * w * vq
-        c = sc / sw[..., None]
-        var = sv / (sw * sw)
-    return c * np.maximum(seen, 0.02) if demodulate else c
+                sv += (w if variant == "variance_w" else w * w) * vq
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c = sc / sw[..., None]
+            var = sv / (sw * sw)
+    return c * np.maximum(seen, floor) if demodulate else c
 
 
 def _doubled(aov):
@@ -557,6 +580,34 @@ def test_guided_filter_matches_the_numpy_reference(rt, renderer, scenes, room_pr
         assert np.array_equal(rgb8, _to_byte(out.astype(np.float32).astype(np.float64)))
         again, again8 = renderer.denoise_guided(linear, g, noise, demodulate=demodulate, real_mode=real_mode, iterations=iterations)
         assert np.array_equal(again, out) and np.array_equal(again8, rgb8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("demodulate", [False, True], ids=["plain", "demodulated"])
+@pytest.mark.parametrize("opts", RICH_OPTIONS, ids=["it1", "defaults", "it8", "sigmas"])
+@pytest.mark.parametrize("source", ["rich", "ragged"])
+def test_guided_filter_matches_the_numpy_reference_on_rich_inputs(rt, renderer, scenes, source, opts, demodulate):
+    """The same comparison on inputs that show every term of the rule (tests/rule_inputs.py, tests/test_rule_sensitivity.py): a
+    second set with its own hit fractions, gradients, normals and seen albedo, albedos below the demodulation floor -- in both
+    real modes.  Worst relative error on an MI355X: DESIGN.md, "What the post-processing tests can see"."""
+    from tests.rule_inputs import rich_filter_case
+
+    renderer.upload(scenes("cornell_box"))
+    sizes = [(64, 48)] if source == "rich" else RAGGED + [(100, 75)]
+    full = dict(DEFAULTS, **opts)
+    for w, h in sizes:
+        linear, g, noise = rich_filter_case(h, w)
+        ref = reference_denoise_guided(linear, g, noise, demodulate=demodulate, **full)   # one reference for both modes
+        for real_mode in (0, 1):
+            out, rgb8 = renderer.denoise_guided(linear, g, noise, demodulate=demodulate, real_mode=real_mode, **opts)
+            rel = (np.abs(out - ref) / np.maximum(1.0, np.abs(ref))).max()
+            print("rich", opts, demodulate, real_mode, out.shape, "rel", rel)
+            assert rel <= 1e-4, (real_mode, out.shape, rel)
+            if real_mode == 1:
+                assert np.array_equal(out, out.astype(np.float32).astype(np.float64))
+            assert np.array_equal(rgb8, _to_byte(out.astype(np.float32).astype(np.float64)))
+            again, again8 = renderer.denoise_guided(linear, g, noise, demodulate=demodulate, real_mode=real_mode, **opts)
+            assert np.array_equal(again, out) and np.array_equal(again8, rgb8)
 
 
 def _first_materials(renderer, cam, seed, n):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import EARTH, ROOT
+from tests.rule_inputs import rich_guides, shade, view_of
 from tests.test_denoise import _read_png, _to_byte
 from tests.test_temporal import _v, synthetic_camera, synthetic_guides
 
@@ -40,32 +41,43 @@ def _positions(n_full, f):
     return x0, (n - 2 * f * x0).astype(np.float32) / np.float32(2 * f)
 
 
-def _depth_gradient(z):
+# Deliberate one-term deviations from the rule: what a subtly wrong kernel would compute.  tests/test_rule_sensitivity.py shows
+# that the device comparison's inputs tell each of them from the rule; none is ever run against the device.
+VARIANTS = ("cos_without_lengths", "no_z_term", "gradient_min", "hit_below_1", "wn_set1_only", "wz_set1_only", "wz2_with_hit1", "wz2_with_grad1",
+            "wa_first_albedo", "o_is_1", "floor_0", "albedo_swapped", "support_omega")
+
+
+def _depth_gradient(z, variant=None):
     """Half the larger central difference, edges clamped."""
     h, w = z.shape
     ii, jj = np.arange(w), np.arange(h)
     zx = np.abs(z[:, np.clip(ii + 1, 0, w - 1)] - z[:, np.clip(ii - 1, 0, w - 1)])
     zy = np.abs(z[np.clip(jj + 1, 0, h - 1), :] - z[np.clip(jj - 1, 0, h - 1), :])
-    return np.maximum(zx, zy) / 2.0
+    return (np.minimum(zx, zy) if variant == "gradient_min" else np.maximum(zx, zy)) / 2.0
 
 
-def _normal_weight(n_p, n_q, sigma_n):
+def _normal_weight(n_p, n_q, sigma_n, variant=None):
     pz, qz = np.all(n_p == 0, -1), np.all(n_q == 0, -1)
     with np.errstate(invalid="ignore", divide="ignore"):
         cos = np.nan_to_num((n_p * n_q).sum(-1) / (np.sqrt((n_p * n_p).sum(-1)) * np.sqrt((n_q * n_q).sum(-1))))
+        if variant == "cos_without_lengths":
+            cos = (n_p * n_q).sum(-1)
         w = np.where(cos > 0, np.power(np.maximum(cos, 0.0), sigma_n), 0.0)
     return np.where(pz | qz, (pz & qz).astype(np.float64), w)
 
 
-def _depth_weight(hit_p, hit_q, z_p, z_q, grad, o, sigma_z):
-    with np.errstate(over="ignore"):
-        w = np.exp(-np.abs(z_p - z_q) / (sigma_z * (grad * o + 1e-3 * z_p) + 1e-6))
+def _depth_weight(hit_p, hit_q, z_p, z_q, grad, o, sigma_z, variant=None):
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        w = np.exp(-np.abs(z_p - z_q) / (sigma_z * (grad * o + (0.0 if variant == "no_z_term" else 1e-3) * z_p) + 1e-6))
+    if variant == "hit_below_1":
+        return np.where((hit_p < 1) | (hit_q < 1), 1.0, w)
     return np.where((hit_p == 0) | (hit_q == 0), 1.0, w)
 
 
-def reference_upsample(w, h, f, low_linear, low_noise, low_guides, guides, demodulate=False, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1):
+def reference_upsample(w, h, f, low_linear, low_noise, low_guides, guides, demodulate=False, sigma_n=128.0, sigma_z=1.0, sigma_a=0.1, variant=None):
     """include/rtk.h, "Guided upsampling", in float64 (positions and bilinear weights in float32, as the rule says).
-    Returns (out (H, W, 3), var_out (H, W), support (H, W), sum_beta (H, W))."""
+    Returns (out (H, W, 3), var_out (H, W), support (H, W), sum_beta (H, W)).  variant: one of VARIANTS, a deliberately wrong rule."""
+    assert variant is None or variant in VARIANTS, variant
     f32 = lambda x: float(np.float32(x))  # noqa: E731  (the options are floats on the device)
     sigma_n, sigma_z, sigma_a = f32(sigma_n), f32(sigma_z), f32(sigma_a)
     lw, lh = low_size(w, h, f)
@@ -73,12 +85,19 @@ def reference_upsample(w, h, f, low_linear, low_noise, low_guides, guides, demod
     var = np.asarray(low_noise, np.float32).astype(np.float64).reshape(lh, lw) ** 2
     G = np.asarray(low_guides, np.float32).astype(np.float64).reshape(lh, lw, 16)
     g = np.asarray(guides, np.float32).astype(np.float64).reshape(h, w, 16)
+    swapped = demodulate and variant == "albedo_swapped"
     if demodulate:
         A_q = np.maximum(G[..., 8:11], 0.02)
-        c, var = c / A_q, var / A_q.mean(-1) ** 2
+        if not swapped:
+            c, var = c / A_q, var / A_q.mean(-1) ** 2
     x0, fx = _positions(w, f)
     y0, fy = _positions(h, f)
-    grad1, grad2 = _depth_gradient(g[..., 7]), _depth_gradient(g[..., 15])
+    grad1, grad2 = _depth_gradient(g[..., 7], variant), _depth_gradient(g[..., 15], variant)
+    if variant == "wz2_with_grad1":
+        grad2 = grad1
+    hit2 = g[..., 3] if variant == "wz2_with_hit1" else g[..., 11]
+    alb = slice(0, 3) if variant == "wa_first_albedo" else slice(8, 11)
+    floor = 0.0 if variant == "floor_0" else 1e-3
     s_om, s_c, s_v, s_beta, s_acc = np.zeros((h, w)), np.zeros((h, w, 3)), np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w))
     for b in (0, 1):
         for a in (0, 1):
@@ -90,20 +109,31 @@ def reference_upsample(w, h, f, low_linear, low_noise, low_guides, guides, demod
             q = G[tj[:, None], ti[None, :]]
             ox, oy = fx.astype(np.float64) - a, fy.astype(np.float64) - b
             o = f * np.sqrt(ox[None, :] ** 2 + oy[:, None] ** 2)
-            w_n = np.minimum(_normal_weight(g[..., 4:7], q[..., 4:7], sigma_n), _normal_weight(g[..., 12:15], q[..., 12:15], sigma_n))
-            w_z = np.minimum(_depth_weight(g[..., 3], q[..., 3], g[..., 7], q[..., 7], grad1, o, sigma_z),
-                             _depth_weight(g[..., 11], q[..., 11], g[..., 15], q[..., 15], grad2, o, sigma_z))
-            w_a = 1.0 if demodulate else np.exp(-np.sqrt(((g[..., 8:11] - q[..., 8:11]) ** 2).sum(-1)) / sigma_a)
+            if variant == "o_is_1":
+                o = 1.0
+            w_n = _normal_weight(g[..., 4:7], q[..., 4:7], sigma_n, variant)
+            w_z = _depth_weight(g[..., 3], q[..., 3], g[..., 7], q[..., 7], grad1, o, sigma_z, variant)
+            if variant != "wn_set1_only":
+                w_n = np.minimum(w_n, _normal_weight(g[..., 12:15], q[..., 12:15], sigma_n, variant))
+            if variant != "wz_set1_only":
+                w_z = np.minimum(w_z, _depth_weight(hit2, q[..., 3] if variant == "wz2_with_hit1" else q[..., 11], g[..., 15], q[..., 15], grad2, o, sigma_z, variant))
+            w_a = 1.0 if demodulate else np.exp(-np.sqrt(((g[..., alb] - q[..., alb]) ** 2).sum(-1)) / sigma_a)
             wt = w_n * w_z * w_a
             beta = np.where(inside, beta, 0.0)
-            om = beta * (wt + 1e-3)
+            om = beta * (wt + floor)
             s_om += om
-            s_c += om[..., None] * c[tj[:, None], ti[None, :]]
-            s_v += om * om * var[tj[:, None], ti[None, :]]
+            cq, vq = c[tj[:, None], ti[None, :]], var[tj[:, None], ti[None, :]]
+            if swapped:                                           # the tap divided by the full pixel's albedo, the blend multiplied by the tap's
+                A_p = np.maximum(g[..., 8:11], 0.02)
+                A_t = A_q[tj[:, None], ti[None, :]]
+                cq, vq = cq / A_p * A_t, vq / A_p.mean(-1) ** 2 * A_t.mean(-1) ** 2
+            s_c += om[..., None] * cq
+            s_v += om * om * vq
             s_beta += beta
-            s_acc += beta * wt
-    out, var_out = s_c / s_om[..., None], s_v / (s_om * s_om)
-    if demodulate:
+            s_acc += (om if variant == "support_omega" else beta * wt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out, var_out = s_c / s_om[..., None], s_v / (s_om * s_om)
+    if demodulate and not swapped:
         A_p = np.maximum(g[..., 8:11], 0.02)
         out, var_out = out * A_p, var_out * A_p.mean(-1) ** 2
     return out, var_out, s_acc / s_beta, s_beta
@@ -301,6 +331,18 @@ def synthetic_case(rt, w, h, f):
     return full, colour, rng.uniform(0.05, 0.15, (lh, lw)).astype(np.float32), low_g, g
 
 
+def rich_case(rt, w, h, f):
+    """synthetic_case on the rich guides of tests/rule_inputs.py: two distinct guide sets, fractional hit fractions, short
+    normals, textured albedo -- the same world seen by the full camera and by its low camera."""
+    full = synthetic_camera(rt, w, h, (0.0, 2.0, 6.0))
+    low = rt.upsample_camera(full, f)
+    g, low_g = rich_guides(view_of(full)), rich_guides(view_of(low))
+    rng = np.random.default_rng(3000 * f + w)
+    lw, lh = low_size(w, h, f)
+    se = rng.uniform(0.05, 0.15, (lh, lw)).astype(np.float32)
+    return full, shade(low_g) + rng.normal(0.0, 1.0, (lh, lw, 3)) * se[..., None], se, low_g, g
+
+
 def _rel(got, ref):
     return float((np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max())
 
@@ -329,6 +371,34 @@ def test_device_equals_the_restatement(rt, renderer, size, f, demodulate, real_m
             assert np.array_equal(x, y)
         if w >= 37 and not demodulate:
             assert support.min() < 0.5 < support.mean()          # edges reject taps, surfaces accept them
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
+@pytest.mark.parametrize("demodulate", [False, True], ids=["plain", "demodulated"])
+@pytest.mark.parametrize("f", FACTORS)
+@pytest.mark.parametrize("size", GPU_SIZES, ids=["%dx%d" % s for s in GPU_SIZES])
+def test_device_equals_the_restatement_on_rich_inputs(rt, renderer, size, f, demodulate, real_mode):
+    """The same comparison on inputs that show every term of the rule (tests/test_rule_sensitivity.py): two distinct guide sets,
+    fractional hit fractions, short normals whose cosines lie where cos^sigma_n is neither 0 nor 1, a textured seen albedo.
+    Worst relative error on an MI355X over all cases: see DESIGN.md, "What the post-processing tests can see"."""
+    w, h = size
+    full, colour, se, low_g, g = rich_case(rt, w, h, f)
+    for opts in (DEFAULTS, OTHER):
+        out, out_se, rgb8, support = renderer.upsample(full, colour, se, low_g, g, factor=f, demodulate=demodulate, real_mode=real_mode, **opts)
+        ref, ref_var, ref_support, _ = reference_upsample(w, h, f, colour, se, low_g, g, demodulate=demodulate, **opts)
+        worst = (_rel(out, ref), _rel(out_se.astype(np.float64), np.sqrt(ref_var)), _rel(support.astype(np.float64), ref_support))
+        partial = float(((support > 0.1) & (support < 0.9)).mean())
+        print("rich", size, f, demodulate, real_mode, opts["sigma_n"], "worst rel: colour %.3g se %.3g support %.3g" % worst,
+              "support: mean %.3f, share strictly between 0.1 and 0.9: %.3f" % (float(support.mean()), partial))
+        assert max(worst) <= 1e-4, worst                          # every pixel: the rule has no threshold
+        assert np.array_equal(out, out.astype(np.float32).astype(np.float64))            # float32 colour arithmetic in both modes
+        assert np.array_equal(rgb8, _to_byte(out))
+        again = renderer.upsample(full, colour, se, low_g, g, factor=f, demodulate=demodulate, real_mode=real_mode, **opts)
+        for x, y in zip(again, (out, out_se, rgb8, support)):
+            assert np.array_equal(x, y)
+        if w >= 37:
+            assert partial >= 0.1, partial                        # taps weighed, not only accepted or rejected
 
 
 @pytest.fixture(scope="module")
