@@ -812,6 +812,89 @@ int rtk_upsample(rtk_ctx* ctx, const rtk_camera* full, int32_t real_mode, const 
 int rtk_upsample_host(rtk_ctx* ctx, const rtk_camera* full, int32_t real_mode, const double* h_low_linear, const float* h_low_noise, const float* h_low_guides,
                       const float* h_guides, const rtk_upsample_opts* opts, double* h_out_linear, float* h_out_noise, uint8_t* h_out_rgb8, float* h_out_support);
 
+/* Display transform -------------------------------------------------------------------
+ * Between a linear frame and its pixels: every other rgb8 output of this header is the reference's conversion (sqrt, clamp to
+ * 0.999, quantise), which clips wherever a light of radiance 7..15 or its first bounce is seen.  An rtk_display object meters
+ * the frame, adapts an exposure over the frames of a moving camera, optionally adds bloom, and applies a tone curve and an
+ * encoding.  It is bound to a context, a size, a real mode and a stream at creation (the stream rules of rtk_render_device:
+ * every launch goes there, opts are read before the call returns, the call never waits for the device); it owns its device
+ * memory (the exposure, two histograms; with bloom a pyramid of about 9.3 bytes per pixel, allocated by the first call that
+ * asks for bloom).  The exposure goes from the metering kernel to the kernels that use it through device memory: there is no
+ * host round trip.  No other rgb8 output changes.
+ *   d_linear  H*W*3 reals of real_mode; outputs d_out_linear H*W*3 reals of real_mode, d_out_rgb8 H*W*3 bytes; either may be
+ *             NULL, not both; they may alias d_linear.  Whole images only.
+ * The rule, for the W x H image with colour c in the real mode's type:
+ *   1. Sanitise, per channel: NaN and values <= 0 become 0, values > 65504 become 65504.
+ *   2. Luminance for metering, in float32: the sanitised channels rounded to float32, y = (0.2126f r + 0.7152f g) + 0.0722f b,
+ *      each product and sum rounded on its own (no fma).
+ *   3. Histogram, in integers: a pixel with y < 2^-20 is black and not counted; any other is counted in bin
+ *      min(bits(y) >> 20, 1175) - 856: 320 bins, 8 per octave from 2^-20 to 2^20, from the exponent and the top three mantissa
+ *      bits.  Counts are uint32 and do not depend on the order of arrival.
+ *   4. Metering, in double: N = the sum of the counts, lo = meter_low N, hi = meter_high N.  Over the bins in index order with
+ *      the running count C_k, bin k has the mass m_k = max(0, min(C_k, hi) - max(C_{k-1}, lo)); L = sum m_k lambda_k / sum m_k
+ *      with lambda_k = e + log2(1 + (m + 0.5) / 8), e = floor(k / 8) - 20 the bin's octave and m = k mod 8 its sub-bin;
+ *      E_target = clamp(key / 2^L, min_exposure, max_exposure).  N = 0: E_target = the previous E, or 1 on a first frame.
+ *   5. Adaptation: on the first frame after create / reset, or with adapt = 1, E = E_target; otherwise
+ *      E = E_prev (E_target / E_prev)^adapt, a blend in the log domain.  With a manual exposure (opts.exposure > 0) steps 2-4
+ *      are skipped, E = E_target = that value, and it becomes E_prev.
+ *   6. Scale: s = E x in the real mode's type (E rounded to it).  E = 1 leaves the bits alone.
+ *   7. Bloom, in float32, only when bloom > 0, with n = bloom_levels: T_0 = max(s - bloom_threshold, 0) per channel.  For
+ *      k = 1..n level k has ceil(half) the previous size in each axis; D_k(i, j) = ((a + b) + (c + d)) / 4 over the 2x2 block
+ *      of T_{k-1} at columns 2i, 2i+1 (a, b: row 2j; c, d: row 2j+1), indices clamped to the edge; T_k = D_k under the
+ *      separable tent ((l + 2 m) + r) / 4, horizontal then vertical, edges clamped.  Upwards U_n = T_n,
+ *      U_k = T_k + bilinear(U_{k+1}); the bloom image is B = bilinear(U_1) / n.  bilinear samples a half-size level at centred
+ *      pixels: for the target index i, m = 2i - 1, x0 = floor(m / 4), fx = (m - 4 x0) / 4, taps x0 and x0 + 1 clamped to the
+ *      level, value (1 - fx) p + fx q; the same in y, y outer.  s' = s + bloom B.  A constant bright image blooms to the same
+ *      constant (B = T_0).
+ *   8. Curve, in the real mode's type: RTK_DISPLAY_CLAMP t = s'; RTK_DISPLAY_REINHARD t = s' (1 + Y / white^2) / (1 + Y) with
+ *      Y = (0.2126 r + 0.7152 g) + 0.0722 b of s'; RTK_DISPLAY_ACES (Narkowicz 2015) per channel
+ *      t = clamp(x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14), 0, 1).
+ *   9. Encode: d_out_linear = t.  RTK_DISPLAY_GAMMA2 bytes are the resolve's gamma / clamp / quantise of double(t);
+ *      RTK_DISPLAY_SRGB: g = t <= 0.0031308 ? 12.92 t : 1.055 t^(1/2.4) - 0.055 in double, clamped to [0, 0.999], byte =
+ *      uint8(int(255.999 g)).
+ * The anchor: with exposure = 1, CLAMP, GAMMA2 and no bloom, d_out_rgb8 is the resolve's own rgb8 of the same linear image,
+ * byte for byte, in both real modes.  No float atomics, fixed orders: the same inputs give the same bits.
+ * Options (NULL = defaults; a 0 field takes its default): exposure 0 = metered, key 0.18, meter_low 0.10 and meter_high 0.90
+ * (0 < low < high <= 1), min_exposure 2^-10, max_exposure 2^10, adapt 1 (0 < adapt <= 1), curve CLAMP, white 4 (REINHARD),
+ * encode GAMMA2, bloom 0 = off, bloom_threshold 1, bloom_levels 4 (1..6).  RTK_ERR_INVALID, naming the field, with nothing
+ * written and the object's state and frame count untouched: a negative or non-finite field, meter_low >= meter_high,
+ * meter_high > 1, min_exposure > max_exposure, adapt > 1, an unknown curve or encode, bloom_levels out of range,
+ * reserved != 0 (these are checked first and need no object), a null object or input, both outputs null.
+ * rtk_display_apply is asynchronous on the object's stream; the _host form (doubles, F32 rounded / widened) blocks.
+ * rtk_display_exposure blocks: out = {E, E_target} of the last apply ({1, 1} before the first apply after create / reset).
+ * rtk_display_histogram blocks: the histogram of the last metered apply (zeros before one).  rtk_display_reset makes the next
+ * frame a first frame; rtk_display_frames = applies since create / reset (negative rtk_status for a null object). */
+#define RTK_DISPLAY_CLAMP 0
+#define RTK_DISPLAY_REINHARD 1
+#define RTK_DISPLAY_ACES 2
+#define RTK_DISPLAY_GAMMA2 0
+#define RTK_DISPLAY_SRGB 1
+#define RTK_DISPLAY_BINS 320
+typedef struct rtk_display rtk_display;
+typedef struct rtk_display_opts {
+    float exposure;                     /* 0 = metered; > 0 sets E and skips the metering pass */
+    float key;                          /* 0 = 0.18 */
+    float meter_low, meter_high;        /* 0 = 0.10, 0.90; 0 < low < high <= 1 */
+    float min_exposure, max_exposure;   /* 0 = 2^-10, 2^10 */
+    float adapt;                        /* 0 = 1; else (0, 1] */
+    int32_t curve;                      /* RTK_DISPLAY_CLAMP / REINHARD / ACES */
+    float white;                        /* 0 = 4; REINHARD only */
+    int32_t encode;                     /* RTK_DISPLAY_GAMMA2 / SRGB */
+    float bloom;                        /* 0 = off; strength */
+    float bloom_threshold;              /* 0 = 1 */
+    int32_t bloom_levels;               /* 0 = 4; else 1..6 */
+    int32_t reserved;                   /* 0 */
+} rtk_display_opts;
+
+int rtk_display_create(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, void* stream, rtk_display** out);
+int rtk_display_apply(rtk_display* d, const void* d_linear, const rtk_display_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8);
+int rtk_display_apply_host(rtk_display* d, const double* h_linear, const rtk_display_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8);
+int rtk_display_exposure(rtk_display* d, double out[2]);
+int rtk_display_histogram(rtk_display* d, uint32_t out[320]);
+int rtk_display_reset(rtk_display* d);
+int rtk_display_frames(const rtk_display* d);
+int rtk_display_destroy(rtk_display* d);
+
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and
  * hit-record code as the render kernel.  Host buffers:

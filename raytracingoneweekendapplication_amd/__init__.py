@@ -235,6 +235,28 @@ def _upsample_opts(factor: int = 2, demodulate: bool = False, sigma_n: float = 0
     return UpsampleOpts(int(factor), float(sigma_n), float(sigma_z), float(sigma_a), UPSAMPLE_DEMODULATE if demodulate else 0, 0)
 
 
+DISPLAY_CLAMP, DISPLAY_REINHARD, DISPLAY_ACES = 0, 1, 2
+DISPLAY_GAMMA2, DISPLAY_SRGB = 0, 1
+DISPLAY_BINS = 320
+
+
+class DisplayOpts(C.Structure):
+    """rtk_display_opts (include/rtk.h): a field left 0 takes its default (exposure metered, key 0.18, meter_low 0.10, meter_high
+    0.90, min_exposure 2^-10, max_exposure 2^10, adapt 1, curve CLAMP, white 4, encode GAMMA2, bloom off, bloom_threshold 1,
+    bloom_levels 4)."""
+
+    _fields_ = [("exposure", C.c_float), ("key", C.c_float), ("meter_low", C.c_float), ("meter_high", C.c_float), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("adapt", C.c_float), ("curve", C.c_int32), ("white", C.c_float), ("encode", C.c_int32), ("bloom", C.c_float),
+                ("bloom_threshold", C.c_float), ("bloom_levels", C.c_int32), ("reserved", C.c_int32)]
+
+
+def _display_opts(exposure: float = 0.0, key: float = 0.0, meter_low: float = 0.0, meter_high: float = 0.0, min_exposure: float = 0.0, max_exposure: float = 0.0,
+                  adapt: float = 0.0, curve: int = DISPLAY_CLAMP, white: float = 0.0, encode: int = DISPLAY_GAMMA2, bloom: float = 0.0,
+                  bloom_threshold: float = 0.0, bloom_levels: int = 0) -> DisplayOpts:
+    return DisplayOpts(float(exposure), float(key), float(meter_low), float(meter_high), float(min_exposure), float(max_exposure), float(adapt), int(curve),
+                       float(white), int(encode), float(bloom), float(bloom_threshold), int(bloom_levels), 0)
+
+
 def host_lib() -> C.CDLL:
     """librtk_host.so: scene construction + flattening (no GPU needed)."""
     global _host_lib
@@ -370,6 +392,14 @@ def hip_lib() -> C.CDLL:
             lib.rtk_upsample.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UpsampleOpts),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.rtk_upsample_host.argtypes = lib.rtk_upsample.argtypes[:-1]
+            lib.rtk_display_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+            lib.rtk_display_apply.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DisplayOpts), C.c_void_p, C.c_void_p]
+            lib.rtk_display_apply_host.argtypes = lib.rtk_display_apply.argtypes
+            lib.rtk_display_exposure.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+            lib.rtk_display_histogram.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            lib.rtk_display_reset.argtypes = [C.c_void_p]
+            lib.rtk_display_frames.argtypes = [C.c_void_p]
+            lib.rtk_display_destroy.argtypes = [C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -751,6 +781,13 @@ class Renderer:
         self._check(self._lib.rtk_temporal_create(self._ctx, int(width), int(height), real_mode, stream or None, C.byref(h)))
         return Temporal(self, h, int(width), int(height), real_mode)
 
+    def display(self, width: int, height: int, real_mode: int = RTK_REAL_F64, stream: int = 0) -> "Display":
+        """rtk_display_create: an object that turns linear frames of ``width`` x ``height`` into display pixels (``Display.apply``:
+        metered exposure, bloom, tone curve, encoding), bound to ``stream`` (0 = the null stream)."""
+        h = C.c_void_p()
+        self._check(self._lib.rtk_display_create(self._ctx, int(width), int(height), real_mode, stream or None, C.byref(h)))
+        return Display(self, h, int(width), int(height), real_mode)
+
     def progressive(self, cam: Camera, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, rank: int = 0, n_ranks: int = 1,
                     stream: int = 0, rel_target: float | None = None, min_samples: int | None = None) -> "Progressive":
         """rtk_progressive_create: a session that renders the frame of ``cam`` (samples_per_pixel = the target) in steps.
@@ -974,6 +1011,77 @@ class Temporal:
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.rtk_temporal_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Display:
+    """The display transform (rtk_display): per frame the luminance is metered into a histogram, an exposure is adapted towards the
+    trimmed log-average, bloom is added on request, and a tone curve and an encoding give the pixels (include/rtk.h has the rule).
+    The exposure stays on the device between the passes; ``exposure()`` and ``histogram()`` fetch it and block."""
+
+    def __init__(self, renderer: Renderer, handle: C.c_void_p, width: int, height: int, real_mode: int):
+        self._r = renderer      # keeps the context alive
+        self._lib = renderer._lib
+        self._h = handle
+        self.width, self.height, self.real_mode = width, height, real_mode
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise RtkError(rc, self._lib.rtk_last_error().decode())
+
+    def frames(self) -> int:
+        """Frames applied since creation / ``reset``."""
+        n = self._lib.rtk_display_frames(self._h)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def apply(self, linear, **opts):
+        """rtk_display_apply_host: ``linear`` (H, W, 3).  ``opts``: the fields of ``DisplayOpts`` but ``reserved`` (0 = default).
+        Returns (out_linear float64 (H, W, 3), rgb8 (H, W, 3), exposure)."""
+        import numpy as np
+
+        h, w = self.height, self.width
+        linear = np.ascontiguousarray(linear, np.float64)
+        if linear.shape != (h, w, 3):
+            raise ValueError(f"apply: shape {linear.shape} does not describe a ({h}, {w}) image")
+        out, rgb8 = np.zeros((h, w, 3)), np.zeros((h, w, 3), np.uint8)
+        o = _display_opts(**opts)
+        self._check(self._lib.rtk_display_apply_host(self._h, linear.ctypes.data, C.byref(o), out.ctypes.data, rgb8.ctypes.data))
+        return out, rgb8, self.exposure()[0]
+
+    def apply_device(self, d_linear: int, d_out_linear: int = 0, d_out_rgb8: int = 0, **opts) -> None:
+        """rtk_display_apply with raw device pointers (one output may be 0); asynchronous on the object's stream."""
+        o = _display_opts(**opts)
+        self._check(self._lib.rtk_display_apply(self._h, d_linear or None, C.byref(o), d_out_linear or None, d_out_rgb8 or None))
+
+    def exposure(self):
+        """(E, E_target) of the last apply; blocks."""
+        out = (C.c_double * 2)()
+        self._check(self._lib.rtk_display_exposure(self._h, out))
+        return float(out[0]), float(out[1])
+
+    def histogram(self):
+        """The luminance histogram of the last metered apply: uint32 [320], 8 bins per octave from 2^-20; blocks."""
+        import numpy as np
+
+        out = (C.c_uint32 * DISPLAY_BINS)()
+        self._check(self._lib.rtk_display_histogram(self._h, out))
+        return np.array(out[:], np.uint32)
+
+    def reset(self) -> None:
+        """The next frame is a first frame: its exposure is its target."""
+        self._check(self._lib.rtk_display_reset(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.rtk_display_destroy(self._h)
             self._h = None
 
     def __del__(self):

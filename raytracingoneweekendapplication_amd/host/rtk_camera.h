@@ -192,6 +192,20 @@ public:
     int render_scale = 1;
     bool upsample_demodulate = false;
     bool last_render_upsampled = false;  // set by render(): the image was rebuilt from a low-resolution frame
+    // Display transform (rtk_display_*; one device, as progressive rendering).  display = true: every PNG render() writes -- the
+    // plain, progressive, denoised, temporal and upsampled paths alike -- is made from the linear frame by one rtk_display object
+    // instead of the reference's sqrt / clamp / quantise.  The object is kept across render() calls on this camera object (and its
+    // copies), like the temporal history, so the exposure adapts along a camera path.  One render() is one adaptation step: the
+    // first image it makes is metered (or takes display_exposure), the further images of the same call -- later previews, the
+    // final image, denoise_image_name -- take that image's exposure (as a float).  false (default): nothing changes, bit for bit.
+    bool display = false;
+    int display_curve = RTK_DISPLAY_CLAMP;   // RTK_DISPLAY_CLAMP / REINHARD / ACES
+    float display_exposure = 0;              // 0 = metered; > 0 sets the exposure
+    float display_adapt = 0;                 // 0 = 1: no lag; else (0, 1], the share of the way to the target (in log) per render()
+    float display_bloom = 0;                 // 0 = off; strength
+    bool display_srgb = false;               // sRGB bytes instead of the reference's gamma 2
+    double last_exposure = 0;                // set by render(): the exposure its images were made with (0: display off)
+    void display_reset() { if (display_) rtk_display_reset(display_->display); }  // the next render() adapts from nothing
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -344,11 +358,18 @@ public:
             const int step = stepped ? (progressive_step + chunk - 1) / chunk * chunk : cam.samples_per_pixel;
             const int start = rtk_progressive_samples_done(p);
             rgb8->assign(size_t(cam.image_width) * cam.image_height * 3, 0);
+            std::vector<double> shown(display ? rgb8->size() : 0);  // the linear frame behind the bytes, for the display transform
+            bool pending = false;                                   // ... which the last step's bytes have yet to go through
             const char* checkpoint = stepped ? checkpoint_file : nullptr;
             std::vector<unsigned char> blob(checkpoint ? size_t(rtk_progressive_checkpoint_bytes(p)) : 0);
             auto t0 = std::chrono::steady_clock::now();
             for (int done = start; rc == RTK_OK && done < cam.samples_per_pixel;) {
-                rc = rtk_progressive_step_host(p, std::min(step, cam.samples_per_pixel - done), nullptr, rgb8->data(), nullptr, nullptr);
+                rc = rtk_progressive_step_host(p, std::min(step, cam.samples_per_pixel - done), display ? shown.data() : nullptr, rgb8->data(), nullptr, nullptr);
+                pending = display;
+                if (rc == RTK_OK && stepped && write_previews && write_image) {  // a preview is about to be written
+                    rc = display_bytes(cam, shown.data(), rgb8->data());
+                    pending = false;
+                }
                 if (rc != RTK_OK) break;
                 done = rtk_progressive_samples_done(p);
                 last_samples_done = done;
@@ -368,14 +389,17 @@ public:
                 if (show_progress) print_progress(done, cam.samples_per_pixel, nullptr);
             }
             last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (rc == RTK_OK && pending) rc = display_bytes(cam, shown.data(), rgb8->data());
             if (rc == RTK_OK && denoise_image_name) {
                 std::vector<uint8_t> den(rgb8->size());
+                double* den_linear = display ? shown.data() : nullptr;
                 if (denoise_follow != 0 || denoise_demodulate) {
                     const rtk_guide_opts go{denoise_follow, 0};
-                    rc = rtk_progressive_denoise_guided_host(p, aov_samples, &go, nullptr, denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, nullptr, den.data());
+                    rc = rtk_progressive_denoise_guided_host(p, aov_samples, &go, nullptr, denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, den_linear, den.data());
                 } else {
-                    rc = rtk_progressive_denoise_host(p, aov_samples, nullptr, nullptr, den.data());
+                    rc = rtk_progressive_denoise_host(p, aov_samples, nullptr, den_linear, den.data());
                 }
+                if (rc == RTK_OK) rc = display_bytes(cam, shown.data(), den.data());
                 if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
             }
         }
@@ -447,13 +471,16 @@ public:
         if (rc == RTK_OK) rc = rtk_temporal_accumulate_host(temporal_->temporal, &cam, linear.data(), guides.data(), noise.data(), &to, linear.data(), noise.data(),
                                                             rgb8->data(), nullptr);
         last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc == RTK_OK) rc = display_bytes(cam, linear.data(), rgb8->data());
         if (rc != RTK_OK) return rc;
         *used = true;
         last_temporal_frames = rtk_temporal_frames(temporal_->temporal);
         if (denoise_image_name) {
             std::vector<uint8_t> den(px * 3);
+            std::vector<double> den_linear(display ? px * 3 : 0);
             rc = rtk_denoise_guided_host(ctx, cam.image_width, cam.image_height, real_mode, linear.data(), guides.data(), noise.data(), nullptr,
-                                         denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, nullptr, den.data());
+                                         denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, display ? den_linear.data() : nullptr, den.data());
+            if (rc == RTK_OK) rc = display_bytes(cam, den_linear.data(), den.data());
             if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
         }
         return rc;
@@ -516,14 +543,61 @@ public:
             if (rc == RTK_OK) last_temporal_frames = rtk_temporal_frames(temporal_->temporal);
         }
         last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc == RTK_OK) rc = display_bytes(cam, linear.data(), rgb8->data());
         if (rc == RTK_OK && denoise_image_name) {
             std::vector<uint8_t> den(px * 3);
+            std::vector<double> den_linear(display ? px * 3 : 0);
             rc = rtk_denoise_guided_host(ctx, cam.image_width, cam.image_height, real_mode, linear.data(), guides.data(), noise.data(), nullptr,
-                                         denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, nullptr, den.data());
+                                         denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, display ? den_linear.data() : nullptr, den.data());
+            if (rc == RTK_OK) rc = display_bytes(cam, den_linear.data(), den.data());
             if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
         }
         if (own) rtk_multi_destroy(own);
         *used = rc == RTK_OK;
+        return rc;
+    }
+
+    // render()'s one-shot path: render_to, and with `display` the bytes from the linear frame through the display object.
+    int render_plain(const hittable& world, const std::vector<point_light>& lights, std::vector<uint8_t>* rgb8) {
+        if (!display) return render_to(world, lights, nullptr, rgb8);
+        std::vector<double> linear;
+        int rc = render_to(world, lights, &linear, rgb8);
+        if (rc == RTK_OK) rc = display_bytes(derive(), linear.data(), rgb8->data());
+        return rc;
+    }
+
+    // With `display`: rgb8 = the display transform of `linear` (see the member); without: nothing.
+    int display_bytes(const rtk_camera& cam, const double* linear, uint8_t* rgb8) {
+        if (!display) return RTK_OK;
+        const int dev = devices.empty() ? device : devices[0];
+        if (display_ && (display_->width != cam.image_width || display_->height != cam.image_height || display_->real_mode != real_mode || display_->device != dev)) {
+            std::cerr << "camera::render: image size, real mode or device changed; the display's exposure starts over" << std::endl;
+            display_.reset();
+        }
+        if (!display_) {
+            auto st = std::make_shared<display_state>();
+            int rc = rtk_init_multi(1, &dev, RTK_GATHER_PEER, &st->multi);
+            if (rc == RTK_OK) rc = rtk_display_create(rtk_multi_ctx(st->multi, 0), cam.image_width, cam.image_height, real_mode, nullptr, &st->display);
+            if (rc != RTK_OK) return rc;
+            st->width = cam.image_width;
+            st->height = cam.image_height;
+            st->real_mode = real_mode;
+            st->device = dev;
+            display_ = st;
+        }
+        rtk_display_opts o{};
+        o.exposure = display_metered_ ? float(last_exposure) : display_exposure;
+        o.adapt = display_adapt;
+        o.curve = display_curve;
+        o.encode = display_srgb ? RTK_DISPLAY_SRGB : RTK_DISPLAY_GAMMA2;
+        o.bloom = display_bloom;
+        int rc = rtk_display_apply_host(display_->display, linear, &o, nullptr, rgb8);
+        if (rc == RTK_OK && !display_metered_) {
+            double e[2];
+            rc = rtk_display_exposure(display_->display, e);
+            if (rc == RTK_OK) last_exposure = e[0];
+            display_metered_ = rc == RTK_OK;
+        }
         return rc;
     }
 
@@ -538,11 +612,13 @@ public:
         std::vector<uint8_t> rgb8;
         bool temporal = false, scaled = false;
         last_render_upsampled = false;
+        last_exposure = 0;
+        display_metered_ = false;
         int rc = render_scale != 1 ? render_scaled(world, lights, &rgb8, &scaled) : RTK_OK;
         last_render_upsampled = scaled;
         if (rc == RTK_OK && !scaled && temporal_history > 0) rc = render_temporal(world, lights, &rgb8, &temporal);
         if (rc == RTK_OK && !temporal && !scaled)
-            rc = progressive_step > 0 || denoise_image_name ? render_progressive(world, lights, &rgb8) : render_to(world, lights, nullptr, &rgb8);
+            rc = progressive_step > 0 || denoise_image_name ? render_progressive(world, lights, &rgb8) : render_plain(world, lights, &rgb8);
         if (rc != RTK_OK) {
             std::cerr << "camera::render failed: " << rtk_last_error() << std::endl;
             return;
@@ -571,6 +647,21 @@ private:
         }
     };
     std::shared_ptr<temporal_state> temporal_;
+    // What `display` keeps between render() calls: the context the object lives on and the object.  Copies of the camera share it.
+    struct display_state {
+        rtk_multi* multi = nullptr;
+        rtk_display* display = nullptr;
+        int width = 0, height = 0, real_mode = 0, device = 0;
+        display_state() = default;
+        display_state(const display_state&) = delete;
+        display_state& operator=(const display_state&) = delete;
+        ~display_state() {
+            if (display) rtk_display_destroy(display);
+            if (multi) rtk_multi_destroy(multi);
+        }
+    };
+    std::shared_ptr<display_state> display_;
+    bool display_metered_ = false;  // within one render(): an image was already metered, the others take last_exposure
 };
 
 #endif  // RTK_CAMERA_H
