@@ -592,6 +592,9 @@ int rtk_checkpoint_read_adaptive(const void* h_buf, int64_t n, rtk_adaptive_opts
  *   k 4-6  the hit record's normal summed over hits (isotropic hits add 0), divided by n
  *   k 7    depth: the mean over hits of t * |rd|; 0 when no sample hits
  * Whole images only: n_ranks != 1, n_samples <= 0 or a null buffer give RTK_ERR_INVALID; no scene gives RTK_ERR_NO_SCENE.
+ * Alignment: d_aov is written and read 16 bytes at a time and must be 16-byte aligned -- rtk_render_aovs and rtk_denoise refuse
+ * another pointer with RTK_ERR_INVALID (the text names d_aov) before anything is launched or written.  Every other device
+ * buffer of this section needs only the alignment of its element type (8 for F64 reals, 4 for floats, 1 for bytes).
  * rtk_render_aovs is asynchronous on opts->stream; rtk_render_aovs_host blocks (count_work and variant are ignored).
  *
  * Denoiser: an edge-avoiding a-trous filter (Dammertz et al. 2010) with the luminance weight of SVGF (Schied et al. 2017),
@@ -652,6 +655,9 @@ int rtk_progressive_denoise_host(rtk_progressive* p, int32_t aov_samples, const 
  * Options (NULL = defaults): follow 0 = RTK_GUIDE_FOLLOW_MIRROR, other bits RTK_ERR_INVALID (glass is followed by the
  * render's own reflect / refract lottery: noisy at few samples, hence opt-in); max_bounces 0 = 4, else 1..8.
  * n_samples 1 .. 2^20.  Otherwise the rules of rtk_render_aovs: whole images only, asynchronous on opts->stream, _host blocks.
+ * Alignment: d_guides must be 16-byte aligned, as d_aov must -- rtk_render_guides and rtk_denoise_guided refuse another pointer
+ * with RTK_ERR_INVALID (the text names d_guides), nothing launched or written; every other device buffer needs only the
+ * alignment of its element type.
  *
  * rtk_denoise_guided is rtk_denoise's iteration (taps, h, tap order, w_l, variance propagation, output conversion) with
  *   w_n = min(w_n of set 1, w_n of set 2), w_z = min(w_z of set 1, w_z of set 2) -- each w_z with its own set's hit fraction,
@@ -697,6 +703,8 @@ int rtk_progressive_denoise_guided_host(rtk_progressive* p, int32_t aov_samples,
  *   outputs   d_out_linear H*W*3 reals of real_mode, d_out_noise H*W floats, d_out_rgb8 H*W*3 bytes, d_out_history H*W floats;
  *             any may be NULL; they may alias d_linear / d_noise (a pixel's inputs are read before its outputs are written and
  *             the taps read the object's own memory), but not d_guides.  Whole images only.
+ *   alignment d_guides must be 16-byte aligned (read 16 bytes at a time); every other device buffer needs only the alignment of
+ *             its element type.
  * The rule, per pixel (i, j) with colour c (float), se and guides g[0..15]; primes mark the previous frame's values:
  *   1. Start of a history: the first frame after create / reset, and any pixel whose first-hit fraction g[3] == 0 (the
  *      background is a constant): out = c, var_out = se^2, n_out = 1.
@@ -717,7 +725,7 @@ int rtk_progressive_denoise_guided_host(rtk_progressive* p, int32_t aov_samples,
  * Options (NULL = defaults; a 0 field takes its default): max_history 32 (1..1024), depth_tol 0.02, normal_cos 0.9, albedo_tol
  * 0.25.  RTK_ERR_INVALID, with nothing written and the history and frame count untouched: a camera whose size is not the
  * object's, negative or non-finite tolerances, normal_cos > 1, unknown flags, reserved != 0, max_history out of range, a null
- * object, camera or input.  Options are checked first (they need no object).
+ * object, camera or input, a d_guides that is not 16-byte aligned (the text names it).  Options are checked first (they need no object).
  * Limits: geometry is taken as static -- moving spheres are time-averaged within every frame and accumulate like anything else;
  * what a mirror shows is reprojected with the mirror's own surface: the opt-in check on the SEEN albedo is the available guard
  * and max_history bounds the lag.
@@ -766,6 +774,8 @@ int rtk_temporal_reproject_matrix(const rtk_camera* cam, double out[12]);
  *                 rtk_render_guides of `full`.  All four are required.
  *   outputs       d_out_linear H*W*3 reals of real_mode, d_out_noise H*W floats, d_out_rgb8 H*W*3 bytes, d_out_support H*W
  *                 floats; any may be NULL, not all.  They may not alias an input.  Whole images only.
+ *   alignment     d_low_guides and d_guides must be 16-byte aligned (read 16 bytes at a time); every other device buffer needs
+ *                 only the alignment of its element type.
  * The rule, per full pixel (i, j) with guides g[0..15]; a low pixel has guides G[0..15], colour c (float) and standard error se:
  *   1. Position, in integers: n = 2i - (f - 1), x0 = floor(n / 2f), fx = float(n - 2f x0) / float(2f); the same in j for y0, fy.
  *      Taps (x0 + a, y0 + b), a, b in {0, 1}, b outer; a tap outside the low image is skipped.  Bilinear weight
@@ -789,7 +799,7 @@ int rtk_temporal_reproject_matrix(const rtk_camera* cam, double out[12]);
  * Options (NULL = defaults; a 0 field takes its default): factor 2 (2..4), sigma_n 128, sigma_z 1, sigma_a 0.1 (the denoiser's).
  * RTK_ERR_INVALID, with nothing written: a factor outside 2..4, unknown flags, reserved != 0, negative or non-finite sigmas
  * (these are checked first and need no context or device), a null context, camera or input, all outputs null, a camera with
- * non-positive size, an unknown real_mode.
+ * non-positive size, an unknown real_mode, a d_low_guides or d_guides that is not 16-byte aligned (the text names the argument).
  * rtk_upsample is asynchronous on `stream` under the stream rules of rtk_render_device: its one launch goes there, `full` and
  * opts are read before it returns, it allocates nothing, uses no context workspace and never waits for the device.
  * rtk_upsample_host (h_low_linear / h_out_linear doubles, F32 rounded / widened) blocks.

@@ -338,6 +338,7 @@ int rtk_render_aovs(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* 
     if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_render_aovs: unknown real_mode %d", opts->real_mode);
     if (n_samples <= 0) return fail(RTK_ERR_INVALID, "rtk_render_aovs: n_samples must be positive (%d)", n_samples);
     if (!d_aov) return fail(RTK_ERR_INVALID, "rtk_render_aovs: null output buffer");
+    if (check_aligned16(d_aov, "rtk_render_aovs", "d_aov") != RTK_OK) return RTK_ERR_INVALID;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
     const hipError_t e = opts->real_mode == RTK_REAL_F64 ? launch_aov<double>(ctx_view<double>(ctx), device_camera<double>(*cam), opts->seed, n_samples, d_aov, st)
@@ -371,6 +372,7 @@ int rtk_denoise(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, 
     if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise: bad image size %dx%d", width, height);
     if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise: unknown real_mode %d", real_mode);
     if (!d_linear || !d_aov || !d_noise) return fail(RTK_ERR_INVALID, "rtk_denoise: d_linear, d_aov and d_noise are required");
+    if (check_aligned16(d_aov, "rtk_denoise", "d_aov") != RTK_OK) return RTK_ERR_INVALID;
     if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise: no output");
     DenoiseParams P{};
     int iterations = 0;
@@ -414,6 +416,7 @@ int rtk_render_guides(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts
     int follow = 0, max_bounces = 0;
     const int rc = check_guide_args("rtk_render_guides", ctx, cam, opts, n_samples, gopts, d_guides, &follow, &max_bounces);
     if (rc != RTK_OK) return rc;
+    if (check_aligned16(d_guides, "rtk_render_guides", "d_guides") != RTK_OK) return RTK_ERR_INVALID;
     uint64_t digest = 0;
     if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "rtk_render_guides: no scene uploaded");
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
@@ -455,6 +458,7 @@ int rtk_denoise_guided(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real
     if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: bad image size %dx%d", width, height);
     if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: unknown real_mode %d", real_mode);
     if (!d_linear || !d_guides || !d_noise) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: d_linear, d_guides and d_noise are required");
+    if (check_aligned16(d_guides, "rtk_denoise_guided", "d_guides") != RTK_OK) return RTK_ERR_INVALID;
     if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: no output");
     P.width = width;
     P.height = height;

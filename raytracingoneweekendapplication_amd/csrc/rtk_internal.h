@@ -36,6 +36,11 @@ struct Fnv64 {
     }
 };
 
+// include/rtk.h: guide and AOV buffers are accessed 16 bytes at a time.  RTK_OK, or RTK_ERR_INVALID with `arg` named in g_error.
+inline int check_aligned16(const void* p, const char* who, const char* arg) {
+    return (reinterpret_cast<uintptr_t>(p) & 15) == 0 ? RTK_OK : fail(RTK_ERR_INVALID, "%s: %s must be 16-byte aligned", who, arg);
+}
+
 int ctx_device(const rtk_ctx* ctx);
 // Progressive sessions (rtk_progressive.cpp) -- what they use of a context and of the one-shot frame's rules:
 int ctx_scene(const rtk_ctx* ctx, uint64_t* digest);  // 1 when a scene is uploaded; *digest = its digest

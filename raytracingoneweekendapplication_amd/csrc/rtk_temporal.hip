@@ -245,6 +245,7 @@ int rtk_temporal_accumulate(rtk_temporal* t, const rtk_camera* cam, const void* 
     if (!t) return fail(RTK_ERR_INVALID, "%s: null object", who);
     if (!cam) return fail(RTK_ERR_INVALID, "%s: null camera", who);
     if (!d_linear || !d_guides || !d_noise) return fail(RTK_ERR_INVALID, "%s: d_linear, d_guides and d_noise are required", who);
+    if (check_aligned16(d_guides, who, "d_guides") != RTK_OK) return RTK_ERR_INVALID;
     if (cam->image_width != t->width || cam->image_height != t->height)
         return fail(RTK_ERR_INVALID, "%s: the camera's image is %dx%d, the object's %dx%d", who, cam->image_width, cam->image_height, t->width, t->height);
     double now[12];
@@ -299,8 +300,8 @@ int rtk_temporal_accumulate_host(rtk_temporal* t, const rtk_camera* cam, const d
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     const bool f64 = t->real_mode == RTK_REAL_F64;
     const size_t px = size_t(t->width) * t->height, elem = f64 ? 8 : 4;
-    // one allocation: linear (in, then out in place), guides, noise (in / out), bytes, history
-    const size_t off_guides = px * 3 * elem, off_noise = off_guides + px * 16 * sizeof(float), off_hist = off_noise + px * sizeof(float),
+    // one allocation: linear (in, then out in place), guides (on the next 16-byte boundary), noise (in / out), history, bytes
+    const size_t off_guides = (px * 3 * elem + 15) / 16 * 16, off_noise = off_guides + px * 16 * sizeof(float), off_hist = off_noise + px * sizeof(float),
                  off_rgb8 = off_hist + px * sizeof(float), total = off_rgb8 + px * 3;
     char* d = nullptr;
     e = hipMalloc(reinterpret_cast<void**>(&d), total);

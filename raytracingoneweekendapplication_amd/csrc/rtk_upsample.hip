@@ -204,6 +204,7 @@ int rtk_upsample(rtk_ctx* ctx, const rtk_camera* full, int32_t real_mode, const 
     const int rc = check_upsample_args(who, opts, P, demod, ctx, full, real_mode, d_low_linear && d_low_noise && d_low_guides && d_guides,
                                        d_out_linear || d_out_noise || d_out_rgb8 || d_out_support);
     if (rc != RTK_OK) return rc;
+    if (check_aligned16(d_low_guides, who, "d_low_guides") != RTK_OK || check_aligned16(d_guides, who, "d_guides") != RTK_OK) return RTK_ERR_INVALID;
     hipError_t e = hipSetDevice(ctx_device(ctx));
     if (e == hipSuccess) {
         const hipStream_t st = static_cast<hipStream_t>(stream);
