@@ -695,12 +695,8 @@ class Renderer:
         Returns (linear float64 (H, W, 3), rgb8 (H, W, 3))."""
         import numpy as np
 
-        linear = np.ascontiguousarray(linear, np.float64)
-        aov = np.ascontiguousarray(aov, np.float32)
-        noise = np.ascontiguousarray(noise, np.float32)
-        h, w = linear.shape[:2]
-        if linear.shape != (h, w, 3) or aov.shape != (h, w, 8) or noise.shape != (h, w):
-            raise ValueError(f"denoise: shapes {linear.shape}, {aov.shape}, {noise.shape} do not describe one (H, W) image")
+        h, w = np.shape(linear)[:2]
+        linear, aov, noise = _host_inputs("denoise", "one (H, W) image", (linear, np.float64, (h, w, 3)), (aov, np.float32, (h, w, 8)), (noise, np.float32, (h, w)))
         out, rgb8 = np.zeros((h, w, 3)), np.zeros((h, w, 3), np.uint8)
         opts = _denoise_opts(iterations, sigma_l, sigma_n, sigma_z, sigma_a)
         self._check(self._lib.rtk_denoise_host(self._ctx, w, h, real_mode, linear.ctypes.data, aov.ctypes.data, noise.ctypes.data, C.byref(opts),
@@ -727,12 +723,9 @@ class Renderer:
         instead (no albedo weight) and multiplies the albedo back.  Returns (linear float64 (H, W, 3), rgb8 (H, W, 3))."""
         import numpy as np
 
-        linear = np.ascontiguousarray(linear, np.float64)
-        guides = np.ascontiguousarray(guides, np.float32)
-        noise = np.ascontiguousarray(noise, np.float32)
-        h, w = linear.shape[:2]
-        if linear.shape != (h, w, 3) or guides.shape != (h, w, 16) or noise.shape != (h, w):
-            raise ValueError(f"denoise_guided: shapes {linear.shape}, {guides.shape}, {noise.shape} do not describe one (H, W) image")
+        h, w = np.shape(linear)[:2]
+        linear, guides, noise = _host_inputs("denoise_guided", "one (H, W) image", (linear, np.float64, (h, w, 3)), (guides, np.float32, (h, w, 16)),
+                                             (noise, np.float32, (h, w)))
         out, rgb8 = np.zeros((h, w, 3)), np.zeros((h, w, 3), np.uint8)
         opts = _denoise_opts(iterations, sigma_l, sigma_n, sigma_z, sigma_a)
         flags = DENOISE_DEMODULATE if demodulate else 0
@@ -751,13 +744,9 @@ class Renderer:
         h, w = full_cam.image_height, full_cam.image_width
         f = int(factor) or 2
         lh, lw = -(-h // f), -(-w // f)
-        low_linear = np.ascontiguousarray(low_linear, np.float64)
-        low_noise = np.ascontiguousarray(low_noise, np.float32)
-        low_guides = np.ascontiguousarray(low_guides, np.float32)
-        guides = np.ascontiguousarray(guides, np.float32)
-        if low_linear.shape != (lh, lw, 3) or low_noise.shape != (lh, lw) or low_guides.shape != (lh, lw, 16) or guides.shape != (h, w, 16):
-            raise ValueError(f"upsample: shapes {low_linear.shape}, {low_noise.shape}, {low_guides.shape}, {guides.shape} do not describe a "
-                             f"({lh}, {lw}) image and the guides of a ({h}, {w}) one")
+        low_linear, low_noise, low_guides, guides = _host_inputs(
+            "upsample", f"a ({lh}, {lw}) image and the guides of a ({h}, {w}) one", (low_linear, np.float64, (lh, lw, 3)), (low_noise, np.float32, (lh, lw)),
+            (low_guides, np.float32, (lh, lw, 16)), (guides, np.float32, (h, w, 16)))
         out, out_noise = np.zeros((h, w, 3)), np.zeros((h, w), np.float32)
         rgb8, support = np.zeros((h, w, 3), np.uint8), np.zeros((h, w), np.float32)
         o = _upsample_opts(factor, demodulate, sigma_n, sigma_z, sigma_a)
@@ -837,20 +826,63 @@ class Renderer:
             pass
 
 
-class Progressive:
-    """A progressive session (rtk_progressive): one frame rendered in steps of whole sample chunks, with a per-pixel noise
-    estimate and checkpoints.  The finished frame is bit-identical to ``Renderer.render_host`` of the same camera."""
+def _host_inputs(who: str, what: str, *inputs):
+    """The array inputs of a ``*_host`` wrapper, (array, dtype, shape) each, as contiguous arrays of those dtypes; ValueError
+    naming ``who``, the shapes found and ``what`` they should describe unless every one has its shape."""
+    import numpy as np
 
-    def __init__(self, renderer: Renderer, handle: C.c_void_p, cam: Camera, real_mode: int, n_ranks: int, rank: int = 0):
+    arrays = [np.ascontiguousarray(a, dtype) for a, dtype, _ in inputs]
+    if any(a.shape != tuple(shape) for a, (_, _, shape) in zip(arrays, inputs)):
+        one = len(arrays) == 1
+        raise ValueError(f"{who}: shape{'' if one else 's'} {', '.join(str(a.shape) for a in arrays)} do{'es' if one else ''} not describe {what}")
+    return arrays
+
+
+class _Handle:
+    """What the wrappers of a C object created through a ``Renderer`` share: the handle, the renderer that keeps its context
+    alive, the error check, and ``close`` through the C destroy function a subclass names in ``_destroy``."""
+
+    _destroy = ""
+
+    def __init__(self, renderer: Renderer, handle: C.c_void_p):
         self._r = renderer      # keeps the context alive
         self._lib = renderer._lib
         self._h = handle
-        self.width, self.height, self.target = cam.image_width, cam.image_height, cam.samples_per_pixel
-        self.real_mode, self.n_ranks, self.rank = real_mode, n_ranks, rank
 
     def _check(self, rc: int) -> None:
         if rc != 0:
             raise RtkError(rc, self._lib.rtk_last_error().decode())
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ImageObject(_Handle):
+    """A stateful image pass bound to one image size and arithmetic type (``Temporal``, ``Display``)."""
+
+    def __init__(self, renderer: Renderer, handle: C.c_void_p, width: int, height: int, real_mode: int):
+        super().__init__(renderer, handle)
+        self.width, self.height, self.real_mode = width, height, real_mode
+
+
+class Progressive(_Handle):
+    """A progressive session (rtk_progressive): one frame rendered in steps of whole sample chunks, with a per-pixel noise
+    estimate and checkpoints.  The finished frame is bit-identical to ``Renderer.render_host`` of the same camera."""
+
+    _destroy = "rtk_progressive_destroy"
+
+    def __init__(self, renderer: Renderer, handle: C.c_void_p, cam: Camera, real_mode: int, n_ranks: int, rank: int = 0):
+        super().__init__(renderer, handle)
+        self.width, self.height, self.target = cam.image_width, cam.image_height, cam.samples_per_pixel
+        self.real_mode, self.n_ranks, self.rank = real_mode, n_ranks, rank
 
     @property
     def samples_done(self) -> int:
@@ -942,33 +974,14 @@ class Progressive:
         self._check(self._lib.rtk_progressive_save(self._h, buf, n))
         return buf.raw
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.rtk_progressive_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Temporal:
+class Temporal(_ImageObject):
     """Temporal accumulation (rtk_temporal): per frame, the history -- the frame returned last time -- is reprojected into the new
     camera, history of another surface is rejected, and colour, variance and history length are blended (include/rtk.h has the
     rule).  Feed ``accumulate`` a noisy frame with its se and the guides of the same camera; its outputs are inputs of
     ``Renderer.denoise_guided``."""
 
-    def __init__(self, renderer: Renderer, handle: C.c_void_p, width: int, height: int, real_mode: int):
-        self._r = renderer      # keeps the context alive
-        self._lib = renderer._lib
-        self._h = handle
-        self.width, self.height, self.real_mode = width, height, real_mode
-
-    def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise RtkError(rc, self._lib.rtk_last_error().decode())
+    _destroy = "rtk_temporal_destroy"
 
     @property
     def frames(self) -> int:
@@ -985,11 +998,8 @@ class Temporal:
         import numpy as np
 
         h, w = self.height, self.width
-        linear = np.ascontiguousarray(linear, np.float64)
-        guides = np.ascontiguousarray(guides, np.float32)
-        noise = np.ascontiguousarray(noise, np.float32)
-        if linear.shape != (h, w, 3) or guides.shape != (h, w, 16) or noise.shape != (h, w):
-            raise ValueError(f"accumulate: shapes {linear.shape}, {guides.shape}, {noise.shape} do not describe one ({h}, {w}) image")
+        linear, guides, noise = _host_inputs("accumulate", f"one ({h}, {w}) image", (linear, np.float64, (h, w, 3)), (guides, np.float32, (h, w, 16)),
+                                             (noise, np.float32, (h, w)))
         out, out_noise = np.zeros((h, w, 3)), np.zeros((h, w), np.float32)
         rgb8, history = np.zeros((h, w, 3), np.uint8), np.zeros((h, w), np.float32)
         o = _temporal_opts(**opts)
@@ -1008,32 +1018,13 @@ class Temporal:
         """The next frame starts a new history."""
         self._check(self._lib.rtk_temporal_reset(self._h))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.rtk_temporal_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Display:
+class Display(_ImageObject):
     """The display transform (rtk_display): per frame the luminance is metered into a histogram, an exposure is adapted towards the
     trimmed log-average, bloom is added on request, and a tone curve and an encoding give the pixels (include/rtk.h has the rule).
     The exposure stays on the device between the passes; ``exposure()`` and ``histogram()`` fetch it and block."""
 
-    def __init__(self, renderer: Renderer, handle: C.c_void_p, width: int, height: int, real_mode: int):
-        self._r = renderer      # keeps the context alive
-        self._lib = renderer._lib
-        self._h = handle
-        self.width, self.height, self.real_mode = width, height, real_mode
-
-    def _check(self, rc: int) -> None:
-        if rc != 0:
-            raise RtkError(rc, self._lib.rtk_last_error().decode())
+    _destroy = "rtk_display_destroy"
 
     def frames(self) -> int:
         """Frames applied since creation / ``reset``."""
@@ -1048,9 +1039,7 @@ class Display:
         import numpy as np
 
         h, w = self.height, self.width
-        linear = np.ascontiguousarray(linear, np.float64)
-        if linear.shape != (h, w, 3):
-            raise ValueError(f"apply: shape {linear.shape} does not describe a ({h}, {w}) image")
+        (linear,) = _host_inputs("apply", f"a ({h}, {w}) image", (linear, np.float64, (h, w, 3)))
         out, rgb8 = np.zeros((h, w, 3)), np.zeros((h, w, 3), np.uint8)
         o = _display_opts(**opts)
         self._check(self._lib.rtk_display_apply_host(self._h, linear.ctypes.data, C.byref(o), out.ctypes.data, rgb8.ctypes.data))
@@ -1078,17 +1067,6 @@ class Display:
     def reset(self) -> None:
         """The next frame is a first frame: its exposure is its target."""
         self._check(self._lib.rtk_display_reset(self._h))
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.rtk_display_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def temporal_reproject_matrix(cam: Camera):

@@ -12,9 +12,6 @@
 // bits on every run.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <vector>
-
 #include "rtk.h"
 #include "rtk_guide_weights.h"
 #include "rtk_internal.h"
@@ -32,27 +29,17 @@ namespace {
 #define RTK_DN __device__ __forceinline__
 
 struct DenoiseParams {
-    int width, height, tiles_x, n_tiles;
+    TileGrid grid;
     float sigma_l, sigma_n, sigma_z, sigma_a;
 };
-
-// Lane -> pixel: wave w of the grid is tile w (row-major over tiles_x), lane l its pixel (l & 7, l >> 3).  False outside.
-RTK_DN bool lane_pixel(const DenoiseParams& P, int& i, int& j) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int tile = int(gid >> 6), pix = int(gid & 63);
-    if (tile >= P.n_tiles) return false;
-    i = (tile % P.tiles_x) * 8 + (pix & 7);
-    j = (tile / P.tiles_x) * 8 + (pix >> 3);
-    return i < P.width && j < P.height;
-}
 
 // {colour, se^2} of the input image, the colour read as `real` and rounded to float.
 template <typename real>
 __global__ __launch_bounds__(256) void rtk_denoise_pack_kernel(DenoiseParams P, const real* __restrict__ linear, const float* __restrict__ noise,
                                                                 float4* __restrict__ cv) {
     int i, j;
-    if (!lane_pixel(P, i, j)) return;
-    const size_t px = size_t(j) * P.width + i;
+    if (!lane_pixel(P.grid, i, j)) return;
+    const size_t px = size_t(j) * P.grid.width + i;
     const float se = noise[px];
     cv[px] = make_float4(float(linear[px * 3]), float(linear[px * 3 + 1]), float(linear[px * 3 + 2]), se * se);
 }
@@ -64,8 +51,8 @@ template <typename real>
 __global__ __launch_bounds__(256) void rtk_denoise_step_kernel(DenoiseParams P, int step, const float4* __restrict__ cv, const float4* __restrict__ aov,
                                                                 float4* __restrict__ out_cv, real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8) {
     int i, j;
-    if (!lane_pixel(P, i, j)) return;
-    const int W = P.width, H = P.height;
+    if (!lane_pixel(P.grid, i, j)) return;
+    const int W = P.grid.width, H = P.grid.height;
     const size_t px = size_t(j) * W + i;
     const float4 cp = cv[px];
     const float4 ap = aov[px * 2], gp = aov[px * 2 + 1];  // {albedo, hit}, {normal, depth}
@@ -130,16 +117,16 @@ __global__ __launch_bounds__(256) void rtk_denoise_step_kernel(DenoiseParams P, 
         out_linear[px * 3 + 2] = real(b);
     }
     if (out_rgb8) {
-        out_rgb8[px * 3] = guide_byte(double(r));
-        out_rgb8[px * 3 + 1] = guide_byte(double(g));
-        out_rgb8[px * 3 + 2] = guide_byte(double(b));
+        out_rgb8[px * 3] = to_byte(double(r));
+        out_rgb8[px * 3 + 1] = to_byte(double(g));
+        out_rgb8[px * 3 + 2] = to_byte(double(b));
     }
 }
 
 template <typename real>
 hipError_t launch_denoise(const DenoiseParams& P, int iterations, const void* linear, const float* noise, const float4* aov, float4* ping, float4* pong,
                           void* out_linear, uint8_t* out_rgb8, hipStream_t stream) {
-    const dim3 grid((P.n_tiles + 3) / 4), block(256);
+    const dim3 grid((P.grid.n_tiles + 3) / 4), block(256);
     rtk_denoise_pack_kernel<real><<<grid, block, 0, stream>>>(P, static_cast<const real*>(linear), noise, ping);
     hipError_t e = hipGetLastError();
     for (int k = 0; k < iterations && e == hipSuccess; k++) {
@@ -167,8 +154,8 @@ template <typename real, bool DEMOD>
 __global__ __launch_bounds__(256) void rtk_denoise_guided_pack_kernel(DenoiseParams P, const real* __restrict__ linear, const float* __restrict__ noise,
                                                                        const float4* __restrict__ guides, float4* __restrict__ cv) {
     int i, j;
-    if (!lane_pixel(P, i, j)) return;
-    const size_t px = size_t(j) * P.width + i;
+    if (!lane_pixel(P.grid, i, j)) return;
+    const size_t px = size_t(j) * P.grid.width + i;
     const float se = noise[px];
     float4 c = make_float4(float(linear[px * 3]), float(linear[px * 3 + 1]), float(linear[px * 3 + 2]), se * se);
     if constexpr (DEMOD) {
@@ -184,8 +171,8 @@ template <typename real, bool DEMOD>
 __global__ __launch_bounds__(256) void rtk_denoise_guided_step_kernel(DenoiseParams P, int step, const float4* __restrict__ cv, const float4* __restrict__ guides,
                                                                        float4* __restrict__ out_cv, real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8) {
     int i, j;
-    if (!lane_pixel(P, i, j)) return;
-    const int W = P.width, H = P.height;
+    if (!lane_pixel(P.grid, i, j)) return;
+    const int W = P.grid.width, H = P.grid.height;
     const size_t px = size_t(j) * W + i;
     const float4 cp = cv[px];
     const float hit1_p = guides[px * 4].w;
@@ -249,16 +236,16 @@ __global__ __launch_bounds__(256) void rtk_denoise_guided_step_kernel(DenoisePar
         out_linear[px * 3 + 2] = real(b);
     }
     if (out_rgb8) {
-        out_rgb8[px * 3] = guide_byte(double(r));
-        out_rgb8[px * 3 + 1] = guide_byte(double(g));
-        out_rgb8[px * 3 + 2] = guide_byte(double(b));
+        out_rgb8[px * 3] = to_byte(double(r));
+        out_rgb8[px * 3 + 1] = to_byte(double(g));
+        out_rgb8[px * 3 + 2] = to_byte(double(b));
     }
 }
 
 template <typename real, bool DEMOD>
 hipError_t launch_denoise_guided(const DenoiseParams& P, int iterations, const void* linear, const float* noise, const float4* guides, float4* ping, float4* pong,
                                  void* out_linear, uint8_t* out_rgb8, hipStream_t stream) {
-    const dim3 grid((P.n_tiles + 3) / 4), block(256);
+    const dim3 grid((P.grid.n_tiles + 3) / 4), block(256);
     rtk_denoise_guided_pack_kernel<real, DEMOD><<<grid, block, 0, stream>>>(P, static_cast<const real*>(linear), noise, guides, ping);
     hipError_t e = hipGetLastError();
     for (int k = 0; k < iterations && e == hipSuccess; k++) {
@@ -332,10 +319,9 @@ int rtk_render_aovs(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* 
     if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_aovs: null argument");
     uint64_t digest = 0;
     if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "rtk_render_aovs: no scene uploaded");
-    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->image_width > 65536 || cam->image_height > 65536)
-        return fail(RTK_ERR_INVALID, "rtk_render_aovs: bad camera dimensions");
+    if (check_camera_size("rtk_render_aovs", *cam) != RTK_OK) return RTK_ERR_INVALID;
     if (opts->n_ranks != 1) return fail(RTK_ERR_INVALID, "rtk_render_aovs: whole images only (n_ranks must be 1, not %d)", opts->n_ranks);
-    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_render_aovs: unknown real_mode %d", opts->real_mode);
+    if (check_real_mode("rtk_render_aovs", opts->real_mode) != RTK_OK) return RTK_ERR_INVALID;
     if (n_samples <= 0) return fail(RTK_ERR_INVALID, "rtk_render_aovs: n_samples must be positive (%d)", n_samples);
     if (!d_aov) return fail(RTK_ERR_INVALID, "rtk_render_aovs: null output buffer");
     if (check_aligned16(d_aov, "rtk_render_aovs", "d_aov") != RTK_OK) return RTK_ERR_INVALID;
@@ -350,37 +336,30 @@ int rtk_render_aovs(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* 
 int rtk_render_aovs_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, float* h_aov) {
     if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_aovs_host: null argument");
     if (!h_aov) return fail(RTK_ERR_INVALID, "rtk_render_aovs_host: null output buffer");
-    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->image_width > 65536 || cam->image_height > 65536)
-        return fail(RTK_ERR_INVALID, "rtk_render_aovs_host: bad camera dimensions");
+    if (check_camera_size("rtk_render_aovs_host", *cam) != RTK_OK) return RTK_ERR_INVALID;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
-    const size_t n = size_t(cam->image_width) * cam->image_height * 8;
-    float* d_aov = nullptr;
-    RTK_HIP(hipMalloc(reinterpret_cast<void**>(&d_aov), n * sizeof(float)));
-    int rc = rtk_render_aovs(ctx, cam, opts, n_samples, d_aov);
-    if (rc == RTK_OK) {
-        hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-        if (e == hipSuccess) e = hipMemcpy(h_aov, d_aov, n * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RTK_ERR_HIP, "rtk_render_aovs_host: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(d_aov);
-    return rc;
+    HostStaging s(false);
+    const int aov = s.piece(size_t(cam->image_width) * cam->image_height * 8 * sizeof(float));
+    RTK_HIP(s.alloc());
+    const int rc = rtk_render_aovs(ctx, cam, opts, n_samples, s.ptr<float>(aov));
+    if (rc != RTK_OK) return rc;
+    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
+    if (e == hipSuccess) e = s.download(aov, h_aov);
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_render_aovs_host: %s", hipGetErrorString(e));
+    return RTK_OK;
 }
 
 int rtk_denoise(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const void* d_linear, const float* d_aov, const float* d_noise,
                 const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8, void* stream) {
     if (!ctx) return fail(RTK_ERR_INVALID, "rtk_denoise: null context");
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise: bad image size %dx%d", width, height);
-    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise: unknown real_mode %d", real_mode);
+    if (check_image_size("rtk_denoise", width, height) != RTK_OK || check_real_mode("rtk_denoise", real_mode) != RTK_OK) return RTK_ERR_INVALID;
     if (!d_linear || !d_aov || !d_noise) return fail(RTK_ERR_INVALID, "rtk_denoise: d_linear, d_aov and d_noise are required");
     if (check_aligned16(d_aov, "rtk_denoise", "d_aov") != RTK_OK) return RTK_ERR_INVALID;
     if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise: no output");
     DenoiseParams P{};
     int iterations = 0;
     if (!resolve_opts(opts, iterations, P, "rtk_denoise")) return RTK_ERR_INVALID;
-    P.width = width;
-    P.height = height;
-    P.tiles_x = (width + 7) / 8;
-    P.n_tiles = P.tiles_x * ((height + 7) / 8);
+    P.grid = tile_grid(width, height);
     hipError_t e = hipSetDevice(ctx_device(ctx));
     void* ws = nullptr;
     const size_t plane = size_t(width) * height * sizeof(float4);
@@ -405,11 +384,9 @@ static int check_guide_args(const char* who, rtk_ctx* ctx, const rtk_camera* cam
     if (n_samples <= 0 || n_samples > (1 << 20)) return fail(RTK_ERR_INVALID, "%s: n_samples must be 1 .. 2^20 (%d)", who, n_samples);
     if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "%s: null argument", who);
     if (!out) return fail(RTK_ERR_INVALID, "%s: null output buffer", who);
-    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->image_width > 65536 || cam->image_height > 65536)
-        return fail(RTK_ERR_INVALID, "%s: bad camera dimensions", who);
+    if (check_camera_size(who, *cam) != RTK_OK) return RTK_ERR_INVALID;
     if (opts->n_ranks != 1) return fail(RTK_ERR_INVALID, "%s: whole images only (n_ranks must be 1, not %d)", who, opts->n_ranks);
-    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, opts->real_mode);
-    return RTK_OK;
+    return check_real_mode(who, opts->real_mode);
 }
 
 int rtk_render_guides(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* d_guides) {
@@ -435,17 +412,15 @@ int rtk_render_guides_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render
     uint64_t digest = 0;
     if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "rtk_render_guides_host: no scene uploaded");
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
-    const size_t n = size_t(cam->image_width) * cam->image_height * 16;
-    float* d_guides = nullptr;
-    RTK_HIP(hipMalloc(reinterpret_cast<void**>(&d_guides), n * sizeof(float)));
-    rc = rtk_render_guides(ctx, cam, opts, n_samples, gopts, d_guides);
-    if (rc == RTK_OK) {
-        hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-        if (e == hipSuccess) e = hipMemcpy(h_guides, d_guides, n * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RTK_ERR_HIP, "rtk_render_guides_host: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(d_guides);
-    return rc;
+    HostStaging s(false);
+    const int guides = s.piece(size_t(cam->image_width) * cam->image_height * 16 * sizeof(float));
+    RTK_HIP(s.alloc());
+    rc = rtk_render_guides(ctx, cam, opts, n_samples, gopts, s.ptr<float>(guides));
+    if (rc != RTK_OK) return rc;
+    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
+    if (e == hipSuccess) e = s.download(guides, h_guides);
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_render_guides_host: %s", hipGetErrorString(e));
+    return RTK_OK;
 }
 
 int rtk_denoise_guided(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const void* d_linear, const float* d_guides, const float* d_noise,
@@ -455,15 +430,11 @@ int rtk_denoise_guided(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real
     int iterations = 0;
     if (!resolve_opts(opts, iterations, P, "rtk_denoise_guided")) return RTK_ERR_INVALID;
     if (!ctx) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: null context");
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: bad image size %dx%d", width, height);
-    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: unknown real_mode %d", real_mode);
+    if (check_image_size("rtk_denoise_guided", width, height) != RTK_OK || check_real_mode("rtk_denoise_guided", real_mode) != RTK_OK) return RTK_ERR_INVALID;
     if (!d_linear || !d_guides || !d_noise) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: d_linear, d_guides and d_noise are required");
     if (check_aligned16(d_guides, "rtk_denoise_guided", "d_guides") != RTK_OK) return RTK_ERR_INVALID;
     if (!d_out_linear && !d_out_rgb8) return fail(RTK_ERR_INVALID, "rtk_denoise_guided: no output");
-    P.width = width;
-    P.height = height;
-    P.tiles_x = (width + 7) / 8;
-    P.n_tiles = P.tiles_x * ((height + 7) / 8);
+    P.grid = tile_grid(width, height);
     hipError_t e = hipSetDevice(ctx_device(ctx));
     void* ws = nullptr;
     const size_t plane = size_t(width) * height * sizeof(float4);
@@ -473,13 +444,9 @@ int rtk_denoise_guided(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real
         float4* pong = reinterpret_cast<float4*>(static_cast<char*>(ws) + plane);
         const auto* guides = reinterpret_cast<const float4*>(d_guides);
         const hipStream_t st = static_cast<hipStream_t>(stream);
-        const bool demod = (flags & RTK_DENOISE_DEMODULATE) != 0, f64 = real_mode == RTK_REAL_F64;
-        if (demod)
-            e = f64 ? launch_denoise_guided<double, true>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st)
-                    : launch_denoise_guided<float, true>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st);
-        else
-            e = f64 ? launch_denoise_guided<double, false>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st)
-                    : launch_denoise_guided<float, false>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st);
+        e = with_real_demod(real_mode == RTK_REAL_F64, (flags & RTK_DENOISE_DEMODULATE) != 0, [&](auto real, auto demod) {
+            return launch_denoise_guided<decltype(real), decltype(demod)::value>(P, iterations, d_linear, d_noise, guides, ping, pong, d_out_linear, d_out_rgb8, st);
+        });
     }
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_denoise_guided: %s", hipGetErrorString(e));
     return RTK_OK;
@@ -490,8 +457,7 @@ int rtk_denoise_guided(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real
 static int denoise_host(const char* who, int guide_floats, int32_t flags, rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, const double* h_linear,
                         const float* h_aov, const float* h_noise, const rtk_denoise_opts* opts, double* h_out_linear, uint8_t* h_out_rgb8) {
     if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "%s: bad image size %dx%d", who, width, height);
-    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, real_mode);
+    if (check_image_size(who, width, height) != RTK_OK || check_real_mode(who, real_mode) != RTK_OK) return RTK_ERR_INVALID;
     if (!h_linear || !h_aov || !h_noise) return fail(RTK_ERR_INVALID, "%s: h_linear, %s and h_noise are required", who, guide_floats == 8 ? "h_aov" : "h_guides");
     if (!h_out_linear && !h_out_rgb8) return fail(RTK_ERR_INVALID, "%s: no output", who);
     {
@@ -501,52 +467,23 @@ static int denoise_host(const char* who, int guide_floats, int32_t flags, rtk_ct
     }
     hipError_t e = hipSetDevice(ctx_device(ctx));
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    const size_t px = size_t(width) * height, elem = real_mode == RTK_REAL_F64 ? 8 : 4;
-    void *d_lin = nullptr, *d_out = nullptr;
-    float *d_aov = nullptr, *d_noise = nullptr;
-    uint8_t* d_rgb8 = nullptr;
-    auto cleanup = [&]() {
-        for (void* d : {d_lin, d_out, static_cast<void*>(d_aov), static_cast<void*>(d_noise), static_cast<void*>(d_rgb8)})
-            if (d) (void)hipFree(d);
-    };
-    std::vector<float> tmp;
-    e = hipMalloc(&d_lin, px * 3 * elem);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_aov), px * guide_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_noise), px * sizeof(float));
-    if (e == hipSuccess && h_out_linear) e = hipMalloc(&d_out, px * 3 * elem);
-    if (e == hipSuccess && h_out_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), px * 3);
-    if (e == hipSuccess) {
-        if (real_mode == RTK_REAL_F64) {
-            e = hipMemcpy(d_lin, h_linear, px * 3 * sizeof(double), hipMemcpyHostToDevice);
-        } else {
-            tmp.resize(px * 3);
-            for (size_t k = 0; k < px * 3; k++) tmp[k] = float(h_linear[k]);
-            e = hipMemcpy(d_lin, tmp.data(), px * 3 * sizeof(float), hipMemcpyHostToDevice);
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpy(d_aov, h_aov, px * guide_floats * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_noise, h_noise, px * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        cleanup();
-        return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    }
-    int rc = guide_floats == 8 ? rtk_denoise(ctx, width, height, real_mode, d_lin, d_aov, d_noise, opts, d_out, d_rgb8, nullptr)
-                               : rtk_denoise_guided(ctx, width, height, real_mode, d_lin, d_aov, d_noise, opts, flags, d_out, d_rgb8, nullptr);
-    if (rc != RTK_OK) {
-        cleanup();
-        return rc;
-    }
+    const size_t px = size_t(width) * height;
+    HostStaging s(real_mode == RTK_REAL_F64);
+    const int lin = s.linear(px * 3), aov = s.piece(px * guide_floats * sizeof(float)), noise = s.piece(px * sizeof(float));
+    const int out = s.linear(px * 3, h_out_linear != nullptr), rgb8 = s.piece(px * 3, h_out_rgb8 != nullptr);
+    e = s.alloc();
+    if (e == hipSuccess) e = s.upload_linear(lin, h_linear);
+    if (e == hipSuccess) e = s.upload(aov, h_aov);
+    if (e == hipSuccess) e = s.upload(noise, h_noise);
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
+    const int rc = guide_floats == 8
+                       ? rtk_denoise(ctx, width, height, real_mode, s.ptr(lin), s.ptr<float>(aov), s.ptr<float>(noise), opts, s.ptr(out), s.ptr<uint8_t>(rgb8), nullptr)
+                       : rtk_denoise_guided(ctx, width, height, real_mode, s.ptr(lin), s.ptr<float>(aov), s.ptr<float>(noise), opts, flags, s.ptr(out),
+                                            s.ptr<uint8_t>(rgb8), nullptr);
+    if (rc != RTK_OK) return rc;
     e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess && h_out_linear) {
-        if (real_mode == RTK_REAL_F64) {
-            e = hipMemcpy(h_out_linear, d_out, px * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        } else {
-            e = hipMemcpy(tmp.data(), d_out, px * 3 * sizeof(float), hipMemcpyDeviceToHost);
-            for (size_t k = 0; k < px * 3; k++) h_out_linear[k] = double(tmp[k]);
-        }
-    }
-    if (e == hipSuccess && h_out_rgb8) e = hipMemcpy(h_out_rgb8, d_rgb8, px * 3, hipMemcpyDeviceToHost);
-    cleanup();
+    if (e == hipSuccess) e = s.download_linear(out, h_out_linear);
+    if (e == hipSuccess) e = s.download(rgb8, h_out_rgb8);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
 }

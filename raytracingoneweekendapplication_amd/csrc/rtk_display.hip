@@ -22,10 +22,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <vector>
 
 #include "rtk.h"
-#include "rtk_device_math.h"
+#include "rtk_image_pass.h"
 #include "rtk_internal.h"
 
 namespace rtk {
@@ -198,7 +197,7 @@ __global__ void rtk_display_set_exposure_kernel(double e, double* state) {
 }
 
 // -------------------------------------------------------------------------------------------------------------- bloom --
-RTK_DEV int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+RTK_DEV int clampi(int v, int hi) { return rtk::clampi(v, 0, hi); }
 
 // ((a + b) + (c + d)) / 4 per channel; a, b the upper row.
 RTK_DEV float4 mean4(float4 a, float4 b, float4 c, float4 d) {
@@ -426,8 +425,6 @@ int resolve_display_opts(const rtk_display_opts* in, DisplayOpts& D, const char*
     return RTK_OK;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 }  // namespace rtk
 
@@ -489,9 +486,9 @@ extern "C" {
 
 int rtk_display_create(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, void* stream, rtk_display** out) {
     if (!ctx || !out) return fail(RTK_ERR_INVALID, "rtk_display_create: null argument");
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_display_create: bad image size %dx%d", width, height);
+    if (check_image_size("rtk_display_create", width, height) != RTK_OK) return RTK_ERR_INVALID;
     if (size_t(width) * height > (size_t(1) << 31) - 4) return fail(RTK_ERR_INVALID, "rtk_display_create: image %dx%d has more than 2^31 pixels", width, height);
-    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_display_create: unknown real_mode %d", real_mode);
+    if (check_real_mode("rtk_display_create", real_mode) != RTK_OK) return RTK_ERR_INVALID;
     hipError_t e = hipSetDevice(ctx_device(ctx));
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_display_create: %s", hipGetErrorString(e));
     const size_t bytes = 2 * sizeof(double) + 2 * kBins * sizeof(unsigned int);
@@ -584,40 +581,17 @@ int rtk_display_apply_host(rtk_display* d, const double* h_linear, const rtk_dis
     if (!h_out_linear && !h_out_rgb8) return fail(RTK_ERR_INVALID, "%s: no output", who);
     hipError_t e = hipSetDevice(d->device);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    const bool f64 = d->real_mode == RTK_REAL_F64;
-    const size_t px = size_t(d->width) * d->height, elem = f64 ? 8 : 4;
-    const size_t off_rgb8 = (px * 3 * elem + 15) / 16 * 16, total = off_rgb8 + px * 3;   // linear (in, then out in place), bytes
-    char* dev = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&dev), total);
+    const size_t px = size_t(d->width) * d->height;
+    HostStaging s(d->real_mode == RTK_REAL_F64);
+    const int lin = s.linear(px * 3), rgb8 = s.piece(px * 3, h_out_rgb8 != nullptr);   // linear is in, then out in place
+    e = s.alloc();
+    if (e == hipSuccess) e = s.upload_linear(lin, h_linear);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    std::vector<float> tmp;
-    if (f64) {
-        e = hipMemcpy(dev, h_linear, px * 3 * sizeof(double), hipMemcpyHostToDevice);
-    } else {
-        tmp.resize(px * 3);
-        for (size_t k = 0; k < px * 3; k++) tmp[k] = float(h_linear[k]);
-        e = hipMemcpy(dev, tmp.data(), px * 3 * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        (void)hipFree(dev);
-        return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    }
-    const int rc = rtk_display_apply(d, dev, opts, h_out_linear ? dev : nullptr, h_out_rgb8 ? reinterpret_cast<uint8_t*>(dev + off_rgb8) : nullptr);
-    if (rc != RTK_OK) {
-        (void)hipFree(dev);
-        return rc;
-    }
+    const int rc = rtk_display_apply(d, s.ptr(lin), opts, h_out_linear ? s.ptr(lin) : nullptr, s.ptr<uint8_t>(rgb8));
+    if (rc != RTK_OK) return rc;
     e = hipStreamSynchronize(d->stream);
-    if (e == hipSuccess && h_out_linear) {
-        if (f64) {
-            e = hipMemcpy(h_out_linear, dev, px * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        } else {
-            e = hipMemcpy(tmp.data(), dev, px * 3 * sizeof(float), hipMemcpyDeviceToHost);
-            for (size_t k = 0; k < px * 3; k++) h_out_linear[k] = double(tmp[k]);
-        }
-    }
-    if (e == hipSuccess && h_out_rgb8) e = hipMemcpy(h_out_rgb8, dev + off_rgb8, px * 3, hipMemcpyDeviceToHost);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = s.download_linear(lin, h_out_linear);
+    if (e == hipSuccess) e = s.download(rgb8, h_out_rgb8);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
 }

@@ -7,11 +7,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rtk_image_pass.h"
+
 namespace rtk {
 
 #define RTK_GW static __device__ __forceinline__
-
-RTK_GW int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Depth gradient of guide float4 `slot` (1 = first hit, 3 = end hit): half the larger central difference, edges clamped.
 RTK_GW float guide_depth_gradient(const float4* __restrict__ g, int slot, int i, int j, int W, int H) {
@@ -19,8 +19,6 @@ RTK_GW float guide_depth_gradient(const float4* __restrict__ g, int slot, int i,
     const float zy = fabsf(g[(size_t(clampi(j + 1, 0, H - 1)) * W + i) * 4 + slot].w - g[(size_t(clampi(j - 1, 0, H - 1)) * W + i) * 4 + slot].w);
     return (zx > zy ? zx : zy) / 2.0f;
 }
-
-RTK_GW bool zero3(float4 v) { return v.x == 0.0f && v.y == 0.0f && v.z == 0.0f; }
 
 RTK_GW float normal_weight(float4 gp, bool np_zero, float np_len, float4 gq, float sigma_n) {
     const bool nq_zero = zero3(gq);
@@ -37,13 +35,6 @@ RTK_GW float depth_weight(float hit_p, float hit_q, float zp, float zq, float gr
 // The albedo a demodulating pass divides by and multiplies back: max(seen albedo, 0.02) per channel.
 RTK_GW float4 demodulation_albedo(float4 seen) {
     return make_float4(seen.x > 0.02f ? seen.x : 0.02f, seen.y > 0.02f ? seen.y : 0.02f, seen.z > 0.02f ? seen.z : 0.02f, 0.0f);
-}
-
-// The resolve's byte conversion (rtk_device_math.h, to_byte; Camera.txt:29-34,77-83), in double.
-RTK_GW uint8_t guide_byte(double x) {
-    double g = x > 0 ? __builtin_sqrt(x) : 0.0;
-    g = g < 0.000 ? 0.000 : (g > 0.999 ? 0.999 : g);
-    return uint8_t(int(255.999 * g));
 }
 
 #undef RTK_GW

@@ -6,6 +6,7 @@
 
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "rtk_device_layout.h"
 
@@ -37,9 +38,74 @@ struct Fnv64 {
 };
 
 // include/rtk.h: guide and AOV buffers are accessed 16 bytes at a time.  RTK_OK, or RTK_ERR_INVALID with `arg` named in g_error.
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int check_aligned16(const void* p, const char* who, const char* arg) {
-    return (reinterpret_cast<uintptr_t>(p) & 15) == 0 ? RTK_OK : fail(RTK_ERR_INVALID, "%s: %s must be 16-byte aligned", who, arg);
+    return aligned16(p) ? RTK_OK : fail(RTK_ERR_INVALID, "%s: %s must be 16-byte aligned", who, arg);
 }
+
+// The checks every image entry point makes of its size and arithmetic type: RTK_OK, or RTK_ERR_INVALID with the text in g_error.
+// The passes that take a camera say "bad camera dimensions", the ones that take a width and a height name the size.
+inline bool image_size_ok(int w, int h) { return w > 0 && h > 0 && w <= 65536 && h <= 65536; }
+inline int check_image_size(const char* who, int w, int h) {
+    return image_size_ok(w, h) ? RTK_OK : fail(RTK_ERR_INVALID, "%s: bad image size %dx%d", who, w, h);
+}
+inline int check_camera_size(const char* who, const rtk_camera& cam) {
+    return image_size_ok(cam.image_width, cam.image_height) ? RTK_OK : fail(RTK_ERR_INVALID, "%s: bad camera dimensions", who);
+}
+inline int check_real_mode(const char* who, int mode) {
+    return mode == RTK_REAL_F64 || mode == RTK_REAL_F32 ? RTK_OK : fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, mode);
+}
+
+// The device side of a *_host entry point: one allocation cut into pieces, each on a 16-byte boundary (guides, AOVs and every
+// 16-byte access need it), freed when the object goes out of scope.  Plan the pieces, alloc(), upload, call the asynchronous
+// entry point with ptr() of each piece, synchronise its stream, download.  A piece planned with wanted = false (an optional
+// output the caller passed as null) takes no memory and has a null ptr(); a download into a null host pointer does nothing.
+// "Linear" pieces hold `real`s (double or float, by f64) that the host sees as doubles.
+class HostStaging {
+public:
+    explicit HostStaging(bool f64) : f64_(f64) {}
+    HostStaging(const HostStaging&) = delete;
+    HostStaging& operator=(const HostStaging&) = delete;
+    ~HostStaging() { (void)hipFree(base_); }
+
+    int piece(size_t bytes, bool wanted = true) {  // the piece's index
+        pieces_.push_back(Piece{wanted ? total_ : kAbsent, bytes});
+        if (wanted) total_ = (total_ + bytes + 15) / 16 * 16;
+        return int(pieces_.size()) - 1;
+    }
+    int linear(size_t n_reals, bool wanted = true) { return piece(n_reals * (f64_ ? sizeof(double) : sizeof(float)), wanted); }
+    hipError_t alloc() { return total_ ? hipMalloc(reinterpret_cast<void**>(&base_), total_) : hipSuccess; }
+
+    template <typename T = void>
+    T* ptr(int k) const { return pieces_[k].offset == kAbsent ? nullptr : reinterpret_cast<T*>(base_ + pieces_[k].offset); }
+
+    hipError_t upload(int k, const void* h) { return hipMemcpy(ptr(k), h, pieces_[k].bytes, hipMemcpyHostToDevice); }
+    hipError_t download(int k, void* h) { return h ? hipMemcpy(h, ptr(k), pieces_[k].bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+    hipError_t upload_linear(int k, const double* h) {  // in F32 mode each double is rounded to float here, on the host
+        if (f64_) return upload(k, h);
+        tmp_.resize(pieces_[k].bytes / sizeof(float));
+        for (size_t n = 0; n < tmp_.size(); n++) tmp_[n] = float(h[n]);
+        return upload(k, tmp_.data());
+    }
+    hipError_t download_linear(int k, double* h) {
+        if (f64_ || !h) return download(k, h);
+        tmp_.resize(pieces_[k].bytes / sizeof(float));
+        const hipError_t e = download(k, tmp_.data());
+        for (size_t n = 0; n < tmp_.size(); n++) h[n] = double(tmp_[n]);
+        return e;
+    }
+
+private:
+    static constexpr size_t kAbsent = ~size_t(0);
+    struct Piece {
+        size_t offset, bytes;
+    };
+    bool f64_;
+    char* base_ = nullptr;
+    size_t total_ = 0;
+    std::vector<Piece> pieces_;
+    std::vector<float> tmp_;   // the float image between the host's doubles and an F32 piece
+};
 
 int ctx_device(const rtk_ctx* ctx);
 // Progressive sessions (rtk_progressive.cpp) -- what they use of a context and of the one-shot frame's rules:

@@ -131,7 +131,7 @@ int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opt
     if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
         return fail(RTK_ERR_INVALID, "%s: bad camera dimensions (samples_per_pixel must be 1..32767)", who);
     if (opts->n_ranks < 1 || opts->rank < 0 || opts->rank >= opts->n_ranks) return fail(RTK_ERR_INVALID, "%s: bad rank %d of %d", who, opts->rank, opts->n_ranks);
-    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, opts->real_mode);
+    if (check_real_mode(who, opts->real_mode) != RTK_OK) return RTK_ERR_INVALID;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     auto* p = new rtk_progressive;
     p->ctx = ctx;
@@ -294,7 +294,7 @@ int parse_checkpoint(const void* h_buf, int64_t n, rtk_checkpoint_info* out, rtk
         return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: checkpoint version %d, this library reads versions %d and %d", info.version,
                     RTK_CHECKPOINT_VERSION, kCheckpointAdaptive);
     const bool adaptive = info.version == kCheckpointAdaptive;
-    if (info.width <= 0 || info.height <= 0 || info.width > 65536 || info.height > 65536 || info.n_ranks < 1 || info.n_ranks > 65536 || info.rank < 0 ||
+    if (!image_size_ok(info.width, info.height) || info.n_ranks < 1 || info.n_ranks > 65536 || info.rank < 0 ||
         info.rank >= info.n_ranks || (info.real_mode != RTK_REAL_F64 && info.real_mode != RTK_REAL_F32) || info.target_spp < 1 || info.target_spp > 32767 ||
         info.chunk_size != frame_chunk_size(info.target_spp) || info.samples_done < 0 || info.samples_done > info.target_spp)
         return fail(RTK_ERR_INVALID, "rtk_checkpoint_read_info: inconsistent header fields");
@@ -373,45 +373,19 @@ int rtk_progressive_step_host(rtk_progressive* p, int32_t n_samples, double* h_l
     RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
     const bool compact = p->n_ranks > 1;
     const size_t pixels = compact ? p->n_slots() : size_t(p->cam.image_width) * p->cam.image_height;
-    const size_t n_lin = pixels * 3;
-    void* d_linear = nullptr;
-    uint8_t* d_rgb8 = nullptr;
-    float* d_noise = nullptr;
-    rtk_work_counters* d_cnt = nullptr;
-    auto cleanup = [&]() {
-        for (void* d : {d_linear, static_cast<void*>(d_rgb8), static_cast<void*>(d_noise), static_cast<void*>(d_cnt)})
-            if (d) (void)hipFree(d);
-    };
-    hipError_t e = hipSuccess;
-    if (h_linear) e = hipMalloc(&d_linear, n_lin * p->elem);
-    if (e == hipSuccess && h_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), n_lin);
-    if (e == hipSuccess && h_noise) e = hipMalloc(reinterpret_cast<void**>(&d_noise), pixels * sizeof(float));
-    if (e == hipSuccess && counters) e = hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(rtk_work_counters));
-    if (e == hipSuccess && counters) e = hipMemsetAsync(d_cnt, 0, sizeof(rtk_work_counters), p->stream);
-    if (e != hipSuccess) {
-        cleanup();
-        return fail(RTK_ERR_HIP, "rtk_progressive_step_host: device buffers: %s", hipGetErrorString(e));
-    }
-    rc = rtk_progressive_step(p, n_samples, d_linear, d_rgb8, d_noise, d_cnt);
-    if (rc != RTK_OK) {
-        const std::string msg = g_error;
-        cleanup();
-        return fail(rc, "%s", msg.c_str());
-    }
+    HostStaging s(p->real_mode == RTK_REAL_F64);
+    const int lin = s.linear(pixels * 3, h_linear != nullptr), rgb8 = s.piece(pixels * 3, h_rgb8 != nullptr);
+    const int noise = s.piece(pixels * sizeof(float), h_noise != nullptr), cnt = s.piece(sizeof(rtk_work_counters), counters != nullptr);
+    hipError_t e = s.alloc();
+    if (e == hipSuccess && counters) e = hipMemsetAsync(s.ptr(cnt), 0, sizeof(rtk_work_counters), p->stream);
+    if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_progressive_step_host: device buffers: %s", hipGetErrorString(e));
+    rc = rtk_progressive_step(p, n_samples, s.ptr(lin), s.ptr<uint8_t>(rgb8), s.ptr<float>(noise), s.ptr<rtk_work_counters>(cnt));
+    if (rc != RTK_OK) return rc;
     e = hipStreamSynchronize(p->stream);
-    if (e == hipSuccess && h_linear) {
-        if (p->real_mode == RTK_REAL_F64) {
-            e = hipMemcpy(h_linear, d_linear, n_lin * sizeof(double), hipMemcpyDeviceToHost);
-        } else {
-            std::vector<float> tmp(n_lin);
-            e = hipMemcpy(tmp.data(), d_linear, n_lin * sizeof(float), hipMemcpyDeviceToHost);
-            for (size_t k = 0; k < n_lin; k++) h_linear[k] = double(tmp[k]);
-        }
-    }
-    if (e == hipSuccess && h_rgb8) e = hipMemcpy(h_rgb8, d_rgb8, n_lin, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_noise) e = hipMemcpy(h_noise, d_noise, pixels * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && counters) e = hipMemcpy(counters, d_cnt, sizeof(rtk_work_counters), hipMemcpyDeviceToHost);
-    cleanup();
+    if (e == hipSuccess) e = s.download_linear(lin, h_linear);
+    if (e == hipSuccess) e = s.download(rgb8, h_rgb8);
+    if (e == hipSuccess) e = s.download(noise, h_noise);
+    if (e == hipSuccess) e = s.download(cnt, counters);
     if (e != hipSuccess) {
         p->poisoned = true;
         return fail(RTK_ERR_HIP, "rtk_progressive_step_host: %s (the session is poisoned)", hipGetErrorString(e));
@@ -686,30 +660,17 @@ static int progressive_denoise_host(const char* who, bool guided, rtk_progressiv
     if (!h_linear && !h_rgb8) return fail(RTK_ERR_INVALID, "%s: no output", who);
     RTK_HIP(hipSetDevice(ctx_device(p->ctx)));
     const size_t n = size_t(p->cam.image_width) * p->cam.image_height * 3;
-    void* d_linear = nullptr;
-    uint8_t* d_rgb8 = nullptr;
-    hipError_t e = hipSuccess;
-    if (h_linear) e = hipMalloc(&d_linear, n * p->elem);
-    if (e == hipSuccess && h_rgb8) e = hipMalloc(reinterpret_cast<void**>(&d_rgb8), n);
+    HostStaging s(p->real_mode == RTK_REAL_F64);
+    const int lin = s.linear(n, h_linear != nullptr), rgb8 = s.piece(n, h_rgb8 != nullptr);
+    hipError_t e = s.alloc();
     if (e == hipSuccess) {
-        rc = guided ? rtk_progressive_denoise_guided(p, aov_samples, gopts, opts, flags, d_linear, d_rgb8) : rtk_progressive_denoise(p, aov_samples, opts, d_linear, d_rgb8);
-        if (rc == RTK_OK) {
-            e = hipStreamSynchronize(p->stream);
-            if (e == hipSuccess && h_linear) {
-                if (p->real_mode == RTK_REAL_F64) {
-                    e = hipMemcpy(h_linear, d_linear, n * sizeof(double), hipMemcpyDeviceToHost);
-                } else {
-                    std::vector<float> tmp(n);
-                    e = hipMemcpy(tmp.data(), d_linear, n * sizeof(float), hipMemcpyDeviceToHost);
-                    for (size_t k = 0; k < n; k++) h_linear[k] = double(tmp[k]);
-                }
-            }
-            if (e == hipSuccess && h_rgb8) e = hipMemcpy(h_rgb8, d_rgb8, n, hipMemcpyDeviceToHost);
-        }
+        rc = guided ? rtk_progressive_denoise_guided(p, aov_samples, gopts, opts, flags, s.ptr(lin), s.ptr<uint8_t>(rgb8))
+                    : rtk_progressive_denoise(p, aov_samples, opts, s.ptr(lin), s.ptr<uint8_t>(rgb8));
+        if (rc != RTK_OK) return rc;
+        e = hipStreamSynchronize(p->stream);
     }
-    if (d_linear) (void)hipFree(d_linear);
-    if (d_rgb8) (void)hipFree(d_rgb8);
-    if (rc != RTK_OK) return rc;
+    if (e == hipSuccess) e = s.download_linear(lin, h_linear);
+    if (e == hipSuccess) e = s.download(rgb8, h_rgb8);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
 }

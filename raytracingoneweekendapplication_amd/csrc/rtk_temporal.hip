@@ -14,25 +14,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <vector>
 
 #include "rtk.h"
+#include "rtk_image_pass.h"
 #include "rtk_internal.h"
 
 namespace rtk {
 namespace {
 
-#define RTK_TP __device__ __forceinline__
-
-// The resolve's byte conversion (rtk_device_math.h, to_byte; Camera.txt:29-34,77-83), in double.
-RTK_TP uint8_t temporal_byte(double x) {
-    double g = x > 0 ? __builtin_sqrt(x) : 0.0;
-    g = g < 0.000 ? 0.000 : (g > 0.999 ? 0.999 : g);
-    return uint8_t(int(255.999 * g));
-}
-
 struct TemporalParams {
-    int width, height, tiles_x, n_tiles;
+    TileGrid grid;
     int have_prev;             // 0: every pixel starts a history
     int check_albedo;
     float max_history, depth_tol, normal_cos, albedo_tol;
@@ -47,18 +38,13 @@ struct History {
     float* n;
 };
 
-RTK_TP bool zero3(float4 v) { return v.x == 0.0f && v.y == 0.0f && v.z == 0.0f; }
-
 template <typename real>
 __global__ __launch_bounds__(256) void rtk_temporal_kernel(TemporalParams P, const real* linear, const float4* __restrict__ guides, const float* noise,
                                                             History prev, History next, real* out_linear, float* out_noise, uint8_t* __restrict__ out_rgb8,
                                                             float* __restrict__ out_history) {  // (out_linear / out_noise may be linear / noise: no __restrict__)
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int tile = int(gid >> 6), pix = int(gid & 63);
-    if (tile >= P.n_tiles) return;
-    const int i = (tile % P.tiles_x) * 8 + (pix & 7), j = (tile / P.tiles_x) * 8 + (pix >> 3);
-    const int W = P.width, H = P.height;
-    if (i >= W || j >= H) return;
+    int i, j;
+    if (!lane_pixel(P.grid, i, j)) return;
+    const int W = P.grid.width, H = P.grid.height;
     const size_t px = size_t(j) * W + i;
     const float4 g0 = guides[px * 4], g1 = guides[px * 4 + 1], g2 = guides[px * 4 + 2];  // {albedo, hit}, {normal, depth}, {seen albedo, end hit}
     const float cr = float(linear[px * 3]), cg = float(linear[px * 3 + 1]), cb = float(linear[px * 3 + 2]);
@@ -141,9 +127,9 @@ __global__ __launch_bounds__(256) void rtk_temporal_kernel(TemporalParams P, con
     if (out_noise) out_noise[px] = sqrtf(var);
     if (out_history) out_history[px] = n;
     if (out_rgb8) {
-        out_rgb8[px * 3] = temporal_byte(double(r));
-        out_rgb8[px * 3 + 1] = temporal_byte(double(g));
-        out_rgb8[px * 3 + 2] = temporal_byte(double(b));
+        out_rgb8[px * 3] = to_byte(double(r));
+        out_rgb8[px * 3 + 1] = to_byte(double(g));
+        out_rgb8[px * 3 + 2] = to_byte(double(b));
     }
 }
 
@@ -210,8 +196,7 @@ int rtk_temporal_reproject_matrix(const rtk_camera* cam, double out[12]) {
 
 int rtk_temporal_create(rtk_ctx* ctx, int32_t width, int32_t height, int32_t real_mode, void* stream, rtk_temporal** out) {
     if (!ctx || !out) return fail(RTK_ERR_INVALID, "rtk_temporal_create: null argument");
-    if (width <= 0 || height <= 0 || width > 65536 || height > 65536) return fail(RTK_ERR_INVALID, "rtk_temporal_create: bad image size %dx%d", width, height);
-    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_temporal_create: unknown real_mode %d", real_mode);
+    if (check_image_size("rtk_temporal_create", width, height) != RTK_OK || check_real_mode("rtk_temporal_create", real_mode) != RTK_OK) return RTK_ERR_INVALID;
     hipError_t e = hipSetDevice(ctx_device(ctx));
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "rtk_temporal_create: %s", hipGetErrorString(e));
     const size_t px = size_t(width) * height, set_bytes = px * (3 * sizeof(float4) + sizeof(float));
@@ -250,10 +235,7 @@ int rtk_temporal_accumulate(rtk_temporal* t, const rtk_camera* cam, const void* 
         return fail(RTK_ERR_INVALID, "%s: the camera's image is %dx%d, the object's %dx%d", who, cam->image_width, cam->image_height, t->width, t->height);
     double now[12];
     if (rtk_temporal_reproject_matrix(cam, now) != RTK_OK) return RTK_ERR_INVALID;
-    P.width = t->width;
-    P.height = t->height;
-    P.tiles_x = (t->width + 7) / 8;
-    P.n_tiles = P.tiles_x * ((t->height + 7) / 8);
+    P.grid = tile_grid(t->width, t->height);
     P.have_prev = t->frames > 0;
     const rtk_vec3* v[4] = {&cam->center, &cam->pixel00_loc, &cam->pixel_delta_u, &cam->pixel_delta_v};
     double* dst[4] = {P.center, P.p00, P.du, P.dv};
@@ -267,7 +249,7 @@ int rtk_temporal_accumulate(rtk_temporal* t, const rtk_camera* cam, const void* 
     hipError_t e = hipSetDevice(t->device);
     if (e == hipSuccess) {
         const History prev = t->set[t->current], next = t->set[t->current ^ 1];
-        const dim3 grid((P.n_tiles + 3) / 4), block(256);
+        const dim3 grid((P.grid.n_tiles + 3) / 4), block(256);
         const auto* guides = reinterpret_cast<const float4*>(d_guides);
         if (t->real_mode == RTK_REAL_F64)
             rtk_temporal_kernel<double><<<grid, block, 0, t->stream>>>(P, static_cast<const double*>(d_linear), guides, d_noise, prev, next,
@@ -298,47 +280,24 @@ int rtk_temporal_accumulate_host(rtk_temporal* t, const rtk_camera* cam, const d
         return fail(RTK_ERR_INVALID, "%s: the camera's image is %dx%d, the object's %dx%d", who, cam->image_width, cam->image_height, t->width, t->height);
     hipError_t e = hipSetDevice(t->device);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    const bool f64 = t->real_mode == RTK_REAL_F64;
-    const size_t px = size_t(t->width) * t->height, elem = f64 ? 8 : 4;
-    // one allocation: linear (in, then out in place), guides (on the next 16-byte boundary), noise (in / out), history, bytes
-    const size_t off_guides = (px * 3 * elem + 15) / 16 * 16, off_noise = off_guides + px * 16 * sizeof(float), off_hist = off_noise + px * sizeof(float),
-                 off_rgb8 = off_hist + px * sizeof(float), total = off_rgb8 + px * 3;
-    char* d = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&d), total);
+    const size_t px = size_t(t->width) * t->height;
+    HostStaging s(t->real_mode == RTK_REAL_F64);
+    // linear and noise are in, then out in place
+    const int lin = s.linear(px * 3), guides = s.piece(px * 16 * sizeof(float)), noise = s.piece(px * sizeof(float));
+    const int hist = s.piece(px * sizeof(float), h_out_history != nullptr), rgb8 = s.piece(px * 3, h_out_rgb8 != nullptr);
+    e = s.alloc();
+    if (e == hipSuccess) e = s.upload_linear(lin, h_linear);
+    if (e == hipSuccess) e = s.upload(guides, h_guides);
+    if (e == hipSuccess) e = s.upload(noise, h_noise);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    std::vector<float> tmp;
-    if (f64) {
-        e = hipMemcpy(d, h_linear, px * 3 * sizeof(double), hipMemcpyHostToDevice);
-    } else {
-        tmp.resize(px * 3);
-        for (size_t k = 0; k < px * 3; k++) tmp[k] = float(h_linear[k]);
-        e = hipMemcpy(d, tmp.data(), px * 3 * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(d + off_guides, h_guides, px * 16 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + off_noise, h_noise, px * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    }
-    const int rc = rtk_temporal_accumulate(t, cam, d, reinterpret_cast<const float*>(d + off_guides), reinterpret_cast<const float*>(d + off_noise), opts, d,
-                                           reinterpret_cast<float*>(d + off_noise), reinterpret_cast<uint8_t*>(d + off_rgb8), reinterpret_cast<float*>(d + off_hist));
-    if (rc != RTK_OK) {
-        (void)hipFree(d);
-        return rc;
-    }
+    const int rc = rtk_temporal_accumulate(t, cam, s.ptr(lin), s.ptr<float>(guides), s.ptr<float>(noise), opts, h_out_linear ? s.ptr(lin) : nullptr,
+                                           h_out_noise ? s.ptr<float>(noise) : nullptr, s.ptr<uint8_t>(rgb8), s.ptr<float>(hist));
+    if (rc != RTK_OK) return rc;
     e = hipStreamSynchronize(t->stream);
-    if (e == hipSuccess && h_out_linear) {
-        if (f64) {
-            e = hipMemcpy(h_out_linear, d, px * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        } else {
-            e = hipMemcpy(tmp.data(), d, px * 3 * sizeof(float), hipMemcpyDeviceToHost);
-            for (size_t k = 0; k < px * 3; k++) h_out_linear[k] = double(tmp[k]);
-        }
-    }
-    if (e == hipSuccess && h_out_noise) e = hipMemcpy(h_out_noise, d + off_noise, px * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_out_history) e = hipMemcpy(h_out_history, d + off_hist, px * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_out_rgb8) e = hipMemcpy(h_out_rgb8, d + off_rgb8, px * 3, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = s.download_linear(lin, h_out_linear);
+    if (e == hipSuccess) e = s.download(noise, h_out_noise);
+    if (e == hipSuccess) e = s.download(hist, h_out_history);
+    if (e == hipSuccess) e = s.download(rgb8, h_out_rgb8);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
 }

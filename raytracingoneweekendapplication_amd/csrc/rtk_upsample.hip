@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <vector>
 
 #include "rtk.h"
 #include "rtk_guide_weights.h"
@@ -27,7 +26,7 @@ namespace rtk {
 namespace {
 
 struct UpsampleParams {
-    int width, height, tiles_x, n_tiles;   // the full image
+    TileGrid grid;   // the full image
     int low_width, low_height, factor;
     float sigma_n, sigma_z, sigma_a;
 };
@@ -43,12 +42,9 @@ __global__ __launch_bounds__(256) void rtk_upsample_kernel(UpsampleParams P, con
                                                             const float4* __restrict__ low_guides, const float4* __restrict__ guides,
                                                             real* __restrict__ out_linear, float* __restrict__ out_noise, uint8_t* __restrict__ out_rgb8,
                                                             float* __restrict__ out_support) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int tile = int(gid >> 6), pix = int(gid & 63);
-    if (tile >= P.n_tiles) return;
-    const int i = (tile % P.tiles_x) * 8 + (pix & 7), j = (tile / P.tiles_x) * 8 + (pix >> 3);
-    const int W = P.width, H = P.height, LW = P.low_width, LH = P.low_height, f = P.factor;
-    if (i >= W || j >= H) return;
+    int i, j;
+    if (!lane_pixel(P.grid, i, j)) return;
+    const int W = P.grid.width, H = P.grid.height, LW = P.low_width, LH = P.low_height, f = P.factor;
     const size_t px = size_t(j) * W + i;
     const float hit1_p = guides[px * 4].w;
     const float4 g1p = guides[px * 4 + 1], ap = guides[px * 4 + 2], g2p = guides[px * 4 + 3];  // {normal, depth}, {seen albedo, end hit}, {end normal, length}
@@ -119,9 +115,9 @@ __global__ __launch_bounds__(256) void rtk_upsample_kernel(UpsampleParams P, con
     if (out_noise) out_noise[px] = sqrtf(var_out);
     if (out_support) out_support[px] = s_acc / s_beta;
     if (out_rgb8) {
-        out_rgb8[px * 3] = guide_byte(double(r));
-        out_rgb8[px * 3 + 1] = guide_byte(double(g));
-        out_rgb8[px * 3 + 2] = guide_byte(double(b));
+        out_rgb8[px * 3] = to_byte(double(r));
+        out_rgb8[px * 3 + 1] = to_byte(double(g));
+        out_rgb8[px * 3 + 2] = to_byte(double(b));
     }
 }
 
@@ -151,22 +147,17 @@ int check_upsample_args(const char* who, const rtk_upsample_opts* opts, Upsample
     if (!full) return fail(RTK_ERR_INVALID, "%s: null camera", who);
     if (!inputs) return fail(RTK_ERR_INVALID, "%s: the low-resolution colour, noise and guides and the full-resolution guides are required", who);
     if (!outputs) return fail(RTK_ERR_INVALID, "%s: no output", who);
-    if (full->image_width <= 0 || full->image_height <= 0 || full->image_width > 65536 || full->image_height > 65536)
-        return fail(RTK_ERR_INVALID, "%s: bad image size %dx%d", who, full->image_width, full->image_height);
-    if (real_mode != RTK_REAL_F64 && real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, real_mode);
-    P.width = full->image_width;
-    P.height = full->image_height;
-    P.tiles_x = (P.width + 7) / 8;
-    P.n_tiles = P.tiles_x * ((P.height + 7) / 8);
-    P.low_width = (P.width + P.factor - 1) / P.factor;
-    P.low_height = (P.height + P.factor - 1) / P.factor;
+    if (check_image_size(who, full->image_width, full->image_height) != RTK_OK || check_real_mode(who, real_mode) != RTK_OK) return RTK_ERR_INVALID;
+    P.grid = tile_grid(full->image_width, full->image_height);
+    P.low_width = (P.grid.width + P.factor - 1) / P.factor;
+    P.low_height = (P.grid.height + P.factor - 1) / P.factor;
     return RTK_OK;
 }
 
 template <typename real, bool DEMOD>
 void launch_upsample(const UpsampleParams& P, const void* low_linear, const float* low_noise, const float* low_guides, const float* guides, void* out_linear,
                      float* out_noise, uint8_t* out_rgb8, float* out_support, hipStream_t stream) {
-    const dim3 grid((P.n_tiles + 3) / 4), block(256);
+    const dim3 grid((P.grid.n_tiles + 3) / 4), block(256);
     rtk_upsample_kernel<real, DEMOD><<<grid, block, 0, stream>>>(P, static_cast<const real*>(low_linear), low_noise, reinterpret_cast<const float4*>(low_guides),
                                                                  reinterpret_cast<const float4*>(guides), static_cast<real*>(out_linear), out_noise, out_rgb8,
                                                                  out_support);
@@ -208,10 +199,11 @@ int rtk_upsample(rtk_ctx* ctx, const rtk_camera* full, int32_t real_mode, const 
     hipError_t e = hipSetDevice(ctx_device(ctx));
     if (e == hipSuccess) {
         const hipStream_t st = static_cast<hipStream_t>(stream);
-        const bool f64 = real_mode == RTK_REAL_F64;
-        auto launch = demod ? (f64 ? launch_upsample<double, true> : launch_upsample<float, true>) : (f64 ? launch_upsample<double, false> : launch_upsample<float, false>);
-        launch(P, d_low_linear, d_low_noise, d_low_guides, d_guides, d_out_linear, d_out_noise, d_out_rgb8, d_out_support, st);
-        e = hipGetLastError();
+        e = with_real_demod(real_mode == RTK_REAL_F64, demod, [&](auto real, auto dm) {
+            launch_upsample<decltype(real), decltype(dm)::value>(P, d_low_linear, d_low_noise, d_low_guides, d_guides, d_out_linear, d_out_noise, d_out_rgb8,
+                                                                 d_out_support, st);
+            return hipGetLastError();
+        });
     }
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
@@ -227,49 +219,25 @@ int rtk_upsample_host(rtk_ctx* ctx, const rtk_camera* full, int32_t real_mode, c
     if (rc != RTK_OK) return rc;
     hipError_t e = hipSetDevice(ctx_device(ctx));
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    const bool f64 = real_mode == RTK_REAL_F64;
-    const size_t px = size_t(P.width) * P.height, lpx = size_t(P.low_width) * P.low_height, elem = f64 ? 8 : 4;
-    // one allocation, 16-byte pieces first: guides, low guides, out linear, low linear, low noise, out noise, support, bytes
-    const size_t off_lg = px * 16 * sizeof(float), off_out = off_lg + lpx * 16 * sizeof(float), off_low = off_out + px * 3 * elem, off_ln = off_low + lpx * 3 * elem,
-                 off_on = off_ln + lpx * sizeof(float), off_sup = off_on + px * sizeof(float), off_rgb8 = off_sup + px * sizeof(float), total = off_rgb8 + px * 3;
-    char* d = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&d), total);
+    const size_t px = size_t(P.grid.width) * P.grid.height, lpx = size_t(P.low_width) * P.low_height;
+    HostStaging s(real_mode == RTK_REAL_F64);
+    const int guides = s.piece(px * 16 * sizeof(float)), low_guides = s.piece(lpx * 16 * sizeof(float)), low = s.linear(lpx * 3), low_noise = s.piece(lpx * sizeof(float));
+    const int out = s.linear(px * 3, h_out_linear != nullptr), noise = s.piece(px * sizeof(float), h_out_noise != nullptr);
+    const int support = s.piece(px * sizeof(float), h_out_support != nullptr), rgb8 = s.piece(px * 3, h_out_rgb8 != nullptr);
+    e = s.alloc();
+    if (e == hipSuccess) e = s.upload_linear(low, h_low_linear);
+    if (e == hipSuccess) e = s.upload(guides, h_guides);
+    if (e == hipSuccess) e = s.upload(low_guides, h_low_guides);
+    if (e == hipSuccess) e = s.upload(low_noise, h_low_noise);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    std::vector<float> tmp;
-    if (f64) {
-        e = hipMemcpy(d + off_low, h_low_linear, lpx * 3 * sizeof(double), hipMemcpyHostToDevice);
-    } else {
-        tmp.resize(px * 3);
-        for (size_t k = 0; k < lpx * 3; k++) tmp[k] = float(h_low_linear[k]);
-        e = hipMemcpy(d + off_low, tmp.data(), lpx * 3 * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(d, h_guides, px * 16 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + off_lg, h_low_guides, lpx * 16 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + off_ln, h_low_noise, lpx * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    }
-    rc = rtk_upsample(ctx, full, real_mode, d + off_low, reinterpret_cast<const float*>(d + off_ln), reinterpret_cast<const float*>(d + off_lg),
-                      reinterpret_cast<const float*>(d), opts, h_out_linear ? d + off_out : nullptr, h_out_noise ? reinterpret_cast<float*>(d + off_on) : nullptr,
-                      h_out_rgb8 ? reinterpret_cast<uint8_t*>(d + off_rgb8) : nullptr, h_out_support ? reinterpret_cast<float*>(d + off_sup) : nullptr, nullptr);
-    if (rc != RTK_OK) {
-        (void)hipFree(d);
-        return rc;
-    }
+    rc = rtk_upsample(ctx, full, real_mode, s.ptr(low), s.ptr<float>(low_noise), s.ptr<float>(low_guides), s.ptr<float>(guides), opts, s.ptr(out), s.ptr<float>(noise),
+                      s.ptr<uint8_t>(rgb8), s.ptr<float>(support), nullptr);
+    if (rc != RTK_OK) return rc;
     e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess && h_out_linear) {
-        if (f64) {
-            e = hipMemcpy(h_out_linear, d + off_out, px * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        } else {
-            e = hipMemcpy(tmp.data(), d + off_out, px * 3 * sizeof(float), hipMemcpyDeviceToHost);
-            for (size_t k = 0; k < px * 3; k++) h_out_linear[k] = double(tmp[k]);
-        }
-    }
-    if (e == hipSuccess && h_out_noise) e = hipMemcpy(h_out_noise, d + off_on, px * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_out_support) e = hipMemcpy(h_out_support, d + off_sup, px * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_out_rgb8) e = hipMemcpy(h_out_rgb8, d + off_rgb8, px * 3, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = s.download_linear(out, h_out_linear);
+    if (e == hipSuccess) e = s.download(noise, h_out_noise);
+    if (e == hipSuccess) e = s.download(support, h_out_support);
+    if (e == hipSuccess) e = s.download(rgb8, h_out_rgb8);
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return RTK_OK;
 }

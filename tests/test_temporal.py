@@ -436,7 +436,7 @@ def test_device_equals_the_restatement_on_rich_frames(rt, renderer, path, size, 
 @pytest.mark.gpu
 @pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
 def test_first_frame_bytes_follow_the_reference_rule_and_linear_is_a_copy(rt, renderer, real_mode):
-    """A first frame returns out = c: chosen colours reach temporal_byte directly.  Every byte threshold with its neighbours one
+    """A first frame returns out = c: chosen colours reach to_byte directly.  Every byte threshold with its neighbours one
     and two float32 units in the last place away, the clamp's edge, zeros, negatives, infinities and NaN (tests/test_output_stage.py)
     must give that file's bytes, and the linear output the float input bit for bit."""
     from tests.test_output_stage import known_values, to_byte
