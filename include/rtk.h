@@ -358,7 +358,7 @@ int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks);
  * Streams (this holds for every entry point that is "asynchronous on" a stream:
  * rtk_render_device, rtk_tiles_unpermute, rtk_progressive_step, rtk_render_aovs,
  * rtk_denoise, rtk_progressive_denoise, rtk_render_guides, rtk_denoise_guided, rtk_progressive_denoise_guided,
- * rtk_temporal_accumulate):
+ * rtk_temporal_accumulate, rtk_query_hits / _occluded / _radiance):
  *   - all work of a call -- kernels, memsets, the upload of the camera record --
  *     is enqueued on the stream it is given and on no other; the call reads its
  *     host arguments (cam, opts) before it returns and never waits for the
@@ -790,7 +790,7 @@ int rtk_temporal_reproject_matrix(const rtk_camera* cam, double out[12]);
  *   3. Blend: omega = beta (w + 1e-3); Omega = sum omega; out = sum omega c_q / Omega; var_out = sum omega^2 se_q^2 / Omega^2;
  *      support = sum beta w / sum beta, the share of the bilinear weight the guides accepted.  The floor 1e-3 makes a pixel
  *      whose taps are all rejected fall back smoothly to the (edge-renormalised) bilinear interpolation; there is no threshold.
- *      A caller can re-render pixels with low support.
+ *      A caller can re-render pixels with low support (rtk_query_radiance with the frame's own streams: INTEGRATION 4g).
  *   4. RTK_UPSAMPLE_DEMODULATE: per tap A_q = max(G[8..10], 0.02) per channel, c_q <- c_q / A_q, se_q^2 <- se_q^2 /
  *      ((A_q.x + A_q.y + A_q.z) / 3)^2; after the blend out <- out * A_p, var_out <- var_out * mean(A_p)^2, A_p from g[8..10].
  *   5. d_out_linear = out, d_out_noise = sqrt(var_out), d_out_support = support, d_out_rgb8 = the resolve's gamma / clamp /
@@ -904,6 +904,70 @@ int rtk_display_histogram(rtk_display* d, uint32_t out[320]);
 int rtk_display_reset(rtk_display* d);
 int rtk_display_frames(const rtk_display* d);
 int rtk_display_destroy(rtk_display* d);
+
+/* Ray queries -------------------------------------------------------------------------
+ * Hits, occlusion and radiance for rays the CALLER chooses -- light probes, lightmaps, picking, line-of-sight tests, other
+ * projections, re-rendering chosen pixels: what the reference offers as world.hit(r, interval, rec) and ray_color (hittable.h:33,
+ * Camera.txt:203-238).  Device resident and asynchronous on opts->stream, on the uploaded scene in either visiting order and both
+ * real modes; one rank only (not through rtk_multi).  The kernels walk the slot program one lane per ray, with every record
+ * kind, through the device functions the render kernel runs.
+ *
+ * Streams of random numbers: a ray's stream is keyed (opts->seed, ray.pixel, ray.sample) -- state pcg_hash(pixel +
+ * pcg_hash(sample + pcg_hash(seed))), the keying of the rtk_debug_* entry points and of the render's samples -- and then
+ * advanced by ray.skip draws (a jump of at most 32 squarings of the generator's step: any skip costs the same).  skip lets a
+ * path continue where the caller's ray generation left the stream: for a camera ray, skip = rtk_debug_get_ray's h_draws, and
+ * the query continues the render's own stream of that pixel and sample.
+ *
+ * rtk_query_hits      hittable::hit(r, interval(ray.tmin, ray.tmax), rec) of the scene root; a constant medium draws from the
+ *                     ray's stream.  With skip = 0 it is rtk_debug_closest_hit, bit for bit.  prim_kind / prim_index name the
+ *                     primitive in the tables of the rtk_scene_desc that was uploaded (rtk_scene_optimize borrows them unchanged,
+ *                     so both visiting orders report the same; a primitive reached through several instances reports one index).
+ * rtk_query_occluded  d_occluded[k] = the hit flag rtk_query_hits returns for the same ray, keys and skip, exactly.  In a scene
+ *                     without a constant_medium the walk stops at the first accepted hit; with one it is the closest-hit walk.
+ * rtk_query_radiance  ray_color(r, opts->max_depth, world, lights) with opts->background: world.hit on interval(0.001, inf)
+ *                     and the shading of the render kernels, point lights included, until the path ends; ray.tmin / tmax are
+ *                     ignored, as ray_color ignores them.  Sample s = 0 .. samples-1 of ray k draws from the stream (seed,
+ *                     pixel, sample + s) advanced by skip; d_radiance[k] = the sum in sample order, divided once by the number
+ *                     of samples, [n][3] reals of real_mode.  d_draws (may be NULL) [n]: the uniforms the paths of ray k drew,
+ *                     skip not counted; giving it selects a counting build of the kernel.
+ * Buffers: every buffer needs the alignment of its element type -- 8 bytes for rtk_ray, rtk_ray_hit and F64 reals, 4 otherwise;
+ * a misaligned pointer is refused (the text names the argument) and nothing is launched.  Outputs may not alias d_rays: an
+ * output whose range overlaps the rays' is refused likewise.  rtk_ray.reserved is not read today; set it to 0.
+ * n == 0 is valid and launches nothing.  RTK_ERR_INVALID, checked first and without a device: a null context, opts, rays or
+ * output; n < 0 or n > 2^31 - 1; an unknown real_mode; negative max_depth or samples; reserved != 0.  RTK_ERR_NO_SCENE
+ * without an uploaded scene.  The stream rules of rtk_render_device hold: every launch goes to opts->stream, opts is read before
+ * the call returns, the call allocates nothing and never waits for the device.  The _host forms take host buffers (h_radiance
+ * doubles, F32 widened) and block. */
+typedef struct rtk_ray {                 /* 88 bytes, 8-byte aligned */
+    double origin[3], direction[3], time, tmin, tmax;
+    uint32_t pixel, sample;              /* stream keys: the ray's random stream is (opts.seed, pixel, sample) */
+    uint32_t skip;                       /* uniforms of that stream the caller has already consumed */
+    uint32_t reserved;                   /* 0 */
+} rtk_ray;
+
+typedef struct rtk_ray_hit {             /* 96 bytes */
+    double t, p[3], normal[3], u, v;     /* the hit record; F32 results widened; all 0 on a miss */
+    int32_t hit, front_face, material;   /* material -1 on a miss */
+    int32_t prim_kind, prim_index;       /* RTK_NODE_SPHERE / QUAD / TRIANGLE / MEDIUM and the index into spheres[] / quads[] /
+                                          * triangles[] / media[]; 0, -1 on a miss */
+    int32_t draws;                       /* random_double() calls inside hit() (skip not counted) */
+} rtk_ray_hit;
+
+typedef struct rtk_query_opts {          /* 56 bytes */
+    uint32_t seed; int32_t real_mode;
+    int32_t max_depth;                   /* radiance only; >= 0, as rtk_camera.max_depth (0 = black) */
+    int32_t samples;                     /* radiance only; 0 = 1 */
+    rtk_vec3 background;                 /* radiance only */
+    void* stream;
+    int32_t reserved[2];                 /* 0 */
+} rtk_query_opts;
+
+int rtk_query_hits(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* d_rays, rtk_ray_hit* d_hits);
+int rtk_query_occluded(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* d_rays, int32_t* d_occluded);
+int rtk_query_radiance(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* d_rays, void* d_radiance, uint32_t* d_draws);
+int rtk_query_hits_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, rtk_ray_hit* h_hits);
+int rtk_query_occluded_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, int32_t* h_occluded);
+int rtk_query_radiance_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, double* h_radiance, uint32_t* h_draws);
 
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and

@@ -257,6 +257,68 @@ def _display_opts(exposure: float = 0.0, key: float = 0.0, meter_low: float = 0.
                        float(white), int(encode), float(bloom), float(bloom_threshold), int(bloom_levels), 0)
 
 
+class Ray(C.Structure):
+    """rtk_ray (include/rtk.h): a caller's ray and the keys of its random stream."""
+
+    _fields_ = [("origin", C.c_double * 3), ("direction", C.c_double * 3), ("time", C.c_double), ("tmin", C.c_double), ("tmax", C.c_double),
+                ("pixel", C.c_uint32), ("sample", C.c_uint32), ("skip", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    """rtk_ray_hit (include/rtk.h): the hit record of rtk_query_hits."""
+
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("normal", C.c_double * 3), ("u", C.c_double), ("v", C.c_double),
+                ("hit", C.c_int32), ("front_face", C.c_int32), ("material", C.c_int32), ("prim_kind", C.c_int32), ("prim_index", C.c_int32),
+                ("draws", C.c_int32)]
+
+
+class QueryOpts(C.Structure):
+    """rtk_query_opts (include/rtk.h)."""
+
+    _fields_ = [("seed", C.c_uint32), ("real_mode", C.c_int32), ("max_depth", C.c_int32), ("samples", C.c_int32), ("background", Vec3),
+                ("stream", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+# numpy structured dtypes with the layout of Ray and RayHit (field lists; numpy is imported where they are used)
+RAY_FIELDS = [("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("time", "<f8"), ("tmin", "<f8"), ("tmax", "<f8"),
+              ("pixel", "<u4"), ("sample", "<u4"), ("skip", "<u4"), ("reserved", "<u4")]
+RAY_HIT_FIELDS = [("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
+                  ("hit", "<i4"), ("front_face", "<i4"), ("material", "<i4"), ("prim_kind", "<i4"), ("prim_index", "<i4"), ("draws", "<i4")]
+NODE_SPHERE, NODE_QUAD, NODE_TRIANGLE, NODE_MEDIUM = 1, 2, 3, 8   # rtk_node_kind values of rtk_ray_hit.prim_kind
+
+
+def ray_dtype():
+    import numpy as np
+
+    return np.dtype(RAY_FIELDS)
+
+
+def ray_hit_dtype():
+    import numpy as np
+
+    return np.dtype(RAY_HIT_FIELDS)
+
+
+def make_rays(origin, direction, *, time=0.0, tmin=0.001, tmax=float("inf"), pixel=0, sample=0, skip=0):
+    """Ray records (``ray_dtype``) from arrays that broadcast to n rays: origin and direction (3,) or (n, 3), the rest scalars
+    or (n,)."""
+    import numpy as np
+
+    origin, direction = np.atleast_2d(np.asarray(origin, np.float64)), np.atleast_2d(np.asarray(direction, np.float64))
+    n = max([origin.shape[0], direction.shape[0]] + [np.size(v) for v in (time, tmin, tmax, pixel, sample, skip)])
+    rays = np.zeros(n, ray_dtype())
+    rays["origin"], rays["direction"] = origin, direction
+    rays["time"], rays["tmin"], rays["tmax"] = time, tmin, tmax
+    rays["pixel"], rays["sample"], rays["skip"] = pixel, sample, skip
+    return rays
+
+
+def _query_opts(seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, max_depth: int = 0, samples: int = 0, background=(0.0, 0.0, 0.0),
+                stream: int = 0) -> QueryOpts:
+    bg = background if isinstance(background, Vec3) else Vec3(*(float(c) for c in background))
+    return QueryOpts(int(seed), int(real_mode), int(max_depth), int(samples), bg, stream or None, (C.c_int32 * 2)(0, 0))
+
+
 def host_lib() -> C.CDLL:
     """librtk_host.so: scene construction + flattening (no GPU needed)."""
     global _host_lib
@@ -400,6 +462,10 @@ def hip_lib() -> C.CDLL:
             lib.rtk_display_reset.argtypes = [C.c_void_p]
             lib.rtk_display_frames.argtypes = [C.c_void_p]
             lib.rtk_display_destroy.argtypes = [C.c_void_p]
+            query = [C.c_void_p, C.POINTER(QueryOpts), C.c_int64, C.c_void_p, C.c_void_p]
+            for name in ("rtk_query_hits", "rtk_query_occluded", "rtk_query_hits_host", "rtk_query_occluded_host"):
+                getattr(lib, name).argtypes = query
+            lib.rtk_query_radiance.argtypes = lib.rtk_query_radiance_host.argtypes = query + [C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -677,6 +743,73 @@ class Renderer:
         out, draws = np.zeros((n, 7), np.float64), np.zeros(n, np.uint64)
         self._check(self._lib.rtk_debug_get_ray(self._ctx, real_mode, C.byref(cam), seed, n, ijs.ctypes.data, out.ctypes.data, draws.ctypes.data))
         return out, draws
+
+    def _query_rays(self, who: str, rays):
+        import numpy as np
+
+        rays = np.ascontiguousarray(rays, ray_dtype())
+        if rays.ndim != 1:
+            raise ValueError(f"{who}: rays must be a one-dimensional array of ray records, not {rays.shape}")
+        return rays
+
+    def query_hits(self, rays, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_query_hits_host: hittable::hit(r, interval(tmin, tmax), rec) of the scene root for ray records (``ray_dtype``,
+        see ``make_rays`` / ``camera_rays``).  Returns hit records (``ray_hit_dtype``)."""
+        import numpy as np
+
+        rays = self._query_rays("query_hits", rays)
+        hits = np.zeros(rays.shape[0], ray_hit_dtype())
+        self._check(self._lib.rtk_query_hits_host(self._ctx, C.byref(_query_opts(seed, real_mode)), rays.shape[0], rays.ctypes.data, hits.ctypes.data))
+        return hits
+
+    def query_occluded(self, rays, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_query_occluded_host: int32 (n,), the ``hit`` flag ``query_hits`` returns for the same rays."""
+        import numpy as np
+
+        rays = self._query_rays("query_occluded", rays)
+        occluded = np.zeros(rays.shape[0], np.int32)
+        self._check(self._lib.rtk_query_occluded_host(self._ctx, C.byref(_query_opts(seed, real_mode)), rays.shape[0], rays.ctypes.data, occluded.ctypes.data))
+        return occluded
+
+    def query_radiance(self, rays, *, max_depth: int, background=(0.0, 0.0, 0.0), samples: int = 1, count: bool = False, seed: int = RENDER_SEED,
+                       real_mode: int = RTK_REAL_F64):
+        """rtk_query_radiance_host: ray_color of every ray, the mean over ``samples`` samples with stream keys (seed, pixel,
+        sample + s).  Returns float64 (n, 3) -- F32 results widened -- or, with ``count``, (radiance, draws uint32 (n,))."""
+        import numpy as np
+
+        rays = self._query_rays("query_radiance", rays)
+        out = np.zeros((rays.shape[0], 3), np.float64)
+        draws = np.zeros(rays.shape[0], np.uint32) if count else None
+        opts = _query_opts(seed, real_mode, max_depth, samples, background)
+        self._check(self._lib.rtk_query_radiance_host(self._ctx, C.byref(opts), rays.shape[0], rays.ctypes.data, out.ctypes.data,
+                                                      draws.ctypes.data if count else None))
+        return (out, draws) if count else out
+
+    def query_hits_device(self, n: int, d_rays: int, d_hits: int, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_query_hits with raw device pointers (n rtk_ray records in, n rtk_ray_hit records out); asynchronous on ``stream``."""
+        self._check(self._lib.rtk_query_hits(self._ctx, C.byref(_query_opts(seed, real_mode, stream=stream)), int(n), d_rays or None, d_hits or None))
+
+    def query_occluded_device(self, n: int, d_rays: int, d_occluded: int, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_query_occluded with raw device pointers (int32 [n] out); asynchronous on ``stream``."""
+        self._check(self._lib.rtk_query_occluded(self._ctx, C.byref(_query_opts(seed, real_mode, stream=stream)), int(n), d_rays or None, d_occluded or None))
+
+    def query_radiance_device(self, n: int, d_rays: int, d_radiance: int, d_draws: int = 0, *, max_depth: int, background=(0.0, 0.0, 0.0), samples: int = 1,
+                              seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_query_radiance with raw device pointers ([n][3] reals of ``real_mode`` out, uint32 [n] draws when ``d_draws`` is
+        given); asynchronous on ``stream``."""
+        opts = _query_opts(seed, real_mode, max_depth, samples, background, stream)
+        self._check(self._lib.rtk_query_radiance(self._ctx, C.byref(opts), int(n), d_rays or None, d_radiance or None, d_draws or None))
+
+    def camera_rays(self, cam: Camera, seed: int, pixel_sample, real_mode: int = RTK_REAL_F64):
+        """The render's own rays as ray records: ``debug_get_ray`` of ``pixel_sample`` [n][3] = i, j, sample, with the stream
+        keys of that pixel and sample (pixel = j * W + i) and skip = the draws get_ray consumed, so that a query continues the
+        stream where the render's ray generation left it.  tmin / tmax are ray_color's interval(0.001, inf)."""
+        import numpy as np
+
+        ijs = np.ascontiguousarray(pixel_sample, np.int32).reshape(-1, 3)
+        ray, draws = self.debug_get_ray(cam, seed, ijs, real_mode)
+        return make_rays(ray[:, 0:3], ray[:, 3:6], time=ray[:, 6], pixel=(ijs[:, 1] * cam.image_width + ijs[:, 0]).astype(np.uint32),
+                         sample=ijs[:, 2].astype(np.uint32), skip=draws.astype(np.uint32))
 
     def aovs(self, cam: Camera, samples: int = 4, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
         """rtk_render_aovs_host: the denoiser's first-hit guide buffers, float32 (H, W, 8) = albedo(3), hit fraction, mean

@@ -1704,6 +1704,8 @@ int ctx_scene(const rtk_ctx* ctx, uint64_t* digest) {
     return ctx->has_scene ? 1 : 0;
 }
 
+uint32_t ctx_features(const rtk_ctx* ctx) { return ctx->features; }
+
 int frame_chunk_size(int spp) { return chunk_size_for(spp, 0); }
 
 int chunks_per_launch(size_t plane_bytes) { return planes_per_pass_for(plane_bytes, 0); }

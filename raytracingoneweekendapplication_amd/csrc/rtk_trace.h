@@ -90,6 +90,17 @@ template <typename real>
 hipError_t launch_guides(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, int follow, int max_bounces, float* d_guides,
                          hipStream_t stream);
 
+// Ray queries (rtk_query_hits / _occluded / _radiance): n caller-supplied rtk_ray records in device memory, one lane each.
+// any_hit = the program holds no medium, so occlusion may stop at the first accepted hit.  cam carries the radiance query's
+// background, max_depth and spp = samples per ray; d_draws selects the counting instantiation.
+template <typename real>
+hipError_t launch_query_hits(const SceneView<real>& sc, uint32_t seed, long long n, const void* d_rays, void* d_hits, hipStream_t stream);
+template <typename real>
+hipError_t launch_query_occluded(const SceneView<real>& sc, uint32_t seed, bool any_hit, long long n, const void* d_rays, int32_t* d_occluded, hipStream_t stream);
+template <typename real>
+hipError_t launch_query_radiance(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, long long n, const void* d_rays, void* d_radiance,
+                                 uint32_t* d_draws, hipStream_t stream);
+
 // A one-rank progressive session's preview and se (row-major) from its running sum and noise sums; tile_spp null = every tile
 // holds `done` samples.  Reads the state only.
 template <typename real>

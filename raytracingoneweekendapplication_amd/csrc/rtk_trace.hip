@@ -2117,12 +2117,16 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
 // hittable::hit of the scene root on the query interval L.tmin .. L.best_t (set up by begin_segment<true>): the slot program
 // walked one lane at a time, with every record kind and the tie table (inert for reference-order uploads).  L.best_pc /
 // L.best_t hold the winner.  The known-answer entry point and the AOV pass share it.
-template <typename real, bool COUNT>
+// ANY_HIT (rtk_query_occluded, programs without media only): the walk stops at the first accepted hit -- without a medium
+// bracket nothing ever takes a winner back, so whether there is one is settled then.
+template <bool ANY_HIT = false, typename real, bool COUNT>
 RTK_DEV void closest_hit_slots(Lane<real>& L, const SceneView<real>& sc, Counters<COUNT>& cnt) {
     const Slot<real>* prog = sc.program;
     auto kind_of = [&](uint32_t pc) -> uint32_t { return prog[pc].kind_payload & 15u; };
     const TieCtx<true, decltype(kind_of)> tie{sc.tie_rank_slot, kind_of};  // inert (null table) for reference-order uploads
     for (;;) {
+        if constexpr (ANY_HIT)
+            if (L.best_pc != kNoHit) break;
         const Slot<real>* rec = prog + L.pc;
         const uint32_t kind = rec->kind_payload & 15u;
         if (kind == OP_END) break;
@@ -2407,6 +2411,135 @@ __global__ __launch_bounds__(256) void rtk_guide_kernel(SceneView<real> sc, Came
     o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(depth / hits) : 0.0f);
     o[2] = make_float4(float(seen.x / n), float(seen.y / n), float(seen.z / n), float(end_hits / n));
     o[3] = make_float4(float(end_normal.x / n), float(end_normal.y / n), float(end_normal.z / n), end_hits > real(0) ? float(end_len / end_hits) : 0.0f);
+}
+
+// ------------------------------------------------------------------ ray queries --
+// Hits, occlusion and radiance for rays the caller chooses (include/rtk.h "Ray queries"): one lane per ray, on the slot program
+// with every record kind, through the functions the known-answer, AOV and guide kernels run.  A ray record (rtk_ray, 88 bytes,
+// 8-byte aligned) is read as eleven 8-byte words: origin, direction, time, tmin, tmax, {pixel, sample}, {skip, reserved}.
+// Lanes of a wave walk different paths; one whose path has ended idles until its wave is done (no refill).
+
+// The state the generator reaches from `state` after n draws (rnd: s <- a s + c), by squaring the step: at most 32 rounds for
+// any n (Brown, "Random number generation with arbitrary strides", 1994).
+RTK_DEV uint32_t rng_skip(uint32_t state, uint32_t n) {
+    uint32_t mult = 747796405u, plus = 2891336453u, acc_mult = 1u, acc_plus = 0u;
+    for (; n != 0u; n >>= 1) {
+        if (n & 1u) {
+            acc_mult *= mult;
+            acc_plus = acc_plus * mult + plus;
+        }
+        plus = (mult + 1u) * plus;
+        mult *= mult;
+    }
+    return acc_mult * state + acc_plus;
+}
+
+template <typename real>
+RTK_DEV void load_query_ray(Lane<real>& L, const double* __restrict__ r, uint32_t seed_hash, uint32_t sample_offset) {
+    const uint2 key = *reinterpret_cast<const uint2*>(r + 9), skip = *reinterpret_cast<const uint2*>(r + 10);
+    L.ro = mk(real(r[0]), real(r[1]), real(r[2]));
+    L.rd = mk(real(r[3]), real(r[4]), real(r[5]));
+    L.tm = real(r[6]);
+    L.rng = rng_skip(pcg_hash(key.x + pcg_hash(key.y + sample_offset + seed_hash)), skip.x);
+    L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
+    L.sv_best_pc = kNoHit;
+    L.segs = 0;
+}
+
+// hittable::hit(r, interval(tmin, tmax), rec) of the scene root: rtk_debug_hit_kernel's steps, bit for bit, on device buffers.
+// A hit record (rtk_ray_hit, 96 bytes) is written as nine doubles and three pairs of 32-bit integers.
+template <typename real, bool ANY_HIT>
+RTK_DEV void query_closest(Lane<real>& L, const double* __restrict__ r, const SceneView<real>& sc, uint32_t seed_hash, Counters<true>& cnt) {
+    cnt.clear();
+    load_query_ray(L, r, seed_hash, 0u);
+    begin_segment<true>(L, cnt);
+    L.tmin = real(r[7]);
+    L.best_t = real(r[8]);
+    closest_hit_slots<ANY_HIT>(L, sc, cnt);
+}
+
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_query_hits_kernel(SceneView<real> sc, uint32_t seed, long long n, const double* __restrict__ rays,
+                                                              double* __restrict__ hits) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= n) return;
+    Counters<true> cnt;
+    Lane<real> L;
+    query_closest<real, false>(L, rays + gid * 11, sc, pcg_hash(seed), cnt);
+    double* o = hits + gid * 12;
+    int2* oi = reinterpret_cast<int2*>(o + 9);
+    if (L.best_pc == kNoHit) {
+        for (int k = 0; k < 9; k++) o[k] = 0.0;
+        oi[0] = make_int2(0, 0);
+        oi[1] = make_int2(-1, 0);
+        oi[2] = make_int2(-1, int(cnt.c[C_RNG]));
+        return;
+    }
+    Surface<real> sf;
+    make_surface<real, kFeatAll>(sc.program, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
+    // the winner's record names its primitive: the payload is the index into the description's table of its kind
+    const uint32_t kp = sc.program[L.best_pc].kind_payload, kind = kp & 15u;
+    const int node_kind = (kind == OP_SPHERE || kind == OP_SPHERE_MOVING) ? RTK_NODE_SPHERE
+                          : (kind == OP_QUAD ? RTK_NODE_QUAD : (kind == OP_TRI ? RTK_NODE_TRIANGLE : RTK_NODE_MEDIUM));
+    o[0] = double(L.best_t);
+    o[1] = double(sf.p.x); o[2] = double(sf.p.y); o[3] = double(sf.p.z);
+    o[4] = double(sf.normal.x); o[5] = double(sf.normal.y); o[6] = double(sf.normal.z);
+    o[7] = double(sf.u); o[8] = double(sf.v);
+    oi[0] = make_int2(1, sf.front_face ? 1 : 0);
+    oi[1] = make_int2(sf.material, node_kind);
+    oi[2] = make_int2(int(kp >> 4), int(cnt.c[C_RNG]));
+}
+
+// The hit flag of rtk_query_hits_kernel for the same ray, keys and skip.  ANY_HIT: the program holds no medium (the launcher
+// knows the scene's features), and the walk ends at the first accepted hit.
+template <typename real, bool ANY_HIT>
+__global__ __launch_bounds__(256) void rtk_query_occluded_kernel(SceneView<real> sc, uint32_t seed, long long n, const double* __restrict__ rays,
+                                                                  int32_t* __restrict__ occluded) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= n) return;
+    Counters<true> cnt;
+    Lane<real> L;
+    query_closest<real, ANY_HIT>(L, rays + gid * 11, sc, pcg_hash(seed), cnt);
+    occluded[gid] = L.best_pc != kNoHit ? 1 : 0;
+}
+
+// ray_color(r, max_depth, world, lights) (Camera.txt:203-238), iteratively, as the render kernels run it: begin_segment,
+// world.hit on interval(0.001, inf), shade -- until the path ends.  cam carries background, max_depth and spp = the samples per
+// ray; sample s of a ray draws from the stream (seed, pixel, sample + s) advanced by skip.  The sum runs in sample order and
+// is divided once.  COUNT: draws[k] = the uniforms the paths of ray k drew.
+template <typename real, bool COUNT>
+__global__ __launch_bounds__(256) void rtk_query_radiance_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, long long n,
+                                                                  const double* __restrict__ rays, real* __restrict__ radiance, uint32_t* __restrict__ draws) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= n) return;
+    const double* r = rays + gid * 11;
+    Counters<COUNT> cnt;
+    cnt.clear();
+#ifdef RTK_PROFILE
+    ShadeProf sprof;  // (the profile build's shade functions take their sub-phase accumulators)
+#endif
+    const uint32_t seed_hash = pcg_hash(seed);
+    V3<real> sum = mk(real(0), real(0), real(0));
+    for (int s = 0; s < cam.spp; s++) {
+        Lane<real> L;
+        load_query_ray(L, r, seed_hash, uint32_t(s));
+        L.radiance = mk(real(0), real(0), real(0));
+        L.throughput = mk(real(1), real(1), real(1));
+        L.depth = cam.max_depth;
+        while (L.depth > 0) {
+            begin_segment<true>(L, cnt);
+            closest_hit_slots(L, sc, cnt);
+            const Slot<real>* hit_rec = sc.program + (L.best_pc != kNoHit ? L.best_pc : 0u);
+            if (shade<real, kFeatAll, COUNT>(L, hit_rec, sc, sc.materials, cam, cnt RTK_SHADE_PROF_ARG)) break;
+        }
+        sum = sum + L.radiance;
+    }
+    const real ns = real(cam.spp);
+    real* o = radiance + gid * 3;
+    o[0] = sum.x / ns;
+    o[1] = sum.y / ns;
+    o[2] = sum.z / ns;
+    if constexpr (COUNT) draws[gid] = cnt.c[C_RNG];
 }
 
 // ------------------------------------------------------------------ launchers --
@@ -2737,6 +2870,41 @@ hipError_t launch_guides(const SceneView<real>& sc, const CameraRec<real>& cam, 
 }
 template hipError_t launch_guides<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, int, int, float*, hipStream_t);
 template hipError_t launch_guides<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, int, int, int, float*, hipStream_t);
+
+static dim3 query_grid(long long n) { return dim3((unsigned int)((n + 255) / 256)); }
+
+template <typename real>
+hipError_t launch_query_hits(const SceneView<real>& sc, uint32_t seed, long long n, const void* d_rays, void* d_hits, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    rtk_query_hits_kernel<real><<<query_grid(n), dim3(256), 0, stream>>>(sc, seed, n, static_cast<const double*>(d_rays), static_cast<double*>(d_hits));
+    return hipGetLastError();
+}
+template hipError_t launch_query_hits<double>(const SceneView<double>&, uint32_t, long long, const void*, void*, hipStream_t);
+template hipError_t launch_query_hits<float>(const SceneView<float>&, uint32_t, long long, const void*, void*, hipStream_t);
+
+template <typename real>
+hipError_t launch_query_occluded(const SceneView<real>& sc, uint32_t seed, bool any_hit, long long n, const void* d_rays, int32_t* d_occluded, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const double* rays = static_cast<const double*>(d_rays);
+    if (any_hit) rtk_query_occluded_kernel<real, true><<<query_grid(n), dim3(256), 0, stream>>>(sc, seed, n, rays, d_occluded);
+    else rtk_query_occluded_kernel<real, false><<<query_grid(n), dim3(256), 0, stream>>>(sc, seed, n, rays, d_occluded);
+    return hipGetLastError();
+}
+template hipError_t launch_query_occluded<double>(const SceneView<double>&, uint32_t, bool, long long, const void*, int32_t*, hipStream_t);
+template hipError_t launch_query_occluded<float>(const SceneView<float>&, uint32_t, bool, long long, const void*, int32_t*, hipStream_t);
+
+template <typename real>
+hipError_t launch_query_radiance(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, long long n, const void* d_rays, void* d_radiance,
+                                 uint32_t* d_draws, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const double* rays = static_cast<const double*>(d_rays);
+    real* out = static_cast<real*>(d_radiance);
+    if (d_draws) rtk_query_radiance_kernel<real, true><<<query_grid(n), dim3(256), 0, stream>>>(sc, cam, seed, n, rays, out, d_draws);
+    else rtk_query_radiance_kernel<real, false><<<query_grid(n), dim3(256), 0, stream>>>(sc, cam, seed, n, rays, out, nullptr);
+    return hipGetLastError();
+}
+template hipError_t launch_query_radiance<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, long long, const void*, void*, uint32_t*, hipStream_t);
+template hipError_t launch_query_radiance<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, long long, const void*, void*, uint32_t*, hipStream_t);
 
 #ifdef RTK_ISA_PROBES
 // Instruction-cost probes (tools/isa_costs.py; never part of the product build): one kernel per unit of work of the lean

@@ -754,4 +754,6 @@ inline rtk_scene_desc flatten(const hittable& world, const std::vector<point_lig
 }
 }  // namespace rtk
 
+#include "rtk_ray_query.h"  // rtk::ray_query: world.hit / ray_color for caller rays, answered on the device
+
 #endif  // RTK_SCENE_API_H
