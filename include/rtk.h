@@ -976,6 +976,7 @@ int rtk_query_radiance_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n,
  *   h_keys [n][3] = seed, pixel, sample of the RNG stream a constant_medium draws from (constant_medium.h:40)
  *   h_out  [n][12] = hit(0/1), t, p(3), normal(3), front_face, u, v, material index (-1 on a miss)
  *   h_draws[n]     = random_double() calls consumed
+ * real_mode is RTK_REAL_F64 or RTK_REAL_F32; any other value is refused with RTK_ERR_INVALID, as by the entry points below.
  * Blocking; not a rendering path. */
 int rtk_debug_closest_hit(rtk_ctx* ctx, int real_mode, int n, const double* h_rays, const uint32_t* h_keys,
                           double* h_out, uint64_t* h_draws);

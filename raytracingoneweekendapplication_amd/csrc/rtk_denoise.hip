@@ -1,5 +1,5 @@
-// rtk_denoise.hip -- the entry points of the AOV and guide passes (their kernels, rtk_aov_kernel and rtk_guide_kernel, share the
-// traversal of rtk_trace.hip) and the variance-guided edge-avoiding a-trous filter of include/rtk.h ("Denoiser"): Dammertz et
+// rtk_denoise.hip -- the entry points of the AOV and guide passes (their kernel, rtk_guide_kernel without and with the chain, shares
+// the traversal of rtk_trace.hip) and the variance-guided edge-avoiding a-trous filter of include/rtk.h ("Denoiser"): Dammertz et
 // al. 2010 with the luminance weight of SVGF (Schied et al. 2017), spatial part only, and its guided form ("Guides that follow
 // mirrors": two sets of guides, optional albedo demodulation).  Hand-written HIP for gfx950, wave64.
 //

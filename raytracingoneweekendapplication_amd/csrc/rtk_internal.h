@@ -111,6 +111,8 @@ int ctx_device(const rtk_ctx* ctx);
 // Progressive sessions (rtk_progressive.cpp) -- what they use of a context and of the one-shot frame's rules:
 int ctx_scene(const rtk_ctx* ctx, uint64_t* digest);  // 1 when a scene is uploaded; *digest = its digest
 uint32_t ctx_features(const rtk_ctx* ctx);            // Feature bits of the uploaded scene (F_MEDIA: rtk_query_occluded's early exit)
+int32_t ctx_n_materials(const rtk_ctx* ctx);          // table sizes of the uploaded description (index checks of rtk_debug_scatter
+int32_t ctx_n_textures(const rtk_ctx* ctx);           // and rtk_debug_texture)
 int frame_chunk_size(int spp);                        // the one-shot frame's chunk size (variant 0)
 int chunks_per_launch(size_t plane_bytes);            // ... and chunk planes per launch
 size_t camera_record_bytes();

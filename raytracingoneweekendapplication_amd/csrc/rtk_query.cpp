@@ -1,7 +1,11 @@
-// rtk_query.cpp -- the C-ABI half of the ray queries (include/rtk.h "Ray queries"): argument checks that need no device, the
-// launches on the caller's stream, and the blocking _host forms.  The kernels are rtk_trace.hip's, next to the device functions
-// they share with the render, known-answer, AOV and guide kernels.
+// rtk_query.cpp -- the C-ABI half of every lane-per-ray entry point.  The ray queries (include/rtk.h "Ray queries"): argument
+// checks that need no device, the launches on the caller's stream, and the blocking _host forms.  The known-answer entry
+// points (rtk_debug_*): host arrays in and out, on the null stream.  The kernels are rtk_trace.hip's, next to the device
+// functions they share with the render, AOV and guide kernels.
 #include <hip/hip_runtime.h>
+
+#include <initializer_list>
+#include <utility>
 
 #include "rtk.h"
 #include "rtk_internal.h"
@@ -45,13 +49,36 @@ int check_query_args(const char* who, const rtk_query_opts* opts, int64_t n, con
 }
 
 // ... then the context and its scene.
-int check_ctx(const char* who, const rtk_ctx* ctx) {
-    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
+int check_scene(const char* who, const rtk_ctx* ctx) {
     uint64_t digest = 0;
     return ctx_scene(ctx, &digest) ? RTK_OK : fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
 }
+int check_ctx(const char* who, const rtk_ctx* ctx) { return ctx ? check_scene(who, ctx) : fail(RTK_ERR_INVALID, "%s: null context", who); }
 
 int launched(const char* who, hipError_t e) { return e == hipSuccess ? RTK_OK : fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
+
+// What the known-answer entry points refuse first, in this order: a null or negative argument (args_ok false), a context
+// without a scene (where the entry point reads one), an arithmetic type that is neither F64 nor F32.
+int check_debug_args(const char* who, bool args_ok, const rtk_ctx* scene_of, int real_mode) {
+    if (!args_ok) return fail(RTK_ERR_INVALID, "%s: bad argument", who);
+    if (scene_of && check_scene(who, scene_of) != RTK_OK) return RTK_ERR_NO_SCENE;
+    return check_real_mode(who, real_mode);
+}
+
+// A known-answer call on the device: the staged inputs go up, `launch` (real{}) enqueues the kernel on the null stream, the
+// device drains, the outputs come down; inputs and outputs are {piece, host array}.  The first HIP error ends it and is the result.
+template <typename Launch>
+int run_debug(const char* who, int real_mode, HostStaging& s, std::initializer_list<std::pair<int, const void*>> inputs, Launch&& launch,
+              std::initializer_list<std::pair<int, void*>> outputs) {
+    hipError_t e = s.alloc();
+    for (const auto& in : inputs)
+        if (e == hipSuccess) e = s.upload(in.first, in.second);
+    if (e == hipSuccess) e = real_mode == RTK_REAL_F64 ? launch(double{}) : launch(float{});
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (const auto& out : outputs)
+        if (e == hipSuccess) e = s.download(out.first, out.second);
+    return launched(who, e);
+}
 
 }  // namespace
 }  // namespace rtk
@@ -159,6 +186,69 @@ int rtk_query_radiance_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n,
     if (e == hipSuccess) e = s.download_linear(rad, h_radiance);
     if (e == hipSuccess) e = s.download(draws, h_draws);
     return launched(who, e);
+}
+
+// Known-answer entry points (include/rtk.h): n cases in host arrays, staged, run one lane each, read back.
+
+int rtk_debug_closest_hit(rtk_ctx* ctx, int real_mode, int n, const double* h_rays, const uint32_t* h_keys, double* h_out, uint64_t* h_draws) {
+    const char* who = "rtk_debug_closest_hit";
+    const int rc = check_debug_args(who, ctx && n >= 0 && h_rays && h_keys && h_out && h_draws, ctx, real_mode);
+    if (rc != RTK_OK || n == 0) return rc;
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    HostStaging s(true);
+    const int rays = s.piece(size_t(n) * 9 * sizeof(double)), keys = s.piece(size_t(n) * 3 * sizeof(uint32_t));
+    const int out = s.piece(size_t(n) * 12 * sizeof(double)), draws = s.piece(size_t(n) * sizeof(uint64_t));
+    return run_debug(who, real_mode, s, {{rays, h_rays}, {keys, h_keys}}, [&](auto real) {
+        return launch_debug_hit(ctx_view<decltype(real)>(ctx), n, s.ptr<double>(rays), s.ptr<uint32_t>(keys), s.ptr<double>(out), s.ptr<unsigned long long>(draws), nullptr);
+    }, {{out, h_out}, {draws, h_draws}});
+}
+
+int rtk_debug_scatter(rtk_ctx* ctx, int real_mode, int n, const int32_t* h_materials, const double* h_rays, const double* h_records, const uint32_t* h_keys,
+                      double* h_out, uint64_t* h_draws) {
+    const char* who = "rtk_debug_scatter";
+    const int rc = check_debug_args(who, ctx && n >= 0 && h_materials && h_rays && h_records && h_keys && h_out && h_draws, ctx, real_mode);
+    if (rc != RTK_OK) return rc;
+    for (int k = 0; k < n; k++)
+        if (h_materials[k] < 0 || h_materials[k] >= ctx_n_materials(ctx)) return fail(RTK_ERR_INVALID, "%s: material %d of case %d out of range", who, h_materials[k], k);
+    if (n == 0) return RTK_OK;
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    HostStaging s(true);
+    const int mat = s.piece(size_t(n) * sizeof(int32_t)), ray = s.piece(size_t(n) * 7 * sizeof(double)), rec = s.piece(size_t(n) * 11 * sizeof(double));
+    const int keys = s.piece(size_t(n) * 3 * sizeof(uint32_t)), out = s.piece(size_t(n) * 14 * sizeof(double)), draws = s.piece(size_t(n) * sizeof(uint64_t));
+    return run_debug(who, real_mode, s, {{mat, h_materials}, {ray, h_rays}, {rec, h_records}, {keys, h_keys}}, [&](auto real) {
+        return launch_debug_scatter(ctx_view<decltype(real)>(ctx), n, s.ptr<int32_t>(mat), s.ptr<double>(ray), s.ptr<double>(rec), s.ptr<uint32_t>(keys), s.ptr<double>(out),
+                                    s.ptr<unsigned long long>(draws), nullptr);
+    }, {{out, h_out}, {draws, h_draws}});
+}
+
+int rtk_debug_texture(rtk_ctx* ctx, int real_mode, int n, const int32_t* h_textures, const double* h_uvp, double* h_out, uint64_t* h_work) {
+    const char* who = "rtk_debug_texture";
+    const int rc = check_debug_args(who, ctx && n >= 0 && h_textures && h_uvp && h_out && h_work, ctx, real_mode);
+    if (rc != RTK_OK) return rc;
+    for (int k = 0; k < n; k++)
+        if (h_textures[k] < 0 || h_textures[k] >= ctx_n_textures(ctx)) return fail(RTK_ERR_INVALID, "%s: texture %d of case %d out of range", who, h_textures[k], k);
+    if (n == 0) return RTK_OK;
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    HostStaging s(true);
+    const int tex = s.piece(size_t(n) * sizeof(int32_t)), uvp = s.piece(size_t(n) * 5 * sizeof(double));
+    const int out = s.piece(size_t(n) * 3 * sizeof(double)), work = s.piece(size_t(n) * 2 * sizeof(uint64_t));
+    return run_debug(who, real_mode, s, {{tex, h_textures}, {uvp, h_uvp}}, [&](auto real) {
+        return launch_debug_texture(ctx_view<decltype(real)>(ctx), n, s.ptr<int32_t>(tex), s.ptr<double>(uvp), s.ptr<double>(out), s.ptr<unsigned long long>(work), nullptr);
+    }, {{out, h_out}, {work, h_work}});
+}
+
+int rtk_debug_get_ray(rtk_ctx* ctx, int real_mode, const rtk_camera* cam, uint32_t seed, int n, const int32_t* h_pixel_sample, double* h_out, uint64_t* h_draws) {
+    const char* who = "rtk_debug_get_ray";
+    const int rc = check_debug_args(who, ctx && cam && n >= 0 && h_pixel_sample && h_out && h_draws, nullptr, real_mode);  // (reads no scene)
+    if (rc != RTK_OK) return rc;
+    if (cam->image_width <= 0 || cam->image_height <= 0) return fail(RTK_ERR_INVALID, "%s: bad camera dimensions", who);
+    if (n == 0) return RTK_OK;
+    RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    HostStaging s(true);
+    const int ijs = s.piece(size_t(n) * 3 * sizeof(int32_t)), out = s.piece(size_t(n) * 7 * sizeof(double)), draws = s.piece(size_t(n) * sizeof(uint64_t));
+    return run_debug(who, real_mode, s, {{ijs, h_pixel_sample}}, [&](auto real) {
+        return launch_debug_get_ray(device_camera<decltype(real)>(*cam), seed, n, s.ptr<int32_t>(ijs), s.ptr<double>(out), s.ptr<unsigned long long>(draws), nullptr);
+    }, {{out, h_out}, {draws, h_draws}});
 }
 
 }  // extern "C"

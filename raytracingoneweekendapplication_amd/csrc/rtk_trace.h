@@ -1,5 +1,5 @@
-// rtk_trace.h -- launch entry points of the device code for the C-ABI layer: the render, debug and AOV kernels of
-// rtk_trace.hip and the frame-assembly kernels of rtk_frame.hip (tile order, resolve, accumulate, preview, noise statistics,
+// rtk_trace.h -- launch entry points of the device code for the C-ABI layer: the render kernel and the lane-per-ray kernels
+// (known-answer, AOV / guide, ray query) of rtk_trace.hip and the frame-assembly kernels of rtk_frame.hip (tile order, resolve, accumulate, preview, noise statistics,
 // adaptive state, un-permute).
 #ifndef RTK_TRACE_H
 #define RTK_TRACE_H
@@ -66,7 +66,8 @@ hipError_t launch_adaptive_init(const TileMap& tmap, int32_t* active, int32_t* t
 hipError_t launch_noise_stats_adaptive(const double* s1, const double* s2, const TileMap& tmap, int width, int height, int chunk_size, const int32_t* tile_spp,
                                        double* partials, double* out3, hipStream_t stream);
 
-// Known-answer helper: closest hit of the scene root for n caller-supplied rays (device buffers).
+// Known-answer helper: closest hit of the scene root for n caller-supplied rays (device buffers), keys[n][3] = seed, pixel,
+// sample of each ray's stream: launch_query_hits' walk with a seed per ray and no skip.
 template <typename real>
 hipError_t launch_debug_hit(const SceneView<real>& sc, int n, const double* d_rays, const uint32_t* d_keys, double* d_out, unsigned long long* d_draws,
                             hipStream_t stream);
@@ -80,12 +81,13 @@ hipError_t launch_debug_texture(const SceneView<real>& sc, int n, const int32_t*
 template <typename real>
 hipError_t launch_debug_get_ray(const CameraRec<real>& cam, uint32_t seed, int n, const int32_t* d_ijs, double* d_out, unsigned long long* d_draws, hipStream_t stream);
 
-// Guide buffers of the denoiser: aov[(j * W + i) * 8 + k] over samples 0 .. n_samples - 1 of every pixel (rtk_render_aovs).
+// Guide buffers of the denoiser: aov[(j * W + i) * 8 + k] over samples 0 .. n_samples - 1 of every pixel (rtk_render_aovs):
+// rtk_guide_kernel compiled without the chain.
 template <typename real>
 hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream);
 
-// The same with the surface seen through followed mirrors / glass: guides[(j * W + i) * 16 + k], k 0-7 = launch_aov's values
-// (rtk_render_guides).  follow = RTK_GUIDE_FOLLOW_* bits, max_bounces 1..8 (both resolved by the caller).
+// The same kernel with the surface seen through followed mirrors / glass: guides[(j * W + i) * 16 + k], k 0-7 = launch_aov's
+// values (rtk_render_guides).  follow = RTK_GUIDE_FOLLOW_* bits, max_bounces 1..8 (both resolved by the caller).
 template <typename real>
 hipError_t launch_guides(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, int follow, int max_bounces, float* d_guides,
                          hipStream_t stream);

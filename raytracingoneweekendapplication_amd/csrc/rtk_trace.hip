@@ -32,6 +32,7 @@
 #include "rtk.h"
 #include "rtk_device_layout.h"
 #include "rtk_device_math.h"
+#include "rtk_image_pass.h"
 #include "rtk_trace.h"
 
 namespace rtk {
@@ -2141,35 +2142,77 @@ RTK_DEV void closest_hit_slots(Lane<real>& L, const SceneView<real>& sc, Counter
     }
 }
 
-// Known-answer entry point (tests): hittable::hit(r, interval(tmin, tmax), rec) of the uploaded scene's
-// root for caller-supplied rays, one lane per ray, lock-step over the traversal program.  Exercises the same
-// step_* / make_surface code as the render kernel.  out[12] = hit, t, p(3), normal(3), front_face, u, v, material.
+// ------------------------------------------------------------------ lane-per-ray kernels --
+// One lane per ray or pixel, next to the persistent render kernel: the known-answer (rtk_debug_*), AOV / guide and ray-query
+// kernels.  What they share (DESIGN.md "What a lane-per-ray kernel is made of"):
+
+// The stream of keys (seed, pixel, sample), the keying of the render's samples: seed_hash = pcg_hash(seed).
+RTK_DEV uint32_t stream_key(uint32_t seed_hash, uint32_t pixel, uint32_t sample) { return pcg_hash(pixel + pcg_hash(sample + seed_hash)); }
+// keys[3] = seed, pixel, sample of one known-answer case
+RTK_DEV uint32_t stream_key(const uint32_t* __restrict__ keys) { return stream_key(pcg_hash(keys[0]), keys[1], keys[2]); }
+
+// r[7] = origin, direction, time -> the lane's world-space ray.
+template <typename real>
+RTK_DEV void load_ray(Lane<real>& L, const double* __restrict__ r) {
+    L.ro = mk(real(r[0]), real(r[1]), real(r[2]));
+    L.rd = mk(real(r[3]), real(r[4]), real(r[5]));
+    L.tm = real(r[6]);
+}
+
+// No outer query of a constant medium is parked (Lane::sv_*): the state a path starts in.
+template <typename real>
+RTK_DEV void clear_parked(Lane<real>& L) {
+    L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
+    L.sv_best_pc = kNoHit;
+}
+
+// ... and world.hit(r, interval(0.001, inf), rec) of L.ro / L.rd begins: closest_hit_slots comes next.
+template <typename real, bool COUNT>
+RTK_DEV void begin_walk(Lane<real>& L, Counters<COUNT>& cnt) {
+    clear_parked(L);
+    begin_segment<true>(L, cnt);
+}
+
+// hittable::hit(r, interval(tmin, tmax), rec) of the scene root for r[9] = origin, direction, time, tmin, tmax: the one walk
+// behind rtk_debug_closest_hit, rtk_query_hits and rtk_query_occluded.  The lane holds the ray (load_ray) and L.rng, the stream
+// a constant medium draws from; L.best_pc / L.best_t hold the winner afterwards, cnt.c[C_RNG] the draws.
+template <bool ANY_HIT = false, typename real>
+RTK_DEV void query_closest(Lane<real>& L, const double* r, const SceneView<real>& sc, Counters<true>& cnt) {
+    cnt.clear();
+    L.segs = 0;
+    begin_walk(L, cnt);
+    L.tmin = real(r[7]);
+    L.best_t = real(r[8]);
+    closest_hit_slots<ANY_HIT>(L, sc, cnt);
+}
+
+// The hit_record of the walk's winner (L.best_pc != kNoHit), u and v included.
+template <typename real>
+RTK_DEV Surface<real> hit_surface(const Lane<real>& L, const SceneView<real>& sc) {
+    Surface<real> sf;
+    make_surface<real, kFeatAll>(sc.program, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
+    return sf;
+}
+
+// Known-answer entry point (tests): hittable::hit(r, interval(tmin, tmax), rec) of the uploaded scene's root for
+// caller-supplied rays with a stream of keys each -- query_closest, as rtk_query_hits_kernel runs it for one seed and a skip.
+// out[12] = hit, t, p(3), normal(3), front_face, u, v, material.
 template <typename real>
 __global__ __launch_bounds__(256) void rtk_debug_hit_kernel(SceneView<real> sc, int n, const double* __restrict__ rays, const uint32_t* __restrict__ keys,
                                                              double* __restrict__ out, unsigned long long* __restrict__ draws) {
     const int gid = blockIdx.x * 256 + threadIdx.x;
     if (gid >= n) return;
-    const double* r = rays + size_t(gid) * 9;
     Counters<true> cnt;
-    cnt.clear();
     Lane<real> L;
-    L.ro = mk(real(r[0]), real(r[1]), real(r[2]));
-    L.rd = mk(real(r[3]), real(r[4]), real(r[5]));
-    L.tm = real(r[6]);
-    L.rng = pcg_hash(keys[gid * 3 + 1] + pcg_hash(keys[gid * 3 + 2] + pcg_hash(keys[gid * 3])));
-    L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
-    L.sv_best_pc = kNoHit;
-    begin_segment<true>(L, cnt);
-    L.tmin = real(r[7]);
-    L.best_t = real(r[8]);
-    closest_hit_slots(L, sc, cnt);
-    const Slot<real>* prog = sc.program;
+    const double* r = rays + size_t(gid) * 9;
+    load_ray(L, r);
+    L.rng = stream_key(keys + gid * 3);
+    query_closest(L, r, sc, cnt);
     double* o = out + size_t(gid) * 12;
     for (int k = 0; k < 12; k++) o[k] = 0.0;
     o[11] = -1.0;
     if (L.best_pc != kNoHit) {
-        Surface<real> sf;
-        make_surface<real, kFeatAll>(prog, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
+        const Surface<real> sf = hit_surface(L, sc);
         o[0] = 1.0;
         o[1] = double(L.best_t);
         o[2] = double(sf.p.x); o[3] = double(sf.p.y); o[4] = double(sf.p.z);
@@ -2195,13 +2238,10 @@ __global__ __launch_bounds__(256) void rtk_debug_scatter_kernel(SceneView<real> 
     sc.n_lights = 0;  // get_lighting (Camera.txt:228) belongs to ray_color, not to scatter()
     Counters<true> cnt;
     cnt.clear();
-    const double* r = ray + size_t(gid) * 7;
     const double* h = rec + size_t(gid) * 11;
     Lane<real> L;
-    L.ro = mk(real(r[0]), real(r[1]), real(r[2]));
-    L.rd = mk(real(r[3]), real(r[4]), real(r[5]));
-    L.tm = real(r[6]);
-    L.rng = pcg_hash(keys[gid * 3 + 1] + pcg_hash(keys[gid * 3 + 2] + pcg_hash(keys[gid * 3])));
+    load_ray(L, ray + size_t(gid) * 7);
+    L.rng = stream_key(keys + gid * 3);
     L.throughput = mk(real(1), real(1), real(1));
     L.radiance = mk(real(0), real(0), real(0));
     L.sum = mk(real(0), real(0), real(0));
@@ -2260,157 +2300,122 @@ __global__ __launch_bounds__(256) void rtk_debug_get_ray_kernel(CameraRec<real> 
     draws[gid] = cnt.c[C_RNG];
 }
 
-// First-hit guide buffers (AOVs) of the denoiser (include/rtk.h, rtk_render_aovs): one lane per pixel, a 256-thread block is
-// four 8x8 tiles (the render's tile convention).  Sample s of pixel (i, j) takes the render's primary ray -- begin_sample with
-// the render's seed, bit for bit -- then re-seeds its stream with keys (seed, pixel, s + 2^31), as rtk_debug_closest_hit does,
-// so a constant medium never draws the render's numbers, and finds world.hit(r, interval(0.001, inf)) (Camera.txt:211) with
-// the known-answer traversal.  Sums run in `real` in sample order and are divided by their count once:
-//   aov[px][0..2] albedo: miss -> background clamped to [0, 1]; lambertian / isotropic -> texture::value; metal / specular ->
-//                 albedo; dielectric -> 1; diffuse_light -> min(1, texture::value)    (mean over n)
-//   aov[px][3]    hits / n (medium hits count)
-//   aov[px][4..6] sum over hits of the record's normal (isotropic hits add 0) / n
-//   aov[px][7]    mean over hits of t * |rd| (0 without hits)
+// ------------------------------------------------------------------ guide buffers --
+// First-hit guide buffers (AOVs) of the denoiser and their mirror-following form (include/rtk.h, rtk_render_aovs and
+// rtk_render_guides): one kernel body, rtk_guide_kernel<real, CHAIN>, one lane per pixel on the image passes' tile grid
+// (rtk_image_pass.h).  Sample s of pixel (i, j) takes the render's primary ray -- begin_sample with the render's seed, bit for
+// bit.  Segment b of the sample (CHAIN = false: b = 0 alone) re-seeds its stream with keys (seed, pixel, 2^31 + (2b << 20) + s),
+// as rtk_debug_closest_hit does, so a constant medium never draws the render's numbers, and finds world.hit(r, interval(0.001,
+// inf)) (Camera.txt:211) with the known-answer traversal.  Sums run in `real` in sample order and are divided by their count
+// once.  What b = 0 finds is the first-hit record, out[px][0..7], the same instructions in both instantiations:
+//   [0..2] albedo: miss -> background clamped to [0, 1]; lambertian / isotropic -> texture::value; metal / specular ->
+//          albedo; dielectric -> 1; diffuse_light -> min(1, texture::value)    (mean over n)
+//   [3]    hits / n (medium hits count)
+//   [4..6] sum over hits of the record's normal (isotropic hits add 0) / n
+//   [7]    mean over hits of t * |rd| (0 without hits)
+// CHAIN adds the surface a chain of followed specular hits ends on, out[px][8..15].  A followed hit (a mirror or glass, by
+// `follow`) with b < max_bounces runs material::scatter on the stream of keys (seed, pixel, 2^31 + ((2b + 1) << 20) + s) --
+// shade_surface without point lights as rtk_debug_scatter runs it, compiled for the two followed kinds alone (FORCE_KIND: no
+// texture code in the chain); L.throughput carries T.  A hit that is not followed, or does not scatter, ends the chain:
+//   [8..10]  seen albedo: T * (albedo rule of the end hit, or the clamped background), mean over n
+//   [11]     end hits / n
+//   [12..14] sum over end hits of the record's normal (isotropic: 0) / n
+//   [15]     mean over end hits of the path length sum_b t_b |rd_b| (0 without end hits)
 template <typename real>
 RTK_DEV real clamp01(real x) { return x < real(0) ? real(0) : (x > real(1) ? real(1) : x); }
 
 template <typename real>
-__global__ __launch_bounds__(256) void rtk_aov_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, int n_samples, int tiles_x, int n_tiles,
-                                                       float4* __restrict__ aov) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int tile = int(gid >> 6), pix = int(gid & 63);
-    if (tile >= n_tiles) return;
-    const int i = (tile % tiles_x) * 8 + (pix & 7), j = (tile / tiles_x) * 8 + (pix >> 3);
-    if (i >= cam.width || j >= cam.height) return;
-    Counters<false> cnt;
-    const uint32_t seed_hash = pcg_hash(seed);
-    const uint32_t pixel = uint32_t(j * cam.width + i);
-    const V3<real> zero = mk(real(0), real(0), real(0));
-    V3<real> albedo = zero, normal = zero;
-    real hits = real(0), depth = real(0);
-    for (int s = 0; s < n_samples; s++) {
-        Lane<real> L;
-        L.s = s;
-        L.segs = 0;
-        begin_sample(L, cam, i, j, seed_hash, cnt);
-        L.rng = pcg_hash(pixel + pcg_hash(uint32_t(s) + 0x80000000u + seed_hash));
-        L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
-        L.sv_best_pc = kNoHit;
-        begin_segment<true>(L, cnt);
-        closest_hit_slots(L, sc, cnt);
-        if (L.best_pc == kNoHit) {
-            albedo = albedo + mk(clamp01(cam.background[0]), clamp01(cam.background[1]), clamp01(cam.background[2]));
-            continue;
-        }
-        Surface<real> sf;
-        make_surface<real, kFeatAll>(sc.program, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
-        const MaterialRec<real>& m = sc.materials[sf.material];
-        V3<real> a = mk(real(1), real(1), real(1));  // dielectric
-        if (m.kind == RTK_MAT_LAMBERTIAN || m.kind == RTK_MAT_ISOTROPIC) {
-            a = material_color<real, kFeatAll>(sc, m, sf.u, sf.v, sf.p, cnt);
-        } else if (m.kind == RTK_MAT_METAL || m.kind == RTK_MAT_SPECULAR) {
-            a = ld3(m.albedo);
-        } else if (m.kind == RTK_MAT_DIFFUSE_LIGHT) {
-            const V3<real> e = material_color<real, kFeatAll>(sc, m, sf.u, sf.v, sf.p, cnt);
-            a = mk(e.x > real(1) ? real(1) : e.x, e.y > real(1) ? real(1) : e.y, e.z > real(1) ? real(1) : e.z);
-        }
-        albedo = albedo + a;
-        hits = hits + real(1);
-        if (m.kind != RTK_MAT_ISOTROPIC) normal = normal + sf.normal;
-        depth = depth + L.best_t * rt_sqrt(length_squared(L.rd));
-    }
-    const real n = real(n_samples);
-    float4* o = aov + (size_t(j) * cam.width + i) * 2;
-    o[0] = make_float4(float(albedo.x / n), float(albedo.y / n), float(albedo.z / n), float(hits / n));
-    o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(depth / hits) : 0.0f);
+RTK_DEV V3<real> clamped_background(const CameraRec<real>& cam) {
+    return mk(clamp01(cam.background[0]), clamp01(cam.background[1]), clamp01(cam.background[2]));
 }
 
-// Mirror-following guide buffers of the denoiser (include/rtk.h, rtk_render_guides): rtk_aov_kernel's lane-per-pixel layout and
-// first-hit sums (guides[px][0..7], the same expressions in the same order: bit-identical), plus the surface a chain of followed
-// specular hits ends on.  Segment b of sample s re-seeds its stream with keys (seed, pixel, 2^31 + (2b << 20) + s) for the
-// closest hit -- b = 0 is rtk_aov_kernel's key -- and (seed, pixel, 2^31 + ((2b + 1) << 20) + s) for material::scatter, which is
-// shade_surface without point lights as rtk_debug_scatter runs it, compiled for the two followed kinds alone (FORCE_KIND: no
-// texture code in the chain).  L.throughput carries T.  A followed hit at b == max_bounces, or one that does not scatter, ends
-// the chain by the first-hit rule.
-//   guides[px][8..10]  seen albedo: T * (albedo rule of the end hit, or the clamped background), mean over n
-//   guides[px][11]     end hits / n
-//   guides[px][12..14] sum over end hits of the record's normal (isotropic: 0) / n
-//   guides[px][15]     mean over end hits of the path length sum_b t_b |rd_b| (0 without end hits)
+// The albedo rule of a hit on material m.
+template <typename real, bool COUNT>
+RTK_DEV V3<real> first_hit_albedo(const SceneView<real>& sc, const MaterialRec<real>& m, const Surface<real>& sf, Counters<COUNT>& cnt) {
+    const int kind = m.kind;
+    V3<real> a = mk(real(1), real(1), real(1));  // dielectric
+    if (kind == RTK_MAT_LAMBERTIAN || kind == RTK_MAT_ISOTROPIC || kind == RTK_MAT_DIFFUSE_LIGHT) {
+        a = material_color<real, kFeatAll>(sc, m, sf.u, sf.v, sf.p, cnt);
+        if (kind == RTK_MAT_DIFFUSE_LIGHT) a = mk(a.x > real(1) ? real(1) : a.x, a.y > real(1) ? real(1) : a.y, a.z > real(1) ? real(1) : a.z);
+    } else if (kind == RTK_MAT_METAL || kind == RTK_MAT_SPECULAR) {
+        a = ld3(m.albedo);
+    }
+    return a;
+}
+
+// One record of eight: the sums over a pixel's samples and their two float4.
 template <typename real>
-__global__ __launch_bounds__(256) void rtk_guide_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, int n_samples, int follow, int max_bounces,
-                                                         int tiles_x, int n_tiles, float4* __restrict__ guides) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int tile = int(gid >> 6), pix = int(gid & 63);
-    if (tile >= n_tiles) return;
-    const int i = (tile % tiles_x) * 8 + (pix & 7), j = (tile / tiles_x) * 8 + (pix >> 3);
-    if (i >= cam.width || j >= cam.height) return;
-    sc.n_lights = 0;  // get_lighting (Camera.txt:228) belongs to ray_color, not to scatter()
+struct HitSums {
+    V3<real> albedo = mk(real(0), real(0), real(0)), normal = mk(real(0), real(0), real(0));
+    real hits = real(0), len = real(0);
+    RTK_DEV void miss(V3<real> colour) { albedo = albedo + colour; }
+    RTK_DEV void hit(V3<real> colour, V3<real> nrm, real length) {
+        albedo = albedo + colour;
+        hits = hits + real(1);
+        normal = normal + nrm;
+        len = len + length;
+    }
+    RTK_DEV void write(float4* __restrict__ o, real n) const {
+        o[0] = make_float4(float(albedo.x / n), float(albedo.y / n), float(albedo.z / n), float(hits / n));
+        o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(len / hits) : 0.0f);
+    }
+};
+
+// follow / max_bounces: read by CHAIN alone.  out holds two float4 per pixel, four with CHAIN.
+template <typename real, bool CHAIN>
+__global__ __launch_bounds__(256) void rtk_guide_kernel(TileGrid grid, SceneView<real> sc, CameraRec<real> cam, uint32_t seed, int n_samples, int follow,
+                                                         int max_bounces, float4* __restrict__ out) {
+    int i, j;
+    if (!lane_pixel(grid, i, j)) return;
+    if constexpr (CHAIN) sc.n_lights = 0;  // get_lighting (Camera.txt:228) belongs to ray_color, not to scatter()
     Counters<false> cnt;
     const uint32_t seed_hash = pcg_hash(seed);
     const uint32_t pixel = uint32_t(j * cam.width + i);
-    const V3<real> zero = mk(real(0), real(0), real(0));
-    V3<real> albedo = zero, normal = zero, seen = zero, end_normal = zero;
-    real hits = real(0), depth = real(0), end_hits = real(0), end_len = real(0);
+    HitSums<real> first, end;
     for (int s = 0; s < n_samples; s++) {
         Lane<real> L;
         L.s = s;
         L.segs = 0;
         begin_sample(L, cam, i, j, seed_hash, cnt);
-        L.depth = 1 << 20;  // (the chain is capped by max_bounces, not by the camera's max_depth)
-        real len = real(0);
+        if constexpr (CHAIN) L.depth = 1 << 20;  // (the chain is capped by max_bounces, not by the camera's max_depth)
+        [[maybe_unused]] real len = real(0);
         for (int b = 0;; b++) {
             const uint32_t key = 0x80000000u + (uint32_t(2 * b) << 20) + uint32_t(s);
-            L.rng = pcg_hash(pixel + pcg_hash(key + seed_hash));
-            L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
-            L.sv_best_pc = kNoHit;
-            begin_segment<true>(L, cnt);
+            L.rng = stream_key(seed_hash, pixel, key);
+            begin_walk(L, cnt);
             closest_hit_slots(L, sc, cnt);
             if (L.best_pc == kNoHit) {
-                const V3<real> bg = mk(clamp01(cam.background[0]), clamp01(cam.background[1]), clamp01(cam.background[2]));
-                if (b == 0) albedo = albedo + bg;
-                seen = seen + L.throughput * bg;
+                const V3<real> bg = clamped_background(cam);
+                if (b == 0) first.miss(bg);
+                if constexpr (CHAIN) end.miss(L.throughput * bg);
                 break;
             }
-            Surface<real> sf;
-            make_surface<real, kFeatAll>(sc.program, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
+            const Surface<real> sf = hit_surface(L, sc);
             const MaterialRec<real>& m = sc.materials[sf.material];
             const int mkind = m.kind;
             const real seg = L.best_t * rt_sqrt(length_squared(L.rd));
-            len = len + seg;
-            V3<real> a = mk(real(1), real(1), real(1));  // dielectric
-            if (mkind == RTK_MAT_LAMBERTIAN || mkind == RTK_MAT_ISOTROPIC || mkind == RTK_MAT_DIFFUSE_LIGHT) {
-                a = material_color<real, kFeatAll>(sc, m, sf.u, sf.v, sf.p, cnt);
-                if (mkind == RTK_MAT_DIFFUSE_LIGHT) a = mk(a.x > real(1) ? real(1) : a.x, a.y > real(1) ? real(1) : a.y, a.z > real(1) ? real(1) : a.z);
-            } else if (mkind == RTK_MAT_METAL || mkind == RTK_MAT_SPECULAR) {
-                a = ld3(m.albedo);
+            if constexpr (CHAIN) len = len + seg;
+            const V3<real> a = first_hit_albedo(sc, m, sf, cnt);
+            const V3<real> nrm = mkind != RTK_MAT_ISOTROPIC ? sf.normal : mk(real(0), real(0), real(0));
+            if (b == 0) first.hit(a, nrm, seg);
+            if constexpr (CHAIN) {
+                const bool mirror = (follow & RTK_GUIDE_FOLLOW_MIRROR) && mkind == RTK_MAT_METAL && m.param == real(0);
+                const bool glass = (follow & RTK_GUIDE_FOLLOW_DIELECTRIC) && mkind == RTK_MAT_DIELECTRIC;
+                if ((mirror || glass) && b < max_bounces) {
+                    L.rng = stream_key(seed_hash, pixel, key + (1u << 20));
+                    const bool ended = mirror ? shade_surface<real, kFeatAll, RTK_MAT_METAL>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG)
+                                              : shade_surface<real, kFeatAll, RTK_MAT_DIELECTRIC>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG);
+                    if (!ended) continue;  // L.ro / L.rd = the scattered ray, L.throughput = T * attenuation, L.tm kept
+                }
+                end.hit(L.throughput * a, nrm, len);
             }
-            const V3<real> nrm = mkind != RTK_MAT_ISOTROPIC ? sf.normal : zero;
-            if (b == 0) {
-                albedo = albedo + a;
-                hits = hits + real(1);
-                normal = normal + nrm;
-                depth = depth + seg;
-            }
-            const bool mirror = (follow & RTK_GUIDE_FOLLOW_MIRROR) && mkind == RTK_MAT_METAL && m.param == real(0);
-            const bool glass = (follow & RTK_GUIDE_FOLLOW_DIELECTRIC) && mkind == RTK_MAT_DIELECTRIC;
-            if ((mirror || glass) && b < max_bounces) {
-                L.rng = pcg_hash(pixel + pcg_hash(key + (1u << 20) + seed_hash));
-                const bool ended = mirror ? shade_surface<real, kFeatAll, RTK_MAT_METAL>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG)
-                                          : shade_surface<real, kFeatAll, RTK_MAT_DIELECTRIC>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG);
-                if (!ended) continue;  // L.ro / L.rd = the scattered ray, L.throughput = T * attenuation, L.tm kept
-            }
-            seen = seen + L.throughput * a;
-            end_normal = end_normal + nrm;
-            end_hits = end_hits + real(1);
-            end_len = end_len + len;
             break;
         }
     }
     const real n = real(n_samples);
-    float4* o = guides + (size_t(j) * cam.width + i) * 4;
-    o[0] = make_float4(float(albedo.x / n), float(albedo.y / n), float(albedo.z / n), float(hits / n));
-    o[1] = make_float4(float(normal.x / n), float(normal.y / n), float(normal.z / n), hits > real(0) ? float(depth / hits) : 0.0f);
-    o[2] = make_float4(float(seen.x / n), float(seen.y / n), float(seen.z / n), float(end_hits / n));
-    o[3] = make_float4(float(end_normal.x / n), float(end_normal.y / n), float(end_normal.z / n), end_hits > real(0) ? float(end_len / end_hits) : 0.0f);
+    float4* o = out + (size_t(j) * cam.width + i) * (CHAIN ? 4 : 2);
+    first.write(o, n);
+    if constexpr (CHAIN) end.write(o + 2, n);
 }
 
 // ------------------------------------------------------------------ ray queries --
@@ -2434,38 +2439,27 @@ RTK_DEV uint32_t rng_skip(uint32_t state, uint32_t n) {
     return acc_mult * state + acc_plus;
 }
 
+// A ray record -> the lane's ray and its stream: keys (seed, pixel, sample + sample_offset), advanced by skip.  With offset 0
+// and skip 0 that is rtk_debug_hit_kernel's stream_key(keys) for keys = {seed, pixel, sample}.
 template <typename real>
 RTK_DEV void load_query_ray(Lane<real>& L, const double* __restrict__ r, uint32_t seed_hash, uint32_t sample_offset) {
     const uint2 key = *reinterpret_cast<const uint2*>(r + 9), skip = *reinterpret_cast<const uint2*>(r + 10);
-    L.ro = mk(real(r[0]), real(r[1]), real(r[2]));
-    L.rd = mk(real(r[3]), real(r[4]), real(r[5]));
-    L.tm = real(r[6]);
-    L.rng = rng_skip(pcg_hash(key.x + pcg_hash(key.y + sample_offset + seed_hash)), skip.x);
-    L.sv_tmin = L.sv_best_t = L.rec1_t = real(0);
-    L.sv_best_pc = kNoHit;
-    L.segs = 0;
+    load_ray(L, r);
+    L.rng = rng_skip(stream_key(seed_hash, key.x, key.y + sample_offset), skip.x);
 }
 
-// hittable::hit(r, interval(tmin, tmax), rec) of the scene root: rtk_debug_hit_kernel's steps, bit for bit, on device buffers.
-// A hit record (rtk_ray_hit, 96 bytes) is written as nine doubles and three pairs of 32-bit integers.
-template <typename real, bool ANY_HIT>
-RTK_DEV void query_closest(Lane<real>& L, const double* __restrict__ r, const SceneView<real>& sc, uint32_t seed_hash, Counters<true>& cnt) {
-    cnt.clear();
-    load_query_ray(L, r, seed_hash, 0u);
-    begin_segment<true>(L, cnt);
-    L.tmin = real(r[7]);
-    L.best_t = real(r[8]);
-    closest_hit_slots<ANY_HIT>(L, sc, cnt);
-}
-
+// hittable::hit(r, interval(tmin, tmax), rec) of the scene root on device buffers.  A hit record (rtk_ray_hit, 96 bytes) is
+// written as nine doubles and three pairs of 32-bit integers.
 template <typename real>
 __global__ __launch_bounds__(256) void rtk_query_hits_kernel(SceneView<real> sc, uint32_t seed, long long n, const double* __restrict__ rays,
                                                               double* __restrict__ hits) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= n) return;
+    const double* r = rays + gid * 11;
     Counters<true> cnt;
     Lane<real> L;
-    query_closest<real, false>(L, rays + gid * 11, sc, pcg_hash(seed), cnt);
+    load_query_ray(L, r, pcg_hash(seed), 0u);
+    query_closest(L, r, sc, cnt);
     double* o = hits + gid * 12;
     int2* oi = reinterpret_cast<int2*>(o + 9);
     if (L.best_pc == kNoHit) {
@@ -2475,8 +2469,7 @@ __global__ __launch_bounds__(256) void rtk_query_hits_kernel(SceneView<real> sc,
         oi[2] = make_int2(-1, int(cnt.c[C_RNG]));
         return;
     }
-    Surface<real> sf;
-    make_surface<real, kFeatAll>(sc.program, sc, sc.materials, L.best_pc, L.best_t, L.ro, L.rd, L.tm, sf, true);
+    const Surface<real> sf = hit_surface(L, sc);
     // the winner's record names its primitive: the payload is the index into the description's table of its kind
     const uint32_t kp = sc.program[L.best_pc].kind_payload, kind = kp & 15u;
     const int node_kind = (kind == OP_SPHERE || kind == OP_SPHERE_MOVING) ? RTK_NODE_SPHERE
@@ -2497,9 +2490,11 @@ __global__ __launch_bounds__(256) void rtk_query_occluded_kernel(SceneView<real>
                                                                   int32_t* __restrict__ occluded) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= n) return;
+    const double* r = rays + gid * 11;
     Counters<true> cnt;
     Lane<real> L;
-    query_closest<real, ANY_HIT>(L, rays + gid * 11, sc, pcg_hash(seed), cnt);
+    load_query_ray(L, r, pcg_hash(seed), 0u);
+    query_closest<ANY_HIT>(L, r, sc, cnt);
     occluded[gid] = L.best_pc != kNoHit ? 1 : 0;
 }
 
@@ -2523,6 +2518,8 @@ __global__ __launch_bounds__(256) void rtk_query_radiance_kernel(SceneView<real>
     for (int s = 0; s < cam.spp; s++) {
         Lane<real> L;
         load_query_ray(L, r, seed_hash, uint32_t(s));
+        clear_parked(L);
+        L.segs = 0;
         L.radiance = mk(real(0), real(0), real(0));
         L.throughput = mk(real(1), real(1), real(1));
         L.depth = cam.max_depth;
@@ -2813,11 +2810,14 @@ const char* render_kernel_name(const SceneView<real>& sc, uint32_t features, boo
 template const char* render_kernel_name<double>(const SceneView<double>&, uint32_t, bool, bool, uint32_t);
 template const char* render_kernel_name<float>(const SceneView<float>&, uint32_t, bool, bool, uint32_t);
 
+// The grid of a lane-per-ray launch: 256-thread blocks over n lanes.
+static dim3 lane_grid(long long n) { return dim3((unsigned int)((n + 255) / 256)); }
+
 template <typename real>
 hipError_t launch_debug_hit(const SceneView<real>& sc, int n, const double* d_rays, const uint32_t* d_keys, double* d_out, unsigned long long* d_draws,
                             hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    rtk_debug_hit_kernel<real><<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(sc, n, d_rays, d_keys, d_out, d_draws);
+    rtk_debug_hit_kernel<real><<<lane_grid(n), dim3(256), 0, stream>>>(sc, n, d_rays, d_keys, d_out, d_draws);
     return hipGetLastError();
 }
 template hipError_t launch_debug_hit<double>(const SceneView<double>&, int, const double*, const uint32_t*, double*, unsigned long long*, hipStream_t);
@@ -2827,7 +2827,7 @@ template <typename real>
 hipError_t launch_debug_scatter(const SceneView<real>& sc, int n, const int32_t* d_mat, const double* d_ray, const double* d_rec, const uint32_t* d_keys, double* d_out,
                                 unsigned long long* d_draws, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    rtk_debug_scatter_kernel<real><<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(sc, n, d_mat, d_ray, d_rec, d_keys, d_out, d_draws);
+    rtk_debug_scatter_kernel<real><<<lane_grid(n), dim3(256), 0, stream>>>(sc, n, d_mat, d_ray, d_rec, d_keys, d_out, d_draws);
     return hipGetLastError();
 }
 template hipError_t launch_debug_scatter<double>(const SceneView<double>&, int, const int32_t*, const double*, const double*, const uint32_t*, double*, unsigned long long*, hipStream_t);
@@ -2836,7 +2836,7 @@ template hipError_t launch_debug_scatter<float>(const SceneView<float>&, int, co
 template <typename real>
 hipError_t launch_debug_texture(const SceneView<real>& sc, int n, const int32_t* d_tex, const double* d_uvp, double* d_out, unsigned long long* d_work, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    rtk_debug_texture_kernel<real><<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(sc, n, d_tex, d_uvp, d_out, d_work);
+    rtk_debug_texture_kernel<real><<<lane_grid(n), dim3(256), 0, stream>>>(sc, n, d_tex, d_uvp, d_out, d_work);
     return hipGetLastError();
 }
 template hipError_t launch_debug_texture<double>(const SceneView<double>&, int, const int32_t*, const double*, double*, unsigned long long*, hipStream_t);
@@ -2845,7 +2845,7 @@ template hipError_t launch_debug_texture<float>(const SceneView<float>&, int, co
 template <typename real>
 hipError_t launch_debug_get_ray(const CameraRec<real>& cam, uint32_t seed, int n, const int32_t* d_ijs, double* d_out, unsigned long long* d_draws, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    rtk_debug_get_ray_kernel<real><<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(cam, seed, n, d_ijs, d_out, d_draws);
+    rtk_debug_get_ray_kernel<real><<<lane_grid(n), dim3(256), 0, stream>>>(cam, seed, n, d_ijs, d_out, d_draws);
     return hipGetLastError();
 }
 template hipError_t launch_debug_get_ray<double>(const CameraRec<double>&, uint32_t, int, const int32_t*, double*, unsigned long long*, hipStream_t);
@@ -2853,8 +2853,8 @@ template hipError_t launch_debug_get_ray<float>(const CameraRec<float>&, uint32_
 
 template <typename real>
 hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream) {
-    const int tiles_x = (cam.width + 7) / 8, n_tiles = tiles_x * ((cam.height + 7) / 8);
-    rtk_aov_kernel<real><<<dim3((n_tiles + 3) / 4), dim3(256), 0, stream>>>(sc, cam, seed, n_samples, tiles_x, n_tiles, reinterpret_cast<float4*>(d_aov));
+    const TileGrid grid = tile_grid(cam.width, cam.height);
+    rtk_guide_kernel<real, false><<<lane_grid(64ll * grid.n_tiles), dim3(256), 0, stream>>>(grid, sc, cam, seed, n_samples, 0, 0, reinterpret_cast<float4*>(d_aov));
     return hipGetLastError();
 }
 template hipError_t launch_aov<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, float*, hipStream_t);
@@ -2863,20 +2863,18 @@ template hipError_t launch_aov<float>(const SceneView<float>&, const CameraRec<f
 template <typename real>
 hipError_t launch_guides(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, int follow, int max_bounces, float* d_guides,
                          hipStream_t stream) {
-    const int tiles_x = (cam.width + 7) / 8, n_tiles = tiles_x * ((cam.height + 7) / 8);
-    rtk_guide_kernel<real><<<dim3((n_tiles + 3) / 4), dim3(256), 0, stream>>>(sc, cam, seed, n_samples, follow, max_bounces, tiles_x, n_tiles,
-                                                                               reinterpret_cast<float4*>(d_guides));
+    const TileGrid grid = tile_grid(cam.width, cam.height);
+    rtk_guide_kernel<real, true><<<lane_grid(64ll * grid.n_tiles), dim3(256), 0, stream>>>(grid, sc, cam, seed, n_samples, follow, max_bounces,
+                                                                                         reinterpret_cast<float4*>(d_guides));
     return hipGetLastError();
 }
 template hipError_t launch_guides<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, int, int, float*, hipStream_t);
 template hipError_t launch_guides<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, int, int, int, float*, hipStream_t);
 
-static dim3 query_grid(long long n) { return dim3((unsigned int)((n + 255) / 256)); }
-
 template <typename real>
 hipError_t launch_query_hits(const SceneView<real>& sc, uint32_t seed, long long n, const void* d_rays, void* d_hits, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    rtk_query_hits_kernel<real><<<query_grid(n), dim3(256), 0, stream>>>(sc, seed, n, static_cast<const double*>(d_rays), static_cast<double*>(d_hits));
+    rtk_query_hits_kernel<real><<<lane_grid(n), dim3(256), 0, stream>>>(sc, seed, n, static_cast<const double*>(d_rays), static_cast<double*>(d_hits));
     return hipGetLastError();
 }
 template hipError_t launch_query_hits<double>(const SceneView<double>&, uint32_t, long long, const void*, void*, hipStream_t);
@@ -2886,8 +2884,8 @@ template <typename real>
 hipError_t launch_query_occluded(const SceneView<real>& sc, uint32_t seed, bool any_hit, long long n, const void* d_rays, int32_t* d_occluded, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     const double* rays = static_cast<const double*>(d_rays);
-    if (any_hit) rtk_query_occluded_kernel<real, true><<<query_grid(n), dim3(256), 0, stream>>>(sc, seed, n, rays, d_occluded);
-    else rtk_query_occluded_kernel<real, false><<<query_grid(n), dim3(256), 0, stream>>>(sc, seed, n, rays, d_occluded);
+    if (any_hit) rtk_query_occluded_kernel<real, true><<<lane_grid(n), dim3(256), 0, stream>>>(sc, seed, n, rays, d_occluded);
+    else rtk_query_occluded_kernel<real, false><<<lane_grid(n), dim3(256), 0, stream>>>(sc, seed, n, rays, d_occluded);
     return hipGetLastError();
 }
 template hipError_t launch_query_occluded<double>(const SceneView<double>&, uint32_t, bool, long long, const void*, int32_t*, hipStream_t);
@@ -2899,8 +2897,8 @@ hipError_t launch_query_radiance(const SceneView<real>& sc, const CameraRec<real
     if (n <= 0) return hipSuccess;
     const double* rays = static_cast<const double*>(d_rays);
     real* out = static_cast<real*>(d_radiance);
-    if (d_draws) rtk_query_radiance_kernel<real, true><<<query_grid(n), dim3(256), 0, stream>>>(sc, cam, seed, n, rays, out, d_draws);
-    else rtk_query_radiance_kernel<real, false><<<query_grid(n), dim3(256), 0, stream>>>(sc, cam, seed, n, rays, out, nullptr);
+    if (d_draws) rtk_query_radiance_kernel<real, true><<<lane_grid(n), dim3(256), 0, stream>>>(sc, cam, seed, n, rays, out, d_draws);
+    else rtk_query_radiance_kernel<real, false><<<lane_grid(n), dim3(256), 0, stream>>>(sc, cam, seed, n, rays, out, nullptr);
     return hipGetLastError();
 }
 template hipError_t launch_query_radiance<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, long long, const void*, void*, uint32_t*, hipStream_t);

@@ -207,6 +207,65 @@ def test_hits_are_the_known_answer_entry_point_bit_for_bit(rt, renderer, tmp_pat
     assert n_hits > 500 and n_draws > 20                          # the comparison saw hits, and media that drew
 
 
+@pytest.mark.gpu
+def test_the_known_answer_entry_point_keys_every_ray_by_itself(rt, renderer, tmp_path):
+    """rtk_debug_closest_hit takes its seed per ray (keys[.][0]); query_hits takes one for the call.  On the media of the
+    known-answer scene -- the objects whose golden rows drew random numbers -- one closest_hit call with seed 7 on the even rows
+    and 11 on the odd ones equals, bit for bit and draw for draw, query_hits(seed=7) on the even rows and query_hits(seed=11) on
+    the odd ones, in F64 and F32.  A seed word taken from another ray, or from the wrong key, moves a medium's scattering
+    distance: at least one odd row's record differs from what seed 7 gives it."""
+    inp = np.load(os.path.join(GOLDEN, "kat_hit_in.npy"))
+    meta = np.load(os.path.join(GOLDEN, "kat_hit_meta.npy"))
+    blob = bytearray(open(os.path.join(GOLDEN, "kat_scene.rtks"), "rb").read())
+    media = [node for node in np.unique(meta[:, 0]) if (meta[meta[:, 0] == node, 3] > 0).any()]
+    assert media
+    for node in media:
+        rows = np.nonzero(meta[:, 0] == node)[0]
+        seeds = np.where(np.arange(len(rows)) % 2 == 0, 7, 11)
+        groups = {seed: np.nonzero(seeds == seed)[0] for seed in (7, 11)}
+        assert all(len(g) > 0 and meta[rows[g], 3].sum() > 0 for g in groups.values()), int(node)   # (the goldens' draws, seed 7)
+        blob[8:12] = np.int32(node).tobytes()                     # make this object the scene root
+        path = tmp_path / f"obj_{int(node)}.rtks"
+        path.write_bytes(bytes(blob))
+        renderer.upload(rt.Scene.load(str(path)))
+        keys = np.stack([seeds, meta[rows, 1], meta[rows, 2]], 1)
+        rays = rt.make_rays(inp[rows, 0:3], inp[rows, 3:6], time=inp[rows, 6], tmin=inp[rows, 7], tmax=inp[rows, 8], pixel=meta[rows, 1].astype(np.uint32),
+                            sample=meta[rows, 2].astype(np.uint32))
+        for mode in (rt.RTK_REAL_F64, rt.RTK_REAL_F32):
+            want, want_draws = renderer.closest_hit(inp[rows], keys, real_mode=mode)
+            for seed, g in groups.items():
+                hits = renderer.query_hits(rays[g], seed=seed, real_mode=mode)
+                assert _same_bits(_as_debug_records(hits), want[g]), (int(node), mode, seed)
+                assert np.array_equal(hits["draws"].astype(np.int64), want_draws[g].astype(np.int64)), (int(node), mode, seed)
+                assert int(want_draws[g].sum()) > 0, (int(node), mode, seed)
+            as_seven = _as_debug_records(renderer.query_hits(rays[groups[11]], seed=7, real_mode=mode))
+            assert not _same_bits(as_seven, want[groups[11]]), (int(node), mode)
+
+
+@pytest.mark.gpu
+def test_the_known_answer_entry_points_refuse_an_unknown_mode(rt, renderer, scenes):
+    """real_mode = 7 is RTK_ERR_INVALID from all four rtk_debug_* entry points, the function and the mode named; nothing is
+    written.  (rtk_debug_closest_hit once ran the float kernel for any mode that was not F64.)"""
+    lib = rt.hip_lib()
+    scene = scenes("three_spheres")
+    renderer.upload(scene)
+    cam = scene.camera(8, 8, 1, 5)
+    ray = np.array([[0.0, 0.0, 3.0, 0.0, 0.0, -1.0, 0.0, 0.001, np.inf]])
+    keys, ids, ijs = np.array([[7, 0, 0]], np.uint32), np.zeros(1, np.int32), np.zeros((1, 3), np.int32)
+    record, uvp = np.zeros((1, 11)), np.zeros((1, 5))
+    out, draws = np.full(14, 123.0), np.full(2, 99, np.uint64)
+    ptr = lambda a: a.ctypes.data  # noqa: E731
+    calls = {"rtk_debug_closest_hit": lambda m: lib.rtk_debug_closest_hit(renderer._ctx, m, 1, ptr(ray), ptr(keys), ptr(out), ptr(draws)),
+             "rtk_debug_scatter": lambda m: lib.rtk_debug_scatter(renderer._ctx, m, 1, ptr(ids), ptr(ray), ptr(record), ptr(keys), ptr(out), ptr(draws)),
+             "rtk_debug_texture": lambda m: lib.rtk_debug_texture(renderer._ctx, m, 1, ptr(ids), ptr(uvp), ptr(out), ptr(draws)),
+             "rtk_debug_get_ray": lambda m: lib.rtk_debug_get_ray(renderer._ctx, m, C.byref(cam), 7, 1, ptr(ijs), ptr(out), ptr(draws))}
+    for name, call in calls.items():
+        assert call(7) == -1, name                                # RTK_ERR_INVALID
+        assert lib.rtk_last_error().decode() == f"{name}: unknown real_mode 7"
+        assert np.all(out == 123.0) and np.all(draws == 99), name
+    assert calls["rtk_debug_closest_hit"](rt.RTK_REAL_F32) == 0 and out[0] == 1.0     # (the ray is a good one: it hits the middle sphere)
+
+
 def _box_quads(b, lo, hi, material):
     """box(a, b, mat) (quad.h:86-108): six quads, front first; returns (list node, index of the front quad)."""
     dx, dy, dz = (hi[0] - lo[0], 0, 0), (0, hi[1] - lo[1], 0), (0, 0, hi[2] - lo[2])
