@@ -376,10 +376,14 @@ static void build_mixed_program(const rtk_scene_desc& sc, const Program& prog, d
             double* cont = reinterpret_cast<double*>(rec + 1);
             cont[0] = s.radius;
             cont[1] = 1.0 / s.radius;
+            // radius * radius of sphere::hit (sphere.h:37): the same IEEE product the kernel formed in every sphere step, once
             if (kind == OP_SPHERE_MOVING) {
                 cont[2] = s.center_dir.x;
                 cont[3] = s.center_dir.y;
                 cont[4] = s.center_dir.z;  // first double of the third unit
+                cont[5] = s.radius * s.radius;
+            } else {
+                cont[2] = s.radius * s.radius;
             }
             rec->aux = (op.aux & 255u) | (uint32_t(s.material) << 8);
         }

@@ -100,8 +100,8 @@ inline constexpr int slots_of(uint32_t kind) {
 // every record carries the header at bytes 24..31, so the kind of the record at pc is always one 8-byte read away:
 //   OP_BOX            1 unit : f[0..5] = centre(3) and half-extent(3) as floats, the half-extent rounded up and grown
 //                              (see rtk_api.cpp); aux = pc (in bytes) to continue at when the slab test fails
-//   OP_SPHERE         2 units: d[0..2] = centre (f64); unit 1 = radius, 1/radius (f64)
-//   OP_SPHERE_MOVING  3 units: as OP_SPHERE; unit 1 also holds dx, dy; unit 2 holds dz (centre2 - centre1)
+//   OP_SPHERE         2 units: d[0..2] = centre (f64); unit 1 = radius, 1/radius, radius^2 (f64)
+//   OP_SPHERE_MOVING  3 units: d[0..2] = centre; unit 1 = radius, 1/radius, dx, dy; unit 2 = dz, radius^2 (centre2 - centre1)
 //   OP_END            1 unit
 // A culling box only decides which primitives get tested; the tests themselves, and so the hit, stay exact f64.
 struct alignas(16) MixedHead {

@@ -92,7 +92,8 @@ RTK_DEV float raw_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : 
 RTK_DEV float raw_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 RTK_DEV float raw_max3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 RTK_DEV float raw_min3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-template <typename real> RTK_DEV V3<real> unit_vector(V3<real> a) { return divide(a, rt_sqrt(length_squared(a))); }
+// (SHORT: see rtk_device_math.h sqrt_site; one guard on |a|^2 serves the square root and the division)
+template <bool SHORT = false, typename real> RTK_DEV V3<real> unit_vector(V3<real> a) { return scale(rcp_sqrt_site<SHORT>(length_squared(a)), a); }
 template <typename real> RTK_DEV bool near_zero(V3<real> a) {
     const real s = real(1e-8);
     return rt_fabs(a.x) < s && rt_fabs(a.y) < s && rt_fabs(a.z) < s;
@@ -112,10 +113,11 @@ RTK_DEV float pow5(float x) {
     return x2 * x2 * x;
 }
 template <typename real> RTK_DEV V3<real> reflect(V3<real> v, V3<real> n) { return v - scale(real(2) * dot(v, n), n); }  // vec3.h:125-127
-template <typename real> RTK_DEV V3<real> refract(V3<real> uv, V3<real> n, real eta) {                                  // vec3.h:128-133
+template <bool SHORT = false, typename real> RTK_DEV V3<real> refract(V3<real> uv, V3<real> n, real eta) {             // vec3.h:128-133
     real cos_theta = rt_fmin(dot(-uv, n), real(1));
     V3<real> perp = scale(eta, uv + scale(cos_theta, n));
-    V3<real> par = scale(-rt_sqrt(rt_fabs(real(1) - length_squared(perp))), n);
+    // (SHORT: |1 - |perp|^2| is exactly 0 at the critical angle and can be NaN -- guarded)
+    V3<real> par = scale(-sqrt_site<SHORT>(rt_fabs(real(1) - length_squared(perp))), n);
     return perp + par;
 }
 
@@ -166,13 +168,16 @@ RTK_DEV real rnd_pm1(uint32_t& s, Counters<COUNT>& cnt) {
     return real(int32_t(((w >> 22u) ^ w) >> 8) - 8388608) * real(1.0 / 8388608.0);
 }
 // vec3.h:107-115 -- always accepts; components drawn z, y, x.
-template <typename real, bool COUNT>
+// (SHORT: the components are multiples of 2^-23 in [-1, 1), so |p|^2 is 0 or within 2^-46 .. 3 -- admitted unless the draw is
+// (0, 0, 0), which must still give the reference's 0 * (1 / 0); the guard sends that wave to the full expansion.  With this
+// generator it never does: of the 2^32 states 256 draw a zero next and none draws two in a row.)
+template <typename real, bool SHORT = false, bool COUNT>
 RTK_DEV V3<real> random_unit_vector(uint32_t& s, Counters<COUNT>& cnt) {
     real c = rnd_pm1<real>(s, cnt);
     real b = rnd_pm1<real>(s, cnt);
     real a = rnd_pm1<real>(s, cnt);
     V3<real> p = mk(a, b, c);
-    return divide(p, rt_sqrt(length_squared(p)));
+    return scale(rcp_sqrt_site<SHORT>(length_squared(p)), p);
 }
 
 // ------------------------------------------------------------------ rays ------
@@ -368,14 +373,17 @@ RTK_DEV bool tie_inclusive_wins(const uint32_t* __restrict__ ranks, uint32_t pc,
 // TIE kernels: the interval test admits r == tmax as well -- the same two comparisons -- and only a root that was admitted
 // is then checked for being that tie, which `wins_tie()` (tie_sphere_wins on the lane's state) decides; a tie that loses is
 // a miss, exactly as in the reference, whose second root then lies beyond tmax.  The common path costs nothing extra.
-template <bool TIE = false, typename real, typename F>
-RTK_DEV bool sphere_root(V3<real> cc, real radius, V3<real> o, V3<real> d, real a, real inv_a, real tmin, real tmax, real& root, F&& wins_tie) {
+// radius2 = radius * radius (sphere.h:37), either formed by the caller or -- lean MIXED program -- the same product stored at
+// upload.  SHORT (rtk_device_math.h sqrt_site): the discriminant can be exactly 0 (a tangent ray) and nothing bounds it from
+// below after the cancellation, so the site is guarded.
+template <bool TIE = false, bool SHORT = false, typename real, typename F>
+RTK_DEV bool sphere_root(V3<real> cc, real radius2, V3<real> o, V3<real> d, real a, real inv_a, real tmin, real tmax, real& root, F&& wins_tie) {
     V3<real> oc = cc - o;
     real h = dot(d, oc);
-    real c = length_squared(oc) - radius * radius;
+    real c = length_squared(oc) - radius2;
     real disc = h * h - a * c;
     if (disc < real(0)) return false;
-    real sq = rt_sqrt(disc);
+    real sq = sqrt_site<SHORT>(disc);
     real r = divide_by(h - sq, a, inv_a);
     if constexpr (TIE) {
         if (!(tmin < r && r <= tmax)) {
@@ -394,7 +402,7 @@ RTK_DEV bool sphere_root(V3<real> cc, real radius, V3<real> o, V3<real> d, real 
 }
 template <typename real>
 RTK_DEV bool sphere_root(V3<real> cc, real radius, V3<real> o, V3<real> d, real a, real inv_a, real tmin, real tmax, real& root) {
-    return sphere_root<false>(cc, radius, o, d, a, inv_a, tmin, tmax, root, [] { return false; });
+    return sphere_root<false>(cc, radius * radius, o, d, a, inv_a, tmin, tmax, root, [] { return false; });
 }
 
 // quad::hit (quad.h:29-73) on the packed record n(3),D,Q(3),w(3),v(3),u(3).
@@ -545,7 +553,8 @@ RTK_DEV void begin_segment(Lane<real>& L, Counters<COUNT>& cnt, float extent = 0
         L.d = L.rd;
     }
     L.a = length_squared(L.rd);
-    L.inv_a = real(1) / L.a;
+    // (lean MIXED kernel, CH == 1: the guarded short reciprocal of rtk_device_math.h -- a = |d|^2 of a ray anyone may hand in)
+    L.inv_a = rcp_site<MIXED && CH == 1>(L.a);
     L.tmin = real(0.001);
     L.best_t = real_inf<real>();
     if constexpr (MIXED) {
@@ -604,11 +613,11 @@ RTK_DEV void take_hit(Lane<real>& L, real t, float extent = 0.0f) {
 }
 // The three primitive tests against the lane's current ray and interval, shared by every program layout: `units` is the
 // record's length in that layout; MIXED kernels keep the float copy of the interval in step.
-template <bool XF, bool MIXED, bool SCALED = false, typename real, bool COUNT, typename Tie>
-RTK_DEV void hit_sphere(Lane<real>& L, V3<real> cc, real radius, uint32_t units, Counters<COUNT>& cnt, const Tie& tie, float extent = 0.0f) {
+template <bool XF, bool MIXED, bool SCALED = false, bool SHORT = false, typename real, bool COUNT, typename Tie>
+RTK_DEV void hit_sphere(Lane<real>& L, V3<real> cc, real radius2, uint32_t units, Counters<COUNT>& cnt, const Tie& tie, float extent = 0.0f) {
     cnt.inc(C_SPHERE);
     real r;
-    if (sphere_root<Tie::enabled>(cc, radius, ray_o<XF>(L), ray_d<XF>(L), L.a, L.inv_a, L.tmin, L.best_t, r, [&] { return tie.sphere_wins(L.pc, L.best_pc); }))
+    if (sphere_root<Tie::enabled, SHORT>(cc, radius2, ray_o<XF>(L), ray_d<XF>(L), L.a, L.inv_a, L.tmin, L.best_t, r, [&] { return tie.sphere_wins(L.pc, L.best_pc); }))
         take_hit<MIXED, SCALED>(L, r, extent);
     L.pc += units;
 }
@@ -743,13 +752,13 @@ RTK_DEV void step_box_mixed_exact(Lane<real>& L, const MixedHead& rec, Counters<
 // sphere::hit on a MIXED record: centre in the head unit, radius in the next one.
 template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie>
 RTK_DEV void step_sphere_mixed(Lane<real>& L, const MixedHead& head, const MixedHead* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie, float extent) {
-    const double radius = reinterpret_cast<const double*>(rec + 1)[0];
-    hit_sphere<false, true, true>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), real(radius), 2u * PCU, cnt, tie, extent);
+    const double radius2 = reinterpret_cast<const double*>(rec + 1)[2];  // radius * radius from the upload: the same product, once
+    hit_sphere<false, true, true, true>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), real(radius2), 2u * PCU, cnt, tie, extent);
 }
 // ... and on a COMPACT record (3 units): the head (centre) is usually in registers already, the radius follows it.
 template <bool XF, typename real, bool COUNT, typename Tie>
 RTK_DEV void step_sphere_compact(Lane<real>& L, const MixedHead& head, const Unit16* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie) {
-    hit_sphere<XF, true>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), packed<real, 3>(rec), 3u, cnt, tie);
+    hit_sphere<XF, true>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), packed<real, 3>(rec) * packed<real, 3>(rec), 3u, cnt, tie);
 }
 // The remaining record kinds of a sphere-only program: a moving sphere, or a box for an irregular ray.
 template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie>
@@ -760,7 +769,7 @@ RTK_DEV void step_other_mixed(Lane<real>& L, const MixedHead* __restrict__ rec, 
     } else if (kind == OP_SPHERE_MOVING) {
         const double* cont = reinterpret_cast<const double*>(rec + 1);
         const V3<real> cc = mk(real(rec->d(0)), real(rec->d(1)), real(rec->d(2))) + scale(L.tm, mk(real(cont[2]), real(cont[3]), real(cont[4])));
-        hit_sphere<false, true, true>(L, cc, real(cont[0]), 3u * PCU, cnt, tie, extent);
+        hit_sphere<false, true, true, true>(L, cc, real(cont[5]), 3u * PCU, cnt, tie, extent);  // cont[5] = radius * radius
     } else {
         L.pc += uint32_t(mixed_units(kind)) * PCU;  // unreachable for a validated sphere-only program
     }
@@ -776,9 +785,9 @@ RTK_DEV void step_box(Lane<real>& L, const Slot<real>& rec, Counters<COUNT>& cnt
 }
 
 // sphere::hit of a stationary sphere.
-template <bool XF, typename real, bool COUNT, typename Tie>
+template <bool XF, bool SHORT = false, typename real, bool COUNT, typename Tie>
 RTK_DEV void step_sphere(Lane<real>& L, const Slot<real>& rec, Counters<COUNT>& cnt, const Tie& tie) {
-    hit_sphere<XF, false>(L, mk(rec.v[0], rec.v[1], rec.v[2]), rec.v[3], 1u, cnt, tie);
+    hit_sphere<XF, false, false, SHORT>(L, mk(rec.v[0], rec.v[1], rec.v[2]), rec.v[3] * rec.v[3], 1u, cnt, tie);
 }
 
 // Which COMPACT programs hold centre / half-extent box records: those of the mesh family -- the same rule
@@ -808,7 +817,7 @@ RTK_DEV void step_other(Lane<real>& L, const Rec* __restrict__ rec, const SceneV
         else step_box<true, XF>(L, *reinterpret_cast<const Slot<real>*>(rec), cnt);
     } else if (kind == OP_SPHERE_MOVING) {
         const V3<real> cc = packed3<real, 0>(rec) + scale(L.tm, moving_dir<real>(rec));
-        hit_sphere<XF, MIXED>(L, cc, packed<real, 3>(rec), rec_units<real>(rec, kind), cnt, tie);
+        hit_sphere<XF, MIXED>(L, cc, packed<real, 3>(rec) * packed<real, 3>(rec), rec_units<real>(rec, kind), cnt, tie);
     } else if ((FEAT & F_QUAD) && kind == OP_QUAD) {
         hit_quad<XF, MIXED>(L, rec, rec_units<real>(rec, kind), cnt, tie);
     } else if ((FEAT & F_TRI) && kind == OP_TRI) {
@@ -1190,7 +1199,11 @@ constexpr bool kNoRadianceState = (FEAT & F_LIGHTS) == 0;
 // material::scatter / emitted on a finished hit record (material.h:22-172) and the rest of ray_color's body
 // (Camera.txt:216-237): what shade() runs after it has built the record -- and what the known-answer entry point
 // rtk_debug_scatter runs on caller-supplied records.  Returns true when the sample's path has ended.
-template <typename real, uint32_t FEAT, int FORCE_KIND = -1, bool COUNT>
+// SHORT: the square roots and 1/t of the branches below take the guarded short forms of rtk_device_math.h -- by default in
+// the lean MIXED f64 kernel alone; rtk_debug_scatter's kernel asks for them too, so that the known-answer tests reach them.
+template <typename real, uint32_t FEAT>
+constexpr bool kShortMath = sizeof(real) == 8 && (FEAT & ~uint32_t(F_MATTE)) == (kFeatLean | uint32_t(F_F32_BOX));
+template <typename real, uint32_t FEAT, int FORCE_KIND = -1, bool SHORT = kShortMath<real, FEAT>, bool COUNT>
 RTK_DEV bool shade_surface(Lane<real>& L, const Surface<real>& sf, const SceneView<real>& sc, const MaterialRec<real>* __restrict__ mats,
                            Counters<COUNT>& cnt RTK_SHADE_PROF_PARAM) {
     RTK_SHADE_PROF_BEGIN
@@ -1211,20 +1224,21 @@ RTK_DEV bool shade_surface(Lane<real>& L, const Surface<real>& sf, const SceneVi
     constexpr bool kHoist = (FEAT & F_XFORM) == 0;
     V3<real> ruv = mk(real(0), real(0), real(0)), unit_in = rd;
     if constexpr (kHoist) {
-        if (mkind == RTK_MAT_LAMBERTIAN || mkind == RTK_MAT_METAL) ruv = random_unit_vector<real>(L.rng, cnt);
+        if (mkind == RTK_MAT_LAMBERTIAN || mkind == RTK_MAT_METAL) ruv = random_unit_vector<real, SHORT>(L.rng, cnt);
         if (mkind == RTK_MAT_METAL) unit_in = reflect(rd, sf.normal);
-        if (mkind == RTK_MAT_METAL || mkind == RTK_MAT_DIELECTRIC || ((FEAT & F_EXOTIC_MAT) && mkind == RTK_MAT_SPECULAR)) unit_in = unit_vector(unit_in);
+        // (SHORT: the direction of a ray anyone may hand in, 1e-150 or 1e150 long -- guarded on its squared length)
+        if (mkind == RTK_MAT_METAL || mkind == RTK_MAT_DIELECTRIC || ((FEAT & F_EXOTIC_MAT) && mkind == RTK_MAT_SPECULAR)) unit_in = unit_vector<SHORT>(unit_in);
     }
     if (mkind == RTK_MAT_LAMBERTIAN) {  // material.h:29-38
-        if constexpr (!kHoist) ruv = random_unit_vector<real>(L.rng, cnt);
+        if constexpr (!kHoist) ruv = random_unit_vector<real, SHORT>(L.rng, cnt);
         V3<real> dir = sf.normal + ruv;
         if (near_zero(dir)) dir = sf.normal;
         next_d = dir;
         attenuation = material_color<real, FEAT>(sc, m, sf.u, sf.v, sf.p, cnt);
     } else if (!(FEAT & F_MATTE) && mkind == RTK_MAT_METAL) {  // material.h:82-88
         if constexpr (!kHoist) {
-            ruv = random_unit_vector<real>(L.rng, cnt);
-            unit_in = unit_vector(reflect(rd, sf.normal));
+            ruv = random_unit_vector<real, SHORT>(L.rng, cnt);
+            unit_in = unit_vector<SHORT>(reflect(rd, sf.normal));
         }
         V3<real> fuzz = scale(m.param, ruv);
         next_d = unit_in + fuzz;
@@ -1235,10 +1249,10 @@ RTK_DEV bool shade_surface(Lane<real>& L, const Surface<real>& sf, const SceneVi
         // 1/refraction_index and Schlick's r0^2 for both faces are per-material constants: computed once at upload,
         // in double, by the same expressions (material.h:50,71-72)
         const real ri = sf.front_face ? m.albedo[0] : m.param;
-        if constexpr (!kHoist) unit_in = unit_vector(rd);
+        if constexpr (!kHoist) unit_in = unit_vector<SHORT>(rd);
         const V3<real> unit_d = unit_in;
         const real cos_theta = rt_fmin(dot(-unit_d, sf.normal), real(1));
-        const real sin_theta = rt_sqrt(real(1) - cos_theta * cos_theta);
+        const real sin_theta = sqrt_site<SHORT>(real(1) - cos_theta * cos_theta);  // (SHORT: exactly 0 at normal incidence -- guarded)
         bool reflect_it = ri * sin_theta > real(1);
         if (!reflect_it) {  // Schlick (material.h:69-74); the draw is skipped on total internal reflection
             const real r0 = sf.front_face ? m.albedo[1] : m.albedo[2];
@@ -1252,7 +1266,7 @@ RTK_DEV bool shade_surface(Lane<real>& L, const Surface<real>& sf, const SceneVi
             const real refl = r0 + (real(1) - r0) * pow5(omc);
             reflect_it = refl > rnd<real>(L.rng, cnt);
         }
-        next_d = reflect_it ? reflect(unit_d, sf.normal) : refract(unit_d, sf.normal, ri);
+        next_d = reflect_it ? reflect(unit_d, sf.normal) : refract<SHORT>(unit_d, sf.normal, ri);
     } else if ((FEAT & F_EXOTIC_MAT) && !(FEAT & F_MATTE) && mkind == RTK_MAT_ISOTROPIC) {  // material.h:129-134
         next_d = random_unit_vector<real>(L.rng, cnt);
         attenuation = material_color<real, FEAT>(sc, m, sf.u, sf.v, sf.p, cnt);
@@ -2135,7 +2149,7 @@ RTK_DEV void closest_hit_slots(Lane<real>& L, const SceneView<real>& sc, Counter
             if (L.box_kind == OP_BOX) step_box<false, true>(L, *rec, cnt);
             else step_box<true, true>(L, *rec, cnt);
         } else if (kind == OP_SPHERE) {
-            step_sphere<true>(L, *rec, cnt, tie);
+            step_sphere<true, sizeof(real) == 8>(L, *rec, cnt, tie);  // f64: the guarded short square root (rtk_device_math.h), which the known-answer tests reach here
         } else {
             step_other<real, kFeatAll>(L, rec, sc, cnt, tie);
         }
@@ -2256,7 +2270,7 @@ __global__ __launch_bounds__(256) void rtk_debug_scatter_kernel(SceneView<real> 
 #ifdef RTK_PROFILE
     ShadeProf sprof;  // (the profile build's shade functions take their sub-phase accumulators)
 #endif
-    const bool ended = shade_surface<real, kFeatAll>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG);
+    const bool ended = shade_surface<real, kFeatAll, -1, sizeof(real) == 8>(L, sf, sc, sc.materials, cnt RTK_SHADE_PROF_ARG);  // f64: with the short forms
     double* o = out + size_t(gid) * 14;
     o[0] = ended ? 0.0 : 1.0;
     o[1] = double(L.ro.x); o[2] = double(L.ro.y); o[3] = double(L.ro.z);
@@ -2372,6 +2386,9 @@ __global__ __launch_bounds__(256) void rtk_guide_kernel(TileGrid grid, SceneView
     const uint32_t seed_hash = pcg_hash(seed);
     const uint32_t pixel = uint32_t(j * cam.width + i);
     HitSums<real> first, end;
+#ifdef RTK_PROFILE
+    ShadeProf sprof;  // (the profile build's shade functions take their sub-phase accumulators)
+#endif
     for (int s = 0; s < n_samples; s++) {
         Lane<real> L;
         L.s = s;
