@@ -969,6 +969,67 @@ int rtk_query_hits_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, con
 int rtk_query_occluded_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, int32_t* h_occluded);
 int rtk_query_radiance_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, double* h_radiance, uint32_t* h_draws);
 
+/* Light probes ------------------------------------------------------------------------
+ * Baked diffuse lighting on top of the radiance query: a probe is a point that looks along a fixed sphere of directions, and
+ * what it sees is kept as nine spherical-harmonic coefficients per colour channel.  rtk_probe_bake makes the rays where they are
+ * used and reduces them where they land (one workgroup per probe); rtk_probe_irradiance turns a grid of probes into irradiance
+ * at points with normals.  Device resident and asynchronous, on the uploaded scene in either visiting order and both real modes.
+ *
+ * Basis: the real spherical harmonics up to l = 2 of a unit direction (x, y, z), in this order and with these constants:
+ *   Y0 = 0.28209479177387814          Y1 = 0.4886025119029199 y          Y2 = 0.4886025119029199 z
+ *   Y3 = 0.4886025119029199 x         Y4 = 1.0925484305920792 x y        Y5 = 1.0925484305920792 y z
+ *   Y6 = 0.31539156525252005 (3 z^2 - 1)   Y7 = 1.0925484305920792 x z   Y8 = 0.5462742152960396 (x^2 - y^2)
+ * Directions: a probe with R = opts->rays rays looks along d_j, j = 0 .. R-1, the same for every probe, computed in double with
+ * no fused operation and not renormalised:  z_j = 1 - (2j + 1) / R;  u_j = (j * 2654435769) mod 2^32;  phi_j = double(u_j) *
+ * (2 pi 2^-32);  r_j = sqrt(1 - z_j z_j);  d_j = (r_j cos phi_j, r_j sin phi_j, z_j)  (a spherical Fibonacci set).
+ * Rays and streams: with S = samples per ray, ray j of probe k is the record { origin = the probe's position, direction = d_j,
+ * time = opts->time, tmin = 0.001, tmax = +inf, pixel = first_key + k (32-bit wrap), sample = j * S, skip = 0 } -- what
+ * rtk_probe_rays writes, [n * rays] records, probe-major -- and its radiance L_kj is what rtk_query_radiance returns for that
+ * record with samples = S and the call's seed, max_depth and background.
+ * Coefficients (of radiance): c[k][i][ch] = (4 pi / R) sum_j L_kj[ch] Y_i(d_j), accumulated in double in both real modes and
+ * written as [n][9][3] reals of real_mode.  The sum has a fixed order -- each pass of 256 rays by a fixed tree inside each of the
+ * four waves, the passes in increasing j, then the four waves in wave order -- so the same call gives the same bits, and a
+ * probe's coefficients do not depend on the other probes of the call.
+ * Irradiance at a unit normal n (Ramamoorthi & Hanrahan 2001): E(n)[ch] = sum_i A_i c[i][ch] Y_i(n), A = pi for i = 0, 2 pi / 3
+ * for i = 1..3, pi / 4 for i = 4..8.  rtk_probe_irradiance interpolates the coefficients of the eight probes around each point
+ * trilinearly (a point outside the grid is clamped to it, an axis with one probe has weight 1) and evaluates E for the normal as
+ * given: no normalisation, nothing clamped at zero, no visibility term.  d_sh, d_points, d_normals and d_irradiance hold reals of
+ * real_mode; the arithmetic is in that type.
+ * Buffers: d_positions [n][3] doubles in both modes, 8-byte aligned; d_rays 8-byte aligned; reals need the alignment of their
+ * type (8 bytes in F64, 4 in F32).  A misaligned pointer is refused (the text names the argument) and nothing is launched.
+ * n == 0 / m == 0 is valid and launches nothing.  RTK_ERR_INVALID, checked first and without a device: null opts, grid,
+ * positions, points, normals or outputs; n or m < 0; n * rays, m or the grid's number of probes over 2^31 - 1; rays not a multiple
+ * of 256 in 256 .. 65536; negative max_depth or samples; reserved != 0 (opts and grid); an unknown real_mode; a grid count < 1; a
+ * spacing that is not > 0 as a real of real_mode (in F32 a positive double that rounds to 0 is refused); then a null context; then
+ * (rtk_probe_bake only) RTK_ERR_NO_SCENE.  rtk_probe_rays and rtk_probe_irradiance need a context for its device but no scene.
+ * The stream rules of rtk_render_device hold: every launch goes to the given stream, the call allocates nothing and never waits.
+ * The _host forms take host buffers (reals as doubles, F32 widened) and block. */
+#define RTK_PROBE_COEFFS 9
+typedef struct rtk_probe_opts {          /* 72 bytes */
+    uint32_t seed; int32_t real_mode;
+    int32_t max_depth;                   /* >= 0 */
+    int32_t samples;                     /* paths per ray; 0 = 1 */
+    int32_t rays;                        /* per probe; 0 = 1024; a multiple of 256 in 256 .. 65536 */
+    uint32_t first_key;                  /* probe k draws from the streams of pixel key first_key + k */
+    rtk_vec3 background;
+    double time;
+    void* stream;
+    int32_t reserved[2];                 /* 0 */
+} rtk_probe_opts;
+typedef struct rtk_probe_grid {          /* 64 bytes: probe (ix, iy, iz) sits at origin + (ix, iy, iz) * spacing,  */
+    rtk_vec3 origin, spacing;            /* its coefficients at index (iz * ny + iy) * nx + ix; spacing > 0 per axis */
+    int32_t counts[3]; int32_t reserved; /* nx, ny, nz >= 1 */
+} rtk_probe_grid;
+
+int rtk_probe_rays(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const double* d_positions, rtk_ray* d_rays);
+int rtk_probe_bake(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const double* d_positions, void* d_sh);
+int rtk_probe_irradiance(rtk_ctx* ctx, int real_mode, const rtk_probe_grid* grid, const void* d_sh, int64_t m, const void* d_points, const void* d_normals,
+                         void* d_irradiance, void* stream);
+int rtk_probe_rays_host(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const double* h_positions, rtk_ray* h_rays);
+int rtk_probe_bake_host(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const double* h_positions, double* h_sh);
+int rtk_probe_irradiance_host(rtk_ctx* ctx, int real_mode, const rtk_probe_grid* grid, const double* h_sh, int64_t m, const double* h_points,
+                              const double* h_normals, double* h_irradiance);
+
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and
  * hit-record code as the render kernel.  Host buffers:

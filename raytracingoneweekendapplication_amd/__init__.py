@@ -319,6 +319,48 @@ def _query_opts(seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, max_dept
     return QueryOpts(int(seed), int(real_mode), int(max_depth), int(samples), bg, stream or None, (C.c_int32 * 2)(0, 0))
 
 
+class ProbeOpts(C.Structure):
+    """rtk_probe_opts (include/rtk.h "Light probes")."""
+
+    _fields_ = [("seed", C.c_uint32), ("real_mode", C.c_int32), ("max_depth", C.c_int32), ("samples", C.c_int32), ("rays", C.c_int32),
+                ("first_key", C.c_uint32), ("background", Vec3), ("time", C.c_double), ("stream", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+class ProbeGrid(C.Structure):
+    """rtk_probe_grid (include/rtk.h): probe (ix, iy, iz) at origin + (ix, iy, iz) * spacing, index (iz * ny + iy) * nx + ix."""
+
+    _fields_ = [("origin", Vec3), ("spacing", Vec3), ("counts", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+PROBE_COEFFS = 9
+
+
+def _probe_opts(seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, max_depth: int = 0, samples: int = 0, rays: int = 0, first_key: int = 0,
+                background=(0.0, 0.0, 0.0), time: float = 0.0, stream: int = 0) -> ProbeOpts:
+    bg = background if isinstance(background, Vec3) else Vec3(*(float(c) for c in background))
+    return ProbeOpts(int(seed), int(real_mode), int(max_depth), int(samples), int(rays), int(first_key) & 0xFFFFFFFF, bg, float(time), stream or None,
+                     (C.c_int32 * 2)(0, 0))
+
+
+def probe_grid(origin, spacing, counts) -> ProbeGrid:
+    """A ``ProbeGrid`` from three (3,) sequences (a ``ProbeGrid`` is passed through)."""
+    if isinstance(origin, ProbeGrid):
+        return origin
+    return ProbeGrid(Vec3(*(float(c) for c in origin)), Vec3(*(float(c) for c in spacing)), (C.c_int32 * 3)(*(int(c) for c in counts)), 0)
+
+
+def probe_grid_positions(origin, spacing, counts):
+    """The probe positions of a grid, float64 (nx * ny * nz, 3), in the grid's index order: x fastest, then y, then z."""
+    import numpy as np
+
+    origin, spacing = np.asarray(origin, np.float64), np.asarray(spacing, np.float64)
+    nx, ny, nz = (int(c) for c in counts)
+    if origin.shape != (3,) or spacing.shape != (3,) or min(nx, ny, nz) < 1:
+        raise ValueError(f"probe_grid_positions: origin {origin.shape}, spacing {spacing.shape}, counts {(nx, ny, nz)} do not describe a grid")
+    iz, iy, ix = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    return origin + np.stack([ix.ravel(), iy.ravel(), iz.ravel()], 1).astype(np.float64) * spacing
+
+
 def host_lib() -> C.CDLL:
     """librtk_host.so: scene construction + flattening (no GPU needed)."""
     global _host_lib
@@ -466,6 +508,10 @@ def hip_lib() -> C.CDLL:
             for name in ("rtk_query_hits", "rtk_query_occluded", "rtk_query_hits_host", "rtk_query_occluded_host"):
                 getattr(lib, name).argtypes = query
             lib.rtk_query_radiance.argtypes = lib.rtk_query_radiance_host.argtypes = query + [C.c_void_p]
+            for name in ("rtk_probe_rays", "rtk_probe_bake", "rtk_probe_rays_host", "rtk_probe_bake_host"):
+                getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(ProbeOpts), C.c_int64, C.c_void_p, C.c_void_p]
+            lib.rtk_probe_irradiance_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(ProbeGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rtk_probe_irradiance.argtypes = lib.rtk_probe_irradiance_host.argtypes + [C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -799,6 +845,65 @@ class Renderer:
         given); asynchronous on ``stream``."""
         opts = _query_opts(seed, real_mode, max_depth, samples, background, stream)
         self._check(self._lib.rtk_query_radiance(self._ctx, C.byref(opts), int(n), d_rays or None, d_radiance or None, d_draws or None))
+
+    def probe_rays(self, positions, *, rays: int = 1024, samples: int = 1, first_key: int = 0, time: float = 0.0):
+        """rtk_probe_rays_host: the ray records (``ray_dtype``, (n * rays,), probe-major) that ``bake_probes`` traces for probes at
+        ``positions`` (n, 3): the fixed direction set, stream keys pixel = first_key + k, sample = j * samples."""
+        import numpy as np
+
+        (positions,) = _host_inputs("probe_rays", "(n, 3) probe positions", (positions, np.float64, (np.shape(positions)[0] if np.ndim(positions) else 0, 3)))
+        n = positions.shape[0]
+        opts = _probe_opts(samples=samples, rays=rays, first_key=first_key, time=time)
+        out = np.zeros(n * (opts.rays or 1024), ray_dtype())
+        self._check(self._lib.rtk_probe_rays_host(self._ctx, C.byref(opts), n, positions.ctypes.data, out.ctypes.data))
+        return out
+
+    def bake_probes(self, positions, *, max_depth: int, rays: int = 1024, samples: int = 1, background=(0.0, 0.0, 0.0), first_key: int = 0, time: float = 0.0,
+                    seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_probe_bake_host: SH coefficients of the radiance arriving at probes at ``positions`` (n, 3): float64 (n, 9, 3) --
+        F32 results widened -- c[k][i] = (4 pi / rays) sum_j L_kj Y_i(d_j) over the rays ``probe_rays`` returns."""
+        import numpy as np
+
+        (positions,) = _host_inputs("bake_probes", "(n, 3) probe positions", (positions, np.float64, (np.shape(positions)[0] if np.ndim(positions) else 0, 3)))
+        n = positions.shape[0]
+        out = np.zeros((n, PROBE_COEFFS, 3), np.float64)
+        opts = _probe_opts(seed, real_mode, max_depth, samples, rays, first_key, background, time)
+        self._check(self._lib.rtk_probe_bake_host(self._ctx, C.byref(opts), n, positions.ctypes.data, out.ctypes.data))
+        return out
+
+    def probe_irradiance(self, grid, sh, points, normals, *, real_mode: int = RTK_REAL_F64):
+        """rtk_probe_irradiance_host: irradiance float64 (m, 3) at ``points`` (m, 3) with ``normals`` (m, 3) from the coefficients
+        ``sh`` (nx * ny * nz, 9, 3) of the probes of ``grid`` (a ``ProbeGrid`` or (origin, spacing, counts))."""
+        import numpy as np
+
+        grid = grid if isinstance(grid, ProbeGrid) else probe_grid(*grid)
+        probes = max(grid.counts[0], 0) * max(grid.counts[1], 0) * max(grid.counts[2], 0)
+        m = np.shape(points)[0] if np.ndim(points) else 0
+        sh, points, normals = _host_inputs("probe_irradiance", f"a grid of {probes} probes and m points with normals", (sh, np.float64, (probes, PROBE_COEFFS, 3)),
+                                           (points, np.float64, (m, 3)), (normals, np.float64, (m, 3)))
+        out = np.zeros((m, 3), np.float64)
+        self._check(self._lib.rtk_probe_irradiance_host(self._ctx, real_mode, C.byref(grid), sh.ctypes.data, m, points.ctypes.data, normals.ctypes.data,
+                                                        out.ctypes.data))
+        return out
+
+    def probe_rays_device(self, n: int, d_positions: int, d_rays: int, *, rays: int = 1024, samples: int = 1, first_key: int = 0, time: float = 0.0,
+                          stream: int = 0) -> None:
+        """rtk_probe_rays with raw device pointers ([n][3] doubles in, n * rays rtk_ray records out); asynchronous on ``stream``."""
+        opts = _probe_opts(samples=samples, rays=rays, first_key=first_key, time=time, stream=stream)
+        self._check(self._lib.rtk_probe_rays(self._ctx, C.byref(opts), int(n), d_positions or None, d_rays or None))
+
+    def bake_probes_device(self, n: int, d_positions: int, d_sh: int, *, max_depth: int, rays: int = 1024, samples: int = 1, background=(0.0, 0.0, 0.0),
+                           first_key: int = 0, time: float = 0.0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_probe_bake with raw device pointers ([n][3] doubles in, [n][9][3] reals of ``real_mode`` out); asynchronous on ``stream``."""
+        opts = _probe_opts(seed, real_mode, max_depth, samples, rays, first_key, background, time, stream)
+        self._check(self._lib.rtk_probe_bake(self._ctx, C.byref(opts), int(n), d_positions or None, d_sh or None))
+
+    def probe_irradiance_device(self, grid, d_sh: int, m: int, d_points: int, d_normals: int, d_irradiance: int, *, real_mode: int = RTK_REAL_F64,
+                                stream: int = 0) -> None:
+        """rtk_probe_irradiance with raw device pointers (reals of ``real_mode`` throughout); asynchronous on ``stream``."""
+        grid = grid if isinstance(grid, ProbeGrid) else probe_grid(*grid)
+        self._check(self._lib.rtk_probe_irradiance(self._ctx, real_mode, C.byref(grid), d_sh or None, int(m), d_points or None, d_normals or None,
+                                                   d_irradiance or None, stream or None))
 
     def camera_rays(self, cam: Camera, seed: int, pixel_sample, real_mode: int = RTK_REAL_F64):
         """The render's own rays as ray records: ``debug_get_ray`` of ``pixel_sample`` [n][3] = i, j, sample, with the stream

@@ -43,6 +43,11 @@ inline int check_aligned16(const void* p, const char* who, const char* arg) {
     return aligned16(p) ? RTK_OK : fail(RTK_ERR_INVALID, "%s: %s must be 16-byte aligned", who, arg);
 }
 
+// Every other device buffer needs the alignment of its element type (`align`, a power of two); null is aligned.
+inline int check_aligned(const void* p, size_t align, const char* who, const char* arg) {
+    return (reinterpret_cast<uintptr_t>(p) & (align - 1)) == 0 ? RTK_OK : fail(RTK_ERR_INVALID, "%s: %s must be %zu-byte aligned", who, arg, align);
+}
+
 // The checks every image entry point makes of its size and arithmetic type: RTK_OK, or RTK_ERR_INVALID with the text in g_error.
 // The passes that take a camera say "bad camera dimensions", the ones that take a width and a height name the size.
 inline bool image_size_ok(int w, int h) { return w > 0 && h > 0 && w <= 65536 && h <= 65536; }

@@ -22,10 +22,6 @@ namespace {
 
 static_assert(sizeof(rtk_ray) == 88 && sizeof(rtk_ray_hit) == 96 && sizeof(rtk_query_opts) == 56, "ray query records");
 
-int check_aligned(const void* p, size_t align, const char* who, const char* arg) {
-    return (reinterpret_cast<uintptr_t>(p) & (align - 1)) == 0 ? RTK_OK : fail(RTK_ERR_INVALID, "%s: %s must be %zu-byte aligned", who, arg, align);
-}
-
 // include/rtk.h: outputs may not alias d_rays.  RTK_OK, or RTK_ERR_INVALID naming the output whose n elements of `bytes` each
 // share an address with the n ray records (a null output overlaps nothing).
 int check_apart(const void* rays, const void* out, int64_t n, size_t bytes, const char* who, const char* arg) {

@@ -1,5 +1,5 @@
 // rtk_trace.h -- launch entry points of the device code for the C-ABI layer: the render kernel and the lane-per-ray kernels
-// (known-answer, AOV / guide, ray query) of rtk_trace.hip and the frame-assembly kernels of rtk_frame.hip (tile order, resolve, accumulate, preview, noise statistics,
+// (known-answer, AOV / guide, ray query, light probes) of rtk_trace.hip and the frame-assembly kernels of rtk_frame.hip (tile order, resolve, accumulate, preview, noise statistics,
 // adaptive state, un-permute).
 #ifndef RTK_TRACE_H
 #define RTK_TRACE_H
@@ -102,6 +102,14 @@ hipError_t launch_query_occluded(const SceneView<real>& sc, uint32_t seed, bool 
 template <typename real>
 hipError_t launch_query_radiance(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, long long n, const void* d_rays, void* d_radiance,
                                  uint32_t* d_draws, hipStream_t stream);
+
+// Light probes (rtk_probe_rays / rtk_probe_bake): n probes at d_positions [n][3] doubles, `rays` rays each (a multiple of 256).
+// launch_probe_rays writes the n * rays ray records, one lane each; launch_probe_bake runs one workgroup per probe and writes
+// [n][9][3] reals.  cam carries background, max_depth and spp = samples per ray, as for launch_query_radiance.
+hipError_t launch_probe_rays(long long n, int rays, int samples, uint32_t first_key, double time, const double* d_positions, void* d_rays, hipStream_t stream);
+template <typename real>
+hipError_t launch_probe_bake(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, uint32_t first_key, int rays, double time, long long n,
+                             const double* d_positions, void* d_sh, hipStream_t stream);
 
 // A one-rank progressive session's preview and se (row-major) from its running sum and noise sums; tile_spp null = every tile
 // holds `done` samples.  Reads the state only.

@@ -2556,6 +2556,137 @@ __global__ __launch_bounds__(256) void rtk_query_radiance_kernel(SceneView<real>
     if constexpr (COUNT) draws[gid] = cnt.c[C_RNG];
 }
 
+// ------------------------------------------------------------------ light probes --
+// Baked SH radiance (include/rtk.h "Light probes"): the rays of a probe are made where they are used and reduced where they land.
+
+// Direction j of a probe with `rays` rays (a spherical Fibonacci set; the header has the formulas).  In double, not renormalised,
+// and with contraction off whatever the flags of the kernel it is inlined into: 1 - z z is the two-rounding form, and the bits
+// are the same in rtk_probe_rays_kernel and rtk_probe_bake_kernel.
+RTK_DEV void probe_direction(uint32_t j, int rays, double d[3]) {
+#pragma clang fp contract(off)
+    const double z = 1.0 - double(2u * j + 1u) / double(rays);
+    const uint32_t u = j * 2654435769u;                            // the golden ratio in 32-bit fixed point
+    const double phi = double(u) * (6.283185307179586476925286766559 * 0x1p-32);
+    const double r = rt_sqrt(1.0 - z * z);
+    d[0] = r * cos(phi);
+    d[1] = r * sin(phi);
+    d[2] = z;
+}
+
+// The nine real spherical harmonics up to l = 2 of d, in the header's order.
+RTK_DEV void probe_basis(const double d[3], double Y[9]) {
+#pragma clang fp contract(off)
+    const double x = d[0], y = d[1], z = d[2];
+    Y[0] = 0.28209479177387814;
+    Y[1] = 0.4886025119029199 * y;
+    Y[2] = 0.4886025119029199 * z;
+    Y[3] = 0.4886025119029199 * x;
+    Y[4] = 1.0925484305920792 * (x * y);
+    Y[5] = 1.0925484305920792 * (y * z);
+    Y[6] = 0.31539156525252005 * (3.0 * (z * z) - 1.0);
+    Y[7] = 1.0925484305920792 * (x * z);
+    Y[8] = 0.5462742152960396 * (x * x - y * y);
+}
+
+// The ray records of n probes, probe-major: lane gid writes ray gid % rays of probe gid / rays as eleven 8-byte words.
+__global__ __launch_bounds__(256) void rtk_probe_rays_kernel(long long n_rays, int rays, int spr, uint32_t first_key, double time,
+                                                              const double* __restrict__ positions, double* __restrict__ out) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= n_rays) return;
+    const long long k = gid / rays;
+    const uint32_t j = uint32_t(gid - k * rays);
+    double d[3];
+    probe_direction(j, rays, d);
+    const double* p = positions + k * 3;
+    double* o = out + gid * 11;
+    o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+    o[3] = d[0]; o[4] = d[1]; o[5] = d[2];
+    o[6] = time;
+    o[7] = 0.001;
+    o[8] = __builtin_inf();
+    uint2* keys = reinterpret_cast<uint2*>(o + 9);
+    keys[0] = make_uint2(first_key + uint32_t(k), j * uint32_t(spr));
+    keys[1] = make_uint2(0u, 0u);
+}
+
+// One workgroup of 256 per probe (blockIdx.x = k); lane t takes rays j = t, t + 256, ... (rays is a multiple of 256, so every
+// lane makes the same number of passes and reaches the barrier).  Per ray: the direction, the lane's ray as load_query_ray sets
+// it from the record rtk_probe_rays_kernel writes, rtk_query_radiance_kernel's sample loop, nine basis values and 27
+// products in double.  No accumulator is live across the path loop, whose register count stays the radiance query's: each pass of
+// 256 rays is reduced at once.  Reduction, in a fixed order: the 64 products of a wave by a butterfly (offsets 32, 16, .. 1),
+// which leaves the sum in every lane; lane c of the wave (c = 0 .. 26) adds sum c to the wave's running sum part[wave][c] in LDS
+// -- passes in increasing j; wave-private, so no barrier --; after one barrier lanes 0 .. 26 add the four waves' sums in wave
+// order, scale once by 4 pi / rays and store as `real`.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_probe_bake_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, uint32_t first_key, int rays, double time,
+                                                              const double* __restrict__ positions, real* __restrict__ sh) {
+    __shared__ double part[4][27];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const long long k = blockIdx.x;
+    if (lane < 27) part[wave][lane] = 0.0;
+    Counters<false> cnt;
+    cnt.clear();
+#ifdef RTK_PROFILE
+    ShadeProf sprof;
+#endif
+    const uint32_t seed_hash = pcg_hash(seed), pixel = first_key + uint32_t(k);
+    const double* p = positions + k * 3;
+    const V3<real> origin = mk(real(p[0]), real(p[1]), real(p[2]));
+    for (int j = t; j < rays; j += 256) {
+        V3<real> rd;
+        {
+            double d[3];
+            probe_direction(uint32_t(j), rays, d);
+            rd = mk(real(d[0]), real(d[1]), real(d[2]));
+        }
+        V3<real> sum = mk(real(0), real(0), real(0));
+        for (int s = 0; s < cam.spp; s++) {
+            Lane<real> L;
+            L.ro = origin;
+            L.rd = rd;
+            L.tm = real(time);
+            L.rng = stream_key(seed_hash, pixel, uint32_t(j) * uint32_t(cam.spp) + uint32_t(s));   // (skip = 0)
+            clear_parked(L);
+            L.segs = 0;
+            L.radiance = mk(real(0), real(0), real(0));
+            L.throughput = mk(real(1), real(1), real(1));
+            L.depth = cam.max_depth;
+            while (L.depth > 0) {
+                begin_segment<true>(L, cnt);
+                closest_hit_slots(L, sc, cnt);
+                const Slot<real>* hit_rec = sc.program + (L.best_pc != kNoHit ? L.best_pc : 0u);
+                if (shade<real, kFeatAll, false>(L, hit_rec, sc, sc.materials, cam, cnt RTK_SHADE_PROF_ARG)) break;
+            }
+            sum = sum + L.radiance;
+        }
+        const real ns = real(cam.spp);
+        const double rgb[3] = {double(sum.x / ns), double(sum.y / ns), double(sum.z / ns)};
+        double Y[9];
+        {
+            // The direction in double is computed again rather than kept in six registers across the path loop (the F32 kernel
+            // would drop from three waves per SIMD to two); the empty asm keeps the compiler from merging the two evaluations.
+            uint32_t j_again = uint32_t(j);
+            asm volatile("" : "+v"(j_again));
+            double d[3];
+            probe_direction(j_again, rays, d);
+            probe_basis(d, Y);
+        }
+        double mine = 0.0;
+        for (int i = 0; i < 9; i++)
+            for (int ch = 0; ch < 3; ch++) {
+                double v = rgb[ch] * Y[i];
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (lane == i * 3 + ch) mine = v;
+            }
+        if (lane < 27) part[wave][lane] += mine;
+    }
+    __syncthreads();
+    if (t < 27) {
+        const double total = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
+        sh[k * 27 + t] = real(total * (12.566370614359172953850573533118 / double(rays)));
+    }
+}
+
 // ------------------------------------------------------------------ launchers --
 
 // Geometry of a persistent launch: waves per workgroup and workgroups per CU so
@@ -2920,6 +3051,22 @@ hipError_t launch_query_radiance(const SceneView<real>& sc, const CameraRec<real
 }
 template hipError_t launch_query_radiance<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, long long, const void*, void*, uint32_t*, hipStream_t);
 template hipError_t launch_query_radiance<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, long long, const void*, void*, uint32_t*, hipStream_t);
+
+hipError_t launch_probe_rays(long long n, int rays, int samples, uint32_t first_key, double time, const double* d_positions, void* d_rays, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    rtk_probe_rays_kernel<<<lane_grid(n * rays), dim3(256), 0, stream>>>(n * rays, rays, samples, first_key, time, d_positions, static_cast<double*>(d_rays));
+    return hipGetLastError();
+}
+
+template <typename real>
+hipError_t launch_probe_bake(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, uint32_t first_key, int rays, double time, long long n,
+                             const double* d_positions, void* d_sh, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    rtk_probe_bake_kernel<real><<<dim3((unsigned int)n), dim3(256), 0, stream>>>(sc, cam, seed, first_key, rays, time, d_positions, static_cast<real*>(d_sh));
+    return hipGetLastError();
+}
+template hipError_t launch_probe_bake<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, uint32_t, int, double, long long, const double*, void*, hipStream_t);
+template hipError_t launch_probe_bake<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, uint32_t, int, double, long long, const double*, void*, hipStream_t);
 
 #ifdef RTK_ISA_PROBES
 // Instruction-cost probes (tools/isa_costs.py; never part of the product build): one kernel per unit of work of the lean

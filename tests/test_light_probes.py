@@ -1,0 +1,649 @@
+"""Light probes (include/rtk.h "Light probes"): SH radiance baked on the device, irradiance looked up from a grid of probes.
+
+This file carries its own restatement of the conventions -- the direction set, the basis, the A_i, the trilinear lookup -- in
+numpy float64 and uses nothing of the package for them.
+
+CPU tests: the six entry points are declared and exported and RTK_ABI_VERSION stays 2; the ctypes structures have the layout a C
+compiler gives the header's structs; every refusal comes back as RTK_ERR_INVALID naming its entry point, with no device and no
+context; the bake kernel has no more scratch and no fewer waves per SIMD than the radiance query of its mode (code-object
+metadata); the conventions themselves (Gram matrix of the basis over the direction set, E(n) = pi for L = 1).
+
+GPU tests, each in both visiting orders and both real modes (1 reads no scene, 5 neither scene nor order; 7 in the reference order, which
+is the C++ class's own):
+  1. the emitted rays are the restatement's (integers, origin, time, tmin, tmax, z exactly; x and y within 4 * 2^-53);
+  2. the bake is the radiance query over those rays, projected: within the classical summation bound, both orders, both modes;
+  3. edges: depth 0, a probe's place in the batch, the 32-bit wrap of the stream key, repeatability, the longest per-lane loop;
+  4. a probe that sees only sky: c0 = 2 sqrt(pi) background, E(n) = pi background;
+  5. the lookup against the restatement: inside, on probes, on faces, outside on every side; 1x1x1, 2x1x1, 2x3x2 grids;
+  6. carved, offset buffers with guard bytes on a caller stream; misaligned pointers and a missing scene; _host = device;
+  7. rtk::light_probes of the host C++ API (tests/helpers/light_probes_check.cpp).
+"""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests.conftest import GOLDEN, ROOT
+from tests.scene_cases import IMAGE_CASES, SCENE_SEED, scene_file
+
+PKG = os.path.join(ROOT, "raytracingoneweekendapplication_amd")
+ENTRY_POINTS = ("rtk_probe_rays", "rtk_probe_bake", "rtk_probe_irradiance", "rtk_probe_rays_host", "rtk_probe_bake_host", "rtk_probe_irradiance_host")
+CASES = {c[0]: c for c in IMAGE_CASES}
+ORDERS = ("reference", "fast")
+MODES = pytest.mark.parametrize("real_mode", [0, 1], ids=["f64", "f32"])
+U64, U32 = 2.0 ** -53, 2.0 ** -24
+SEED = 5
+
+# Probe positions off every surface (checked against host/scenes/scene_library.h: the Cornell boxes reach y = 330 and 165 and
+# stand clear of the first and third point; the spheres of three_spheres and material_zoo are at least 0.25 away).
+PROBES = {"cornell_box": [(278.0, 278.0, 278.0), (100.0, 400.0, 300.0), (450.0, 120.0, 80.0)],
+          "cornell_smoke": [(278.0, 278.0, 278.0), (100.0, 400.0, 300.0), (450.0, 120.0, 80.0)],
+          "three_spheres": [(0.0, 1.0, 0.0), (-2.0, 0.5, 1.0), (0.0, 0.25, -0.45)],
+          "material_zoo": [(0.0, 2.0, 2.0), (3.0, 1.5, 6.5), (-3.0, 0.5, 3.0)]}
+
+
+# ----------------------------------------------------------------------------------------- the conventions, restated --
+K0, K1, K2, K20, K22 = 0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396
+A = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+
+
+def directions(rays):
+    j = np.arange(rays, dtype=np.uint64)
+    z = 1.0 - (2 * j + 1).astype(np.float64) / np.float64(rays)
+    u = (j * np.uint64(2654435769)) % np.uint64(2 ** 32)
+    phi = u.astype(np.float64) * (2.0 * np.pi * 2.0 ** -32)
+    r = np.sqrt(1.0 - z * z)
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
+
+
+def basis(d):
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    return np.stack([np.full_like(x, K0), K1 * y, K1 * z, K1 * x, K2 * x * y, K2 * y * z, K20 * (3.0 * z * z - 1.0), K2 * x * z, K22 * (x * x - y * y)], -1)
+
+
+def irradiance(c, normals):
+    """E(n) [m][3] of coefficients c [9][3] (or [m][9][3]) at normals [m][3]."""
+    return np.einsum("i,ic,mi->mc" if c.ndim == 2 else "i,mic,mi->mc", A, c, basis(normals))
+
+
+def lookup(origin, spacing, counts, sh, points, normals):
+    """(E, B): the trilinear lookup [m][3] and B = sum |w_p A_i c_p,i Y_i(n)| of its terms, in float64."""
+    origin, spacing, counts = np.asarray(origin, np.float64), np.asarray(spacing, np.float64), np.asarray(counts)
+    g = np.clip((points - origin) / spacing, 0.0, counts - 1.0)
+    i0 = np.minimum(np.floor(g).astype(np.int64), np.maximum(counts - 2, 0))
+    f = g - i0
+    ay = A * basis(normals)                                                    # [m][9]
+    e, b = np.zeros((len(points), 3)), np.zeros((len(points), 3))
+    for corner in range(8):
+        d = np.array([corner & 1, (corner >> 1) & 1, corner >> 2])
+        idx = np.minimum(i0 + d, counts - 1)
+        w = np.prod(np.where(d == 1, f, 1.0 - f), axis=1)
+        terms = w[:, None, None] * ay[:, :, None] * sh[(idx[:, 2] * counts[1] + idx[:, 1]) * counts[0] + idx[:, 0]]
+        e += terms.sum(1)
+        b += np.abs(terms).sum(1)
+    return e, b
+
+
+def unit_normals(m, seed):
+    v = np.random.default_rng(seed).standard_normal((m, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+# ------------------------------------------------------------------------------------------------------------- CPU --
+def test_conventions_in_numpy():
+    """(4 pi / R) sum_j Y_a(d_j) Y_b(d_j) is the identity to 2e-3 at R = 256 (observed 1.3e-3; 1.8e-4 at 1024, 3.2e-7 at 65536),
+    and a probe that sees L = 1 everywhere has E(n) / pi within 1e-3 of 1 over 64 normals."""
+    worst = {}
+    for rays in (256, 1024, 65536):
+        y = basis(directions(rays))
+        worst[rays] = float(np.abs(4.0 * np.pi / rays * y.T @ y - np.eye(9)).max())
+    print("Gram matrix - identity:", worst)
+    assert worst[256] <= 2e-3 and worst[1024] <= 3e-4 and worst[65536] <= 1e-6
+    d = directions(256)
+    assert np.abs(np.linalg.norm(d, axis=1) - 1.0).max() < 4 * U64 and d[0, 2] == 1.0 - 1.0 / 256 and np.array_equal(d[0, :2], [np.sqrt(1 - d[0, 2] ** 2), 0.0])
+    c = 4.0 * np.pi / 256 * basis(d).sum(0)[:, None] * np.ones(3)              # L = 1
+    e = irradiance(c, unit_normals(64, 1))
+    print("L = 1: worst |E / pi - 1| = %.2e" % np.abs(e / np.pi - 1.0).max())
+    assert np.abs(e / np.pi - 1.0).max() <= 1e-3
+
+
+def test_entry_points_are_declared_and_exported(rt):
+    header = open(os.path.join(ROOT, "include", "rtk.h")).read()
+    assert "#define RTK_ABI_VERSION 2" in header and "#define RTK_PROBE_COEFFS 9" in header and "Light probes ---" in header
+    for name in ENTRY_POINTS:
+        assert re.search(r"\bint %s\(rtk_ctx\* ctx, " % name, header), name
+    lib = C.CDLL(rt.HIP_LIB_PATH)                                 # loads without a GPU
+    missing = [n for n in ENTRY_POINTS if not hasattr(lib, n)]
+    assert not missing, missing
+    assert lib.rtk_abi_version() == 2 and rt.PROBE_COEFFS == 9
+    import __graft_entry__
+
+    assert "rtk_probe.cpp" in __graft_entry__.HIP_SOURCES and "rtk_probe.hip" in __graft_entry__.HIP_SOURCES
+    for method in ("probe_rays", "bake_probes", "probe_irradiance", "probe_rays_device", "bake_probes_device", "probe_irradiance_device"):
+        assert callable(getattr(rt.Renderer, method)), method
+    assert "rtk_light_probes.h" in open(os.path.join(PKG, "host", "rtk_scene_api.h")).read()
+    pos = rt.probe_grid_positions((1.0, 2.0, 3.0), (0.5, 1.0, 2.0), (2, 3, 2))
+    assert pos.shape == (12, 3) and np.array_equal(pos[1], [1.5, 2.0, 3.0]) and np.array_equal(pos[2], [1.0, 3.0, 3.0]) and np.array_equal(pos[6], [1.0, 2.0, 5.0])
+    with pytest.raises(ValueError):
+        rt.probe_grid_positions((1.0, 2.0), (0.5, 1.0, 2.0), (2, 3, 2))
+    for call in (lambda: rt.Renderer.probe_rays(None, np.zeros((2, 2))), lambda: rt.Renderer.bake_probes(None, np.zeros(3), max_depth=1),
+                 lambda: rt.Renderer.probe_irradiance(None, ((0, 0, 0), (1, 1, 1), (2, 1, 1)), np.zeros((1, 9, 3)), np.zeros((4, 3)), np.zeros((4, 3))),
+                 lambda: rt.Renderer.probe_irradiance(None, ((0, 0, 0), (1, 1, 1), (2, 1, 1)), np.zeros((2, 9, 3)), np.zeros((4, 3)), np.zeros((5, 3)))):
+        with pytest.raises(ValueError):
+            call()
+
+
+STRUCTS = {"rtk_probe_opts": "ProbeOpts", "rtk_probe_grid": "ProbeGrid"}
+
+
+def test_structures_have_the_headers_layout(rt, tmp_path):
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "rtk.h"', "int main(void) {"]
+    for cname, pyname in STRUCTS.items():
+        lines.append('    printf("%s size %%zu\\n", sizeof(%s));' % (cname, cname))
+        for field, _ in getattr(rt, pyname)._fields_:
+            lines.append('    printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, field, cname, field))
+    lines += ["    return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    want = {}
+    for line in subprocess.check_output([str(exe)]).decode().splitlines():
+        cname, field, value = line.split()
+        want[(cname, field)] = int(value)
+    assert (want["rtk_probe_opts", "size"], want["rtk_probe_grid", "size"]) == (72, 64)
+    for cname, pyname in STRUCTS.items():
+        s = getattr(rt, pyname)
+        assert C.sizeof(s) == want[cname, "size"], cname
+        for field, _ in s._fields_:
+            assert getattr(s, field).offset == want[cname, field], (cname, field)
+
+
+def _opts(rt, **kw):
+    o = rt.ProbeOpts(7, 0, 5, 1, 256, 0, rt.Vec3(0.5, 0.5, 0.5), 0.0, None, (C.c_int32 * 2)(0, 0))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _grid(rt, counts=(2, 1, 1), spacing=(1.0, 1.0, 1.0), reserved=0):
+    return rt.ProbeGrid(rt.Vec3(0.0, 0.0, 0.0), rt.Vec3(*spacing), (C.c_int32 * 3)(*counts), reserved)
+
+
+def test_refusals_need_no_device(rt):
+    """Every refusal is RTK_ERR_INVALID with the entry point and the argument named, with a null context: the argument checks
+    come before anything that needs a device.  Nothing is written."""
+    lib = rt.hip_lib()
+    err = lambda: lib.rtk_last_error().decode()  # noqa: E731
+    pos = np.zeros((4, 3))
+    out = np.full(4 * 256 * 88 + 16, 0x5A, np.uint8)               # large enough for the rays of four probes
+    out_ptr = out.ctypes.data + (-out.ctypes.data) % 8
+    bad_opts = [(dict(real_mode=2), "real_mode"), (dict(real_mode=-1), "real_mode"), (dict(max_depth=-1), "max_depth"), (dict(samples=-1), "samples"),
+                (dict(reserved=(C.c_int32 * 2)(1, 0)), "reserved"), (dict(reserved=(C.c_int32 * 2)(0, -5)), "reserved"),
+                (dict(rays=255), "rays"), (dict(rays=128), "rays"), (dict(rays=257), "rays"), (dict(rays=1000), "rays"), (dict(rays=65536 + 256), "rays"), (dict(rays=-256), "rays")]
+    for name in ("rtk_probe_rays", "rtk_probe_bake", "rtk_probe_rays_host", "rtk_probe_bake_host"):
+        fn = getattr(lib, name)
+        host = name.endswith("_host")
+        good = C.byref(_opts(rt))
+        for fields, word in bad_opts:
+            assert fn(None, C.byref(_opts(rt, **fields)), 4, pos.ctypes.data, out_ptr) == -1, (name, fields)
+            assert word in err() and err().startswith(name + ":"), (name, fields, err())
+        assert fn(None, None, 4, pos.ctypes.data, out_ptr) == -1 and "null opts" in err() and err().startswith(name + ":")
+        assert fn(None, good, -1, pos.ctypes.data, out_ptr) == -1 and " n " in err() and err().startswith(name + ":"), err()
+        for rays, n in ((256, 2 ** 23), (65536, 2 ** 15), (0, 2 ** 21), (256, 2 ** 40)):    # n * rays = 2^31 (rays 0 = 1024) and beyond
+            assert fn(None, C.byref(_opts(rt, rays=rays)), n, pos.ctypes.data, out_ptr) == -1 and "n * rays" in err() and err().startswith(name + ":"), (name, rays, n, err())
+        assert fn(None, C.byref(_opts(rt, rays=65536)), 2 ** 15 - 1, pos.ctypes.data, out_ptr) == -1 and "null context" in err()   # 2^31 - 65536 rays: fine
+        assert fn(None, good, 4, None, out_ptr) == -1 and ("null h_positions" if host else "null d_positions") in err() and err().startswith(name + ":")
+        assert fn(None, good, 4, pos.ctypes.data, None) == -1 and re.search(r"null [dh]_(rays|sh)", err()) and err().startswith(name + ":"), err()
+        if not host:
+            assert fn(None, good, 4, pos.ctypes.data + 4, out_ptr) == -1 and "d_positions" in err() and "aligned" in err(), err()
+            assert fn(None, good, 4, pos.ctypes.data, out_ptr + 4) == -1 and "aligned" in err() and "d_positions" not in err(), err()
+        if name == "rtk_probe_bake":                              # F32 coefficients need 4 bytes only
+            f32 = C.byref(_opts(rt, real_mode=1))
+            assert fn(None, f32, 4, pos.ctypes.data, out_ptr + 4) == -1 and "null context" in err()
+            assert fn(None, f32, 4, pos.ctypes.data, out_ptr + 2) == -1 and "d_sh" in err()
+        for n in (4, 0):
+            assert fn(None, good, n, pos.ctypes.data, out_ptr) == -1 and "null context" in err() and err().startswith(name + ":"), (name, err())
+    sh, pts = np.zeros((2, 9, 3)), np.zeros((4, 3))
+    for name in ("rtk_probe_irradiance", "rtk_probe_irradiance_host"):
+        fn = getattr(lib, name)
+        host = name.endswith("_host")
+        extra = () if host else (None,)
+        call = lambda mode, grid, s, m, p, n, o: fn(None, mode, grid, s, m, p, n, o, *extra)  # noqa: E731
+        args = (sh.ctypes.data, 4, pts.ctypes.data, pts.ctypes.data, out_ptr)
+        good = C.byref(_grid(rt))
+        for mode in (2, -1):
+            assert call(mode, good, *args) == -1 and "real_mode" in err() and err().startswith(name + ":")
+        assert call(0, None, *args) == -1 and "null grid" in err() and err().startswith(name + ":")
+        for counts in ((0, 1, 1), (2, -1, 1), (2, 1, 0)):
+            assert call(0, C.byref(_grid(rt, counts=counts)), *args) == -1 and "counts" in err() and err().startswith(name + ":"), err()
+        for spacing in ((0.0, 1.0, 1.0), (1.0, -2.0, 1.0), (1.0, 1.0, float("nan"))):
+            assert call(0, C.byref(_grid(rt, spacing=spacing)), *args) == -1 and "spacing" in err() and err().startswith(name + ":"), err()
+        assert call(0, C.byref(_grid(rt, reserved=3)), *args) == -1 and "reserved" in err()
+        tiny = C.byref(_grid(rt, spacing=(1.0, 1e-50, 1.0)))      # positive as a double, 0 as a float: no spacing for the F32 kernel
+        assert call(1, tiny, *args) == -1 and "spacing" in err() and err().startswith(name + ":"), err()
+        assert call(0, tiny, *args) == -1 and "null context" in err()
+        assert call(0, good, sh.ctypes.data, -1, pts.ctypes.data, pts.ctypes.data, out_ptr) == -1 and " m " in err() and err().startswith(name + ":")
+        for k, word in ((0, "sh"), (2, "points"), (3, "normals"), (4, "irradiance")):
+            a = list(args)
+            a[k] = None
+            assert call(0, good, *a) == -1 and re.search(r"null [dh]_" + word, err()) and err().startswith(name + ":"), (name, word, err())
+            if not host:
+                a[k] = args[k] + 4
+                assert call(0, good, *a) == -1 and "d_" + word in err() and "aligned" in err(), (name, word, err())
+                assert call(1, good, *a) == -1 and "null context" in err()          # F32: 4 bytes are enough
+        for m in (4, 0):
+            assert call(0, good, sh.ctypes.data, m, pts.ctypes.data, pts.ctypes.data, out_ptr) == -1 and "null context" in err() and err().startswith(name + ":")
+    assert np.all(out == 0x5A)
+
+
+def _kernel_metadata(hip_lib_path, tmp_dir):
+    """{kernel symbol: {vgpr, scratch, lds}} of the gfx950 code object inside librtk_hip.so (its metadata notes); None where
+    ROCm's LLVM binary tools are missing."""
+    from tests.kernel_matrix import _LLVM
+
+    tools = [os.path.join(_LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
+    if not all(os.path.exists(t) for t in tools):
+        return None
+    fat, dev = os.path.join(str(tmp_dir), "fat.bin"), os.path.join(str(tmp_dir), "dev.co")
+    subprocess.check_call([tools[0], f"--dump-section=.hip_fatbin={fat}", hip_lib_path, os.path.join(str(tmp_dir), "copy.so")])
+    subprocess.check_call([tools[1], "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={dev}", "--unbundle"])
+    notes = subprocess.check_output([tools[2], "--notes", dev], text=True)
+    out = {}
+    for block in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:     # one block per kernel: .agpr_count is its first key
+        get = lambda key: int(re.search(r"\.%s:\s*(\d+)" % key, block).group(1))  # noqa: E731
+        name = re.search(r"\.name:\s*(\S+)", block).group(1)
+        out[name] = {"vgpr": get("vgpr_count"), "scratch": get("private_segment_fixed_size"), "lds": get("group_segment_fixed_size")}
+    return out
+
+
+def _waves_per_simd(k):
+    """gfx950: 512 unified registers per SIMD lane in granules of 8, at most 8 waves; 160 KB of LDS per CU, workgroups of four
+    waves, one per SIMD."""
+    by_registers = min(8, 512 // (-(-k["vgpr"] // 8) * 8))
+    return min(by_registers, (160 * 1024) // max(k["lds"], 1))
+
+
+def test_the_bake_kernel_keeps_the_querys_resources(rt, tmp_path):
+    """rtk_probe_bake_kernel<real> has no more scratch and no fewer waves per SIMD than rtk_query_radiance_kernel<real, false>:
+    nothing of the reduction is live across the path loop.  (DESIGN: 32 B and 2 waves in F64, 16 B and 3 waves in F32.)"""
+    meta = _kernel_metadata(rt.HIP_LIB_PATH, tmp_path)
+    assert meta is not None, "ROCm's LLVM binary tools (llvm-objcopy, clang-offload-bundler, llvm-readelf) belong to the toolchain that built the library"
+    for tag, scratch, waves in (("d", 32, 2), ("f", 16, 3)):
+        bake = [v for k, v in meta.items() if re.search(r"rtk_probe_bake_kernelI%sE" % tag, k)]
+        query = [v for k, v in meta.items() if re.search(r"rtk_query_radiance_kernelI%sLb0EE" % tag, k)]
+        assert len(bake) == 1 and len(query) == 1, sorted(meta)[:8]
+        print(tag, "bake", bake[0], _waves_per_simd(bake[0]), "query", query[0], _waves_per_simd(query[0]))
+        assert (query[0]["scratch"], _waves_per_simd(query[0])) == (scratch, waves)
+        assert bake[0]["scratch"] <= query[0]["scratch"] and _waves_per_simd(bake[0]) >= _waves_per_simd(query[0])
+    assert any("rtk_probe_rays_kernel" in k for k in meta)
+
+
+# ------------------------------------------------------------------------------------------------------------- GPU --
+@pytest.fixture(scope="module")
+def scenes(rt):
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = rt.Scene.build(name, SCENE_SEED, scene_file(name, GOLDEN))
+        return cache[name]
+    return get
+
+
+def _upload(renderer, scene, order):
+    if order == "fast":
+        renderer.upload_fast(scene, scene.camera(8, 8, 1, 1).center)
+    else:
+        renderer.upload(scene)
+
+
+def _same_bits(a, b):
+    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def _projected(rt, renderer, positions, *, rays, samples, max_depth, background, first_key=0, real_mode=0, seed=SEED):
+    """(want, bound): the radiance query over the emitted rays, projected in numpy float64, and the bound of test 2."""
+    records = renderer.probe_rays(positions, rays=rays, samples=samples, first_key=first_key)
+    radiance = renderer.query_radiance(records, max_depth=max_depth, background=background, samples=samples, seed=seed, real_mode=real_mode)
+    n = len(positions)
+    terms = radiance.reshape(n, rays, 1, 3) * basis(records["direction"]).reshape(n, rays, 9, 1)
+    want = 4.0 * np.pi / rays * terms.sum(1)
+    bound = (rays + 8) * U64 * (4.0 * np.pi / rays) * np.abs(terms).sum(1)
+    if real_mode == rt.RTK_REAL_F32:
+        bound = bound + U32 * np.abs(want)
+    return want, bound
+
+
+@pytest.mark.gpu
+def test_emitted_rays_are_the_restatement(rt, renderer):
+    """Needs no scene.  Integer fields, origin, time, tmin, tmax and z exactly; x and y within 4 * 2^-53: beyond the two-rounding
+    r the device and numpy differ only in sin / cos, each within one ulp of a value at most 1, and one rounding of the product.
+    Observed on the MI355X: 1.000 * 2^-53."""
+    r = rt.Renderer(0)                                            # a context without a scene
+    worst = 0.0
+    for n in (1, 3):
+        for rays in (256, 768):
+            for samples in (1, 2):
+                positions = np.array(PROBES["cornell_box"][:n]) + 0.1
+                got = r.probe_rays(positions, rays=rays, samples=samples, first_key=2 ** 32 - 2, time=0.375)
+                assert got.shape == (n * rays,) and got.dtype == rt.ray_dtype()
+                k, j = np.repeat(np.arange(n), rays), np.tile(np.arange(rays), n)
+                d = directions(rays)[j]
+                assert np.array_equal(got["origin"], positions[k]) and np.all(got["time"] == 0.375) and np.all(got["tmin"] == 0.001) and np.all(got["tmax"] == np.inf)
+                assert np.array_equal(got["pixel"], ((2 ** 32 - 2 + k) % 2 ** 32).astype(np.uint32)) and np.array_equal(got["sample"], (j * samples).astype(np.uint32))
+                assert not got["skip"].any() and not got["reserved"].any()
+                assert np.array_equal(got["direction"][:, 2], d[:, 2])
+                worst = max(worst, float(np.abs(got["direction"][:, :2] - d[:, :2]).max()))
+    print("emitted rays: worst |x, y - numpy| = %.3f * 2^-53" % (worst / U64))
+    assert worst <= 4 * U64
+    assert len(r.probe_rays(np.zeros((0, 3)))) == 0
+    r.close()
+
+
+@pytest.mark.gpu
+@MODES
+@pytest.mark.parametrize("name", ["three_spheres", "cornell_box", "cornell_smoke", "material_zoo"])
+def test_the_bake_is_the_query_projected(rt, renderer, scenes, name, real_mode):
+    """n = 3, R in {256, 512}, S in {1, 2}, the case's depth, both orders: |got - want| <= (R + 8) 2^-53 (4 pi / R) sum_j |L_j
+    Y_i(d_j)| per coefficient -- the classical bound for any summation order, with or without fused multiply-adds; the 8 covers
+    the basis evaluation and the final scale -- plus 2^-24 |want| for the final rounding in F32, where L is the F32 query's.
+    The ray-query tests hold the query to the oracle, so this chain holds the bake to it.  Observed on the MI355X: worst ratio
+    to the bound 0.18 in F64 and 0.96 in F32, where the final rounding to float is the bound."""
+    scene = scenes(name)
+    depth = CASES[name][4]
+    bg = scene.camera(8, 8, 1, depth).background
+    positions = np.array(PROBES[name])
+    worst, results = 0.0, {}
+    for order in ORDERS:
+        _upload(renderer, scene, order)
+        for rays in (256, 512):
+            for samples in (1, 2):
+                got = renderer.bake_probes(positions, max_depth=depth, rays=rays, samples=samples, background=bg, seed=SEED, real_mode=real_mode)
+                want, bound = _projected(rt, renderer, positions, rays=rays, samples=samples, max_depth=depth, background=bg, real_mode=real_mode)
+                assert got.shape == (3, 9, 3) and np.isfinite(got).all() and np.abs(want[:, 0]).min() > 0
+                ratio = np.abs(got - want) / np.where(bound > 0, bound, 1.0)
+                worst = max(worst, float(ratio.max()))
+                assert np.all(np.abs(got - want) <= bound), (order, rays, samples, float(ratio.max()))
+                results[order, rays, samples] = got
+    print(f"{name} mode {real_mode}: worst |bake - projected query| / bound = {worst:.3f}")
+    if real_mode == rt.RTK_REAL_F64:                              # the visiting order changes nothing a caller sees
+        assert all(_same_bits(results["reference", r, s], results["fast", r, s]) for r in (256, 512) for s in (1, 2))
+    assert not _same_bits(results["reference", 256, 1], results["reference", 256, 2])
+
+
+@pytest.mark.gpu
+@MODES
+@pytest.mark.parametrize("order", ORDERS)
+def test_stream_keys_and_shapes_at_their_edges(rt, renderer, scenes, real_mode, order):
+    import torch
+
+    name = "material_zoo"
+    scene = scenes(name)
+    depth = CASES[name][4]
+    bg = scene.camera(8, 8, 1, depth).background
+    p = np.array(PROBES[name])
+    _upload(renderer, scene, order)
+    bake = lambda positions, **kw: renderer.bake_probes(positions, **{**dict(max_depth=depth, rays=256, samples=2, background=bg, seed=SEED, real_mode=real_mode), **kw})  # noqa: E731
+    assert not bake(p, max_depth=0).any()                         # depth 0: black
+    batch = bake(p, first_key=7)
+    assert batch.any() and _same_bits(batch[2], bake(p[2:], first_key=9)[0])          # a probe's place in the batch does not matter
+    assert not _same_bits(batch[2], bake(p[2:], first_key=7)[0])                      # ... its key does
+    wrapped = bake(p[[0, 1]], first_key=2 ** 32 - 1)              # probe 1 has key 0
+    assert _same_bits(wrapped[1], bake(p[1:2], first_key=0)[0]) and _same_bits(wrapped[0], bake(p[0:1], first_key=2 ** 32 - 1)[0])
+    # the same bake twice, the second through the device form on a caller stream: the same bits
+    real = np.float64 if real_mode == rt.RTK_REAL_F64 else np.float32
+    dev = torch.device("cuda:0")
+    d_pos = torch.from_numpy(p.copy()).to(dev)
+    d_sh = torch.zeros(3 * 27, dtype=torch.float64 if real is np.float64 else torch.float32, device=dev)
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(stream):
+        renderer.bake_probes_device(3, d_pos.data_ptr(), d_sh.data_ptr(), max_depth=depth, rays=256, samples=2, background=bg, first_key=7, seed=SEED,
+                                    real_mode=real_mode, stream=stream.cuda_stream)
+    stream.synchronize()
+    assert _same_bits(d_sh.cpu().numpy(), batch.astype(real)) and _same_bits(bake(p, first_key=7), batch)
+    # n = 1 with R = 65536 at depth 1: the longest per-lane loop (256 passes), against the projected query
+    got = bake(p[:1], rays=65536, samples=1, max_depth=1)
+    want, bound = _projected(rt, renderer, p[:1], rays=65536, samples=1, max_depth=1, background=bg, real_mode=real_mode)
+    print("R = 65536 %s: worst ratio to the bound %.3f" % (order, float((np.abs(got - want) / np.where(bound > 0, bound, 1.0)).max())))
+    assert got.any() and np.all(np.abs(got - want) <= bound)
+    assert renderer.bake_probes(np.zeros((0, 3)), max_depth=3).shape == (0, 9, 3)
+
+
+SKY_PROBE = (0.0, 1.0e6, -1.0)   # a million above the ground sphere's centre: the scene fills a cone of 1e-4 rad around -y
+
+
+@pytest.mark.gpu
+@MODES
+def test_a_probe_that_sees_only_sky(rt, renderer, scenes, real_mode):
+    """three_spheres from so far above that no emitted ray meets the scene (asserted through rtk_query_occluded): every L is the
+    background, so c0 = 2 sqrt(pi) background within the bound of test 2, and E(n) = pi background within 1e-3 at R = 256."""
+    scene = scenes("three_spheres")
+    bg = np.array([0.7, 0.8, 1.0])
+    d = directions(256)
+    assert np.degrees(np.arccos(-d[:, 1])).min() > 1.0            # no direction within a degree of straight down
+    positions = np.array([SKY_PROBE])
+    for order in ORDERS:
+        _upload(renderer, scene, order)
+        records = renderer.probe_rays(positions, rays=256)
+        assert not renderer.query_occluded(records, seed=SEED, real_mode=real_mode).any()
+        got = renderer.bake_probes(positions, max_depth=10, rays=256, background=bg, seed=SEED, real_mode=real_mode)
+        want, bound = _projected(rt, renderer, positions, rays=256, samples=1, max_depth=10, background=bg, real_mode=real_mode)
+        bg_real = bg if real_mode == rt.RTK_REAL_F64 else bg.astype(np.float32).astype(np.float64)
+        c0 = 2.0 * np.sqrt(np.pi) * bg_real                      # every L is the background exactly -- as the kernel holds it: a real of the mode
+        assert np.all(np.abs(got[0, 0] - c0) <= bound[0, 0]) and np.all(np.abs(got - want) <= bound)
+        e = irradiance(got[0], unit_normals(64, 2))
+        print(f"sky probe {order} mode {real_mode}: worst |E / (pi background) - 1| = {np.abs(e / (np.pi * bg) - 1.0).max():.2e}")
+        assert np.abs(e / (np.pi * bg) - 1.0).max() <= 1e-3
+
+
+GRIDS = [((1, 1, 1), (1.0, -2.0, 0.5), (2.0, 0.5, 1.0)), ((2, 1, 1), (1.0, -2.0, 0.5), (2.0, 0.5, 1.0)), ((2, 3, 2), (-1.0, 4.0, 0.0), (0.5, 2.0, 1.0))]
+
+
+def _lookup_points(origin, spacing, counts, m, seed):
+    """m points: generic ones inside, ones on a 1/64 lattice of the cells (exact in float32), every probe, face points, and
+    points outside the grid on every side -- cycled to m."""
+    rng = np.random.default_rng(seed)
+    origin, spacing, counts = np.array(origin), np.array(spacing), np.array(counts)
+    extent = (counts - 1) * spacing
+    probes = origin + np.stack(np.meshgrid(*[np.arange(c) for c in counts], indexing="ij"), -1).reshape(-1, 3) * spacing
+    faces = origin + rng.integers(0, 65, (12, 3)) / 64.0 * extent
+    axes = np.arange(12) % 3                                      # ... each pinned to the low or the high face of one axis
+    faces[np.arange(12), axes] = np.where(np.arange(12) % 2 == 0, origin[axes], (origin + extent)[axes])
+    outside = []
+    for axis in range(3):
+        for side in (-1.0, 1.0):
+            q = origin + rng.random(3) * extent
+            q[axis] = origin[axis] - 3.0 * spacing[axis] if side < 0 else origin[axis] + extent[axis] + 2.5 * spacing[axis]
+            outside.append(q)
+    outside.append(origin - spacing)                              # beyond a corner
+    outside.append(origin + extent + spacing)
+    generic = origin + rng.random((16, 3)) * extent
+    lattice = origin + rng.integers(0, 64 * np.maximum(counts - 1, 1) + 1, (16, 3)) / 64.0 * spacing * (counts > 1)
+    pool = np.vstack([generic, lattice, probes, faces, np.array(outside)])
+    return pool[np.arange(m) % len(pool)] if m >= len(pool) else pool[rng.permutation(len(pool))[:m]]
+
+
+@pytest.mark.gpu
+@MODES
+@pytest.mark.parametrize("grid", GRIDS, ids=["1x1x1", "2x1x1", "2x3x2"])
+def test_lookup_against_the_restatement(rt, renderer, real_mode, grid):
+    """|E - restatement| <= 32 u sum |w_p A_i c_p,i Y_i(n)|, u = 2^-53 or 2^-24: eight weights times nine terms in any order,
+    with or without fused operations.  Inputs are rounded to the mode's type first, so both sides see the same numbers."""
+    counts, origin, spacing = grid
+    real = np.float64 if real_mode == rt.RTK_REAL_F64 else np.float32
+    u = U64 if real_mode == rt.RTK_REAL_F64 else U32
+    n = counts[0] * counts[1] * counts[2]
+    sh = np.random.default_rng(n).standard_normal((n, 9, 3)).astype(real).astype(np.float64)
+    g = (origin, spacing, counts)
+    worst = 0.0
+    for m in (1, 63, 257):
+        points = _lookup_points(origin, spacing, counts, m, m).astype(real).astype(np.float64)
+        normals = unit_normals(m, m + 1).astype(real).astype(np.float64)
+        got = renderer.probe_irradiance(g, sh, points, normals, real_mode=real_mode)
+        want, b = lookup(origin, spacing, counts, sh, points, normals)
+        assert got.shape == (m, 3) and b.min() > 0
+        worst = max(worst, float((np.abs(got - want) / (32 * u * b)).max()))
+        assert np.all(np.abs(got - want) <= 32 * u * b), (m, worst)
+    print(f"lookup {counts} mode {real_mode}: worst ratio to the bound {worst:.3f}")
+    # a point on a probe returns that probe's E exactly as the 1x1x1 grid of that probe does
+    positions = rt.probe_grid_positions(*g)
+    normals = unit_normals(n, 9).astype(real).astype(np.float64)
+    on_probes = renderer.probe_irradiance(g, sh, positions, normals, real_mode=real_mode)
+    for k in range(n):
+        alone = renderer.probe_irradiance((positions[k], spacing, (1, 1, 1)), sh[k:k + 1], positions[k:k + 1] + 0.25, normals[k:k + 1], real_mode=real_mode)
+        assert np.array_equal(on_probes[k], alone[0]), k
+    # a constant field returns itself
+    points = _lookup_points(origin, spacing, counts, 63, 3).astype(real).astype(np.float64)
+    normals = unit_normals(63, 4).astype(real).astype(np.float64)
+    const = np.repeat(sh[:1], n, axis=0)
+    got = renderer.probe_irradiance(g, const, points, normals, real_mode=real_mode)
+    want, b = lookup((0, 0, 0), (1, 1, 1), (1, 1, 1), sh[:1], points, normals)
+    assert np.all(np.abs(got - want) <= 32 * u * b)
+    assert renderer.probe_irradiance(g, sh, np.zeros((0, 3)), np.zeros((0, 3)), real_mode=real_mode).shape == (0, 3)
+
+
+# --- buffers and streams ------------------------------------------------------------------------------------------
+POISON = 0xA5
+
+
+def _arena_layout(sizes):
+    """Byte offsets of the pieces in one allocation: each 8 past a 16-byte boundary (8-byte aligned, not 16), with at least 64
+    guard bytes behind it."""
+    offsets, at = [], 8
+    for size in sizes:
+        offsets.append(at)
+        at = (at + size + 64 + 15) // 16 * 16 + 8
+    return offsets, at + 64
+
+
+@pytest.mark.gpu
+@MODES
+@pytest.mark.parametrize("order", ORDERS)
+def test_carved_buffers_guard_bytes_and_a_caller_stream(rt, renderer, scenes, real_mode, order):
+    """Three probes as a 3x1x1 grid in cornell_smoke: rays, bake and a lookup from the coefficients the bake has just written,
+    all on one caller stream with a producer in front and a consumer behind, in buffers carved at 8-mod-16 offsets out of a
+    poisoned arena.  Every output equals its _host form byte for byte; no guard byte changes."""
+    import torch
+
+    name = "cornell_smoke"
+    scene = scenes(name)
+    depth = CASES[name][4]
+    _upload(renderer, scene, order)
+    real = np.float64 if real_mode == rt.RTK_REAL_F64 else np.float32
+    rb = np.dtype(real).itemsize
+    n, rays, m = 3, 256, 63
+    g = ((100.0, 400.0, 300.0), (150.0, 25.0, 50.0), (3, 1, 1))
+    positions = rt.probe_grid_positions(*g)
+    points = _lookup_points(*g[:2], g[2], m, 7).astype(real)
+    normals = unit_normals(m, 8).astype(real)
+    want_rays = renderer.probe_rays(positions, rays=rays, samples=2, first_key=3)
+    want_sh = renderer.bake_probes(positions, max_depth=depth, rays=rays, samples=2, first_key=3, seed=SEED, real_mode=real_mode)
+    want_e = renderer.probe_irradiance(g, want_sh, points.astype(np.float64), normals.astype(np.float64), real_mode=real_mode)
+    assert want_sh.any() and want_e.any()
+    sizes = (24 * n, 88 * n * rays, 27 * rb * n, 3 * rb * m, 3 * rb * m, 3 * rb * m)
+    (o_pos, o_rays, o_sh, o_pts, o_nrm, o_e), total = _arena_layout(sizes)
+    dev = torch.device("cuda:0")
+    as_bytes = lambda a: torch.from_numpy(np.frombuffer(np.ascontiguousarray(a).tobytes(), np.uint8).copy()).to(dev)  # noqa: E731
+    src_pos, src_pts, src_nrm = as_bytes(positions), as_bytes(points), as_bytes(normals)
+    arena = torch.full((total,), POISON, dtype=torch.uint8, device=dev)
+    base = arena.data_ptr()
+    assert base % 16 == 0 and all((base + o) % 16 == 8 for o in (o_pos, o_rays, o_sh, o_pts, o_nrm, o_e))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(stream):
+        arena[o_pos:o_pos + sizes[0]].copy_(src_pos)              # the producer: until it has run the inputs are poison
+        arena[o_pts:o_pts + sizes[3]].copy_(src_pts)
+        arena[o_nrm:o_nrm + sizes[4]].copy_(src_nrm)
+        s = stream.cuda_stream
+        renderer.probe_rays_device(n, base + o_pos, base + o_rays, rays=rays, samples=2, first_key=3, stream=s)
+        renderer.bake_probes_device(n, base + o_pos, base + o_sh, max_depth=depth, rays=rays, samples=2, first_key=3, seed=SEED, real_mode=real_mode, stream=s)
+        renderer.probe_irradiance_device(g, base + o_sh, m, base + o_pts, base + o_nrm, base + o_e, real_mode=real_mode, stream=s)
+        after = arena.clone()                                     # the consumer, same stream, no host synchronisation in between
+    stream.synchronize()
+    got = after.cpu().numpy()
+    piece = lambda o, size: got[o:o + size].tobytes()  # noqa: E731
+    assert piece(o_rays, sizes[1]) == want_rays.tobytes()
+    assert piece(o_sh, sizes[2]) == want_sh.astype(real).tobytes()
+    assert piece(o_e, sizes[5]) == want_e.astype(real).tobytes()
+    outside = np.ones(total, bool)
+    for o, size in zip((o_pos, o_rays, o_sh, o_pts, o_nrm, o_e), sizes):
+        outside[o:o + size] = False
+    assert np.all(got[outside] == POISON)                         # every guard byte before, between and behind the buffers
+    arena2 = torch.full((total,), POISON, dtype=torch.uint8, device=dev)   # n = 0 and m = 0: RTK_OK, nothing written
+    base2 = arena2.data_ptr()
+    renderer.probe_rays_device(0, base2 + o_pos, base2 + o_rays)
+    renderer.bake_probes_device(0, base2 + o_pos, base2 + o_sh, max_depth=depth, real_mode=real_mode)
+    renderer.probe_irradiance_device(g, base2 + o_sh, 0, base2 + o_pts, base2 + o_nrm, base2 + o_e, real_mode=real_mode)
+    torch.cuda.synchronize()
+    assert bool((arena2 == POISON).all())
+
+
+@pytest.mark.gpu
+def test_misaligned_device_pointers_and_a_missing_scene_are_refused(rt):
+    import torch
+
+    r = rt.Renderer(0)
+    buf = torch.full((1 << 17,), POISON, dtype=torch.uint8, device="cuda:0")
+    p = buf.data_ptr()
+    g = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0), (1, 1, 1))
+    with pytest.raises(rt.RtkError) as e:
+        r.bake_probes_device(1, p, p + 1024, max_depth=2, rays=256)
+    assert e.value.code == -5 and "no scene" in str(e.value) and "rtk_probe_bake" in str(e.value)      # RTK_ERR_NO_SCENE
+    for call, word in ((lambda: r.probe_rays_device(1, p + 4, p + 1024, rays=256), "d_positions"), (lambda: r.probe_rays_device(1, p, p + 1028, rays=256), "d_rays"),
+                       (lambda: r.bake_probes_device(1, p + 4, p + 1024, max_depth=2, rays=256), "d_positions"),
+                       (lambda: r.bake_probes_device(1, p, p + 1028, max_depth=2, rays=256), "d_sh"),
+                       (lambda: r.bake_probes_device(1, p, p + 1026, max_depth=2, rays=256, real_mode=1), "d_sh"),
+                       (lambda: r.probe_irradiance_device(g, p + 4, 1, p + 1024, p + 2048, p + 3072), "d_sh"),
+                       (lambda: r.probe_irradiance_device(g, p, 1, p + 1028, p + 2048, p + 3072), "d_points"),
+                       (lambda: r.probe_irradiance_device(g, p, 1, p + 1024, p + 2052, p + 3072), "d_normals"),
+                       (lambda: r.probe_irradiance_device(g, p, 1, p + 1024, p + 2048, p + 3074, real_mode=1), "d_irradiance")):
+        with pytest.raises(rt.RtkError) as e:
+            call()
+        assert e.value.code == -1 and word in str(e.value) and "aligned" in str(e.value), str(e.value)
+    torch.cuda.synchronize()
+    assert bool((buf == POISON).all())
+    r.probe_rays_device(1, p, p + 1024, rays=256)                 # rays and lookups need no scene
+    buf[:27 * 8].zero_()                                          # coefficients 0; the point and the normal are poison, which is finite
+    r.probe_irradiance_device(g, p, 1, p + 32768, p + 40960, p + 65536)
+    torch.cuda.synchronize()
+    assert not bool((buf[1024:1024 + 88] == POISON).all()) and bool((buf[65536:65536 + 24] == 0).all())
+    r.close()
+
+
+# --- the host C++ API ---------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@MODES
+def test_host_api_light_probes(rt, renderer, scenes, tmp_path, real_mode):
+    """rtk::light_probes (host/rtk_light_probes.h) bakes a 2x2x2 grid in the Cornell box and looks irradiance up at two points;
+    the coefficients and both lookups equal what the Python calls give for the same scene (the library is deterministic, so
+    equality is the bound of tests 2 and 5 met with nothing to spare), in both real modes; a refused bake shows in status() and
+    rtk_last_error(), whether the options or the grid are at fault.  The reference order is the class's own."""
+    exe = str(tmp_path / "light_probes_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "helpers", "light_probes_check.cpp"),
+                           "-I" + os.path.join(PKG, "host"), "-I" + os.path.join(ROOT, "include"), "-L" + PKG, "-lrtk_hip", "-Wl,-rpath," + PKG, "-o", exe])
+    name, rays, depth, samples = "cornell_box", 256, 6, 2
+    scene = scenes(name)
+    renderer.upload(scene)                                        # the reference order, as rtk::light_probes uploads
+    g = ((100.0, 350.0, 100.0), (350.0, 100.0, 350.0), (2, 2, 2))
+    points, normals = np.array([[200.0, 400.0, 300.0], [500.0, 330.0, 90.0]]), np.array([[0.0, 1.0, 0.0], [-0.6, 0.0, 0.8]])
+    sh = renderer.bake_probes(rt.probe_grid_positions(*g), max_depth=depth, rays=rays, samples=samples, background=(0.0, 0.0, 0.0), first_key=11, seed=5,
+                              real_mode=real_mode)
+    e = renderer.probe_irradiance(g, sh, points, normals, real_mode=real_mode)
+    want, bound = _projected(rt, renderer, rt.probe_grid_positions(*g), rays=rays, samples=samples, max_depth=depth, background=(0.0, 0.0, 0.0), first_key=11, seed=5,
+                             real_mode=real_mode)
+    assert sh.any() and e.any() and np.all(np.abs(sh - want) <= bound)
+    p = subprocess.run([exe, name, scene_file(name, GOLDEN), str(rays), str(depth), str(samples), str(real_mode)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "light_probes_check: ok" in p.stdout, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
+    lines = p.stdout.splitlines()
+    got_sh = np.array([float(line.split()[2]) for line in lines if line.startswith("sh ")]).reshape(8, 9, 3)
+    got_e = np.array([[float(v) for v in line.split()[1:]] for line in lines if line.startswith(("single ", "batch "))])
+    assert np.array_equal(got_sh, sh)
+    assert got_e.shape == (3, 3) and np.array_equal(got_e[0], e[0]) and np.array_equal(got_e[1:], e)
+    refused = [line for line in lines if line.startswith("refused ")]
+    assert refused and refused[0].split()[1] == "-1" and "rtk_probe_bake_host" in refused[0] and "rays" in refused[0]
+    bad_grid = [line for line in lines if line.startswith("refused-grid ")]
+    assert bad_grid and "rtk_probe_irradiance_host" in bad_grid[0] and "counts" in bad_grid[0]
