@@ -922,6 +922,8 @@ int rtk_display_destroy(rtk_display* d);
  *                     ray's stream.  With skip = 0 it is rtk_debug_closest_hit, bit for bit.  prim_kind / prim_index name the
  *                     primitive in the tables of the rtk_scene_desc that was uploaded (rtk_scene_optimize borrows them unchanged,
  *                     so both visiting orders report the same; a primitive reached through several instances reports one index).
+ *                     A constant medium's record has u = v = 0 (the reference leaves them as the record held them); an
+ *                     empty interval, tmin > tmax, is a miss.
  * rtk_query_occluded  d_occluded[k] = the hit flag rtk_query_hits returns for the same ray, keys and skip, exactly.  In a scene
  *                     without a constant_medium the walk stops at the first accepted hit; with one it is the closest-hit walk.
  * rtk_query_radiance  ray_color(r, opts->max_depth, world, lights) with opts->background: world.hit on interval(0.001, inf)

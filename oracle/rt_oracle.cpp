@@ -765,4 +765,69 @@ void orc_kat_get_ray(const rtk_camera* cam, uint32_t seed, int i, int j, int sam
     if (draws) *draws = cx.rng.draws;
 }
 
+// ---- a caller's ray (include/rtk.h "Ray queries") --------------------------
+// The stream (seed, pixel, sample) with `skip` uniforms drawn and discarded, draws counted from there.
+static void seed_and_skip(Ctx& cx, const rtk_scene_desc* sc, uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t skip) {
+    cx.sc = sc;
+    std::memset(&cx.cnt, 0, sizeof cx.cnt);
+    rng_seed(cx.rng, seed, pixel, sample);
+    for (uint32_t k = 0; k < skip; k++) rnd(cx.rng);
+    cx.rng.draws = 0;
+}
+
+// world.hit(r, interval(tmin, tmax), rec) of the scene root: orc_kat_node_hit with `skip`.  kind (may be null): the kind
+// of the node that made the record (RTK_NODE_SPHERE / QUAD / TRIANGLE / MEDIUM), 0 on a miss.
+int orc_ray_hit(const rtk_scene_desc* sc, const double ray_odt[7], double tmin, double tmax, uint32_t seed, uint32_t pixel,
+                uint32_t sample, uint32_t skip, double out[11], uint64_t* draws, int32_t* kind) {
+    Ctx cx;
+    seed_and_skip(cx, sc, seed, pixel, sample, skip);
+    Ray r{v3(ray_odt[0], ray_odt[1], ray_odt[2]), v3(ray_odt[3], ray_odt[4], ray_odt[5]), ray_odt[6]};
+    HitRec rec;
+    bool h = node_hit(cx, sc->root, r, tmin, tmax, rec);
+    pack_rec(rec, out);
+    if (draws) *draws = cx.rng.draws;
+    if (kind) *kind = h ? rec.prim_kind : 0;
+    return h ? 1 : 0;
+}
+
+// ray_color(r, max_depth) with the given background; draws: the uniforms the path drew, skip not counted.
+int orc_ray_color(const rtk_scene_desc* sc, const double ray_odt[7], const double background[3], int max_depth, uint32_t seed,
+                  uint32_t pixel, uint32_t sample, uint32_t skip, double rgb[3], uint64_t* draws) {
+    Ctx cx;
+    seed_and_skip(cx, sc, seed, pixel, sample, skip);
+    rtk_camera cam;
+    std::memset(&cam, 0, sizeof cam);
+    cam.background = rtk_vec3{background[0], background[1], background[2]};
+    Ray r{v3(ray_odt[0], ray_odt[1], ray_odt[2]), v3(ray_odt[3], ray_odt[4], ray_odt[5]), ray_odt[6]};
+    V3 c = ray_color(cx, cam, r, max_depth);
+    rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
+    if (draws) *draws = cx.rng.draws;
+    return 0;
+}
+
+// The two above over n rtk_ray records.  records [n][11] as pack_rec (all 0, material -1 on a miss: what a record holds
+// after a miss is nobody's contract).  orc_ray_colors adds sample_offset to every ray's sample key (sample s of a query).
+void orc_ray_hits(const rtk_scene_desc* sc, int64_t n, const rtk_ray* rays, uint32_t seed, double* records, int32_t* hit, int32_t* kind,
+                  uint64_t* draws) {
+    for (int64_t k = 0; k < n; k++) {
+        const rtk_ray& q = rays[k];
+        const double odt[7] = {q.origin[0], q.origin[1], q.origin[2], q.direction[0], q.direction[1], q.direction[2], q.time};
+        double* out = records + 11 * k;
+        hit[k] = orc_ray_hit(sc, odt, q.tmin, q.tmax, seed, q.pixel, q.sample, q.skip, out, draws + k, kind + k);
+        if (!hit[k]) {
+            for (int c = 0; c < 10; c++) out[c] = 0.0;
+            out[10] = -1.0;
+        }
+    }
+}
+
+void orc_ray_colors(const rtk_scene_desc* sc, int64_t n, const rtk_ray* rays, const double background[3], int max_depth, uint32_t seed,
+                    uint32_t sample_offset, double* rgb, uint64_t* draws) {
+    for (int64_t k = 0; k < n; k++) {
+        const rtk_ray& q = rays[k];
+        const double odt[7] = {q.origin[0], q.origin[1], q.origin[2], q.direction[0], q.direction[1], q.direction[2], q.time};
+        orc_ray_color(sc, odt, background, max_depth, seed, q.pixel, q.sample + sample_offset, q.skip, rgb + 3 * k, draws + k);
+    }
+}
+
 }  // extern "C"
