@@ -358,7 +358,7 @@ int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks);
  * Streams (this holds for every entry point that is "asynchronous on" a stream:
  * rtk_render_device, rtk_tiles_unpermute, rtk_progressive_step, rtk_render_aovs,
  * rtk_denoise, rtk_progressive_denoise, rtk_render_guides, rtk_denoise_guided, rtk_progressive_denoise_guided,
- * rtk_temporal_accumulate, rtk_query_hits / _occluded / _radiance):
+ * rtk_temporal_accumulate, rtk_query_hits / _occluded / _radiance, rtk_probe_*, rtk_lens_*):
  *   - all work of a call -- kernels, memsets, the upload of the camera record --
  *     is enqueued on the stream it is given and on no other; the call reads its
  *     host arguments (cam, opts) before it returns and never waits for the
@@ -1031,6 +1031,83 @@ int rtk_probe_rays_host(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, con
 int rtk_probe_bake_host(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const double* h_positions, double* h_sh);
 int rtk_probe_irradiance_host(rtk_ctx* ctx, int real_mode, const rtk_probe_grid* grid, const double* h_sh, int64_t m, const double* h_points,
                               const double* h_normals, double* h_irradiance);
+
+/* Lens models ---------------------------------------------------------------------------
+ * Whole frames through other projections than get_ray's pinhole / thin lens: a 360-degree panorama from a point (also an
+ * environment map or reflection capture), an equidistant fisheye for domes, an orthographic view for plans and elevations.  The
+ * rays are made on the device, one lane per pixel, and traced by the radiance query's path loop; the frame comes with the noise
+ * estimate and the guide buffers the denoiser and the display transform take.  Device resident and asynchronous on opts->stream,
+ * on the uploaded scene in either visiting order and both real modes; one rank only.  rtk_render_kernel, the scheduler and
+ * every other output are untouched.
+ *
+ * The sample rule.  Sample s = 0 .. S-1 of pixel (i, j) of a W x H frame draws from the stream keyed (seed, j*W+i,
+ * first_sample+s) (the keying of the ray queries).
+ *   RTK_LENS_PERSPECTIVE is begin_sample -- get_ray, Camera.txt:177-200 -- on lens->cam, unchanged: in the real mode's type, with
+ *   the defocus rejection loop, so skip is what rtk_debug_get_ray reports as h_draws.  It reads all of lens->cam and none of the
+ *   other fields (model and reserved excepted).
+ *   The other three models make three draws and then compute in double in both real modes, with no fused operation and no
+ *   renormalisation.  A draw is v * 2^-24 for a 24-bit v, exact in either type.  In order:
+ *       oy = draw - 0.5;   ox = draw - 0.5  (y first, as get_ray);   time = draw;   skip = 3
+ *   Film coordinates:      x = 2 * ((i + ox) + 0.5) / W - 1        y = 1 - 2 * ((j + oy) + 0.5) / H
+ *   EQUIRECT      lon = x * (fov_h / 2), lat = y * (fov_v / 2), c = cos(lat); local direction (c * sin(lon), sin(lat),
+ *                 -(c * cos(lon))); origin = cam.center.
+ *   FISHEYE       yy = y * (double(H) / double(W)), r = sqrt(x * x + yy * yy), theta = r * (fov_h / 2); local direction
+ *                 (sin(theta) * (x / r), sin(theta) * (yy / r), -cos(theta)), or (0, 0, -1) when r == 0; origin = cam.center.
+ *                 There is no mask: beyond r = 1 the mapping simply continues, and the caller may mask.
+ *   ORTHOGRAPHIC  local direction (0, 0, -1); origin = (center + (x * (ortho_width / 2)) * u) + (y * (ortho_height / 2)) * v,
+ *                 per component.
+ *   World direction, per component: (lx * u + ly * v) + lz * w, with u, v, w as given (not normalised, not orthogonalised).
+ * A record is { origin, direction, time, tmin = 0.001, tmax = +inf, pixel = j*W+i, sample = first_sample+s, skip, reserved = 0 }
+ * (rtk_ray).  In RTK_REAL_F32 the ray a lane traces is the record rounded to float, as the ray queries round a caller's record.
+ * One device function computes the record; rtk_lens_rays stores it, rtk_lens_render and rtk_lens_aovs / _guides trace it
+ * from registers: the bits are the same in all of them.
+ *
+ * rtk_lens_rays    d_rays[(j*W+i) * n_samples + s] = the record of sample first_sample+s: pixel-major, samples inner.  Needs a
+ *                  context but no scene; 8-byte aligned.
+ * rtk_lens_render  S = cam.samples_per_pixel samples per pixel.  L_s = what rtk_query_radiance returns for the record of sample
+ *                  first_sample+s with samples = 1 and cam.max_depth / cam.background.  d_linear[j][i][0..2] = (the sum of L_s
+ *                  in sample order, in the real mode's type) * cam.pixel_samples_scale, reals of real_mode (set the scale to
+ *                  1 / S for a mean, as the helpers do).  d_noise (may be NULL) [H][W] floats: with y_s = ((r + g) + b) / 3, the
+ *                  channels of L_s widened to double first, S1 = sum y_s and S2 = sum y_s^2 in double in sample order, m = S1 / S,
+ *                  v = max(0, (S2 - S m^2) / (S - 1)), se = float(sqrt(v / S)); se = 0 when S < 2 -- the session estimate's
+ *                  form, over samples instead of chunks.  No atomics: the result does not depend on the launch geometry.
+ * rtk_lens_aovs    the 8 floats per pixel of rtk_render_aovs, and
+ * rtk_lens_guides  the 16 floats per pixel of rtk_render_guides, by their rules, with the lens's record for samples
+ *                  0 .. n_samples-1 as the primary ray (the same kernel with another sample generator; the first-hit walks draw
+ *                  from the keys 2^31 + ... as there).  With RTK_LENS_PERSPECTIVE they are rtk_render_aovs / _guides of lens->cam,
+ *                  bit for bit.  d_aov / d_guides must be 16-byte aligned.
+ * opts supplies seed, real_mode and stream; n_ranks other than 1 is refused; rank, count_work and variant are ignored.
+ * RTK_ERR_INVALID, checked first and without a device, the text naming the argument: a null lens, opts or output; an unknown
+ * model; reserved != 0; a camera size outside 1 .. 65536; negative samples_per_pixel (rtk_lens_render needs >= 1) or max_depth;
+ * n_samples < 0 (rtk_lens_rays; 0 launches nothing) or < 1 (_aovs, _guides; _guides at most 2^20); first_sample < 0;
+ * H * W * n_samples over 2^31 - 1 (rtk_lens_render: H * W * samples_per_pixel); an unknown real_mode; n_ranks != 1; a non-finite
+ * real anywhere in the lens, whatever the model; fov_h outside (0, 2 pi] (0 = the default), for EQUIRECT fov_v outside (0, pi]
+ * (0 = the default), for ORTHOGRAPHIC ortho_width or ortho_height <= 0; a misaligned buffer; bad rtk_guide_opts.  Then a null context, then (all but rtk_lens_rays) RTK_ERR_NO_SCENE.  The stream rules of rtk_render_device
+ * hold: every launch goes to opts->stream, lens and opts are read before the call returns, the call allocates nothing and never
+ * waits for the device.  The _host forms take host buffers (h_linear doubles, F32 widened) and block.
+ * rtk_lens_look_at (host-only): cam.center = lookfrom, w = unit_vector(lookfrom - lookat), u = unit_vector(cross(vup, w)),
+ * v = cross(w, u) (Camera.txt:147-149, the operations of vec3.h in their order); RTK_ERR_INVALID for a null lens. */
+#define RTK_LENS_PERSPECTIVE  0   /* get_ray itself (Camera.txt:177-200): the anchor the tests hold the rest to */
+#define RTK_LENS_EQUIRECT     1   /* longitude x latitude */
+#define RTK_LENS_FISHEYE      2   /* equidistant: angle from the axis proportional to the radius on the film */
+#define RTK_LENS_ORTHOGRAPHIC 3
+typedef struct rtk_lens {          /* 312 bytes */
+    rtk_camera cam;                /* size, samples_per_pixel, max_depth, background, center, pixel_samples_scale; PERSPECTIVE reads all of it */
+    int32_t model, reserved;       /* reserved = 0 */
+    rtk_vec3 u, v, w;              /* camera frame as Camera.txt:147-149: right, up, back (the view direction is -w); used as given */
+    double fov_h, fov_v;           /* radians.  EQUIRECT: extents, 0 = 2 pi and pi.  FISHEYE: fov_h = full angle across the image width, 0 = pi */
+    double ortho_width, ortho_height; /* ORTHOGRAPHIC: the window in world units, > 0 */
+} rtk_lens;
+
+int rtk_lens_look_at(rtk_lens* lens, rtk_vec3 lookfrom, rtk_vec3 lookat, rtk_vec3 vup);
+int rtk_lens_rays(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, int32_t n_samples, rtk_ray* d_rays);
+int rtk_lens_render(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, void* d_linear, float* d_noise);
+int rtk_lens_aovs(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, float* d_aov);
+int rtk_lens_guides(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* d_guides);
+int rtk_lens_rays_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, int32_t n_samples, rtk_ray* h_rays);
+int rtk_lens_render_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, double* h_linear, float* h_noise);
+int rtk_lens_aovs_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, float* h_aov);
+int rtk_lens_guides_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* h_guides);
 
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and

@@ -361,6 +361,43 @@ def probe_grid_positions(origin, spacing, counts):
     return origin + np.stack([ix.ravel(), iy.ravel(), iz.ravel()], 1).astype(np.float64) * spacing
 
 
+LENS_PERSPECTIVE, LENS_EQUIRECT, LENS_FISHEYE, LENS_ORTHOGRAPHIC = 0, 1, 2, 3   # RTK_LENS_*
+
+
+class Lens(C.Structure):
+    """rtk_lens (include/rtk.h "Lens models"): a camera record, a projection and its frame and extents."""
+
+    _fields_ = [("cam", Camera), ("model", C.c_int32), ("reserved", C.c_int32), ("u", Vec3), ("v", Vec3), ("w", Vec3),
+                ("fov_h", C.c_double), ("fov_v", C.c_double), ("ortho_width", C.c_double), ("ortho_height", C.c_double)]
+
+
+def derive_lens(model: int = LENS_PERSPECTIVE, image_width: int = 0, image_height: int = 0, *, cam: Optional[Camera] = None, spp: int = 1, max_depth: int = 10,
+                lookfrom=(0.0, 0.0, 0.0), lookat=(0.0, 0.0, -1.0), vup=(0.0, 1.0, 0.0), background=(0.0, 0.0, 0.0), fov_h: float = 0.0, fov_v: float = 0.0,
+                ortho_width: float = 0.0, ortho_height: float = 0.0) -> Lens:
+    """An rtk_lens.  LENS_PERSPECTIVE takes a whole camera: ``derive_lens(cam=...)`` (get_ray itself).  The other models take
+    the image size, ``spp`` (pixel_samples_scale = 1 / spp), ``max_depth``, ``background``, the frame of ``lookfrom`` /
+    ``lookat`` / ``vup`` (rtk_lens_look_at) and their extents: ``fov_h`` / ``fov_v`` in radians (0 = the model's default),
+    ``ortho_width`` / ``ortho_height`` in world units."""
+    lens = Lens()
+    if cam is not None:
+        if model != LENS_PERSPECTIVE:
+            raise ValueError("derive_lens: cam= is the perspective lens; the other models take a size and a frame")
+        C.memmove(C.byref(lens.cam), C.byref(cam), C.sizeof(Camera))
+        return lens
+    if model == LENS_PERSPECTIVE:
+        raise ValueError("derive_lens: the perspective lens needs cam=")
+    lens.cam.image_width, lens.cam.image_height = int(image_width), int(image_height)
+    lens.cam.samples_per_pixel, lens.cam.max_depth = int(spp), int(max_depth)
+    lens.cam.background = background if isinstance(background, Vec3) else Vec3(*(float(c) for c in background))
+    lens.cam.pixel_samples_scale = 1.0 / spp if spp > 0 else 0.0
+    lens.model = int(model)
+    lens.fov_h, lens.fov_v, lens.ortho_width, lens.ortho_height = float(fov_h), float(fov_v), float(ortho_width), float(ortho_height)
+    v3 = lambda v: v if isinstance(v, Vec3) else Vec3(*(float(c) for c in v))  # noqa: E731
+    if hip_lib().rtk_lens_look_at(C.byref(lens), v3(lookfrom), v3(lookat), v3(vup)) != 0:
+        raise ValueError("rtk_lens_look_at failed")
+    return lens
+
+
 def host_lib() -> C.CDLL:
     """librtk_host.so: scene construction + flattening (no GPU needed)."""
     global _host_lib
@@ -512,6 +549,12 @@ def hip_lib() -> C.CDLL:
                 getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(ProbeOpts), C.c_int64, C.c_void_p, C.c_void_p]
             lib.rtk_probe_irradiance_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(ProbeGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.rtk_probe_irradiance.argtypes = lib.rtk_probe_irradiance_host.argtypes + [C.c_void_p]
+            lens = [C.c_void_p, C.POINTER(Lens), C.POINTER(RenderOpts)]
+            lib.rtk_lens_look_at.argtypes = [C.POINTER(Lens), Vec3, Vec3, Vec3]
+            lib.rtk_lens_rays.argtypes = lib.rtk_lens_rays_host.argtypes = lens + [C.c_int32, C.c_int32, C.c_void_p]
+            lib.rtk_lens_render.argtypes = lib.rtk_lens_render_host.argtypes = lens + [C.c_int32, C.c_void_p, C.c_void_p]
+            lib.rtk_lens_aovs.argtypes = lib.rtk_lens_aovs_host.argtypes = lens + [C.c_int32, C.c_void_p]
+            lib.rtk_lens_guides.argtypes = lib.rtk_lens_guides_host.argtypes = lens + [C.c_int32, C.POINTER(GuideOpts), C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -905,6 +948,72 @@ class Renderer:
         self._check(self._lib.rtk_probe_irradiance(self._ctx, real_mode, C.byref(grid), d_sh or None, int(m), d_points or None, d_normals or None,
                                                    d_irradiance or None, stream or None))
 
+    def lens_rays(self, lens: Lens, samples: int = 1, *, first_sample: int = 0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_lens_rays_host: the ray records (``ray_dtype``, (H * W * samples,), pixel-major, samples inner) of samples
+        first_sample .. first_sample + samples - 1 of every pixel of ``lens``.  Needs no scene."""
+        import numpy as np
+
+        out = np.zeros(max(lens.cam.image_height, 0) * max(lens.cam.image_width, 0) * max(int(samples), 0), ray_dtype())
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        self._check(self._lib.rtk_lens_rays_host(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), int(samples), out.ctypes.data))
+        return out
+
+    def lens_render(self, lens: Lens, *, first_sample: int = 0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_lens_render_host: (linear float64 (H, W, 3) -- F32 widened --, se float32 (H, W)) of lens.cam.samples_per_pixel
+        samples per pixel from ``first_sample`` on: the sum in sample order times lens.cam.pixel_samples_scale."""
+        import numpy as np
+
+        h, w = lens.cam.image_height, lens.cam.image_width
+        linear, noise = np.zeros((h, w, 3), np.float64), np.zeros((h, w), np.float32)
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        self._check(self._lib.rtk_lens_render_host(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), linear.ctypes.data, noise.ctypes.data))
+        return linear, noise
+
+    def lens_aovs(self, lens: Lens, samples: int = 4, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_lens_aovs_host: ``aovs`` through ``lens``, float32 (H, W, 8)."""
+        import numpy as np
+
+        out = np.zeros((lens.cam.image_height, lens.cam.image_width, 8), np.float32)
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        self._check(self._lib.rtk_lens_aovs_host(self._ctx, C.byref(lens), C.byref(opts), int(samples), out.ctypes.data))
+        return out
+
+    def lens_guides(self, lens: Lens, samples: int = 4, *, follow: int = GUIDE_FOLLOW_MIRROR, max_bounces: int = 0, seed: int = RENDER_SEED,
+                    real_mode: int = RTK_REAL_F64):
+        """rtk_lens_guides_host: ``guides`` through ``lens``, float32 (H, W, 16)."""
+        import numpy as np
+
+        out = np.zeros((lens.cam.image_height, lens.cam.image_width, 16), np.float32)
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        gopts = GuideOpts(int(follow), int(max_bounces))
+        self._check(self._lib.rtk_lens_guides_host(self._ctx, C.byref(lens), C.byref(opts), int(samples), C.byref(gopts), out.ctypes.data))
+        return out
+
+    def lens_rays_device(self, lens: Lens, samples: int, d_rays: int, *, first_sample: int = 0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64,
+                         stream: int = 0) -> None:
+        """rtk_lens_rays with a raw device pointer (H * W * samples rtk_ray records out); asynchronous on ``stream``."""
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        self._check(self._lib.rtk_lens_rays(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), int(samples), d_rays or None))
+
+    def lens_render_device(self, lens: Lens, d_linear: int, d_noise: int = 0, *, first_sample: int = 0, seed: int = RENDER_SEED,
+                           real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_lens_render with raw device pointers ([H][W][3] reals of ``real_mode``, float [H][W] se when ``d_noise`` is given);
+        asynchronous on ``stream``."""
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        self._check(self._lib.rtk_lens_render(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), d_linear or None, d_noise or None))
+
+    def lens_aovs_device(self, lens: Lens, samples: int, d_aov: int, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_lens_aovs with a raw device pointer (float [H][W][8], 16-byte aligned); asynchronous on ``stream``."""
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        self._check(self._lib.rtk_lens_aovs(self._ctx, C.byref(lens), C.byref(opts), int(samples), d_aov or None))
+
+    def lens_guides_device(self, lens: Lens, samples: int, d_guides: int, *, follow: int = GUIDE_FOLLOW_MIRROR, max_bounces: int = 0,
+                           seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_lens_guides with a raw device pointer (float [H][W][16], 16-byte aligned); asynchronous on ``stream``."""
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        gopts = GuideOpts(int(follow), int(max_bounces))
+        self._check(self._lib.rtk_lens_guides(self._ctx, C.byref(lens), C.byref(opts), int(samples), C.byref(gopts), d_guides or None))
+
     def camera_rays(self, cam: Camera, seed: int, pixel_sample, real_mode: int = RTK_REAL_F64):
         """The render's own rays as ray records: ``debug_get_ray`` of ``pixel_sample`` [n][3] = i, j, sample, with the stream
         keys of that pixel and sample (pixel = j * W + i) and skip = the draws get_ray consumed, so that a query continues the
@@ -953,6 +1062,13 @@ class Renderer:
         gopts = GuideOpts(int(follow), int(max_bounces))
         self._check(self._lib.rtk_render_guides_host(self._ctx, C.byref(cam), C.byref(opts), int(samples), C.byref(gopts), out.ctypes.data))
         return out
+
+    def guides_device(self, cam: Camera, samples: int, d_guides: int, *, follow: int = GUIDE_FOLLOW_MIRROR, max_bounces: int = 0, seed: int = RENDER_SEED,
+                      real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_render_guides with a raw device pointer (float [H][W][16], 16-byte aligned); asynchronous on ``stream``."""
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        gopts = GuideOpts(int(follow), int(max_bounces))
+        self._check(self._lib.rtk_render_guides(self._ctx, C.byref(cam), C.byref(opts), int(samples), C.byref(gopts), d_guides or None))
 
     def denoise_guided(self, linear, guides, noise, *, demodulate: bool = False, real_mode: int = RTK_REAL_F64, iterations: int = 0,
                        sigma_l: float = 0.0, sigma_n: float = 0.0, sigma_z: float = 0.0, sigma_a: float = 0.0):

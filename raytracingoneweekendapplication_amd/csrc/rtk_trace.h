@@ -111,6 +111,29 @@ template <typename real>
 hipError_t launch_probe_bake(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, uint32_t first_key, int rays, double time, long long n,
                              const double* d_positions, void* d_sh, hipStream_t stream);
 
+// Lens models (rtk_lens_*): what the kernels read of an rtk_lens besides its camera record, in double in both real modes.
+// half_h / half_v = fov_h / 2, fov_v / 2 with the defaults resolved (EQUIRECT, FISHEYE) or ortho_width / 2, ortho_height / 2
+// (ORTHOGRAPHIC): halving is exact, so the rule's x * (fov_h / 2) is x * half_h.
+struct LensRec {
+    double center[3], u[3], v[3], w[3];
+    double half_h, half_v;
+    int32_t model, reserved;
+};
+// launch_lens_rays: the records of samples first_sample .. + n_samples - 1 of every pixel, one lane each, [H * W * n_samples].
+// launch_lens_render: cam.spp samples per pixel, a pixel's samples spread over up to 16 lanes and summed in sample order;
+// d_linear [H][W][3] reals, d_noise [H][W] or null.
+// launch_lens_aov / _guides: launch_aov / launch_guides with the lens's record as the primary ray.
+template <typename real>
+hipError_t launch_lens_rays(const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, uint32_t first_sample, int n_samples, void* d_rays, hipStream_t stream);
+template <typename real>
+hipError_t launch_lens_render(const SceneView<real>& sc, const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, uint32_t first_sample, void* d_linear,
+                              float* d_noise, hipStream_t stream);
+template <typename real>
+hipError_t launch_lens_aov(const SceneView<real>& sc, const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream);
+template <typename real>
+hipError_t launch_lens_guides(const SceneView<real>& sc, const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, int n_samples, int follow, int max_bounces,
+                              float* d_guides, hipStream_t stream);
+
 // A one-rank progressive session's preview and se (row-major) from its running sum and noise sums; tile_spp null = every tile
 // holds `done` samples.  Reads the state only.
 template <typename real>

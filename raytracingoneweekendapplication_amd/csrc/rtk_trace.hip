@@ -2187,6 +2187,101 @@ RTK_DEV void begin_walk(Lane<real>& L, Counters<COUNT>& cnt) {
     begin_segment<true>(L, cnt);
 }
 
+// Lens models (include/rtk.h "Lens models"): the primary ray of sample `sample` of pixel (i, j) through another projection than
+// get_ray's.  The rule of the three film models: three draws from the sample's stream, then double arithmetic in both real
+// modes, contraction off whatever the flags of the kernel it lands in, nothing renormalised.
+struct LensLocal { double x, y, z; };
+#ifndef RTK_LENS_INLINE
+#define RTK_LENS_LOCAL RTK_NOINLINE   // (tools/kernel_resources.py -DRTK_LENS_INLINE: the inlined form DESIGN.md compares it with)
+#else
+#define RTK_LENS_LOCAL RTK_DEV
+#endif
+// The local direction at film coordinates (x, y) of EQUIRECT and FISHEYE; aspect = double(H) / double(W).  Out of line, on
+// scalars alone and returned in registers: the double sin / cos carry a large-argument path that the path-loop kernels would
+// otherwise pay for in registers (DESIGN.md "lens models" has the counts), as the render kernels keep acos / atan2 / sin out.
+RTK_LENS_LOCAL LensLocal lens_local(int model, double half_h, double half_v, double aspect, double x, double y) {
+#pragma clang fp contract(off)
+    LensLocal l{0.0, 0.0, -1.0};
+    if (model == RTK_LENS_EQUIRECT) {
+        const double lon = x * half_h, lat = y * half_v, c = cos(lat);
+        l.x = c * sin(lon);
+        l.y = sin(lat);
+        l.z = -(c * cos(lon));
+    } else {  // RTK_LENS_FISHEYE
+        const double yy = y * aspect;
+        const double rr = rt_sqrt(x * x + yy * yy);
+        if (rr != 0.0) {
+            const double theta = rr * half_h, st = sin(theta);
+            l.x = st * (x / rr);
+            l.y = st * (yy / rr);
+            l.z = -cos(theta);
+        }
+    }
+    return l;
+}
+
+// r[7] = origin, direction, time of the film models; rng = the sample's stream, left three draws on.
+RTK_DEV void lens_film_ray(const LensRec& lens, int width, int height, int i, int j, uint32_t& rng, double* __restrict__ r) {
+#pragma clang fp contract(off)
+    Counters<false> cnt;
+    const double oy = rnd<double>(rng, cnt) - 0.5;
+    const double ox = rnd<double>(rng, cnt) - 0.5;
+    r[6] = rnd<double>(rng, cnt);
+    const double x = 2.0 * ((double(i) + ox) + 0.5) / double(width) - 1.0;
+    const double y = 1.0 - 2.0 * ((double(j) + oy) + 0.5) / double(height);
+    LensLocal l{0.0, 0.0, -1.0};
+    r[0] = lens.center[0]; r[1] = lens.center[1]; r[2] = lens.center[2];
+    if (lens.model == RTK_LENS_ORTHOGRAPHIC) {
+        const double ax = x * lens.half_h, ay = y * lens.half_v;
+        for (int k = 0; k < 3; k++) r[k] = (lens.center[k] + ax * lens.u[k]) + ay * lens.v[k];
+    } else {
+        l = lens_local(lens.model, lens.half_h, lens.half_v, double(height) / double(width), x, y);
+    }
+    for (int k = 0; k < 3; k++) r[3 + k] = (l.x * lens.u[k] + l.y * lens.v[k]) + l.z * lens.w[k];
+}
+
+// The one function behind rtk_lens_rays, rtk_lens_render and the lens forms of the AOV / guide kernel: the lane's ray, its
+// stream where ray generation left it, and the start of a path (radiance, throughput, depth, as begin_sample leaves them); the
+// record's reals in double in r[7]; returns the record's skip.  PERSPECTIVE is begin_sample itself, in `real`, and the record its
+// values widened; the film models compute the record and the lane takes it rounded to `real`, as load_query_ray would.
+template <typename real>
+RTK_DEV uint32_t lens_begin(Lane<real>& L, const LensRec& lens, const CameraRec<real>& cam, int i, int j, uint32_t sample, uint32_t seed_hash,
+                            double* __restrict__ r) {
+    L.s = int(sample);
+    if (lens.model == RTK_LENS_PERSPECTIVE) {
+        Counters<true> cnt;
+        cnt.clear();
+        begin_sample(L, cam, i, j, seed_hash, cnt);
+        r[0] = double(L.ro.x); r[1] = double(L.ro.y); r[2] = double(L.ro.z);
+        r[3] = double(L.rd.x); r[4] = double(L.rd.y); r[5] = double(L.rd.z);
+        r[6] = double(L.tm);
+        return cnt.c[C_RNG];
+    }
+    L.rng = stream_key(seed_hash, uint32_t(j * cam.width + i), sample);
+    lens_film_ray(lens, cam.width, cam.height, i, j, L.rng, r);
+    load_ray(L, r);
+    L.radiance = mk(real(0), real(0), real(0));
+    L.throughput = mk(real(1), real(1), real(1));
+    L.depth = cam.max_depth;
+    return 3u;
+}
+
+// The sample generators of rtk_guide_kernel: sample L.s of pixel (i, j) from the render's camera, or through a lens.
+struct CameraSamples {
+    template <typename real, bool COUNT>
+    RTK_DEV void begin(Lane<real>& L, const CameraRec<real>& cam, int i, int j, uint32_t seed_hash, Counters<COUNT>& cnt) const {
+        begin_sample(L, cam, i, j, seed_hash, cnt);
+    }
+};
+struct LensSamples {
+    LensRec lens;
+    template <typename real, bool COUNT>
+    RTK_DEV void begin(Lane<real>& L, const CameraRec<real>& cam, int i, int j, uint32_t seed_hash, Counters<COUNT>&) const {
+        double r[7];
+        (void)lens_begin(L, lens, cam, i, j, uint32_t(L.s), seed_hash, r);
+    }
+};
+
 // hittable::hit(r, interval(tmin, tmax), rec) of the scene root for r[9] = origin, direction, time, tmin, tmax: the one walk
 // behind rtk_debug_closest_hit, rtk_query_hits and rtk_query_occluded.  The lane holds the ray (load_ray) and L.rng, the stream
 // a constant medium draws from; L.best_pc / L.best_t hold the winner afterwards, cnt.c[C_RNG] the draws.
@@ -2375,10 +2470,11 @@ struct HitSums {
     }
 };
 
-// follow / max_bounces: read by CHAIN alone.  out holds two float4 per pixel, four with CHAIN.
-template <typename real, bool CHAIN>
+// follow / max_bounces: read by CHAIN alone.  out holds two float4 per pixel, four with CHAIN.  gen makes the primary ray of
+// sample L.s: CameraSamples (begin_sample: rtk_render_aovs / _guides) or LensSamples (rtk_lens_aovs / _guides).
+template <typename real, bool CHAIN, typename Gen>
 __global__ __launch_bounds__(256) void rtk_guide_kernel(TileGrid grid, SceneView<real> sc, CameraRec<real> cam, uint32_t seed, int n_samples, int follow,
-                                                         int max_bounces, float4* __restrict__ out) {
+                                                         int max_bounces, float4* __restrict__ out, Gen gen) {
     int i, j;
     if (!lane_pixel(grid, i, j)) return;
     if constexpr (CHAIN) sc.n_lights = 0;  // get_lighting (Camera.txt:228) belongs to ray_color, not to scatter()
@@ -2393,7 +2489,7 @@ __global__ __launch_bounds__(256) void rtk_guide_kernel(TileGrid grid, SceneView
         Lane<real> L;
         L.s = s;
         L.segs = 0;
-        begin_sample(L, cam, i, j, seed_hash, cnt);
+        gen.begin(L, cam, i, j, seed_hash, cnt);
         if constexpr (CHAIN) L.depth = 1 << 20;  // (the chain is capped by max_bounces, not by the camera's max_depth)
         [[maybe_unused]] real len = real(0);
         for (int b = 0;; b++) {
@@ -2519,6 +2615,20 @@ __global__ __launch_bounds__(256) void rtk_query_occluded_kernel(SceneView<real>
 // world.hit on interval(0.001, inf), shade -- until the path ends.  cam carries background, max_depth and spp = the samples per
 // ray; sample s of a ray draws from the stream (seed, pixel, sample + s) advanced by skip.  The sum runs in sample order and
 // is divided once.  COUNT: draws[k] = the uniforms the paths of ray k drew.
+// The path of the ray and stream a lane holds (L.ro, L.rd, L.tm, L.rng; radiance 0, throughput 1, depth = max_depth), to its end:
+// the loop the radiance query, the probe bake and the lens frames share.  L.radiance is ray_color's value afterwards.
+template <typename real, bool COUNT>
+RTK_DEV void trace_path(Lane<real>& L, const SceneView<real>& sc, const CameraRec<real>& cam, Counters<COUNT>& cnt RTK_SHADE_PROF_PARAM) {
+    clear_parked(L);
+    L.segs = 0;
+    while (L.depth > 0) {
+        begin_segment<true>(L, cnt);
+        closest_hit_slots(L, sc, cnt);
+        const Slot<real>* hit_rec = sc.program + (L.best_pc != kNoHit ? L.best_pc : 0u);
+        if (shade<real, kFeatAll, COUNT>(L, hit_rec, sc, sc.materials, cam, cnt RTK_SHADE_PROF_ARG)) break;
+    }
+}
+
 template <typename real, bool COUNT>
 __global__ __launch_bounds__(256) void rtk_query_radiance_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, long long n,
                                                                   const double* __restrict__ rays, real* __restrict__ radiance, uint32_t* __restrict__ draws) {
@@ -2535,17 +2645,10 @@ __global__ __launch_bounds__(256) void rtk_query_radiance_kernel(SceneView<real>
     for (int s = 0; s < cam.spp; s++) {
         Lane<real> L;
         load_query_ray(L, r, seed_hash, uint32_t(s));
-        clear_parked(L);
-        L.segs = 0;
         L.radiance = mk(real(0), real(0), real(0));
         L.throughput = mk(real(1), real(1), real(1));
         L.depth = cam.max_depth;
-        while (L.depth > 0) {
-            begin_segment<true>(L, cnt);
-            closest_hit_slots(L, sc, cnt);
-            const Slot<real>* hit_rec = sc.program + (L.best_pc != kNoHit ? L.best_pc : 0u);
-            if (shade<real, kFeatAll, COUNT>(L, hit_rec, sc, sc.materials, cam, cnt RTK_SHADE_PROF_ARG)) break;
-        }
+        trace_path(L, sc, cam, cnt RTK_SHADE_PROF_ARG);
         sum = sum + L.radiance;
     }
     const real ns = real(cam.spp);
@@ -2646,17 +2749,10 @@ __global__ __launch_bounds__(256) void rtk_probe_bake_kernel(SceneView<real> sc,
             L.rd = rd;
             L.tm = real(time);
             L.rng = stream_key(seed_hash, pixel, uint32_t(j) * uint32_t(cam.spp) + uint32_t(s));   // (skip = 0)
-            clear_parked(L);
-            L.segs = 0;
             L.radiance = mk(real(0), real(0), real(0));
             L.throughput = mk(real(1), real(1), real(1));
             L.depth = cam.max_depth;
-            while (L.depth > 0) {
-                begin_segment<true>(L, cnt);
-                closest_hit_slots(L, sc, cnt);
-                const Slot<real>* hit_rec = sc.program + (L.best_pc != kNoHit ? L.best_pc : 0u);
-                if (shade<real, kFeatAll, false>(L, hit_rec, sc, sc.materials, cam, cnt RTK_SHADE_PROF_ARG)) break;
-            }
+            trace_path(L, sc, cam, cnt RTK_SHADE_PROF_ARG);
             sum = sum + L.radiance;
         }
         const real ns = real(cam.spp);
@@ -2685,6 +2781,104 @@ __global__ __launch_bounds__(256) void rtk_probe_bake_kernel(SceneView<real> sc,
         const double total = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
         sh[k * 27 + t] = real(total * (12.566370614359172953850573533118 / double(rays)));
     }
+}
+
+// ------------------------------------------------------------------ lens models --
+// Whole frames through a lens (include/rtk.h "Lens models"): lens_begin above makes the sample; these kernels store it or trace it.
+
+// The records of samples first_sample .. first_sample + n_samples - 1 of every pixel, pixel-major, samples inner: lane gid writes
+// sample gid % n_samples of pixel gid / n_samples as eleven 8-byte words.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_lens_rays_kernel(long long n_rays, LensRec lens, CameraRec<real> cam, uint32_t seed, uint32_t first_sample, int n_samples,
+                                                             double* __restrict__ out) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= n_rays) return;
+    const uint32_t pixel = uint32_t(gid / n_samples), sample = first_sample + uint32_t(gid - (long long)pixel * n_samples);
+    Lane<real> L;
+    double r[7];
+    const uint32_t skip = lens_begin(L, lens, cam, int(pixel % uint32_t(cam.width)), int(pixel / uint32_t(cam.width)), sample, pcg_hash(seed), r);
+    double* o = out + gid * 11;
+    for (int k = 0; k < 7; k++) o[k] = r[k];
+    o[7] = 0.001;
+    o[8] = __builtin_inf();
+    uint2* keys = reinterpret_cast<uint2*>(o + 9);
+    keys[0] = make_uint2(pixel, sample);
+    keys[1] = make_uint2(skip, 0u);
+}
+
+// The standard error of a pixel's mean from the sums of y_s and y_s^2 over its n samples (the session estimate's form).
+RTK_DEV float lens_se(double s1, double s2, int n) {
+    if (n < 2) return 0.0f;
+    const double m = s1 / double(n);
+    double v = (s2 - double(n) * m * m) / double(n - 1);
+    v = v > 0.0 ? v : 0.0;
+    return float(__builtin_sqrt(v / double(n)));
+}
+
+// The lanes of a lens frame.  G = 1 << group_log2 consecutive lanes share a pixel (G = 1, 2, 4, 8, 16: the largest that does not exceed
+// the samples per pixel) and a wave holds the 64 / G pixels of a small tile, 8x8, 8x4, 4x4, 4x2 or 2x2.  Lane `slot` of a pixel
+// traces samples slot, slot + G, ...; after each round of G samples every lane of the pixel reads the round's radiance from its
+// G lanes IN SAMPLE ORDER and adds it to its own copy of the sums, so the pixel's sums are ((0 + L_0) + L_1) + ... whatever G is:
+// no atomics, nothing depends on the launch geometry.  Per sample: the record in registers (no record touches memory), then the
+// radiance query's path; the record's doubles die before the path starts, and only the three colour sums and the two noise sums
+// live across it.  Why not one lane per pixel with the whole sample loop inside, as the guide kernel has it: a wave then lasts
+// the sum over the samples of its longest path, and a frame has G times fewer, G times longer waves -- where the cost sits in a
+// few tiles (an equirect view of book1_final: 6.7 ms against 6.0 for rtk_lens_rays + rtk_query_radiance) the tail decides
+// (DESIGN.md "lens models").
+struct LensLanes {
+    int width, height, tiles_x, n_tiles, group_log2;
+};
+static LensLanes lens_lanes(int width, int height, int spp) {
+    int g = 0;
+    while (g < 4 && (2 << g) <= spp) g++;
+    const int tw = 8 >> (g / 2), th = 8 >> ((g + 1) / 2);
+    const int tiles_x = (width + tw - 1) / tw;
+    return LensLanes{width, height, tiles_x, tiles_x * ((height + th - 1) / th), g};
+}
+
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_lens_render_kernel(LensLanes lanes, SceneView<real> sc, CameraRec<real> cam, LensRec lens, uint32_t seed, uint32_t first_sample,
+                                                               real* __restrict__ out, float* __restrict__ noise) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int tile = int(gid >> 6), lane = int(gid & 63), g = lanes.group_log2, group = 1 << g;
+    if (tile >= lanes.n_tiles) return;
+    const int lw = 3 - g / 2, slot = lane & (group - 1), p = lane >> g;
+    const int i = ((tile % lanes.tiles_x) << lw) + (p & ((1 << lw) - 1)), j = (tile / lanes.tiles_x) * (8 >> ((g + 1) / 2)) + (p >> lw);
+    if (i >= lanes.width || j >= lanes.height) return;            // (the G lanes of a pixel leave together)
+    Counters<false> cnt;
+#ifdef RTK_PROFILE
+    ShadeProf sprof;  // (the profile build's shade functions take their sub-phase accumulators)
+#endif
+    const uint32_t seed_hash = pcg_hash(seed);
+    V3<real> sum = mk(real(0), real(0), real(0));
+    double s1 = 0.0, s2 = 0.0;
+    for (int base = 0; base < cam.spp; base += group) {
+        V3<real> radiance = mk(real(0), real(0), real(0));
+        if (base + slot < cam.spp) {
+            Lane<real> L;
+            {
+                double r[7];
+                (void)lens_begin(L, lens, cam, i, j, first_sample + uint32_t(base + slot), seed_hash, r);
+            }
+            trace_path(L, sc, cam, cnt RTK_SHADE_PROF_ARG);
+            radiance = radiance + L.radiance;                     // (what the query returns for samples = 1: 0 + L, never -0)
+        }
+        const int n = cam.spp - base < group ? cam.spp - base : group;
+        for (int k = 0; k < n; k++) {                             // the round's samples in sample order, from the pixel's own lanes
+            const V3<real> r = mk(__shfl(radiance.x, k, group), __shfl(radiance.y, k, group), __shfl(radiance.z, k, group));
+            sum = sum + r;
+            const double y = ((double(r.x) + double(r.y)) + double(r.z)) / 3.0;
+            s1 = s1 + y;
+            s2 = s2 + y * y;
+        }
+    }
+    if (slot != 0) return;
+    const size_t px = size_t(j) * cam.width + i;
+    real* o = out + px * 3;
+    o[0] = sum.x * cam.samples_scale;
+    o[1] = sum.y * cam.samples_scale;
+    o[2] = sum.z * cam.samples_scale;
+    if (noise) noise[px] = lens_se(s1, s2, cam.spp);
 }
 
 // ------------------------------------------------------------------ launchers --
@@ -3002,7 +3196,7 @@ template hipError_t launch_debug_get_ray<float>(const CameraRec<float>&, uint32_
 template <typename real>
 hipError_t launch_aov(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream) {
     const TileGrid grid = tile_grid(cam.width, cam.height);
-    rtk_guide_kernel<real, false><<<lane_grid(64ll * grid.n_tiles), dim3(256), 0, stream>>>(grid, sc, cam, seed, n_samples, 0, 0, reinterpret_cast<float4*>(d_aov));
+    rtk_guide_kernel<real, false><<<lane_grid(64ll * grid.n_tiles), dim3(256), 0, stream>>>(grid, sc, cam, seed, n_samples, 0, 0, reinterpret_cast<float4*>(d_aov), CameraSamples{});
     return hipGetLastError();
 }
 template hipError_t launch_aov<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, float*, hipStream_t);
@@ -3013,7 +3207,7 @@ hipError_t launch_guides(const SceneView<real>& sc, const CameraRec<real>& cam, 
                          hipStream_t stream) {
     const TileGrid grid = tile_grid(cam.width, cam.height);
     rtk_guide_kernel<real, true><<<lane_grid(64ll * grid.n_tiles), dim3(256), 0, stream>>>(grid, sc, cam, seed, n_samples, follow, max_bounces,
-                                                                                         reinterpret_cast<float4*>(d_guides));
+                                                                                         reinterpret_cast<float4*>(d_guides), CameraSamples{});
     return hipGetLastError();
 }
 template hipError_t launch_guides<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, int, int, int, float*, hipStream_t);
@@ -3067,6 +3261,47 @@ hipError_t launch_probe_bake(const SceneView<real>& sc, const CameraRec<real>& c
 }
 template hipError_t launch_probe_bake<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, uint32_t, int, double, long long, const double*, void*, hipStream_t);
 template hipError_t launch_probe_bake<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, uint32_t, int, double, long long, const double*, void*, hipStream_t);
+
+template <typename real>
+hipError_t launch_lens_rays(const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, uint32_t first_sample, int n_samples, void* d_rays, hipStream_t stream) {
+    const long long n = (long long)cam.width * cam.height * n_samples;
+    if (n <= 0) return hipSuccess;
+    rtk_lens_rays_kernel<real><<<lane_grid(n), dim3(256), 0, stream>>>(n, lens, cam, seed, first_sample, n_samples, static_cast<double*>(d_rays));
+    return hipGetLastError();
+}
+template hipError_t launch_lens_rays<double>(const LensRec&, const CameraRec<double>&, uint32_t, uint32_t, int, void*, hipStream_t);
+template hipError_t launch_lens_rays<float>(const LensRec&, const CameraRec<float>&, uint32_t, uint32_t, int, void*, hipStream_t);
+
+template <typename real>
+hipError_t launch_lens_render(const SceneView<real>& sc, const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, uint32_t first_sample, void* d_linear,
+                              float* d_noise, hipStream_t stream) {
+    const LensLanes lanes = lens_lanes(cam.width, cam.height, cam.spp);
+    rtk_lens_render_kernel<real><<<lane_grid(64ll * lanes.n_tiles), dim3(256), 0, stream>>>(lanes, sc, cam, lens, seed, first_sample, static_cast<real*>(d_linear), d_noise);
+    return hipGetLastError();
+}
+template hipError_t launch_lens_render<double>(const SceneView<double>&, const LensRec&, const CameraRec<double>&, uint32_t, uint32_t, void*, float*, hipStream_t);
+template hipError_t launch_lens_render<float>(const SceneView<float>&, const LensRec&, const CameraRec<float>&, uint32_t, uint32_t, void*, float*, hipStream_t);
+
+template <typename real>
+hipError_t launch_lens_aov(const SceneView<real>& sc, const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, int n_samples, float* d_aov, hipStream_t stream) {
+    const TileGrid grid = tile_grid(cam.width, cam.height);
+    rtk_guide_kernel<real, false><<<lane_grid(64ll * grid.n_tiles), dim3(256), 0, stream>>>(grid, sc, cam, seed, n_samples, 0, 0, reinterpret_cast<float4*>(d_aov),
+                                                                                          LensSamples{lens});
+    return hipGetLastError();
+}
+template hipError_t launch_lens_aov<double>(const SceneView<double>&, const LensRec&, const CameraRec<double>&, uint32_t, int, float*, hipStream_t);
+template hipError_t launch_lens_aov<float>(const SceneView<float>&, const LensRec&, const CameraRec<float>&, uint32_t, int, float*, hipStream_t);
+
+template <typename real>
+hipError_t launch_lens_guides(const SceneView<real>& sc, const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, int n_samples, int follow, int max_bounces,
+                              float* d_guides, hipStream_t stream) {
+    const TileGrid grid = tile_grid(cam.width, cam.height);
+    rtk_guide_kernel<real, true><<<lane_grid(64ll * grid.n_tiles), dim3(256), 0, stream>>>(grid, sc, cam, seed, n_samples, follow, max_bounces,
+                                                                                         reinterpret_cast<float4*>(d_guides), LensSamples{lens});
+    return hipGetLastError();
+}
+template hipError_t launch_lens_guides<double>(const SceneView<double>&, const LensRec&, const CameraRec<double>&, uint32_t, int, int, int, float*, hipStream_t);
+template hipError_t launch_lens_guides<float>(const SceneView<float>&, const LensRec&, const CameraRec<float>&, uint32_t, int, int, int, float*, hipStream_t);
 
 #ifdef RTK_ISA_PROBES
 // Instruction-cost probes (tools/isa_costs.py; never part of the product build): one kernel per unit of work of the lean

@@ -206,6 +206,37 @@ public:
     bool display_srgb = false;               // sRGB bytes instead of the reference's gamma 2
     double last_exposure = 0;                // set by render(): the exposure its images were made with (0: display off)
     void display_reset() { if (display_) rtk_display_reset(display_->display); }  // the next render() adapts from nothing
+    // Lens models (rtk_lens_*; one device, as progressive rendering).  projection = equirect / fisheye / orthographic: render()
+    // makes the frame with rtk_lens_render -- lookfrom / lookat / vup give the frame (rtk_lens_look_at), image_width and
+    // aspect_ratio the size, samples_per_pixel, max_depth and background their usual meaning; vfov, defocus_angle and focus_dist
+    // are not read -- and writes it to image_name through the reference's sqrt / clamp / quantise, or through `display`.  With
+    // denoise_image_name set it also writes the guided filter (rtk_lens_guides with aov_samples and denoise_follow, then
+    // rtk_denoise_guided on the frame and its se; samples_per_pixel >= 2 for the se).  temporal_history > 0 or render_scale > 1
+    // with such a projection make render() fail with a message: reprojection and the low-resolution camera assume a pinhole.
+    // perspective (default): nothing changes, bit for bit.
+    enum projection_kind { perspective = RTK_LENS_PERSPECTIVE, equirect = RTK_LENS_EQUIRECT, fisheye = RTK_LENS_FISHEYE, orthographic = RTK_LENS_ORTHOGRAPHIC };
+    int projection = perspective;
+    double fov_h = 0, fov_v = 0;             // radians; equirect: the extents (0 = 2 pi, pi); fisheye: fov_h across the width (0 = pi)
+    double ortho_width = 0, ortho_height = 0;  // orthographic: the window in world units
+
+    // The rtk_lens of a non-perspective projection.
+    rtk_lens derive_lens() const {
+        rtk_lens l{};
+        int image_height = int(image_width / aspect_ratio);
+        l.cam.image_width = image_width;
+        l.cam.image_height = (image_height < 1) ? 1 : image_height;
+        l.cam.samples_per_pixel = samples_per_pixel;
+        l.cam.max_depth = max_depth;
+        l.cam.background = rtk::to_abi(background);
+        l.cam.pixel_samples_scale = 1.0 / samples_per_pixel;
+        l.model = projection;
+        l.fov_h = fov_h;
+        l.fov_v = fov_v;
+        l.ortho_width = ortho_width;
+        l.ortho_height = ortho_height;
+        rtk_lens_look_at(&l, rtk::to_abi(lookfrom), rtk::to_abi(lookat), rtk::to_abi(vup));
+        return l;
+    }
 
     // Camera.txt:136-175.
     rtk_camera derive() const {
@@ -566,6 +597,57 @@ public:
         return rc;
     }
 
+    // render() with another projection than perspective (see the member): one device, the frame and its se from rtk_lens_render,
+    // the bytes by the reference's conversion (Camera.txt:29-34,77-83) or the display object.
+    int render_lens(const hittable& world, const std::vector<point_light>& lights, std::vector<uint8_t>* rgb8) {
+        rtk::scene_builder sb;
+        rtk_scene_desc desc = rtk::flatten(world, lights, sb);
+        const rtk_lens lens = derive_lens();
+        const rtk_camera& cam = lens.cam;
+        int dev = devices.empty() ? device : devices[0];
+        rtk_multi* multi = nullptr;
+        int rc = rtk_init_multi(1, &dev, RTK_GATHER_PEER, &multi);
+        if (rc != RTK_OK) return rc;
+        rc = upload(multi, desc, cam);
+        rtk_render_opts opts{};
+        opts.seed = seed;
+        opts.real_mode = real_mode;
+        opts.rank = 0;
+        opts.n_ranks = 1;
+        rtk_ctx* ctx = rtk_multi_ctx(multi, 0);
+        const size_t px = size_t(cam.image_width) * cam.image_height;
+        std::vector<double> linear(px * 3);
+        std::vector<float> noise(denoise_image_name ? px : 0);
+        if (rc == RTK_OK) {
+            auto t0 = std::chrono::steady_clock::now();
+            rc = rtk_lens_render_host(ctx, &lens, &opts, 0, linear.data(), denoise_image_name ? noise.data() : nullptr);
+            last_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        if (rc == RTK_OK) {
+            rgb8->resize(px * 3);
+            for (size_t k = 0; k < px * 3; k++) {
+                double g = linear[k] > 0 ? std::sqrt(linear[k]) : 0.0;
+                g = g < 0.000 ? 0.000 : (g > 0.999 ? 0.999 : g);
+                (*rgb8)[k] = uint8_t(int(255.999 * g));
+            }
+            rc = display_bytes(cam, linear.data(), rgb8->data());
+        }
+        if (rc == RTK_OK && denoise_image_name) {
+            std::vector<float> guides(px * 16);
+            std::vector<uint8_t> den(px * 3);
+            std::vector<double> den_linear(display ? px * 3 : 0);
+            const rtk_guide_opts go{denoise_follow, 0};
+            rc = rtk_lens_guides_host(ctx, &lens, &opts, aov_samples, &go, guides.data());
+            if (rc == RTK_OK)
+                rc = rtk_denoise_guided_host(ctx, cam.image_width, cam.image_height, real_mode, linear.data(), guides.data(), noise.data(), nullptr,
+                                             denoise_demodulate ? RTK_DENOISE_DEMODULATE : 0, display ? den_linear.data() : nullptr, den.data());
+            if (rc == RTK_OK) rc = display_bytes(cam, den_linear.data(), den.data());
+            if (rc == RTK_OK && write_image) rtk::write_png(denoise_image_name, cam.image_width, cam.image_height, den.data());
+        }
+        rtk_multi_destroy(multi);
+        return rc;
+    }
+
     // With `display`: rgb8 = the display transform of `linear` (see the member); without: nothing.
     int display_bytes(const rtk_camera& cam, const double* linear, uint8_t* rgb8) {
         if (!display) return RTK_OK;
@@ -614,10 +696,16 @@ public:
         last_render_upsampled = false;
         last_exposure = 0;
         display_metered_ = false;
-        int rc = render_scale != 1 ? render_scaled(world, lights, &rgb8, &scaled) : RTK_OK;
+        const bool lens = projection != perspective;
+        if (lens && (temporal_history > 0 || render_scale > 1)) {
+            std::cerr << "camera::render failed: temporal_history and render_scale need the perspective projection (reprojection and the low-resolution "
+                         "camera assume a pinhole)" << std::endl;
+            return;
+        }
+        int rc = lens ? render_lens(world, lights, &rgb8) : (render_scale != 1 ? render_scaled(world, lights, &rgb8, &scaled) : RTK_OK);
         last_render_upsampled = scaled;
-        if (rc == RTK_OK && !scaled && temporal_history > 0) rc = render_temporal(world, lights, &rgb8, &temporal);
-        if (rc == RTK_OK && !temporal && !scaled)
+        if (rc == RTK_OK && !lens && !scaled && temporal_history > 0) rc = render_temporal(world, lights, &rgb8, &temporal);
+        if (rc == RTK_OK && !lens && !temporal && !scaled)
             rc = progressive_step > 0 || denoise_image_name ? render_progressive(world, lights, &rgb8) : render_plain(world, lights, &rgb8);
         if (rc != RTK_OK) {
             std::cerr << "camera::render failed: " << rtk_last_error() << std::endl;
