@@ -790,7 +790,8 @@ int rtk_temporal_reproject_matrix(const rtk_camera* cam, double out[12]);
  *   3. Blend: omega = beta (w + 1e-3); Omega = sum omega; out = sum omega c_q / Omega; var_out = sum omega^2 se_q^2 / Omega^2;
  *      support = sum beta w / sum beta, the share of the bilinear weight the guides accepted.  The floor 1e-3 makes a pixel
  *      whose taps are all rejected fall back smoothly to the (edge-renormalised) bilinear interpolation; there is no threshold.
- *      A caller can re-render pixels with low support (rtk_query_radiance with the frame's own streams: INTEGRATION 4g).
+ *      A caller can re-render pixels with low support (whole tiles with the render kernel: "Tile lists" below; single pixels
+ *      with rtk_query_radiance and the frame's own streams: INTEGRATION 4g).
  *   4. RTK_UPSAMPLE_DEMODULATE: per tap A_q = max(G[8..10], 0.02) per channel, c_q <- c_q / A_q, se_q^2 <- se_q^2 /
  *      ((A_q.x + A_q.y + A_q.z) / 3)^2; after the blend out <- out * A_p, var_out <- var_out * mean(A_p)^2, A_p from g[8..10].
  *   5. d_out_linear = out, d_out_noise = sqrt(var_out), d_out_support = support, d_out_rgb8 = the resolve's gamma / clamp /
@@ -1108,6 +1109,67 @@ int rtk_lens_rays_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts
 int rtk_lens_render_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, double* h_linear, float* h_noise);
 int rtk_lens_aovs_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, float* h_aov);
 int rtk_lens_guides_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* h_guides);
+
+/* Tile lists --------------------------------------------------------------------------
+ * Render a chosen set of the frame's 8x8 tiles with the render kernel itself: the pixels of the chosen tiles come out with the
+ * bits rtk_render_device gives them, at a cost that follows the number of tiles, and every other pixel of the caller's buffers
+ * is left alone.  A tile set is an array of rtk_tiles_per_rank(width, height, 1) int32 flags, row-major over the tiles (tile t
+ * covers pixels x in 8 (t % tiles_x) .. + 7, y in 8 (t / tiles_x) .. + 7, clipped to the image); a tile is chosen when its flag
+ * is non-zero.  One rank only.  New entry points; RTK_ABI_VERSION stays 2.
+ *
+ * rtk_tiles_select makes a tile set from per-pixel maps (W*H floats each, row-major) -- the support map of rtk_upsample, a
+ * noise map, any per-pixel score.  The rule, in integers after two float comparisons per pixel:
+ *   1. Raw flags.  An in-image pixel q is raw-flagged when d_below_map is given and !(below_map[q] >= opts->below), or when
+ *      d_above_map is given and !(above_map[q] <= opts->above).  A NaN flags; a value equal to its threshold does not; with
+ *      both maps the two tests are OR-ed.  Either map may be NULL, not both.
+ *   2. Dilation.  With r = opts->dilate (0..8) tile t is flagged -- d_tile_flags[t] = 1, otherwise 0 -- iff some raw-flagged
+ *      in-image pixel q lies within r of an in-image pixel p of the tile in both x and y (Chebyshev distance): with the tile's
+ *      in-image pixels x0 .. x1, y0 .. y1, iff a raw-flagged q has x0 - r <= q.x <= x1 + r and y0 - r <= q.y <= y1 + r.
+ * Every one of the flags is written.  One wave per tile tests the (8 + 2r)^2 window and one ballot decides: no atomics, the
+ * same result on every run.  RTK_ERR_INVALID, checked first and without a device, nothing written, the text naming the
+ * argument: a width or height outside 1..65536, both maps null, null d_tile_flags or opts, dilate outside 0..8, a non-finite
+ * `below` (`above`) when its map is given, reserved != 0, a map or d_tile_flags that is not 4-byte aligned; then a null
+ * context.  The stream rules are rtk_upsample's: the one launch goes to `stream`, opts are read before the call returns, it
+ * allocates nothing, needs a context for its device but no scene, and never waits for the device.  rtk_tiles_select_host takes
+ * host maps, returns host flags and blocks.  sizeof(rtk_tile_select_opts) = 16.
+ *
+ * rtk_render_tiles renders the flagged tiles of `cam`'s frame.  For every in-image pixel of every tile whose flag is non-zero:
+ *   d_linear  (H*W*3 reals of opts->real_mode) and d_rgb8 (H*W*3 bytes) get the values rtk_render_device writes for the same
+ *             scene, camera, seed, real mode and variant, bit for bit and byte for byte, in both real modes and both visiting
+ *             orders;
+ *   d_noise   (H*W floats) gets the standard error a progressive session of the same camera, seed and mode writes after one
+ *             step of all samples_per_pixel samples: batch means over the full chunks of the frame's chunk size (the session's
+ *             chunk size when samples_per_pixel <= 512, where the two agree), 0 with fewer than two full chunks;
+ *   d_support (H*W floats) gets 1.0f -- the pixel is rendered, not interpolated (rtk_upsample's support map).
+ * Pixels of unflagged tiles are not written in any buffer.  Any of the four may be NULL, not all.  max_tiles = 0 is no limit;
+ * otherwise, when more tiles are flagged than max_tiles, nothing is rendered and nothing is written -- decided on the device,
+ * without a host round trip.  d_info (2 int32, may be NULL) = {tiles flagged, tiles rendered}.  The flags are compacted on the
+ * device, in ascending tile index, into a list the context owns; the render kernel hands out that list up to its device-side
+ * length, and a resolve over the list's positions performs rtk_render_device's additions in its order.  The context's learned
+ * tile order is neither used nor changed: a tile render does not change the next full frame's hand-out.
+ * RTK_ERR_INVALID, checked without a device and with nothing written or launched: rtk_render_device's own checks of camera and
+ * opts (count_work is ignored), null d_tile_flags, max_tiles < 0, all four outputs null, a buffer without the alignment of its
+ * element type (the text names it), n_ranks != 1 (or the tile-buffer layout, variant bit 22), and a camera and opts for which
+ * rtk_frame_launches() > 1 (more chunks than the workspace holds planes for: 1920x1080 f64 above 168 samples per pixel);
+ * then a null context; then RTK_ERR_NO_SCENE.  Allocation and stream behaviour are rtk_render_device's: it may grow context
+ * workspace (the partial sums, the list), and every launch goes to opts->stream.
+ * rtk_render_tiles_host takes host flags (required) and blocks; h_linear (doubles; F32 rounded / widened), h_rgb8, h_noise and
+ * h_support are in-out -- their contents on entry are what unflagged pixels keep -- and any may be NULL, not all; h_info [2]. */
+typedef struct rtk_tile_select_opts {
+    float below;       /* with d_below_map: pixel q is raw-flagged when !(map[q] >= below) */
+    float above;       /* with d_above_map: pixel q is raw-flagged when !(map[q] <= above) */
+    int32_t dilate;    /* 0..8 pixels, Chebyshev */
+    int32_t reserved;  /* 0 */
+} rtk_tile_select_opts;
+
+int rtk_tiles_select(rtk_ctx* ctx, int32_t width, int32_t height, const float* d_below_map, const float* d_above_map, const rtk_tile_select_opts* opts,
+                     int32_t* d_tile_flags, void* stream);
+int rtk_tiles_select_host(rtk_ctx* ctx, int32_t width, int32_t height, const float* h_below_map, const float* h_above_map, const rtk_tile_select_opts* opts,
+                          int32_t* h_tile_flags);
+int rtk_render_tiles(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const int32_t* d_tile_flags, int32_t max_tiles, void* d_linear,
+                     uint8_t* d_rgb8, float* d_noise, float* d_support, int32_t* d_info);
+int rtk_render_tiles_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const int32_t* h_tile_flags, int32_t max_tiles, double* h_linear,
+                          uint8_t* h_rgb8, float* h_noise, float* h_support, int32_t* h_info);
 
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and

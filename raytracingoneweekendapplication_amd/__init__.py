@@ -240,6 +240,27 @@ DISPLAY_GAMMA2, DISPLAY_SRGB = 0, 1
 DISPLAY_BINS = 320
 
 
+class TileSelectOpts(C.Structure):
+    """rtk_tile_select_opts (include/rtk.h, "Tile lists"): a pixel is raw-flagged when !(below_map >= below) or !(above_map <= above);
+    a tile is flagged when a raw-flagged pixel lies within ``dilate`` (0..8, Chebyshev) of one of its pixels."""
+    _fields_ = [("below", C.c_float), ("above", C.c_float), ("dilate", C.c_int32), ("reserved", C.c_int32)]
+
+
+def tile_flags_from_mask(mask):
+    """Tile flags (int32, one per 8x8 tile, row-major over the tiles) of an (H, W) bool array: a tile is flagged when the mask is
+    set at one of its pixels -- a region of interest for ``Renderer.render_tiles``."""
+    import numpy as np
+
+    m = np.asarray(mask, dtype=bool)
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError(f"tile_flags_from_mask: an (H, W) array is needed, not shape {m.shape}")
+    h, w = m.shape
+    ty, tx = -(-h // 8), -(-w // 8)
+    padded = np.zeros((ty * 8, tx * 8), bool)
+    padded[:h, :w] = m
+    return padded.reshape(ty, 8, tx, 8).any(axis=(1, 3)).reshape(-1).astype(np.int32)
+
+
 class DisplayOpts(C.Structure):
     """rtk_display_opts (include/rtk.h): a field left 0 takes its default (exposure metered, key 0.18, meter_low 0.10, meter_high
     0.90, min_exposure 2^-10, max_exposure 2^10, adapt 1, curve CLAMP, white 4, encode GAMMA2, bloom off, bloom_threshold 1,
@@ -555,6 +576,10 @@ def hip_lib() -> C.CDLL:
             lib.rtk_lens_render.argtypes = lib.rtk_lens_render_host.argtypes = lens + [C.c_int32, C.c_void_p, C.c_void_p]
             lib.rtk_lens_aovs.argtypes = lib.rtk_lens_aovs_host.argtypes = lens + [C.c_int32, C.c_void_p]
             lib.rtk_lens_guides.argtypes = lib.rtk_lens_guides_host.argtypes = lens + [C.c_int32, C.POINTER(GuideOpts), C.c_void_p]
+            lib.rtk_tiles_select_host.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(TileSelectOpts), C.c_void_p]
+            lib.rtk_tiles_select.argtypes = lib.rtk_tiles_select_host.argtypes + [C.c_void_p]
+            lib.rtk_render_tiles.argtypes = lib.rtk_render_tiles_host.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_void_p, C.c_int32,
+                                                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         except AttributeError:
             if HIP_LIB_PATH == DEFAULT_HIP_LIB_PATH:   # (an A/B library of an older round lacks the progressive entry points)
                 raise
@@ -1116,6 +1141,75 @@ class Renderer:
         self._check(self._lib.rtk_upsample(self._ctx, C.byref(full_cam), real_mode, d_low_linear or None, d_low_noise or None, d_low_guides or None,
                                            d_guides or None, C.byref(o), d_out_linear or None, d_out_noise or None, d_out_rgb8 or None, d_out_support or None,
                                            stream or None))
+
+    def tiles_select(self, below_map=None, above_map=None, *, below: float = 0.0, above: float = 0.0, dilate: int = 0):
+        """rtk_tiles_select_host: tile flags (int32, one per 8x8 tile, row-major) from (H, W) float32 maps: a pixel is raw-flagged
+        when ``below_map`` is given and not >= ``below``, or ``above_map`` is given and not <= ``above`` (a NaN flags); a tile is
+        flagged when a raw-flagged pixel lies within ``dilate`` pixels of it."""
+        import numpy as np
+
+        given = [m for m in (below_map, above_map) if m is not None]
+        if not given:
+            raise ValueError("tiles_select: below_map or above_map is needed")
+        h, w = np.shape(given[0])
+        maps = _host_inputs("tiles_select", f"({h}, {w}) maps", *[(m, np.float32, (h, w)) for m in given])
+        b = maps[0] if below_map is not None else None
+        a = maps[-1] if above_map is not None else None
+        flags = np.zeros(tiles_per_rank(w, h, 1), np.int32)
+        o = TileSelectOpts(float(below), float(above), int(dilate), 0)
+        self._check(self._lib.rtk_tiles_select_host(self._ctx, w, h, None if b is None else b.ctypes.data, None if a is None else a.ctypes.data, C.byref(o),
+                                                    flags.ctypes.data))
+        return flags
+
+    def tiles_select_device(self, width: int, height: int, d_below_map: int, d_above_map: int, d_tile_flags: int, *, below: float = 0.0, above: float = 0.0,
+                            dilate: int = 0, stream: int = 0) -> None:
+        """rtk_tiles_select with raw device pointers (either map may be 0, not both); asynchronous on ``stream``."""
+        o = TileSelectOpts(float(below), float(above), int(dilate), 0)
+        self._check(self._lib.rtk_tiles_select(self._ctx, int(width), int(height), d_below_map or None, d_above_map or None, C.byref(o), d_tile_flags or None,
+                                               stream or None))
+
+    def render_tiles(self, cam: Camera, tile_flags, *, linear=None, rgb8=None, noise=None, support=None, max_tiles: int = 0, seed: int = RENDER_SEED,
+                     real_mode: int = RTK_REAL_F64, variant: int = 0):
+        """rtk_render_tiles_host: render the tiles of ``cam``'s frame whose flag is non-zero with the render kernel.  ``linear``
+        (H, W, 3) float64, ``rgb8`` (H, W, 3) uint8, ``noise`` and ``support`` (H, W) float32 are the initial contents (zeros when
+        not given): pixels of unflagged tiles keep them, pixels of flagged tiles get ``render_host``'s values, a one-step
+        session's standard error and support 1.  More than ``max_tiles`` (> 0) flagged tiles: nothing is rendered.  Returns
+        (linear, rgb8, noise, support, {"flagged", "rendered"}); the arrays are new ones."""
+        import numpy as np
+
+        h, w = cam.image_height, cam.image_width
+        init = [(linear, np.float64, (h, w, 3)), (rgb8, np.uint8, (h, w, 3)), (noise, np.float32, (h, w)), (support, np.float32, (h, w))]
+        outs = [np.zeros(shape, dtype) if a is None else np.array(_host_inputs("render_tiles", f"a ({h}, {w}) image", (a, dtype, shape))[0])
+                for a, dtype, shape in init]
+        (flags,) = _host_inputs("render_tiles", f"the {tiles_per_rank(w, h, 1)} tile flags of a ({h}, {w}) image", (tile_flags, np.int32, (tiles_per_rank(w, h, 1),)))
+        info = np.zeros(2, np.int32)
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, variant, None)
+        self._check(self._lib.rtk_render_tiles_host(self._ctx, C.byref(cam), C.byref(opts), flags.ctypes.data, int(max_tiles), *[o.ctypes.data for o in outs],
+                                                    info.ctypes.data))
+        return (*outs, {"flagged": int(info[0]), "rendered": int(info[1])})
+
+    def render_tiles_device(self, cam: Camera, d_tile_flags: int, d_linear: int = 0, d_rgb8: int = 0, d_noise: int = 0, d_support: int = 0, d_info: int = 0, *,
+                            max_tiles: int = 0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, variant: int = 0, stream: int = 0) -> None:
+        """rtk_render_tiles with raw device pointers (any output may be 0, not all); every launch goes to ``stream``."""
+        opts = RenderOpts(seed, real_mode, 0, 1, 0, variant, stream or None)
+        self._check(self._lib.rtk_render_tiles(self._ctx, C.byref(cam), C.byref(opts), d_tile_flags or None, int(max_tiles), d_linear or None, d_rgb8 or None,
+                                               d_noise or None, d_support or None, d_info or None))
+
+    def upsample_refined(self, full_cam: Camera, low_linear, low_noise, low_guides, guides, *, refine_below: float, refine_dilate: int = 1, max_share: float = 0.0,
+                         factor: int = 2, demodulate: bool = False, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, sigma_n: float = 0.0,
+                         sigma_z: float = 0.0, sigma_a: float = 0.0):
+        """``upsample``, then ``tiles_select`` on its support map (support not >= ``refine_below``, grown by ``refine_dilate``
+        pixels), then ``render_tiles`` of ``full_cam`` into the upsample's four outputs: the tiles the interpolation had nothing
+        to go on are the full-resolution frame's.  ``max_share`` > 0: with more than that share of the tiles flagged nothing is
+        re-rendered.  Returns (linear, se, rgb8, support, info), info = {"flagged", "rendered", "tiles"}."""
+        out, out_noise, rgb8, support = self.upsample(full_cam, low_linear, low_noise, low_guides, guides, factor=factor, demodulate=demodulate,
+                                                      real_mode=real_mode, sigma_n=sigma_n, sigma_z=sigma_z, sigma_a=sigma_a)
+        flags = self.tiles_select(support, below=refine_below, dilate=refine_dilate)
+        max_tiles = max(1, int(max_share * flags.size)) if max_share > 0.0 else 0
+        out, rgb8, out_noise, support, info = self.render_tiles(full_cam, flags, linear=out, rgb8=rgb8, noise=out_noise, support=support, max_tiles=max_tiles,
+                                                                seed=seed, real_mode=real_mode)
+        info["tiles"] = int(flags.size)
+        return out, out_noise, rgb8, support, info
 
     def temporal(self, width: int, height: int, real_mode: int = RTK_REAL_F64, stream: int = 0) -> "Temporal":
         """rtk_temporal_create: an object that carries the frames of a moving camera along (``Temporal.accumulate``), bound to

@@ -978,6 +978,9 @@ struct rtk_ctx {
     // The denoiser's ping-pong colour / variance buffers (rtk_denoise), grown on demand.
     void* d_denoise = nullptr;
     size_t denoise_bytes = 0;
+    // rtk_render_tiles: the compacted list of the flagged tiles [list_capacity] and, behind it, the word with its length.
+    int32_t* d_tile_list = nullptr;
+    int list_capacity = 0;
 };
 // Sample chunks per launch: the partial-sum workspace holds up to this many planes [local tile][3][64] at 1920x1080 f64 (+ one
 // for the running sum of a frame that needs several launches): 21 + 1 planes = 1.09 GB, where the 63 chunks of a 1000-spp
@@ -1142,6 +1145,7 @@ int rtk_destroy(rtk_ctx* ctx) {
     if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
     if (ctx->d_tile_cost) (void)hipFree(ctx->d_tile_cost);
     if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
+    if (ctx->d_tile_list) (void)hipFree(ctx->d_tile_list);
     if (ctx->progress_stream) (void)hipStreamDestroy(ctx->progress_stream);
     if (ctx->progress_word) (void)hipHostFree(ctx->progress_word);
     delete ctx;
@@ -1311,18 +1315,21 @@ int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks) {
     return (tiles + n_ranks - 1) / n_ranks;
 }
 
-int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters) {
-    if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_device: null argument");
-    if (!ctx->has_scene) return fail(RTK_ERR_NO_SCENE, "rtk_render_device: no scene uploaded");
-    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
-        return fail(RTK_ERR_INVALID, "rtk_render_device: bad camera dimensions (samples_per_pixel must be 1..32767)");
-    if (opts->n_ranks < 1 || opts->rank < 0 || opts->rank >= opts->n_ranks) return fail(RTK_ERR_INVALID, "rtk_render_device: bad rank %d of %d", opts->rank, opts->n_ranks);
-    const bool compact_out = opts->n_ranks > 1 || (opts->variant & (1 << 22)) != 0;  // variant bit 22: the tile-buffer layout for a single rank too
-    if (compact_out && d_rgb8) return fail(RTK_ERR_INVALID, "rtk_render_device: d_rgb8 must be null when n_ranks > 1 (use rtk_tiles_unpermute)");
-    if (opts->count_work && !d_counters) return fail(RTK_ERR_INVALID, "rtk_render_device: count_work needs d_counters");
-    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_render_device: unknown real_mode %d", opts->real_mode);
-    RTK_HIP(hipSetDevice(ctx->device));
-    TileMap tm;
+// What rtk_render_device and rtk_render_tiles share of a frame's set-up.  plan_frame is host arithmetic on camera and options;
+// stage_frame makes the context ready for the launches: the partial-sum workspace grown to the frame's need, the camera record
+// in its device slot (copied on the frame's stream unless it is the cached one).
+struct FramePlan {
+    TileMap tm;  // every chunk of the frame
+    int chunk_size = 0, planes_per_pass = 0, n_passes = 0;
+    size_t plane = 0;  // bytes of one chunk plane [local tile][3][64]
+    unsigned char* d_cam = nullptr;
+    bool allow_lds = true;
+    uint32_t diag = 0;
+    hipStream_t stream = nullptr;
+};
+
+static void plan_frame(const rtk_camera* cam, const rtk_render_opts* opts, bool compact_out, FramePlan& f) {
+    TileMap& tm = f.tm;
     tm.tiles_x = (cam->image_width + RTK_TILE_W - 1) / RTK_TILE_W;
     tm.tiles_y = (cam->image_height + RTK_TILE_H - 1) / RTK_TILE_H;
     tm.rank = opts->rank;
@@ -1346,15 +1353,21 @@ int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts
         tm.chunk_start[++n] = int16_t(spp);
         tm.n_chunks = n;
         for (int k = n + 1; k <= kMaxChunks; k++) tm.chunk_start[k] = int16_t(spp);
+        f.chunk_size = size;
     }
     const size_t elem = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
     // Up to kMaxPlanesPerPass chunks per launch; a frame with more is rendered in consecutive passes, the resolve kernel
     // carrying the running sum in one extra plane -- the same additions in the same order as one pass over all chunks.
-    const int n_chunks_total = tm.n_chunks;
-    const size_t plane = size_t(tm.n_tiles_local) * 192 * elem;
-    const int planes_per_pass = planes_per_pass_for(plane, opts->variant);
-    const int n_passes = (n_chunks_total + planes_per_pass - 1) / planes_per_pass;
-    const size_t need = plane * size_t(n_passes > 1 ? planes_per_pass + 1 : n_chunks_total);
+    f.plane = size_t(tm.n_tiles_local) * 192 * elem;
+    f.planes_per_pass = planes_per_pass_for(f.plane, opts->variant);
+    f.n_passes = (tm.n_chunks + f.planes_per_pass - 1) / f.planes_per_pass;
+    f.allow_lds = (opts->variant & 1) == 0;            // variant bit 0: keep the program in global memory (A/B)
+    f.diag = uint32_t(opts->variant) & 0xBFFF00u;      // bits 8..21, 23: scheduler policy / program layout A/B used by tools/ and tests only
+    f.stream = static_cast<hipStream_t>(opts->stream);
+}
+
+static int stage_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, FramePlan& f) {
+    const size_t need = f.plane * size_t(f.n_passes > 1 ? f.planes_per_pass + 1 : f.tm.n_chunks);
     if (need > ctx->partial_bytes) {
         if (ctx->d_partial) {
             RTK_HIP(hipDeviceSynchronize());  // earlier launches may still read the old workspace
@@ -1365,7 +1378,51 @@ int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts
         RTK_HIP(hipMalloc(&ctx->d_partial, need));
         ctx->partial_bytes = need;
     }
-    hipStream_t stream = static_cast<hipStream_t>(opts->stream);
+    const int cam_mode = opts->real_mode == RTK_REAL_F64 ? 0 : 1;
+    const bool cam_cached = ctx->cam_valid[cam_mode] && std::memcmp(&ctx->cam_last[cam_mode], cam, sizeof(rtk_camera)) == 0;
+    const unsigned int cslot = cam_cached ? ctx->cam_slot[cam_mode] : (ctx->next_camera++ % kCounterRing);
+    if (!cam_cached) {
+        // a slot about to be overwritten may still be the other mode's cached camera
+        for (int m = 0; m < 2; m++)
+            if (ctx->cam_valid[m] && ctx->cam_slot[m] == cslot) ctx->cam_valid[m] = false;
+        ctx->cam_last[cam_mode] = *cam;
+        ctx->cam_slot[cam_mode] = cslot;
+        ctx->cam_valid[cam_mode] = true;
+    }
+    f.d_cam = ctx->d_cameras + cslot * kCameraStride;
+    if (!cam_cached) {
+        if (opts->real_mode == RTK_REAL_F64) {
+            ctx->h_cameras64[cslot] = to_device_camera<double>(*cam);
+            RTK_HIP(hipMemcpyAsync(f.d_cam, &ctx->h_cameras64[cslot], sizeof(CameraRec<double>), hipMemcpyHostToDevice, f.stream));
+        } else {
+            ctx->h_cameras32[cslot] = to_device_camera<float>(*cam);
+            RTK_HIP(hipMemcpyAsync(f.d_cam, &ctx->h_cameras32[cslot], sizeof(CameraRec<float>), hipMemcpyHostToDevice, f.stream));
+        }
+    }
+    return RTK_OK;
+}
+
+int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters) {
+    if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_device: null argument");
+    if (!ctx->has_scene) return fail(RTK_ERR_NO_SCENE, "rtk_render_device: no scene uploaded");
+    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
+        return fail(RTK_ERR_INVALID, "rtk_render_device: bad camera dimensions (samples_per_pixel must be 1..32767)");
+    if (opts->n_ranks < 1 || opts->rank < 0 || opts->rank >= opts->n_ranks) return fail(RTK_ERR_INVALID, "rtk_render_device: bad rank %d of %d", opts->rank, opts->n_ranks);
+    const bool compact_out = opts->n_ranks > 1 || (opts->variant & (1 << 22)) != 0;  // variant bit 22: the tile-buffer layout for a single rank too
+    if (compact_out && d_rgb8) return fail(RTK_ERR_INVALID, "rtk_render_device: d_rgb8 must be null when n_ranks > 1 (use rtk_tiles_unpermute)");
+    if (opts->count_work && !d_counters) return fail(RTK_ERR_INVALID, "rtk_render_device: count_work needs d_counters");
+    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_render_device: unknown real_mode %d", opts->real_mode);
+    RTK_HIP(hipSetDevice(ctx->device));
+    FramePlan f;
+    plan_frame(cam, opts, compact_out, f);
+    if (const int rc = stage_frame(ctx, cam, opts, f); rc != RTK_OK) return rc;
+    const TileMap& tm = f.tm;
+    const int n_chunks_total = tm.n_chunks, planes_per_pass = f.planes_per_pass, n_passes = f.n_passes;
+    const size_t plane = f.plane;
+    unsigned char* const d_cam = f.d_cam;
+    const bool allow_lds = f.allow_lds;
+    const uint32_t diag = f.diag;
+    hipStream_t stream = f.stream;
     auto* counters = reinterpret_cast<unsigned long long*>(d_counters);
     // tile order / cost buffers for this shape
     const int shape[5] = {cam->image_width, cam->image_height, opts->rank, opts->n_ranks, tm.n_tiles_local};
@@ -1389,30 +1446,7 @@ int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts
     unsigned int* tile_cost = learn ? ctx->d_tile_cost : nullptr;
     ctx->last_n_passes = n_passes;
     ctx->last_n_items = int64_t(tm.n_tiles_local) * n_chunks_total;
-    const int cam_mode = opts->real_mode == RTK_REAL_F64 ? 0 : 1;
-    const bool cam_cached = ctx->cam_valid[cam_mode] && std::memcmp(&ctx->cam_last[cam_mode], cam, sizeof(rtk_camera)) == 0;
-    const unsigned int cslot = cam_cached ? ctx->cam_slot[cam_mode] : (ctx->next_camera++ % kCounterRing);
-    if (!cam_cached) {
-        // a slot about to be overwritten may still be the other mode's cached camera
-        for (int m = 0; m < 2; m++)
-            if (ctx->cam_valid[m] && ctx->cam_slot[m] == cslot) ctx->cam_valid[m] = false;
-        ctx->cam_last[cam_mode] = *cam;
-        ctx->cam_slot[cam_mode] = cslot;
-        ctx->cam_valid[cam_mode] = true;
-    }
-    unsigned char* d_cam = ctx->d_cameras + cslot * kCameraStride;
-    const bool allow_lds = (opts->variant & 1) == 0;  // variant bit 0: keep the program in global memory (A/B)
-    const uint32_t diag = uint32_t(opts->variant) & 0xBFFF00u;  // bits 8..21, 23: scheduler policy / program layout A/B used by tools/ and tests only
     hipError_t e = hipSuccess;
-    if (!cam_cached) {
-        if (opts->real_mode == RTK_REAL_F64) {
-            ctx->h_cameras64[cslot] = to_device_camera<double>(*cam);
-            RTK_HIP(hipMemcpyAsync(d_cam, &ctx->h_cameras64[cslot], sizeof(CameraRec<double>), hipMemcpyHostToDevice, stream));
-        } else {
-            ctx->h_cameras32[cslot] = to_device_camera<float>(*cam);
-            RTK_HIP(hipMemcpyAsync(d_cam, &ctx->h_cameras32[cslot], sizeof(CameraRec<float>), hipMemcpyHostToDevice, stream));
-        }
-    }
     void* const acc = n_passes > 1 ? static_cast<char*>(ctx->d_partial) + plane * size_t(planes_per_pass) : nullptr;
     unsigned int* pass_counter[kMaxPasses];
     for (int pass = 0; pass < n_passes; pass++) {  // every pass's work-item counter reads 0 from now on (progress reports add them up)
@@ -1622,7 +1656,8 @@ hipError_t denoise_workspace(rtk_ctx* ctx, size_t bytes, void** out) {
 }
 
 hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
-                         const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial) {
+                         const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial, bool allow_lds,
+                         uint32_t diag) {
     hipError_t e = hipSuccess;
     if (workspace_bytes > ctx->partial_bytes) {
         if (ctx->d_partial) {
@@ -1638,10 +1673,45 @@ hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const T
     unsigned int* tile_counter = ctx->tile_counters + (ctx->next_counter++ % kCounterRing);
     const bool count = counters != nullptr;
     if (real_mode == RTK_REAL_F64)
-        return launch_render<double>(ctx->scene64.view, static_cast<const CameraRec<double>*>(d_cam), tp, seed, ctx->features, count, true, 0u, ctx->d_partial,
-                                     counters, tile_counter, tile_order, tile_cost, stream);
-    return launch_render<float>(ctx->scene32.view, static_cast<const CameraRec<float>*>(d_cam), tp, seed, ctx->features, count, true, 0u, ctx->d_partial,
+        return launch_render<double>(ctx->scene64.view, static_cast<const CameraRec<double>*>(d_cam), tp, seed, ctx->features, count, allow_lds, diag,
+                                     ctx->d_partial, counters, tile_counter, tile_order, tile_cost, stream);
+    return launch_render<float>(ctx->scene32.view, static_cast<const CameraRec<float>*>(d_cam), tp, seed, ctx->features, count, allow_lds, diag, ctx->d_partial,
                                 counters, tile_counter, tile_order, tile_cost, stream);
+}
+
+int stage_tile_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, TileFrame& out) {
+    FramePlan f;
+    plan_frame(cam, opts, false, f);
+    if (f.n_passes > 1)
+        return fail(RTK_ERR_INVALID, "%s: a frame of %d launches (rtk_frame_launches: more sample chunks than the workspace holds planes for) is not supported", who,
+                    f.n_passes);
+    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
+    if (!ctx->has_scene) return fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
+    RTK_HIP(hipSetDevice(ctx->device));
+    if (const int rc = stage_frame(ctx, cam, opts, f); rc != RTK_OK) return rc;
+    const int n = f.tm.n_tiles_local;
+    if (n > ctx->list_capacity) {
+        if (ctx->d_tile_list) {
+            RTK_HIP(hipDeviceSynchronize());  // earlier launches may still read the old list
+            RTK_HIP(hipFree(ctx->d_tile_list));
+            ctx->d_tile_list = nullptr;
+            ctx->list_capacity = 0;
+        }
+        RTK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_tile_list), (size_t(n) + 1) * sizeof(int32_t)));
+        ctx->list_capacity = n;
+        // positions beyond the list's length are read (the render kernel stages the whole array) and never used: defined bytes
+        RTK_HIP(hipMemset(ctx->d_tile_list, 0, (size_t(n) + 1) * sizeof(int32_t)));
+    }
+    out.tm = f.tm;
+    out.chunk_size = f.chunk_size;
+    out.workspace_bytes = f.plane * size_t(f.tm.n_chunks);
+    out.d_cam = f.d_cam;
+    out.allow_lds = f.allow_lds;
+    out.diag = f.diag;
+    out.stream = f.stream;
+    out.d_list = ctx->d_tile_list;
+    out.d_count = ctx->d_tile_list + ctx->list_capacity;
+    return RTK_OK;
 }
 
 }  // namespace rtk

@@ -512,6 +512,73 @@ hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ tile lists --
+// (include/rtk.h, "Tile lists"): rtk_render_tiles renders the tiles of a compacted list -- rtk_adaptive_compact_kernel's output
+// over the caller's flags, in ascending tile index -- and the kernels below decide its length and turn its tiles into pixels.
+
+// After the compaction: count[0] tiles are flagged.  More than max_tiles (> 0) of them: the list's length becomes 0, so the
+// render hands out nothing and the resolve writes nothing.  info = {flagged, rendered}.  One lane.
+__global__ __launch_bounds__(64) void rtk_tile_gate_kernel(int32_t* __restrict__ count, int max_tiles, int32_t* __restrict__ info) {
+    if (threadIdx.x != 0) return;
+    const int flagged = *count;
+    const int rendered = (max_tiles > 0 && flagged > max_tiles) ? 0 : flagged;
+    *count = rendered;
+    if (info) {
+        info[0] = flagged;
+        info[1] = rendered;
+    }
+}
+
+hipError_t launch_tile_gate(int32_t* count, int max_tiles, int32_t* info, hipStream_t stream) {
+    rtk_tile_gate_kernel<<<dim3(1), dim3(64), 0, stream>>>(count, max_tiles, info);
+    return hipGetLastError();
+}
+
+// pixel_slot over list positions: wave w takes tile list[w] (one rank: the local tile is the tile); false at positions >= count.
+RTK_DEV bool list_slot(const TileMap& tmap, const int32_t* __restrict__ list, const int32_t* __restrict__ count, int width, int height, PixelSlot& p) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long pos = gid >> 6;
+    if (pos >= tmap.n_tiles_local || pos >= *count) return false;
+    const int tile = list[pos];
+    p.pix = int(gid & 63);
+    p.local_tile = tile;
+    p.i = (tile % tmap.tiles_x) * 8 + (p.pix & 7);
+    p.j = (tile / tmap.tiles_x) * 8 + (p.pix >> 3);
+    p.in_grid = tile >= 0 && tile < tmap.n_tiles_local;
+    p.inside = p.in_grid && p.i < width && p.j < height;
+    return true;
+}
+
+// The resolve of a one-launch frame for the listed tiles only: the resolve's fold and output (fold_planes, write_pixel), the
+// session's noise (batch means over the full chunks, noise_se) and support 1 -- rendered, not interpolated.  Row-major outputs.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_resolve_tiles_kernel(const real* __restrict__ partial, TileMap tmap, int width, int height, int chunk_size, int k_full,
+                                                                 real samples_scale, const int32_t* __restrict__ list, const int32_t* __restrict__ count,
+                                                                 real* __restrict__ out_linear, uint8_t* __restrict__ out_rgb8, float* __restrict__ out_noise,
+                                                                 float* __restrict__ out_support) {
+    PixelSlot p;
+    if (!list_slot(tmap, list, count, width, height, p) || !p.inside) return;
+    double n1 = 0.0, n2 = 0.0;
+    const V3<real> sum = scale(samples_scale, fold_planes<true>(partial, tmap, p, true, static_cast<const real*>(nullptr), chunk_size, &n1, &n2));
+    write_pixel<real>(p, false, width, sum, noise_se(n1, n2, k_full), out_linear, out_rgb8, out_noise);
+    if (out_support) out_support[size_t(p.j) * width + p.i] = 1.0f;
+}
+
+template <typename real>
+hipError_t launch_resolve_tiles(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, double samples_scale, const int32_t* list,
+                                const int32_t* count, void* out_linear, uint8_t* out_rgb8, float* out_noise, float* out_support, hipStream_t stream) {
+    if (tmap.n_tiles_local <= 0) return hipSuccess;
+    const int k_full = int(tmap.chunk_start[tmap.n_chunks]) / chunk_size;
+    rtk_resolve_tiles_kernel<real><<<dim3(pixel_slot_blocks(tmap)), dim3(256), 0, stream>>>(static_cast<const real*>(partial), tmap, width, height, chunk_size, k_full,
+                                                                                           real(samples_scale), list, count, static_cast<real*>(out_linear), out_rgb8,
+                                                                                           out_noise, out_support);
+    return hipGetLastError();
+}
+template hipError_t launch_resolve_tiles<double>(const void*, const TileMap&, int, int, int, double, const int32_t*, const int32_t*, void*, uint8_t*, float*, float*,
+                                                 hipStream_t);
+template hipError_t launch_resolve_tiles<float>(const void*, const TileMap&, int, int, int, double, const int32_t*, const int32_t*, void*, uint8_t*, float*, float*,
+                                                hipStream_t);
+
 // ------------------------------------------------------------------ session set-up --
 // A session is set up on ITS stream by kernels and asynchronous memsets: a blocking call on the NULL stream can be queued
 // behind another stream's backlog (streams share the hardware queues), and rtk_progressive_create would then wait for the

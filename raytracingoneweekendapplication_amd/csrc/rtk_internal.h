@@ -122,8 +122,27 @@ int frame_chunk_size(int spp);                        // the one-shot frame's ch
 int chunks_per_launch(size_t plane_bytes);            // ... and chunk planes per launch
 size_t camera_record_bytes();
 // One render launch over tp's chunks into the context's partial-sum workspace (grown to workspace_bytes; *partial = it).
+// allow_lds / diag: what rtk_render_device derives from opts->variant (sessions render with variant 0).
 hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
-                         const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial);
+                         const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial, bool allow_lds = true,
+                         uint32_t diag = 0u);
+
+// rtk_render_tiles (rtk_tiles.hip): rtk_render_device's own frame set-up for `cam` and `opts` -- tile map and chunk boundaries, the
+// partial-sum workspace grown, the camera record in its device slot on the frame's stream -- plus the context's tile list
+// (d_list[n_tiles_local], its length at d_count).  The learned tile order is not touched.  Refuses, in this order: a frame of more
+// than one launch (RTK_ERR_INVALID; host arithmetic only), a null context, RTK_ERR_NO_SCENE; `who` names the caller in the text.
+struct TileFrame {
+    TileMap tm;
+    int chunk_size = 0;
+    size_t workspace_bytes = 0;
+    const void* d_cam = nullptr;
+    bool allow_lds = true;
+    uint32_t diag = 0;
+    hipStream_t stream = nullptr;
+    int32_t* d_list = nullptr;
+    int32_t* d_count = nullptr;
+};
+int stage_tile_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, TileFrame& out);
 
 // The uploaded scene's device view per arithmetic type, and a camera's device record (for the AOV pass, rtk_denoise.hip).
 template <typename real>

@@ -58,6 +58,14 @@ hipError_t launch_adaptive_restore(const double* s1, const double* s2, const Til
                                    int done, bool retire_ok, double rel_target, int32_t* active, hipStream_t stream);
 // list = the positions of `order` (identity when null; n entries) whose tile is active, in order; *count = their number.
 hipError_t launch_adaptive_compact(const int32_t* active, const int32_t* order, int n, int32_t* list, int32_t* count, hipStream_t stream);
+// Tile lists (rtk_render_tiles).  launch_tile_gate: *count tiles are listed; more than max_tiles (> 0) of them makes *count 0;
+// info (may be null) = {listed, *count afterwards}.  launch_resolve_tiles: launch_resolve of a one-launch frame for the tiles
+// list[0 .. *count - 1] only (one rank, row-major outputs), plus the session's standard error over the full chunks of chunk_size
+// samples (out_noise) and 1.0f (out_support); pixels of other tiles are not written.
+hipError_t launch_tile_gate(int32_t* count, int max_tiles, int32_t* info, hipStream_t stream);
+template <typename real>
+hipError_t launch_resolve_tiles(const void* partial, const TileMap& tmap, int width, int height, int chunk_size, double samples_scale, const int32_t* list,
+                                const int32_t* count, void* out_linear, uint8_t* out_rgb8, float* out_noise, float* out_support, hipStream_t stream);
 // Session set-up on the session's stream: a record of up to 256 bytes (a multiple of 4) stored from a kernel argument; the
 // state of a fresh adaptive session (in-image tiles active, no samples).
 hipError_t launch_store_record(const void* h_record, size_t bytes, void* d_dst, hipStream_t stream);

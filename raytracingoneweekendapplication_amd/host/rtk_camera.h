@@ -13,6 +13,7 @@
 #ifndef RTK_CAMERA_H
 #define RTK_CAMERA_H
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -192,6 +193,16 @@ public:
     int render_scale = 1;
     bool upsample_demodulate = false;
     bool last_render_upsampled = false;  // set by render(): the image was rebuilt from a low-resolution frame
+    // Refinement of the upsampled frame (rtk_tiles_select + rtk_render_tiles).  refine_support > 0: after step 3 the 8x8 tiles with
+    // a pixel whose support is not >= refine_support -- the interpolation had nothing to go on there: silhouettes, the borders of
+    // lights -- grown by refine_dilate pixels (0..8), are rendered at full resolution with samples_per_pixel samples and replace
+    // the upsampled colour, se and bytes.  With more than refine_max_share of the tiles chosen (0 = no limit) nothing is
+    // re-rendered and render() says so in one line: the full-resolution frame is the cheaper way there.  0 (default): nothing
+    // changes, bit for bit.
+    double refine_support = 0;
+    int refine_dilate = 1;
+    double refine_max_share = 0.5;
+    int last_refined_tiles = 0;          // set by render(): tiles re-rendered at full resolution
     // Display transform (rtk_display_*; one device, as progressive rendering).  display = true: every PNG render() writes -- the
     // plain, progressive, denoised, temporal and upsampled paths alike -- is made from the linear frame by one rtk_display object
     // instead of the reference's sqrt / clamp / quantise.  The object is kept across render() calls on this camera object (and its
@@ -554,6 +565,9 @@ public:
         const size_t px = size_t(cam.image_width) * cam.image_height, lpx = size_t(low.image_width) * low.image_height;
         std::vector<double> linear(px * 3), low_linear(lpx * 3);
         std::vector<float> noise(px), guides(px * 16), low_noise(lpx), low_guides(lpx * 16);
+        const bool refine = refine_support > 0;
+        std::vector<float> support(refine ? px : 0);
+        last_refined_tiles = 0;
         rgb8->assign(px * 3, 0);
         auto t0 = std::chrono::steady_clock::now();
         if (rc == RTK_OK) rc = rtk_progressive_step_host(p, low.samples_per_pixel, low_linear.data(), nullptr, low_noise.data(), nullptr);
@@ -565,7 +579,8 @@ public:
         uo.factor = render_scale;
         uo.flags = upsample_demodulate ? RTK_UPSAMPLE_DEMODULATE : 0;
         if (rc == RTK_OK) rc = rtk_upsample_host(ctx, &cam, real_mode, low_linear.data(), low_noise.data(), low_guides.data(), guides.data(), &uo, linear.data(),
-                                                 noise.data(), rgb8->data(), nullptr);
+                                                 noise.data(), rgb8->data(), refine ? support.data() : nullptr);
+        if (rc == RTK_OK && refine) rc = refine_tiles(ctx, cam, opts, support, linear, noise, rgb8);
         if (rc == RTK_OK && temporal) {  // the upsampled colour and se are what is accumulated
             rtk_temporal_opts to{};
             to.max_history = temporal_history;
@@ -586,6 +601,27 @@ public:
         if (own) rtk_multi_destroy(own);
         *used = rc == RTK_OK;
         return rc;
+    }
+
+    // render_scaled's refinement (see refine_support): the low-support tiles of the upsampled frame rendered at full resolution.
+    int refine_tiles(rtk_ctx* ctx, const rtk_camera& cam, const rtk_render_opts& opts, const std::vector<float>& support, std::vector<double>& linear,
+                     std::vector<float>& noise, std::vector<uint8_t>* rgb8) {
+        const int64_t n_tiles = rtk_tiles_per_rank(cam.image_width, cam.image_height, 1);
+        std::vector<int32_t> flags(size_t(n_tiles), 0);
+        rtk_tile_select_opts so{};
+        so.below = float(refine_support);
+        so.dilate = refine_dilate;
+        int rc = rtk_tiles_select_host(ctx, cam.image_width, cam.image_height, support.data(), nullptr, &so, flags.data());
+        if (rc != RTK_OK) return rc;
+        const int32_t max_tiles = refine_max_share > 0 ? std::max<int32_t>(1, int32_t(refine_max_share * double(n_tiles))) : 0;
+        int32_t info[2] = {0, 0};
+        rc = rtk_render_tiles_host(ctx, &cam, &opts, flags.data(), max_tiles, linear.data(), rgb8->data(), noise.data(), nullptr, info);
+        if (rc != RTK_OK) return rc;
+        last_refined_tiles = info[1];
+        if (info[1] < info[0])
+            std::cerr << "camera::render: refine_support chose " << info[0] << " of " << n_tiles << " tiles, more than refine_max_share allows; none re-rendered"
+                      << std::endl;
+        return RTK_OK;
     }
 
     // render()'s one-shot path: render_to, and with `display` the bytes from the linear frame through the display object.
