@@ -358,7 +358,7 @@ int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks);
  * Streams (this holds for every entry point that is "asynchronous on" a stream:
  * rtk_render_device, rtk_tiles_unpermute, rtk_progressive_step, rtk_render_aovs,
  * rtk_denoise, rtk_progressive_denoise, rtk_render_guides, rtk_denoise_guided, rtk_progressive_denoise_guided,
- * rtk_temporal_accumulate, rtk_query_hits / _occluded / _radiance, rtk_probe_*, rtk_lens_*):
+ * rtk_temporal_accumulate, rtk_query_hits / _occluded / _radiance, rtk_probe_*, rtk_lens_*, rtk_gather_*):
  *   - all work of a call -- kernels, memsets, the upload of the camera record --
  *     is enqueued on the stream it is given and on no other; the call reads its
  *     host arguments (cam, opts) before it returns and never waits for the
@@ -1170,6 +1170,71 @@ int rtk_render_tiles(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts*
                      uint8_t* d_rgb8, float* d_noise, float* d_support, int32_t* d_info);
 int rtk_render_tiles_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const int32_t* h_tile_flags, int32_t max_tiles, double* h_linear,
                           uint8_t* h_rgb8, float* h_noise, float* h_support, int32_t* h_info);
+
+/* Surface gathers ---------------------------------------------------------------------
+ * Lighting that arrives at points ON surfaces -- the texels of a lightmap, the vertices of a mesh -- and how open each point is:
+ * irradiance over the cosine-weighted hemisphere around the point's own normal, and ambient occlusion with the bent normal.
+ * The rays are made on the device where they are used; a point's rays are cut into passes of 64 that run as separate waves
+ * anywhere on the chip, and a second stage adds the passes in order.  Device resident and asynchronous, on the uploaded scene in
+ * either visiting order and both real modes; one rank only.  New entry points; RTK_ABI_VERSION stays 2.
+ *
+ * Everything below is computed in double with no fused operation, every sum and product left to right as written, and nothing
+ * is renormalised.  The normals are used as given: the caller supplies unit normals.
+ * Local directions: a cosine-weighted Fibonacci set (Malley's construction over a Fibonacci disc).  For point k and ray
+ * j = 0 .. R-1, R = opts->rays:  u_j = (2j + 1) / (2R);  r_j = sqrt(u_j);  z_j = sqrt(1 - u_j);  a_j = (j * 2654435769 + rot_k)
+ * mod 2^32;  phi_j = double(a_j) * (2 pi 2^-32);  local direction (x, y, z) = (r_j cos phi_j, r_j sin phi_j, z_j).
+ * rot_k = 0 when opts->rotate == 0, else ((first_key + k) mod 2^32) * 0x85EBCA6B mod 2^32, in integers: each point has its own
+ * rotation of the set, so neighbouring points do not alias alike.
+ * Frame: the branch-free basis of Duff et al. 2017 ("Building an Orthonormal Basis, Revisited").  With normal n:
+ *   s = copysign(1, n.z);  a = -1 / (s + n.z);  b = n.x n.y a;
+ *   t = (1 + s n.x n.x a, s b, -s n.x);  bt = (b, s + n.y n.y a, -n.y);  world direction d = x t + y bt + z n.
+ * Rays and streams: with S = samples per ray, ray j of point k is the record { origin = the point as given (no offset: tmin
+ * does that job), direction = d, time = opts->time, tmin = 0.001, tmax = max_distance or +inf, pixel = first_key + k (32-bit
+ * wrap), sample = j * S, skip = 0 } -- what rtk_gather_rays writes, [n * R] records, point-major.  L_kj is what
+ * rtk_query_radiance returns for that record with samples = S and the call's seed, max_depth and background.
+ * Irradiance: E[k][ch] = (pi / R) sum_j L_kj[ch], accumulated in double in both real modes, [n][3] reals of real_mode.
+ * Occlusion: ray j is open when the flag rtk_query_occluded returns for its record is 0 (in a scene with a constant medium the
+ * walk draws from the record's stream, as the query's does).  open[k] = (open rays) / R, [n] reals; bent[k] = (the sum of the
+ * world directions d -- the doubles of the record -- of the open rays) / R, [n][3] reals, not normalised, zero when none is
+ * open.  Either of d_open and d_bent may be NULL, not both.
+ * Order of the sums: rays 64q .. 64q + 63 of a point form pass q; a pass is reduced by a butterfly across its wave (offsets
+ * 32, 16, .. 1); the passes are added in increasing q; the result is scaled (by pi / R) or divided (by R) once and stored once.
+ * The same call gives the same bits, and a point's result does not depend on n, on its place in the call or on batch_points.
+ * Workspace: the passes' sums, 32 bytes per pass, live in a buffer the context owns, grown on demand up to
+ * RTK_GATHER_WORKSPACE_BYTES; a call that needs more, or sets batch_points, runs consecutive batches of points on the stream.
+ * Allocation and stream behaviour are rtk_render_device's: growing the buffer allocates and waits for the device, every launch
+ * goes to opts->stream, opts is read before the call returns, and one context serves one stream at a time.
+ * Buffers: d_points and d_normals [n][3] doubles in both modes, 8-byte aligned; d_rays 8-byte aligned; reals need the alignment
+ * of their type.  A misaligned pointer is refused (the text names the argument); so is an output whose range overlaps d_points
+ * or d_normals.  n == 0 is valid and launches nothing.  RTK_ERR_INVALID, checked first and without a device: null opts; n < 0;
+ * an unknown real_mode; negative max_depth or samples; reserved != 0; rays not a multiple of 64 in 64 .. 16384; n * rays over
+ * 2^31 - 1; rotate not 0 or 1; negative batch_points; max_distance negative or NaN; null points, normals or outputs; then
+ * alignment, then overlap, then a null context, then (not rtk_gather_rays, which needs a context for its device but no scene)
+ * RTK_ERR_NO_SCENE.  The _host forms take host buffers (reals as doubles, F32 widened) and block.
+ * sizeof(rtk_gather_opts) = 96. */
+#define RTK_GATHER_WORKSPACE_BYTES (64u << 20)
+typedef struct rtk_gather_opts {         /* 96 bytes */
+    uint32_t seed; int32_t real_mode;
+    int32_t max_depth;                   /* irradiance only; >= 0 */
+    int32_t samples;                     /* paths per ray; 0 = 1 (occlusion: only the stream key j * samples) */
+    int32_t rays;                        /* R per point; 0 = 256; a multiple of 64 in 64 .. 16384 */
+    uint32_t first_key;                  /* point k draws from the streams of pixel key first_key + k */
+    int32_t rotate;                      /* 0: every point uses the same set; 1: each point's own rotation of it */
+    int32_t batch_points;                /* 0 = as many points per launch as the workspace budget holds; else that many */
+    rtk_vec3 background;                 /* irradiance only */
+    double time;
+    double max_distance;                 /* the records' tmax, so occlusion's reach; 0 = +inf */
+    void* stream;
+    int32_t reserved[4];                 /* 0 */
+} rtk_gather_opts;
+
+int rtk_gather_rays(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* d_points, const double* d_normals, rtk_ray* d_rays);
+int rtk_gather_irradiance(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* d_points, const double* d_normals, void* d_irradiance);
+int rtk_gather_occlusion(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* d_points, const double* d_normals, void* d_open, void* d_bent);
+int rtk_gather_rays_host(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* h_points, const double* h_normals, rtk_ray* h_rays);
+int rtk_gather_irradiance_host(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* h_points, const double* h_normals, double* h_irradiance);
+int rtk_gather_occlusion_host(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* h_points, const double* h_normals, double* h_open,
+                              double* h_bent);
 
 /* Known-answer / diagnostic entry point: hittable::hit(r, interval(tmin, tmax), rec) of the uploaded
  * scene's root (hittable.h:33) for n caller-supplied rays, run through the same device traversal and

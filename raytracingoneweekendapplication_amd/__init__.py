@@ -382,6 +382,38 @@ def probe_grid_positions(origin, spacing, counts):
     return origin + np.stack([ix.ravel(), iy.ravel(), iz.ravel()], 1).astype(np.float64) * spacing
 
 
+class GatherOpts(C.Structure):
+    """rtk_gather_opts (include/rtk.h "Surface gathers")."""
+
+    _fields_ = [("seed", C.c_uint32), ("real_mode", C.c_int32), ("max_depth", C.c_int32), ("samples", C.c_int32), ("rays", C.c_int32),
+                ("first_key", C.c_uint32), ("rotate", C.c_int32), ("batch_points", C.c_int32), ("background", Vec3), ("time", C.c_double),
+                ("max_distance", C.c_double), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+def _gather_opts(seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, max_depth: int = 0, samples: int = 0, rays: int = 0, first_key: int = 0,
+                 rotate: int = 0, batch_points: int = 0, background=(0.0, 0.0, 0.0), time: float = 0.0, max_distance: float = 0.0, stream: int = 0) -> GatherOpts:
+    bg = background if isinstance(background, Vec3) else Vec3(*(float(c) for c in background))
+    return GatherOpts(int(seed), int(real_mode), int(max_depth), int(samples), int(rays), int(first_key) & 0xFFFFFFFF, int(rotate), int(batch_points), bg,
+                      float(time), float(max_distance), stream or None, (C.c_int32 * 4)(0, 0, 0, 0))
+
+
+def quad_texels(Q, u, v, nu: int, nv: int):
+    """The texel centres of a quad Q, u, v (quad.h) on an nu x nv grid and the quad's normal: (points, normals), float64
+    (nu * nv, 3) each, texel (i, j) at index j * nu + i, point Q + ((i + .5) / nu) u + ((j + .5) / nv) v, every normal
+    unit_vector(cross(u, v)) as the reference's quad computes it."""
+    import numpy as np
+
+    Q, u, v = (np.asarray(a, np.float64) for a in (Q, u, v))
+    nu, nv = int(nu), int(nv)
+    if Q.shape != (3,) or u.shape != (3,) or v.shape != (3,) or nu < 1 or nv < 1:
+        raise ValueError(f"quad_texels: Q {Q.shape}, u {u.shape}, v {v.shape}, {nu} x {nv} texels do not describe a quad's grid")
+    n = np.array([u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]])
+    n = (1.0 / np.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2])) * n   # unit_vector: (1 / length) * v
+    j, i = np.meshgrid(np.arange(nv), np.arange(nu), indexing="ij")
+    points = Q + ((i.ravel() + 0.5) / nu)[:, None] * u + ((j.ravel() + 0.5) / nv)[:, None] * v
+    return points, np.tile(n, (nu * nv, 1))
+
+
 LENS_PERSPECTIVE, LENS_EQUIRECT, LENS_FISHEYE, LENS_ORTHOGRAPHIC = 0, 1, 2, 3   # RTK_LENS_*
 
 
@@ -570,6 +602,10 @@ def hip_lib() -> C.CDLL:
                 getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(ProbeOpts), C.c_int64, C.c_void_p, C.c_void_p]
             lib.rtk_probe_irradiance_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(ProbeGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.rtk_probe_irradiance.argtypes = lib.rtk_probe_irradiance_host.argtypes + [C.c_void_p]
+            gather = [C.c_void_p, C.POINTER(GatherOpts), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+            for name in ("rtk_gather_rays", "rtk_gather_irradiance", "rtk_gather_rays_host", "rtk_gather_irradiance_host"):
+                getattr(lib, name).argtypes = gather
+            lib.rtk_gather_occlusion.argtypes = lib.rtk_gather_occlusion_host.argtypes = gather + [C.c_void_p]
             lens = [C.c_void_p, C.POINTER(Lens), C.POINTER(RenderOpts)]
             lib.rtk_lens_look_at.argtypes = [C.POINTER(Lens), Vec3, Vec3, Vec3]
             lib.rtk_lens_rays.argtypes = lib.rtk_lens_rays_host.argtypes = lens + [C.c_int32, C.c_int32, C.c_void_p]
@@ -973,6 +1009,68 @@ class Renderer:
         self._check(self._lib.rtk_probe_irradiance(self._ctx, real_mode, C.byref(grid), d_sh or None, int(m), d_points or None, d_normals or None,
                                                    d_irradiance or None, stream or None))
 
+    def gather_rays(self, points, normals, *, rays: int = 256, samples: int = 1, first_key: int = 0, rotate: int = 0, time: float = 0.0,
+                    max_distance: float = 0.0):
+        """rtk_gather_rays_host: the ray records (``ray_dtype``, (n * rays,), point-major) that ``gather_irradiance`` and
+        ``gather_occlusion`` trace for ``points`` (n, 3) with unit ``normals`` (n, 3): the cosine-weighted set around each normal,
+        stream keys pixel = first_key + k, sample = j * samples, tmax = max_distance (0 = inf).  Needs no scene."""
+        import numpy as np
+
+        points, normals = _gather_inputs("gather_rays", points, normals)
+        n = points.shape[0]
+        opts = _gather_opts(samples=samples, rays=rays, first_key=first_key, rotate=rotate, time=time, max_distance=max_distance)
+        out = np.zeros(n * (opts.rays or 256), ray_dtype())
+        self._check(self._lib.rtk_gather_rays_host(self._ctx, C.byref(opts), n, points.ctypes.data, normals.ctypes.data, out.ctypes.data))
+        return out
+
+    def gather_irradiance(self, points, normals, *, max_depth: int, rays: int = 256, samples: int = 1, background=(0.0, 0.0, 0.0), first_key: int = 0,
+                          rotate: int = 0, batch_points: int = 0, time: float = 0.0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_gather_irradiance_host: E[k] = (pi / rays) sum_j L_kj over the rays ``gather_rays`` returns: float64 (n, 3), F32
+        results widened."""
+        import numpy as np
+
+        points, normals = _gather_inputs("gather_irradiance", points, normals)
+        n = points.shape[0]
+        out = np.zeros((n, 3), np.float64)
+        opts = _gather_opts(seed, real_mode, max_depth, samples, rays, first_key, rotate, batch_points, background, time)
+        self._check(self._lib.rtk_gather_irradiance_host(self._ctx, C.byref(opts), n, points.ctypes.data, normals.ctypes.data, out.ctypes.data))
+        return out
+
+    def gather_occlusion(self, points, normals, *, rays: int = 256, samples: int = 1, max_distance: float = 0.0, first_key: int = 0, rotate: int = 0,
+                         batch_points: int = 0, time: float = 0.0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+        """rtk_gather_occlusion_host: (open, bent): the open fraction of each point's rays, float64 (n,), and the mean of the open
+        rays' directions over all rays (the bent normal, not normalised), float64 (n, 3); F32 results widened."""
+        import numpy as np
+
+        points, normals = _gather_inputs("gather_occlusion", points, normals)
+        n = points.shape[0]
+        open_, bent = np.zeros(n, np.float64), np.zeros((n, 3), np.float64)
+        opts = _gather_opts(seed, real_mode, 0, samples, rays, first_key, rotate, batch_points, (0.0, 0.0, 0.0), time, max_distance)
+        self._check(self._lib.rtk_gather_occlusion_host(self._ctx, C.byref(opts), n, points.ctypes.data, normals.ctypes.data, open_.ctypes.data,
+                                                        bent.ctypes.data))
+        return open_, bent
+
+    def gather_rays_device(self, n: int, d_points: int, d_normals: int, d_rays: int, *, rays: int = 256, samples: int = 1, first_key: int = 0, rotate: int = 0,
+                           time: float = 0.0, max_distance: float = 0.0, stream: int = 0) -> None:
+        """rtk_gather_rays with raw device pointers ([n][3] doubles twice in, n * rays rtk_ray records out); asynchronous on ``stream``."""
+        opts = _gather_opts(samples=samples, rays=rays, first_key=first_key, rotate=rotate, time=time, max_distance=max_distance, stream=stream)
+        self._check(self._lib.rtk_gather_rays(self._ctx, C.byref(opts), int(n), d_points or None, d_normals or None, d_rays or None))
+
+    def gather_irradiance_device(self, n: int, d_points: int, d_normals: int, d_irradiance: int, *, max_depth: int, rays: int = 256, samples: int = 1,
+                                 background=(0.0, 0.0, 0.0), first_key: int = 0, rotate: int = 0, batch_points: int = 0, time: float = 0.0,
+                                 seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_gather_irradiance with raw device pointers ([n][3] reals of ``real_mode`` out); asynchronous on ``stream``."""
+        opts = _gather_opts(seed, real_mode, max_depth, samples, rays, first_key, rotate, batch_points, background, time, 0.0, stream)
+        self._check(self._lib.rtk_gather_irradiance(self._ctx, C.byref(opts), int(n), d_points or None, d_normals or None, d_irradiance or None))
+
+    def gather_occlusion_device(self, n: int, d_points: int, d_normals: int, d_open: int, d_bent: int, *, rays: int = 256, samples: int = 1,
+                                max_distance: float = 0.0, first_key: int = 0, rotate: int = 0, batch_points: int = 0, time: float = 0.0,
+                                seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_gather_occlusion with raw device pointers ([n] and [n][3] reals of ``real_mode`` out, either may be 0); asynchronous
+        on ``stream``."""
+        opts = _gather_opts(seed, real_mode, 0, samples, rays, first_key, rotate, batch_points, (0.0, 0.0, 0.0), time, max_distance, stream)
+        self._check(self._lib.rtk_gather_occlusion(self._ctx, C.byref(opts), int(n), d_points or None, d_normals or None, d_open or None, d_bent or None))
+
     def lens_rays(self, lens: Lens, samples: int = 1, *, first_sample: int = 0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
         """rtk_lens_rays_host: the ray records (``ray_dtype``, (H * W * samples,), pixel-major, samples inner) of samples
         first_sample .. first_sample + samples - 1 of every pixel of ``lens``.  Needs no scene."""
@@ -1284,6 +1382,14 @@ def _host_inputs(who: str, what: str, *inputs):
         one = len(arrays) == 1
         raise ValueError(f"{who}: shape{'' if one else 's'} {', '.join(str(a.shape) for a in arrays)} do{'es' if one else ''} not describe {what}")
     return arrays
+
+
+def _gather_inputs(who: str, points, normals):
+    """The points and normals of a ``gather_*`` wrapper as float64 (n, 3) arrays (``_host_inputs``)."""
+    import numpy as np
+
+    n = np.shape(points)[0] if np.ndim(points) else 0
+    return _host_inputs(who, "(n, 3) points with (n, 3) normals", (points, np.float64, (n, 3)), (normals, np.float64, (n, 3)))
 
 
 class _Handle:

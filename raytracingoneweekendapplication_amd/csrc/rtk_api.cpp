@@ -981,6 +981,9 @@ struct rtk_ctx {
     // rtk_render_tiles: the compacted list of the flagged tiles [list_capacity] and, behind it, the word with its length.
     int32_t* d_tile_list = nullptr;
     int list_capacity = 0;
+    // The surface gathers' per-unit partial sums (rtk_gather_*), grown on demand up to their byte budget.
+    void* d_gather = nullptr;
+    size_t gather_bytes = 0;
 };
 // Sample chunks per launch: the partial-sum workspace holds up to this many planes [local tile][3][64] at 1920x1080 f64 (+ one
 // for the running sum of a frame that needs several launches): 21 + 1 planes = 1.09 GB, where the 63 chunks of a 1000-spp
@@ -1143,6 +1146,7 @@ int rtk_destroy(rtk_ctx* ctx) {
     if (ctx->d_cameras) (void)hipFree(ctx->d_cameras);
     if (ctx->d_partial) (void)hipFree(ctx->d_partial);
     if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
+    if (ctx->d_gather) (void)hipFree(ctx->d_gather);
     if (ctx->d_tile_cost) (void)hipFree(ctx->d_tile_cost);
     if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
     if (ctx->d_tile_list) (void)hipFree(ctx->d_tile_list);
@@ -1652,6 +1656,22 @@ hipError_t denoise_workspace(rtk_ctx* ctx, size_t bytes, void** out) {
         ctx->denoise_bytes = bytes;
     }
     *out = ctx->d_denoise;
+    return e;
+}
+
+hipError_t gather_workspace(rtk_ctx* ctx, size_t bytes, void** out) {
+    hipError_t e = hipSuccess;
+    if (bytes > ctx->gather_bytes) {
+        if (ctx->d_gather) {
+            if ((e = hipDeviceSynchronize()) != hipSuccess) return e;  // earlier launches may still read the old workspace
+            if ((e = hipFree(ctx->d_gather)) != hipSuccess) return e;
+            ctx->d_gather = nullptr;
+            ctx->gather_bytes = 0;
+        }
+        if ((e = hipMalloc(&ctx->d_gather, bytes)) != hipSuccess) return e;
+        ctx->gather_bytes = bytes;
+    }
+    *out = ctx->d_gather;
     return e;
 }
 

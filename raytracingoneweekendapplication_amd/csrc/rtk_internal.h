@@ -153,6 +153,9 @@ CameraRec<real> device_camera(const rtk_camera& cam);
 // The denoiser's ping-pong buffers: context-owned device memory of at least `bytes`, grown on demand (apart from the render's
 // partial-sum workspace).  Growing waits for the device: earlier launches may still read the old buffers.
 hipError_t denoise_workspace(rtk_ctx* ctx, size_t bytes, void** out);
+// The surface gathers' partial sums (rtk_gather.cpp): context-owned device memory of at least `bytes`, grown like the render's
+// workspace (growing waits for the device) and apart from it.
+hipError_t gather_workspace(rtk_ctx* ctx, size_t bytes, void** out);
 // RTK_OK, or RTK_ERR_INVALID with the reason in g_error, for rtk_denoise_opts out of range (null = every default).
 int check_denoise_opts(const rtk_denoise_opts* opts, const char* who);
 // The same for rtk_guide_opts (null = every default) and the guided filter's flags; *follow / *max_bounces = the resolved options.

@@ -119,6 +119,26 @@ template <typename real>
 hipError_t launch_probe_bake(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, uint32_t first_key, int rays, double time, long long n,
                              const double* d_positions, void* d_sh, hipStream_t stream);
 
+// Surface gathers (rtk_gather_irradiance / _occlusion), stage 1: n points of one batch at d_points / d_normals [n][3] doubles,
+// `rays` rays each (a multiple of 64), one wave per 64 rays; first_key is the key of the batch's first point.  d_partial gets
+// [n * rays / 64][4] doubles -- the sums of each unit's radiance (three words), or its open rays and their directions (four) --
+// for launch_gather_reduce (rtk_gather.hip).  cam as for launch_query_radiance, any_hit as for launch_query_occluded.
+template <typename real>
+hipError_t launch_gather_irradiance(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, uint32_t first_key, int rays, uint32_t rotate, double time,
+                                    long long n, const double* d_points, const double* d_normals, double* d_partial, hipStream_t stream);
+template <typename real>
+hipError_t launch_gather_occlusion(const SceneView<real>& sc, uint32_t seed, bool any_hit, uint32_t first_key, int rays, int samples, uint32_t rotate, double time,
+                                   double tmax, long long n, const double* d_points, const double* d_normals, double* d_partial, hipStream_t stream);
+// ... and what rtk_gather.hip holds: the n * rays ray records of rtk_gather_rays, one lane each, and stage 2, one lane per
+// (point, channel): a point's rays / 64 partial sums added in order, scaled once by pi / rays (irradiance, [n][3] reals) or divided
+// once by rays (occlusion: d_open [n], d_bent [n][3] reals, either may be null).
+hipError_t launch_gather_rays(long long n, int rays, int samples, uint32_t first_key, uint32_t rotate, double time, double tmax, const double* d_points,
+                              const double* d_normals, void* d_rays, hipStream_t stream);
+template <typename real>
+hipError_t launch_gather_irradiance_reduce(long long n, int rays, const double* d_partial, void* d_irradiance, hipStream_t stream);
+template <typename real>
+hipError_t launch_gather_occlusion_reduce(long long n, int rays, const double* d_partial, void* d_open, void* d_bent, hipStream_t stream);
+
 // Lens models (rtk_lens_*): what the kernels read of an rtk_lens besides its camera record, in double in both real modes.
 // half_h / half_v = fov_h / 2, fov_v / 2 with the defaults resolved (EQUIRECT, FISHEYE) or ortho_width / 2, ortho_height / 2
 // (ORTHOGRAPHIC): halving is exact, so the rule's x * (fov_h / 2) is x * half_h.

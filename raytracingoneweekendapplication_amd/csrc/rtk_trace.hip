@@ -32,6 +32,7 @@
 #include "rtk.h"
 #include "rtk_device_layout.h"
 #include "rtk_device_math.h"
+#include "rtk_gather_rule.h"
 #include "rtk_image_pass.h"
 #include "rtk_trace.h"
 
@@ -2783,6 +2784,99 @@ __global__ __launch_bounds__(256) void rtk_probe_bake_kernel(SceneView<real> sc,
     }
 }
 
+// ------------------------------------------------------------------ surface gathers --
+// Irradiance and occlusion at points with normals (include/rtk.h "Surface gathers"), stage 1 of two: one wave per unit
+// w = (point k, pass q) = 64 rays j = 64 q .. 64 q + 63 of that point, four consecutive units per workgroup, so that a point's
+// passes spread over the chip as the query's workgroups do and no launch is as long as its slowest point.  A wave whose unit
+// is past the end leaves whole; no barrier, no LDS.  Each unit's sums go to the workspace as doubles, four words per unit;
+// stage 2 (rtk_gather.hip) adds a point's passes in order.  first_key, points and normals are the batch's: k counts from its
+// first point.
+
+// Per lane: the direction (rtk_gather_rule.h) through the rounding load_ray applies to a record, the stream of the record
+// rtk_gather_rays_kernel writes, rtk_query_radiance_kernel's sample loop restated, then three butterflies (offsets 32 .. 1), which
+// leave each sum in every lane; lanes 0 .. 2 store.  Nothing but the unit's index is live across the path loop.
+template <typename real>
+__global__ __launch_bounds__(256) void rtk_gather_irradiance_kernel(SceneView<real> sc, CameraRec<real> cam, uint32_t seed, uint32_t first_key, int rays,
+                                                                     uint32_t rotate, double time, long long units, const double* __restrict__ points,
+                                                                     const double* __restrict__ normals, double* __restrict__ partial) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= units) return;
+    const int passes = rays >> 6;
+    const long long k = w / passes;
+    const uint32_t j = uint32_t(w - k * passes) * 64u + uint32_t(lane);
+    Counters<false> cnt;
+    cnt.clear();
+#ifdef RTK_PROFILE
+    ShadeProf sprof;
+#endif
+    const uint32_t seed_hash = pcg_hash(seed), pixel = first_key + uint32_t(k);
+    const double* p = points + k * 3;
+    const V3<real> origin = mk(real(p[0]), real(p[1]), real(p[2]));
+    V3<real> rd;
+    {
+        double d[3];
+        gather_direction(j, rays, gather_rotation(rotate, pixel), normals + k * 3, d);
+        rd = mk(real(d[0]), real(d[1]), real(d[2]));
+    }
+    V3<real> sum = mk(real(0), real(0), real(0));
+    for (int s = 0; s < cam.spp; s++) {
+        Lane<real> L;
+        L.ro = origin;
+        L.rd = rd;
+        L.tm = real(time);
+        L.rng = stream_key(seed_hash, pixel, j * uint32_t(cam.spp) + uint32_t(s));   // (skip = 0)
+        L.radiance = mk(real(0), real(0), real(0));
+        L.throughput = mk(real(1), real(1), real(1));
+        L.depth = cam.max_depth;
+        trace_path(L, sc, cam, cnt RTK_SHADE_PROF_ARG);
+        sum = sum + L.radiance;
+    }
+    const real ns = real(cam.spp);
+    const double rgb[3] = {double(sum.x / ns), double(sum.y / ns), double(sum.z / ns)};
+    double mine = 0.0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        double v = rgb[ch];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == ch) mine = v;
+    }
+    if (lane < 3) partial[w * 4 + lane] = mine;
+}
+
+// The same units for occlusion: rtk_query_occluded_kernel's walk of the record (tmin 0.001, tmax as given, the stream of sample
+// j * spr), then four butterflies -- the open rays as a double and the sum of their directions, the doubles of the record --
+// and lanes 0 .. 3 store.
+template <typename real, bool ANY_HIT>
+__global__ __launch_bounds__(256) void rtk_gather_occlusion_kernel(SceneView<real> sc, uint32_t seed, uint32_t first_key, int rays, int spr, uint32_t rotate,
+                                                                    double time, double tmax, long long units, const double* __restrict__ points,
+                                                                    const double* __restrict__ normals, double* __restrict__ partial) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= units) return;
+    const int passes = rays >> 6;
+    const long long k = w / passes;
+    const uint32_t j = uint32_t(w - k * passes) * 64u + uint32_t(lane);
+    const uint32_t pixel = first_key + uint32_t(k);
+    const double* p = points + k * 3;
+    double r[9] = {p[0], p[1], p[2], 0.0, 0.0, 0.0, time, 0.001, tmax};
+    gather_direction(j, rays, gather_rotation(rotate, pixel), normals + k * 3, r + 3);
+    Counters<true> cnt;
+    Lane<real> L;
+    load_ray(L, r);
+    L.rng = stream_key(pcg_hash(seed), pixel, j * uint32_t(spr));   // (skip = 0)
+    query_closest<ANY_HIT>(L, r, sc, cnt);
+    const bool open = L.best_pc == kNoHit;
+    double mine = 0.0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        double v = open ? (c == 0 ? 1.0 : r[2 + c]) : 0.0;
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == c) mine = v;
+    }
+    if (lane < 4) partial[w * 4 + lane] = mine;
+}
+
 // ------------------------------------------------------------------ lens models --
 // Whole frames through a lens (include/rtk.h "Lens models"): lens_begin above makes the sample; these kernels store it or trace it.
 
@@ -3261,6 +3355,35 @@ hipError_t launch_probe_bake(const SceneView<real>& sc, const CameraRec<real>& c
 }
 template hipError_t launch_probe_bake<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, uint32_t, int, double, long long, const double*, void*, hipStream_t);
 template hipError_t launch_probe_bake<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, uint32_t, int, double, long long, const double*, void*, hipStream_t);
+
+template <typename real>
+hipError_t launch_gather_irradiance(const SceneView<real>& sc, const CameraRec<real>& cam, uint32_t seed, uint32_t first_key, int rays, uint32_t rotate, double time,
+                                    long long n, const double* d_points, const double* d_normals, double* d_partial, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const long long units = n * (rays / 64);
+    rtk_gather_irradiance_kernel<real><<<dim3((unsigned int)((units + 3) / 4)), dim3(256), 0, stream>>>(sc, cam, seed, first_key, rays, rotate, time, units, d_points,
+                                                                                                         d_normals, d_partial);
+    return hipGetLastError();
+}
+template hipError_t launch_gather_irradiance<double>(const SceneView<double>&, const CameraRec<double>&, uint32_t, uint32_t, int, uint32_t, double, long long, const double*,
+                                                     const double*, double*, hipStream_t);
+template hipError_t launch_gather_irradiance<float>(const SceneView<float>&, const CameraRec<float>&, uint32_t, uint32_t, int, uint32_t, double, long long, const double*,
+                                                    const double*, double*, hipStream_t);
+
+template <typename real>
+hipError_t launch_gather_occlusion(const SceneView<real>& sc, uint32_t seed, bool any_hit, uint32_t first_key, int rays, int samples, uint32_t rotate, double time,
+                                   double tmax, long long n, const double* d_points, const double* d_normals, double* d_partial, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const long long units = n * (rays / 64);
+    const dim3 grid((unsigned int)((units + 3) / 4));
+    if (any_hit) rtk_gather_occlusion_kernel<real, true><<<grid, dim3(256), 0, stream>>>(sc, seed, first_key, rays, samples, rotate, time, tmax, units, d_points, d_normals, d_partial);
+    else rtk_gather_occlusion_kernel<real, false><<<grid, dim3(256), 0, stream>>>(sc, seed, first_key, rays, samples, rotate, time, tmax, units, d_points, d_normals, d_partial);
+    return hipGetLastError();
+}
+template hipError_t launch_gather_occlusion<double>(const SceneView<double>&, uint32_t, bool, uint32_t, int, int, uint32_t, double, double, long long, const double*,
+                                                    const double*, double*, hipStream_t);
+template hipError_t launch_gather_occlusion<float>(const SceneView<float>&, uint32_t, bool, uint32_t, int, int, uint32_t, double, double, long long, const double*,
+                                                   const double*, double*, hipStream_t);
 
 template <typename real>
 hipError_t launch_lens_rays(const LensRec& lens, const CameraRec<real>& cam, uint32_t seed, uint32_t first_sample, int n_samples, void* d_rays, hipStream_t stream) {

@@ -756,5 +756,6 @@ inline rtk_scene_desc flatten(const hittable& world, const std::vector<point_lig
 
 #include "rtk_ray_query.h"  // rtk::ray_query: world.hit / ray_color for caller rays, answered on the device
 #include "rtk_light_probes.h"  // rtk::light_probes: a grid of SH probes baked on the device, irradiance looked up from it
+#include "rtk_surface_gather.h"  // rtk::surface_gather: irradiance and occlusion at surface points with normals (lightmaps, AO)
 
 #endif  // RTK_SCENE_API_H
