@@ -1280,6 +1280,53 @@ int rtk_frame_launches(const rtk_camera* cam, const rtk_render_opts* opts);
  * traces.  Returns a static string. */
 const char* rtk_kernel_name(rtk_ctx* ctx, int real_mode, int variant);
 
+/* View batches --------------------------------------------------------------------------
+ * Many cameras' frames of one size in one launch: cube faces, a camera path, thumbnails, a light field.  Device resident and
+ * asynchronous on opts->stream, on the uploaded scene in either visiting order and both real modes; one rank only.  New entry
+ * points; RTK_ABI_VERSION stays 2.
+ *
+ * The rule.  View v of the batch is, bit for bit, the frame that
+ *     rtk_render_device(ctx, &h_cams[v], opts with seed = h_seeds ? h_seeds[v] : opts->seed, ...)
+ * writes, linear and rgb8: d_linear = [n_views][H][W][3] reals (double for F64, float for F32), d_rgb8 = [n_views][H][W][3]
+ * bytes; either may be NULL.  A sample's random stream is keyed (seed of its view, j * W + i, s) with (i, j) the pixel INSIDE
+ * its view, as in the single frame.  A pixel's samples are cut into the single frame's chunks -- their boundaries depend on
+ * samples_per_pixel only -- and a pixel's chunk sums are added in the single frame's order, through the same code.
+ *
+ * Shared by all views, and checked: image_width, image_height, samples_per_pixel, and therefore pixel_samples_scale.  Free
+ * per view: everything else in rtk_camera -- the pose (center, pixel00_loc, pixel_delta_u / _v), background, max_depth (0
+ * included), the defocus disk -- and the seed.
+ *
+ * What runs.  Work items are (view, tile, chunk), handed out from one counter to the persistent waves of ONE launch per pass
+ * of rtk_view_batch_kernel<real, FEAT, IN_LDS>, the render kernel's body with a camera per lane read from a table of view
+ * records.  It exists for the instantiations that stage the traversal program, its hot part or its boxes in LDS (DESIGN.md
+ * "View batches" has the table).  For every other choice -- variant bit 0, programs too large for any LDS form -- and whenever
+ * opts->count_work != 0, the call renders the batch as n_views plain frames, one rtk_render_kernel launch (per pass) each
+ * into the view's plane: the same bits by construction, and d_counters (zeroed by the caller) receives the sum over the views.
+ * rtk_view_kernel_name returns the symbol a batch would dispatch for (real_mode, variant) without work counters, as
+ * rtk_kernel_name does for a frame: the view kernel's, or the plain kernel's where the per-view form runs.  Passes follow
+ * rtk_frame_launches' budget with the batch's n_views * tiles in place of a frame's tiles.
+ *
+ * Refusals (RTK_ERR_INVALID, rtk_last_error names the cause): null ctx / h_cams / opts; n_views < 1 or > 65536; a view whose
+ * shared fields differ from view 0's (the message names the view), or with max_depth < 0; bad dimensions (as
+ * rtk_render_device); opts->n_ranks != 1 (or rank != 0); variant bit 22; opts->count_work without d_counters; n_views * tiles *
+ * sample chunks beyond 2^31 - 1.  RTK_ERR_NO_SCENE without an uploaded scene.
+ *
+ * Streams: the rules of rtk_render_device.  h_cams, h_seeds and opts are read before the call returns; any number of batches
+ * may be in flight on the stream.  The view records travel through a ring of four context-owned pinned buffers into a
+ * context-owned device table (grown on demand like the partial-sum workspace, reused in stream order); with more than four
+ * batches in flight the call waits until the upload of the fourth-last batch's records has run, and for nothing else.
+ * Context state: a batch neither reads nor changes the tile order the context learned from its frames (per-view form
+ * included: its frames are handed out row-major and measure nothing).  A progress callback sees the batch's work items like a
+ * frame's (per-view form: those of its last view).
+ *
+ * rtk_render_views_host allocates, renders, waits and copies back: h_linear [n_views][H][W][3] doubles (F32 widened), h_rgb8
+ * bytes, either may be NULL; counters != NULL selects count_work. */
+int rtk_render_views(rtk_ctx* ctx, int32_t n_views, const rtk_camera* h_cams, const uint32_t* h_seeds /* NULL: opts->seed for all */,
+                     const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters);
+int rtk_render_views_host(rtk_ctx* ctx, int32_t n_views, const rtk_camera* h_cams, const uint32_t* h_seeds, const rtk_render_opts* opts,
+                          double* h_linear, uint8_t* h_rgb8, rtk_work_counters* counters);
+const char* rtk_view_kernel_name(rtk_ctx* ctx, int real_mode, int variant);
+
 #ifdef __cplusplus
 }
 #endif

@@ -527,6 +527,10 @@ def hip_lib() -> C.CDLL:
         lib.rtk_scene_optimized_free.argtypes = [C.c_void_p]
         lib.rtk_kernel_name.restype = C.c_char_p
         lib.rtk_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.rtk_render_views.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Camera), C.POINTER(C.c_uint32), C.POINTER(RenderOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rtk_render_views_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Camera), C.POINTER(C.c_uint32), C.POINTER(RenderOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rtk_view_kernel_name.restype = C.c_char_p
+        lib.rtk_view_kernel_name.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.rtk_scene_upload_optimized.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(OptimizeOpts)]
         lib.rtk_init_multi.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
         lib.rtk_multi_destroy.argtypes = [C.c_void_p]
@@ -752,6 +756,24 @@ def derive_camera(image_width: int, aspect_ratio: float, *, spp: int = 10, max_d
     return cam
 
 
+# The six faces of a cube capture, in this order, as (forward axis, up vector): the layout of cube maps in graphics APIs
+# (+x, -x, +y, -y, +z, -z; the side faces hang from -y, the top and bottom faces from +z / -z).
+CUBE_FACES = (((1.0, 0.0, 0.0), (0.0, -1.0, 0.0)), ((-1.0, 0.0, 0.0), (0.0, -1.0, 0.0)), ((0.0, 1.0, 0.0), (0.0, 0.0, 1.0)),
+              ((0.0, -1.0, 0.0), (0.0, 0.0, -1.0)), ((0.0, 0.0, 1.0), (0.0, -1.0, 0.0)), ((0.0, 0.0, -1.0), (0.0, -1.0, 0.0)))
+
+
+def cube_face_cameras(center, face_size: int, *, spp: int = 10, max_depth: int = 10, background=(0.0, 0.0, 0.0)):
+    """Six square 90-degree cameras at `center` looking down CUBE_FACES' axes with their up vectors, each derive_camera's (so
+    a batch of them is Renderer.render_views' cube capture); `background` is set on every face."""
+    cams = []
+    for axis, up in CUBE_FACES:
+        cam = derive_camera(face_size, 1.0, spp=spp, max_depth=max_depth, vfov=90.0, lookfrom=tuple(center),
+                            lookat=tuple(center[k] + axis[k] for k in range(3)), vup=up, defocus_angle=0.0, focus_dist=1.0)
+        cam.background = Vec3(*background)
+        cams.append(cam)
+    return cams
+
+
 def load_image_texels(path: str):
     """The RGB8 texels image_texture reads for an image file (PPM or baseline JPEG), as rtw_image holds them
     (stbi_loadf's gamma-2.2 mapping and float_to_byte applied).  Returns an (H, W, 3) uint8 array or None."""
@@ -844,6 +866,44 @@ class Renderer:
         opts = RenderOpts(seed, real_mode, 0, 1, 1 if count else 0, variant, None)
         self._check(self._lib.rtk_render_host(self._ctx, C.byref(cam), C.byref(opts), linear.ctypes.data, rgb8.ctypes.data,
                                               C.byref(counters) if count else None))
+        return linear, rgb8, (counters.as_dict() if count else None)
+
+    @staticmethod
+    def _view_arrays(cams, seeds):
+        cams = list(cams)
+        c_cams = (Camera * max(len(cams), 1))(*cams)
+        c_seeds = None
+        if seeds is not None:
+            seeds = [int(x) for x in seeds]
+            if len(seeds) != len(cams):
+                raise ValueError("render_views: one seed per camera")
+            c_seeds = (C.c_uint32 * max(len(seeds), 1))(*seeds)
+        return len(cams), c_cams, c_seeds
+
+    def view_kernel_name(self, real_mode: int = RTK_REAL_F64, variant: int = 0) -> str:
+        """rtk_view_kernel_name: what a view batch dispatches -- the view kernel, or the plain kernel where it runs view by view."""
+        return self._lib.rtk_view_kernel_name(self._ctx, real_mode, variant).decode()
+
+    def render_views_device(self, cams, d_linear: int, d_rgb8: int = 0, d_counters: int = 0, *, seeds=None, seed: int = RENDER_SEED,
+                            real_mode: int = RTK_REAL_F64, variant: int = 0, stream: int = 0) -> None:
+        """rtk_render_views: enqueue a batch of same-sized views into [N,H,W,3] device planes (raw addresses); nothing synchronises."""
+        n, c_cams, c_seeds = self._view_arrays(cams, seeds)
+        opts = RenderOpts(seed, real_mode, 0, 1, 1 if d_counters else 0, variant, stream or None)
+        self._check(self._lib.rtk_render_views(self._ctx, n, c_cams, c_seeds, C.byref(opts), d_linear or None, d_rgb8 or None, d_counters or None))
+
+    def render_views(self, cams, *, seeds=None, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, count: bool = False, variant: int = 0):
+        """rtk_render_views_host: render the batch and return (linear float64 [N,H,W,3], rgb8 [N,H,W,3], counters dict | None);
+        view v is render_host(cams[v], seed=seeds[v]) bit for bit."""
+        import numpy as np
+
+        n, c_cams, c_seeds = self._view_arrays(cams, seeds)
+        h, w = (c_cams[0].image_height, c_cams[0].image_width) if n else (0, 0)
+        linear = np.zeros((n, max(h, 0), max(w, 0), 3), np.float64)
+        rgb8 = np.zeros((n, max(h, 0), max(w, 0), 3), np.uint8)
+        counters = WorkCounters()
+        opts = RenderOpts(seed, real_mode, 0, 1, 1 if count else 0, variant, None)
+        self._check(self._lib.rtk_render_views_host(self._ctx, n, c_cams, c_seeds, C.byref(opts), linear.ctypes.data, rgb8.ctypes.data,
+                                                    C.byref(counters) if count else None))
         return linear, rgb8, (counters.as_dict() if count else None)
 
     def closest_hit(self, rays, keys, real_mode: int = RTK_REAL_F64):

@@ -984,6 +984,18 @@ struct rtk_ctx {
     // The surface gathers' per-unit partial sums (rtk_gather_*), grown on demand up to their byte budget.
     void* d_gather = nullptr;
     size_t gather_bytes = 0;
+    // rtk_render_views: the batch's view records in device memory, grown on demand like the partial-sum workspace and reused
+    // in stream order, and a ring of pinned host buffers they are uploaded from -- a buffer is rewritten only after the
+    // event behind its last upload has passed, so batches enqueued back to back never share one.
+    void* d_views = nullptr;
+    size_t views_bytes = 0;
+    struct ViewStage {
+        void* host = nullptr;
+        size_t bytes = 0;
+        hipEvent_t done = nullptr;
+    };
+    ViewStage view_stage[4];
+    unsigned int next_view_stage = 0;
 };
 // Sample chunks per launch: the partial-sum workspace holds up to this many planes [local tile][3][64] at 1920x1080 f64 (+ one
 // for the running sum of a frame that needs several launches): 21 + 1 planes = 1.09 GB, where the 63 chunks of a 1000-spp
@@ -1103,6 +1115,23 @@ int wait_with_progress(rtk_ctx* const* ctxs, const hipStream_t* streams, int n) 
 
 }  // namespace rtk
 
+// View batches (rtk_render_views): a view's record as the view kernel reads it.
+static uint32_t seed_hash_of(uint32_t v) {  // pcg_hash (rtk_trace.hip): what the render kernel makes of opts->seed before it keys a sample's stream
+    const uint32_t st = v * 747796405u + 2891336453u;
+    const uint32_t w = ((st >> ((st >> 28u) + 4u)) ^ st) * 277803737u;
+    return (w >> 22u) ^ w;
+}
+
+template <typename real>
+static void fill_view_records(void* dst, int32_t n_views, const rtk_camera* cams, const uint32_t* seeds, uint32_t seed) {
+    auto* out = static_cast<ViewRec<real>*>(dst);
+    for (int32_t v = 0; v < n_views; v++) {
+        out[v].cam = to_device_camera<real>(cams[v]);
+        out[v].seed_hash = seed_hash_of(seeds ? seeds[v] : seed);
+        out[v].reserved = 0;
+    }
+}
+
 extern "C" {
 
 int rtk_abi_version(void) { return RTK_ABI_VERSION; }
@@ -1150,6 +1179,11 @@ int rtk_destroy(rtk_ctx* ctx) {
     if (ctx->d_tile_cost) (void)hipFree(ctx->d_tile_cost);
     if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
     if (ctx->d_tile_list) (void)hipFree(ctx->d_tile_list);
+    if (ctx->d_views) (void)hipFree(ctx->d_views);
+    for (auto& st : ctx->view_stage) {
+        if (st.done) (void)hipEventDestroy(st.done);
+        if (st.host) (void)hipHostFree(st.host);
+    }
     if (ctx->progress_stream) (void)hipStreamDestroy(ctx->progress_stream);
     if (ctx->progress_word) (void)hipHostFree(ctx->progress_word);
     delete ctx;
@@ -1406,7 +1440,10 @@ static int stage_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opt
     return RTK_OK;
 }
 
-int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters) {
+// rtk_render_device; use_order = false (a view batch's per-view fallback): the frame neither reads nor touches the context's
+// learned tile order -- row-major hand-out, no cost measured, the stored order and the shape it belongs to left as they are.
+static int render_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters,
+                        bool use_order) {
     if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_device: null argument");
     if (!ctx->has_scene) return fail(RTK_ERR_NO_SCENE, "rtk_render_device: no scene uploaded");
     if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
@@ -1430,7 +1467,7 @@ int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts
     auto* counters = reinterpret_cast<unsigned long long*>(d_counters);
     // tile order / cost buffers for this shape
     const int shape[5] = {cam->image_width, cam->image_height, opts->rank, opts->n_ranks, tm.n_tiles_local};
-    if (tm.n_tiles_local > ctx->order_capacity) {
+    if (use_order && tm.n_tiles_local > ctx->order_capacity) {
         if (ctx->d_tile_cost) {
             RTK_HIP(hipDeviceSynchronize());
             RTK_HIP(hipFree(ctx->d_tile_cost));
@@ -1443,8 +1480,8 @@ int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts
         ctx->order_capacity = tm.n_tiles_local;
         ctx->order_valid = false;
     }
-    if (std::memcmp(shape, ctx->order_shape, sizeof shape) != 0) ctx->order_valid = false;
-    const bool learn = (opts->variant & 4) == 0;  // variant bit 2: fixed row-major tile order (A/B, tests)
+    if (use_order && std::memcmp(shape, ctx->order_shape, sizeof shape) != 0) ctx->order_valid = false;
+    const bool learn = use_order && (opts->variant & 4) == 0;  // variant bit 2: fixed row-major tile order (A/B, tests)
     if (!ctx->order_valid && learn) RTK_HIP(hipMemsetAsync(ctx->d_tile_cost, 0, size_t(tm.n_tiles_local) * sizeof(unsigned int), stream));
     const int32_t* tile_order = (ctx->order_valid && learn) ? ctx->d_tile_order : nullptr;
     unsigned int* tile_cost = learn ? ctx->d_tile_cost : nullptr;
@@ -1486,6 +1523,10 @@ int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts
     }
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "render kernel launch failed: %s", hipGetErrorString(e));
     return RTK_OK;
+}
+
+int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters) {
+    return render_frame(ctx, cam, opts, d_linear, d_rgb8, d_counters, true);
 }
 
 int rtk_tiles_unpermute(rtk_ctx* ctx, int image_width, int image_height, int n_ranks, int real_mode, const void* d_gathered, void* d_linear, uint8_t* d_rgb8,
@@ -1697,6 +1738,80 @@ hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const T
                                      ctx->d_partial, counters, tile_counter, tile_order, tile_cost, stream);
     return launch_render<float>(ctx->scene32.view, static_cast<const CameraRec<float>*>(d_cam), tp, seed, ctx->features, count, allow_lds, diag, ctx->d_partial,
                                 counters, tile_counter, tile_order, tile_cost, stream);
+}
+
+int frame_chunk_count(int spp, int variant) {
+    const int size = chunk_size_for(spp, variant);
+    return (spp + size - 1) / size;
+}
+
+int render_frame_apart(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters) {
+    return render_frame(ctx, cam, opts, d_linear, d_rgb8, d_counters, false);
+}
+
+int stage_view_batch(rtk_ctx* ctx, int32_t n_views, const rtk_camera* cams, const uint32_t* seeds, const rtk_render_opts* opts, ViewBatch& out) {
+    FramePlan f;
+    plan_frame(&cams[0], opts, false, f);  // one view's tiles; the chunk boundaries (a function of spp) are the single frame's
+    out.tm = f.tm;
+    out.tm.n_tiles_local = n_views * f.tm.n_tiles_local;  // local tiles are [view][tile]
+    out.tm.rank = 0;
+    out.tm.n_ranks = 1;
+    out.allow_lds = f.allow_lds;
+    out.diag = f.diag;
+    out.stream = f.stream;
+    const bool f64 = opts->real_mode == RTK_REAL_F64;
+    out.plane = size_t(out.tm.n_tiles_local) * 192 * (f64 ? sizeof(double) : sizeof(float));
+    out.planes_per_pass = planes_per_pass_for(out.plane, opts->variant);
+    out.n_passes = (out.tm.n_chunks + out.planes_per_pass - 1) / out.planes_per_pass;
+    RTK_HIP(hipSetDevice(ctx->device));
+    const size_t need = out.plane * size_t(out.n_passes > 1 ? out.planes_per_pass + 1 : out.tm.n_chunks);
+    if (need > ctx->partial_bytes) {
+        if (ctx->d_partial) {
+            RTK_HIP(hipDeviceSynchronize());  // earlier launches may still read the old workspace
+            RTK_HIP(hipFree(ctx->d_partial));
+            ctx->d_partial = nullptr;
+            ctx->partial_bytes = 0;
+        }
+        RTK_HIP(hipMalloc(&ctx->d_partial, need));
+        ctx->partial_bytes = need;
+    }
+    out.d_partial = ctx->d_partial;
+    const size_t rec_bytes = size_t(n_views) * (f64 ? sizeof(ViewRec<double>) : sizeof(ViewRec<float>));
+    if (rec_bytes > ctx->views_bytes) {
+        if (ctx->d_views) {
+            RTK_HIP(hipDeviceSynchronize());  // earlier batches may still read the old table
+            RTK_HIP(hipFree(ctx->d_views));
+            ctx->d_views = nullptr;
+            ctx->views_bytes = 0;
+        }
+        RTK_HIP(hipMalloc(&ctx->d_views, rec_bytes));
+        ctx->views_bytes = rec_bytes;
+    }
+    out.d_views = ctx->d_views;
+    rtk_ctx::ViewStage& stage = ctx->view_stage[ctx->next_view_stage++ % 4u];
+    if (!stage.done) RTK_HIP(hipEventCreateWithFlags(&stage.done, hipEventDisableTiming));
+    RTK_HIP(hipEventSynchronize(stage.done));  // the upload that last read this buffer (four batches ago) has run
+    if (rec_bytes > stage.bytes) {
+        if (stage.host) RTK_HIP(hipHostFree(stage.host));
+        stage.host = nullptr;
+        stage.bytes = 0;
+        RTK_HIP(hipHostMalloc(&stage.host, rec_bytes, hipHostMallocDefault));
+        stage.bytes = rec_bytes;
+    }
+    if (f64) fill_view_records<double>(stage.host, n_views, cams, seeds, opts->seed);
+    else fill_view_records<float>(stage.host, n_views, cams, seeds, opts->seed);
+    RTK_HIP(hipMemcpyAsync(ctx->d_views, stage.host, rec_bytes, hipMemcpyHostToDevice, out.stream));
+    RTK_HIP(hipEventRecord(stage.done, out.stream));
+    ctx->last_n_passes = out.n_passes;
+    ctx->last_n_items = int64_t(out.tm.n_tiles_local) * out.tm.n_chunks;
+    for (int pass = 0; pass < out.n_passes; pass++) {  // every pass's work-item counter reads 0 from now on (progress reports add them up)
+        out.pass_counter[pass] = ctx->tile_counters + (ctx->next_counter++ % kCounterRing);
+        if (out.n_passes > 1) RTK_HIP(hipMemsetAsync(out.pass_counter[pass], 0, sizeof(unsigned int), out.stream));
+        const int k0 = pass * out.planes_per_pass, k1 = std::min(out.tm.n_chunks, k0 + out.planes_per_pass);
+        ctx->last_tile_counter[pass] = out.pass_counter[pass];
+        ctx->last_pass_items[pass] = int64_t(out.tm.n_tiles_local) * (k1 - k0);
+    }
+    return RTK_OK;
 }
 
 int stage_tile_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, TileFrame& out) {

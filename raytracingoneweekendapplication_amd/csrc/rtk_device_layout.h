@@ -229,6 +229,14 @@ struct CameraRec {  // Camera.txt:122-131
     int32_t width, height, spp, max_depth;
 };
 
+// One view of a view batch (rtk_render_views): its camera and pcg_hash of its seed.  The view kernel's lanes read the table
+// [n_views] with per-lane loads -- lanes of one wave hold pixels of different views -- at a byte offset they carry.
+template <typename real>
+struct ViewRec {
+    CameraRec<real> cam;
+    uint32_t seed_hash, reserved;
+};
+
 template <typename real>
 struct SceneView {  // device pointers, passed to the kernel by value
     const Slot<real>* program;  // the traversal program (copied to LDS by each workgroup when it fits)

@@ -144,6 +144,28 @@ struct TileFrame {
 };
 int stage_tile_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, TileFrame& out);
 
+// rtk_render_views (rtk_views.hip).  stage_view_batch: the batch's set-up on opts->stream for n_views validated cameras of one
+// size -- the tile map over local tiles [view][tile of a view's grid] with the single frame's chunk boundaries, the passes
+// under the workspace budget, the partial-sum workspace grown, the view records (camera + hashed seed; seeds null = opts->seed)
+// uploaded into the context's table through its ring of pinned buffers, a work-item counter per pass, the progress
+// callback's items.  The learned tile order is not touched.
+struct ViewBatch {
+    TileMap tm;  // every chunk of the batch
+    int planes_per_pass = 0, n_passes = 0;
+    size_t plane = 0;  // bytes of one chunk plane [view * tiles + tile][3][64]
+    void* d_partial = nullptr;
+    const void* d_views = nullptr;
+    unsigned int* pass_counter[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool allow_lds = true;
+    uint32_t diag = 0;
+    hipStream_t stream = nullptr;
+};
+int stage_view_batch(rtk_ctx* ctx, int32_t n_views, const rtk_camera* cams, const uint32_t* seeds, const rtk_render_opts* opts, ViewBatch& out);
+// rtk_render_device apart from the context's learned tile order: row-major hand-out, no cost measured, the stored order and the
+// shape it belongs to left as they are (a batch's per-view form).
+int render_frame_apart(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters);
+int frame_chunk_count(int spp, int variant);  // sample chunks of a pixel (rtk_render_opts.variant's chunk-size bits included)
+
 // The uploaded scene's device view per arithmetic type, and a camera's device record (for the AOV pass, rtk_denoise.hip).
 template <typename real>
 const SceneView<real>& ctx_view(const rtk_ctx* ctx);

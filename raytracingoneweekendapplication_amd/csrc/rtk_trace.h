@@ -21,6 +21,20 @@ template <typename real>
 hipError_t launch_render(const SceneView<real>& sc, const CameraRec<real>* d_cam, const TileMap& tmap, uint32_t seed, uint32_t features, bool count,
                          bool allow_lds, uint32_t diag, void* partial, unsigned long long* counters, unsigned int* tile_counter,
                          const int32_t* tile_order, unsigned int* tile_cost, hipStream_t stream);
+// A view batch (rtk_render_views): the view kernel of the instantiation launch_render would choose (count = false), over tmap's
+// local tiles [view][tile of a view's tiles_x x tiles_y grid] (rank 0 of 1), cameras and hashed seeds from the table d_views --
+// hipErrorInvalidValue where that instantiation has no view kernel, which view_kernel_name tells beforehand (*is_view_kernel;
+// its return value is the symbol a batch dispatches: the view kernel's, or else the plain kernel's).
+template <typename real>
+hipError_t launch_view_batch(const SceneView<real>& sc, const ViewRec<real>* d_views, const TileMap& tmap, uint32_t features, bool allow_lds, uint32_t diag,
+                             void* partial, unsigned int* tile_counter, hipStream_t stream);
+template <typename real>
+const char* view_kernel_name(const SceneView<real>& sc, uint32_t features, bool allow_lds, uint32_t diag, bool* is_view_kernel);
+// The resolve of a view batch (rtk_views.hip): launch_resolve's fold, carry and outputs over tmap's [view][tile] tiles, written
+// to the planes [view][H][W][3] of out_linear / out_rgb8 (either may be null).
+template <typename real>
+hipError_t launch_resolve_views(const void* partial, const TileMap& tmap, int width, int height, double samples_scale, void* out_linear, uint8_t* out_rgb8,
+                                void* acc, bool first_pass, bool last_pass, hipStream_t stream);
 
 // cost[n] (segments per local tile, measured by the frame just rendered) -> order[n], most expensive first; clears cost.
 hipError_t launch_tile_order(unsigned int* cost, int n, int32_t* order, hipStream_t stream);

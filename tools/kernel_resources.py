@@ -27,6 +27,9 @@ for block in re.split(r"remark: [^\n]*Function Name: ", p.stderr)[1:]:
     m = re.match(r"_ZN3rtk17rtk_render_kernelI([df])Lj(\d+)ELb([01])ELb([01])E", name)
     if m:
         demangled = "rtk_render_kernel<%s, %su, %s, %s>" % ("double" if m.group(1) == "d" else "float", m.group(2), "true" if m.group(3) == "1" else "false", "true" if m.group(4) == "1" else "false")
+    elif re.match(r"_ZN3rtk21rtk_view_batch_kernelI([df])Lj(\d+)ELb([01])E", name):   # the view kernels (rtk_render_views): no COUNT parameter
+        m = re.match(r"_ZN3rtk21rtk_view_batch_kernelI([df])Lj(\d+)ELb([01])E", name)
+        demangled = "rtk_view_batch_kernel<%s, %su, %s>" % ("double" if m.group(1) == "d" else "float", m.group(2), "true" if m.group(3) == "1" else "false")
     else:
         demangled = name.split(" ")[0][:60]
     if only and only not in demangled:
