@@ -78,6 +78,11 @@ class RenderOpts(C.Structure):
     ]
 
 
+def _whole_image_opts(seed: int, real_mode: int, stream: int = 0) -> RenderOpts:
+    """rtk_render_opts of a pass over the whole image: rank 0 of 1, no work counters, variant 0."""
+    return RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+
+
 class OptimizeOpts(C.Structure):
     """rtk_optimize_opts (include/rtk.h)."""
 
@@ -1137,7 +1142,7 @@ class Renderer:
         import numpy as np
 
         out = np.zeros(max(lens.cam.image_height, 0) * max(lens.cam.image_width, 0) * max(int(samples), 0), ray_dtype())
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        opts = _whole_image_opts(seed, real_mode)
         self._check(self._lib.rtk_lens_rays_host(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), int(samples), out.ctypes.data))
         return out
 
@@ -1148,7 +1153,7 @@ class Renderer:
 
         h, w = lens.cam.image_height, lens.cam.image_width
         linear, noise = np.zeros((h, w, 3), np.float64), np.zeros((h, w), np.float32)
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        opts = _whole_image_opts(seed, real_mode)
         self._check(self._lib.rtk_lens_render_host(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), linear.ctypes.data, noise.ctypes.data))
         return linear, noise
 
@@ -1157,7 +1162,7 @@ class Renderer:
         import numpy as np
 
         out = np.zeros((lens.cam.image_height, lens.cam.image_width, 8), np.float32)
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        opts = _whole_image_opts(seed, real_mode)
         self._check(self._lib.rtk_lens_aovs_host(self._ctx, C.byref(lens), C.byref(opts), int(samples), out.ctypes.data))
         return out
 
@@ -1167,7 +1172,7 @@ class Renderer:
         import numpy as np
 
         out = np.zeros((lens.cam.image_height, lens.cam.image_width, 16), np.float32)
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        opts = _whole_image_opts(seed, real_mode)
         gopts = GuideOpts(int(follow), int(max_bounces))
         self._check(self._lib.rtk_lens_guides_host(self._ctx, C.byref(lens), C.byref(opts), int(samples), C.byref(gopts), out.ctypes.data))
         return out
@@ -1175,25 +1180,25 @@ class Renderer:
     def lens_rays_device(self, lens: Lens, samples: int, d_rays: int, *, first_sample: int = 0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64,
                          stream: int = 0) -> None:
         """rtk_lens_rays with a raw device pointer (H * W * samples rtk_ray records out); asynchronous on ``stream``."""
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        opts = _whole_image_opts(seed, real_mode, stream)
         self._check(self._lib.rtk_lens_rays(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), int(samples), d_rays or None))
 
     def lens_render_device(self, lens: Lens, d_linear: int, d_noise: int = 0, *, first_sample: int = 0, seed: int = RENDER_SEED,
                            real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
         """rtk_lens_render with raw device pointers ([H][W][3] reals of ``real_mode``, float [H][W] se when ``d_noise`` is given);
         asynchronous on ``stream``."""
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        opts = _whole_image_opts(seed, real_mode, stream)
         self._check(self._lib.rtk_lens_render(self._ctx, C.byref(lens), C.byref(opts), int(first_sample), d_linear or None, d_noise or None))
 
     def lens_aovs_device(self, lens: Lens, samples: int, d_aov: int, *, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
         """rtk_lens_aovs with a raw device pointer (float [H][W][8], 16-byte aligned); asynchronous on ``stream``."""
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        opts = _whole_image_opts(seed, real_mode, stream)
         self._check(self._lib.rtk_lens_aovs(self._ctx, C.byref(lens), C.byref(opts), int(samples), d_aov or None))
 
     def lens_guides_device(self, lens: Lens, samples: int, d_guides: int, *, follow: int = GUIDE_FOLLOW_MIRROR, max_bounces: int = 0,
                            seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
         """rtk_lens_guides with a raw device pointer (float [H][W][16], 16-byte aligned); asynchronous on ``stream``."""
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        opts = _whole_image_opts(seed, real_mode, stream)
         gopts = GuideOpts(int(follow), int(max_bounces))
         self._check(self._lib.rtk_lens_guides(self._ctx, C.byref(lens), C.byref(opts), int(samples), C.byref(gopts), d_guides or None))
 
@@ -1214,7 +1219,7 @@ class Renderer:
         import numpy as np
 
         out = np.zeros((cam.image_height, cam.image_width, 8), np.float32)
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        opts = _whole_image_opts(seed, real_mode)
         self._check(self._lib.rtk_render_aovs_host(self._ctx, C.byref(cam), C.byref(opts), int(samples), out.ctypes.data))
         return out
 
@@ -1241,7 +1246,7 @@ class Renderer:
         import numpy as np
 
         out = np.zeros((cam.image_height, cam.image_width, 16), np.float32)
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, None)
+        opts = _whole_image_opts(seed, real_mode)
         gopts = GuideOpts(int(follow), int(max_bounces))
         self._check(self._lib.rtk_render_guides_host(self._ctx, C.byref(cam), C.byref(opts), int(samples), C.byref(gopts), out.ctypes.data))
         return out
@@ -1249,7 +1254,7 @@ class Renderer:
     def guides_device(self, cam: Camera, samples: int, d_guides: int, *, follow: int = GUIDE_FOLLOW_MIRROR, max_bounces: int = 0, seed: int = RENDER_SEED,
                       real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
         """rtk_render_guides with a raw device pointer (float [H][W][16], 16-byte aligned); asynchronous on ``stream``."""
-        opts = RenderOpts(seed, real_mode, 0, 1, 0, 0, stream or None)
+        opts = _whole_image_opts(seed, real_mode, stream)
         gopts = GuideOpts(int(follow), int(max_bounces))
         self._check(self._lib.rtk_render_guides(self._ctx, C.byref(cam), C.byref(opts), int(samples), C.byref(gopts), d_guides or None))
 

@@ -45,12 +45,6 @@ namespace {
 using rtk::fail;
 using rtk::g_error;
 
-#define RTK_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 using namespace rtk;
 
 // ---------------------------------------------------------------------------

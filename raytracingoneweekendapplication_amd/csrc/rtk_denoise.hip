@@ -17,12 +17,6 @@
 #include "rtk_internal.h"
 #include "rtk_trace.h"
 
-#define RTK_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 namespace rtk {
 namespace {
 

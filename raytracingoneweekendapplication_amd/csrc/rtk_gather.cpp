@@ -1,22 +1,16 @@
 // rtk_gather.cpp -- the C-ABI half of the surface gathers (include/rtk.h "Surface gathers"): rtk_gather_rays, rtk_gather_irradiance
-// and rtk_gather_occlusion with their _host forms.  Argument checks that need no device, the batches of points the workspace
-// budget allows, the two launches per batch on the caller's stream, the staging of the blocking forms.  Stage 1 is rtk_trace.hip's
-// (rtk_gather_irradiance_kernel, rtk_gather_occlusion_kernel), the ray records and stage 2 are rtk_gather.hip's.
+// and rtk_gather_occlusion with their _host forms.  Here: the gathers' own argument checks, the batches of points the workspace
+// budget allows, the two launches per batch on the caller's stream, the pieces a _host form stages; the checks and the staging
+// every lane-per-ray family shares are rtk_internal.h's.  Stage 1 is rtk_trace.hip's (rtk_gather_irradiance_kernel,
+// rtk_gather_occlusion_kernel), the ray records and stage 2 are rtk_gather.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <initializer_list>
 #include <limits>
 
 #include "rtk.h"
 #include "rtk_internal.h"
 #include "rtk_trace.h"
-
-#define RTK_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace rtk {
 namespace {
@@ -34,8 +28,8 @@ int64_t gather_batch(const rtk_gather_opts* opts, int64_t n) {
     return std::min(n, opts->batch_points > 0 ? int64_t(opts->batch_points) : budget);
 }
 
-// What the entry points and their _host forms check before they touch a device, in the light probes' order (check_probe_args);
-// alignment, overlap and the context come afterwards.
+// What the entry points and their _host forms check before they touch a device; alignment, overlap (an output may not share an
+// address with the n points or the n normals) and the context come afterwards.
 int check_gather_args(const char* who, const rtk_gather_opts* opts, int64_t n, const void* points, const char* points_name, const void* normals,
                       const char* normals_name, const void* out, const char* out_name) {
     if (!opts) return fail(RTK_ERR_INVALID, "%s: null opts", who);
@@ -57,24 +51,10 @@ int check_gather_args(const char* who, const rtk_gather_opts* opts, int64_t n, c
     return RTK_OK;
 }
 
-// An output of `bytes` bytes may not share an address with the n points or the n normals (a null output overlaps nothing).
-int check_apart(const char* who, int64_t n, const void* points, const void* normals, const void* out, size_t bytes, const char* arg) {
-    if (!out || n == 0) return RTK_OK;
-    const uintptr_t o = reinterpret_cast<uintptr_t>(out), in_bytes = uintptr_t(n) * 3 * sizeof(double);
-    for (const void* in : {points, normals}) {
-        const uintptr_t i = reinterpret_cast<uintptr_t>(in);
-        if (!(o + bytes <= i || i + in_bytes <= o)) return fail(RTK_ERR_INVALID, "%s: %s overlaps %s", who, arg, in == points ? "d_points" : "d_normals");
-    }
-    return RTK_OK;
+int check_apart_from_inputs(const char* who, int64_t n, const double* d_points, const double* d_normals, const Span& out) {
+    const size_t in_bytes = size_t(n) * 3 * sizeof(double);
+    return check_apart(who, out, {{d_points, in_bytes, "d_points"}, {d_normals, in_bytes, "d_normals"}});
 }
-
-int check_gather_ctx(const char* who, const rtk_ctx* ctx, bool needs_scene) {
-    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    uint64_t digest = 0;
-    return !needs_scene || ctx_scene(ctx, &digest) ? RTK_OK : fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
-}
-
-int launched(const char* who, hipError_t e) { return e == hipSuccess ? RTK_OK : fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
 
 // The context's workspace for batches of `batch` points.
 hipError_t batch_workspace(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t batch, double** out) {
@@ -98,8 +78,8 @@ int rtk_gather_rays(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const 
         check_aligned(d_rays, 8, who, "d_rays") != RTK_OK)
         return RTK_ERR_INVALID;
     const int rays = gather_rays_of(opts);
-    if (check_apart(who, n, d_points, d_normals, d_rays, size_t(n) * size_t(rays) * sizeof(rtk_ray), "d_rays") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_gather_ctx(who, ctx, false);
+    if (check_apart_from_inputs(who, n, d_points, d_normals, {d_rays, size_t(n) * size_t(rays) * sizeof(rtk_ray), "d_rays"}) != RTK_OK) return RTK_ERR_INVALID;
+    const int rc = check_ctx(who, ctx, false);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     return launched(who, launch_gather_rays(n, rays, opts->samples > 0 ? opts->samples : 1, opts->first_key, uint32_t(opts->rotate), opts->time, gather_tmax(opts),
@@ -109,50 +89,47 @@ int rtk_gather_rays(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const 
 int rtk_gather_irradiance(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* d_points, const double* d_normals, void* d_irradiance) {
     const char* who = "rtk_gather_irradiance";
     if (check_gather_args(who, opts, n, d_points, "d_points", d_normals, "d_normals", d_irradiance, "d_irradiance") != RTK_OK) return RTK_ERR_INVALID;
-    const bool f64 = opts->real_mode == RTK_REAL_F64;
-    const size_t real_bytes = f64 ? sizeof(double) : sizeof(float);
+    const size_t real_bytes = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
     if (check_aligned(d_points, 8, who, "d_points") != RTK_OK || check_aligned(d_normals, 8, who, "d_normals") != RTK_OK ||
         check_aligned(d_irradiance, real_bytes, who, "d_irradiance") != RTK_OK)
         return RTK_ERR_INVALID;
-    if (check_apart(who, n, d_points, d_normals, d_irradiance, size_t(n) * 3 * real_bytes, "d_irradiance") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_gather_ctx(who, ctx, true);
+    if (check_apart_from_inputs(who, n, d_points, d_normals, {d_irradiance, size_t(n) * 3 * real_bytes, "d_irradiance"}) != RTK_OK) return RTK_ERR_INVALID;
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
-    rtk_camera cam{};  // what the kernel reads of a camera, as rtk_query_radiance: background, max_depth and the samples per ray
-    cam.background = opts->background;
-    cam.max_depth = opts->max_depth;
-    cam.samples_per_pixel = opts->samples > 0 ? opts->samples : 1;
+    const rtk_camera cam = path_camera(opts->background, opts->max_depth, opts->samples);
     const int rays = gather_rays_of(opts);
     const int64_t batch = gather_batch(opts, n);
     double* ws = nullptr;
     RTK_HIP(batch_workspace(ctx, opts, batch, &ws));
-    for (int64_t k0 = 0; k0 < n; k0 += batch) {
-        const int64_t m = std::min(batch, n - k0);
-        const double *p = d_points + k0 * 3, *nrm = d_normals + k0 * 3;
-        const uint32_t key = opts->first_key + uint32_t(k0), rot = uint32_t(opts->rotate);
-        void* out = static_cast<char*>(d_irradiance) + size_t(k0) * 3 * real_bytes;
-        hipError_t e = f64 ? launch_gather_irradiance<double>(ctx_view<double>(ctx), device_camera<double>(cam), opts->seed, key, rays, rot, opts->time, m, p, nrm, ws, st)
-                           : launch_gather_irradiance<float>(ctx_view<float>(ctx), device_camera<float>(cam), opts->seed, key, rays, rot, opts->time, m, p, nrm, ws, st);
-        if (e == hipSuccess) e = f64 ? launch_gather_irradiance_reduce<double>(m, rays, ws, out, st) : launch_gather_irradiance_reduce<float>(m, rays, ws, out, st);
-        if (e != hipSuccess) return launched(who, e);
-    }
-    return RTK_OK;
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        using R = decltype(real);
+        for (int64_t k0 = 0; k0 < n; k0 += batch) {
+            const int64_t m = std::min(batch, n - k0);
+            const double *p = d_points + k0 * 3, *nrm = d_normals + k0 * 3;
+            const uint32_t key = opts->first_key + uint32_t(k0), rot = uint32_t(opts->rotate);
+            void* out = static_cast<char*>(d_irradiance) + size_t(k0) * 3 * real_bytes;
+            hipError_t e = launch_gather_irradiance(ctx_view<R>(ctx), device_camera<R>(cam), opts->seed, key, rays, rot, opts->time, m, p, nrm, ws, st);
+            if (e == hipSuccess) e = launch_gather_irradiance_reduce<R>(m, rays, ws, out, st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }));
 }
 
 int rtk_gather_occlusion(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* d_points, const double* d_normals, void* d_open, void* d_bent) {
     const char* who = "rtk_gather_occlusion";
     if (check_gather_args(who, opts, n, d_points, "d_points", d_normals, "d_normals", d_open ? d_open : d_bent, "d_open and d_bent") != RTK_OK)
         return RTK_ERR_INVALID;
-    const bool f64 = opts->real_mode == RTK_REAL_F64;
-    const size_t real_bytes = f64 ? sizeof(double) : sizeof(float);
+    const size_t real_bytes = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
     if (check_aligned(d_points, 8, who, "d_points") != RTK_OK || check_aligned(d_normals, 8, who, "d_normals") != RTK_OK ||
         check_aligned(d_open, real_bytes, who, "d_open") != RTK_OK || check_aligned(d_bent, real_bytes, who, "d_bent") != RTK_OK)
         return RTK_ERR_INVALID;
-    if (check_apart(who, n, d_points, d_normals, d_open, size_t(n) * real_bytes, "d_open") != RTK_OK ||
-        check_apart(who, n, d_points, d_normals, d_bent, size_t(n) * 3 * real_bytes, "d_bent") != RTK_OK)
+    if (check_apart_from_inputs(who, n, d_points, d_normals, {d_open, size_t(n) * real_bytes, "d_open"}) != RTK_OK ||
+        check_apart_from_inputs(who, n, d_points, d_normals, {d_bent, size_t(n) * 3 * real_bytes, "d_bent"}) != RTK_OK)
         return RTK_ERR_INVALID;
-    const int rc = check_gather_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
@@ -162,55 +139,45 @@ int rtk_gather_occlusion(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, c
     const int64_t batch = gather_batch(opts, n);
     double* ws = nullptr;
     RTK_HIP(batch_workspace(ctx, opts, batch, &ws));
-    for (int64_t k0 = 0; k0 < n; k0 += batch) {
-        const int64_t m = std::min(batch, n - k0);
-        const double *p = d_points + k0 * 3, *nrm = d_normals + k0 * 3;
-        const uint32_t key = opts->first_key + uint32_t(k0), rot = uint32_t(opts->rotate);
-        void* open = d_open ? static_cast<char*>(d_open) + size_t(k0) * real_bytes : nullptr;
-        void* bent = d_bent ? static_cast<char*>(d_bent) + size_t(k0) * 3 * real_bytes : nullptr;
-        hipError_t e = f64 ? launch_gather_occlusion<double>(ctx_view<double>(ctx), opts->seed, any_hit, key, rays, samples, rot, opts->time, tmax, m, p, nrm, ws, st)
-                           : launch_gather_occlusion<float>(ctx_view<float>(ctx), opts->seed, any_hit, key, rays, samples, rot, opts->time, tmax, m, p, nrm, ws, st);
-        if (e == hipSuccess) e = f64 ? launch_gather_occlusion_reduce<double>(m, rays, ws, open, bent, st) : launch_gather_occlusion_reduce<float>(m, rays, ws, open, bent, st);
-        if (e != hipSuccess) return launched(who, e);
-    }
-    return RTK_OK;
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        using R = decltype(real);
+        for (int64_t k0 = 0; k0 < n; k0 += batch) {
+            const int64_t m = std::min(batch, n - k0);
+            const double *p = d_points + k0 * 3, *nrm = d_normals + k0 * 3;
+            const uint32_t key = opts->first_key + uint32_t(k0), rot = uint32_t(opts->rotate);
+            void* open = d_open ? static_cast<char*>(d_open) + size_t(k0) * real_bytes : nullptr;
+            void* bent = d_bent ? static_cast<char*>(d_bent) + size_t(k0) * 3 * real_bytes : nullptr;
+            hipError_t e = launch_gather_occlusion(ctx_view<R>(ctx), opts->seed, any_hit, key, rays, samples, rot, opts->time, tmax, m, p, nrm, ws, st);
+            if (e == hipSuccess) e = launch_gather_occlusion_reduce<R>(m, rays, ws, open, bent, st);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }));
 }
 
 int rtk_gather_rays_host(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* h_points, const double* h_normals, rtk_ray* h_rays) {
     const char* who = "rtk_gather_rays_host";
     if (check_gather_args(who, opts, n, h_points, "h_points", h_normals, "h_normals", h_rays, "h_rays") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_gather_ctx(who, ctx, false);
+    const int rc = check_ctx(who, ctx, false);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(true);
     const int pts = s.piece(size_t(n) * 3 * sizeof(double)), nrm = s.piece(size_t(n) * 3 * sizeof(double));
     const int rays = s.piece(size_t(n) * size_t(gather_rays_of(opts)) * sizeof(rtk_ray));
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(pts, h_points));
-    RTK_HIP(s.upload(nrm, h_normals));
-    const int q = rtk_gather_rays(ctx, opts, n, s.ptr<double>(pts), s.ptr<double>(nrm), s.ptr<rtk_ray>(rays));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download(rays, h_rays);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{pts, h_points}, {nrm, h_normals}},
+                         [&] { return rtk_gather_rays(ctx, opts, n, s.ptr<double>(pts), s.ptr<double>(nrm), s.ptr<rtk_ray>(rays)); }, {{rays, h_rays}});
 }
 
 int rtk_gather_irradiance_host(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* h_points, const double* h_normals, double* h_irradiance) {
     const char* who = "rtk_gather_irradiance_host";
     if (check_gather_args(who, opts, n, h_points, "h_points", h_normals, "h_normals", h_irradiance, "h_irradiance") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_gather_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(opts->real_mode == RTK_REAL_F64);
     const int pts = s.piece(size_t(n) * 3 * sizeof(double)), nrm = s.piece(size_t(n) * 3 * sizeof(double)), out = s.linear(size_t(n) * 3);
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(pts, h_points));
-    RTK_HIP(s.upload(nrm, h_normals));
-    const int q = rtk_gather_irradiance(ctx, opts, n, s.ptr<double>(pts), s.ptr<double>(nrm), s.ptr<void>(out));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download_linear(out, h_irradiance);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{pts, h_points}, {nrm, h_normals}},
+                         [&] { return rtk_gather_irradiance(ctx, opts, n, s.ptr<double>(pts), s.ptr<double>(nrm), s.ptr<void>(out)); }, {{out, h_irradiance, true}});
 }
 
 int rtk_gather_occlusion_host(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t n, const double* h_points, const double* h_normals, double* h_open,
@@ -218,21 +185,15 @@ int rtk_gather_occlusion_host(rtk_ctx* ctx, const rtk_gather_opts* opts, int64_t
     const char* who = "rtk_gather_occlusion_host";
     if (check_gather_args(who, opts, n, h_points, "h_points", h_normals, "h_normals", h_open ? h_open : h_bent, "h_open and h_bent") != RTK_OK)
         return RTK_ERR_INVALID;
-    const int rc = check_gather_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(opts->real_mode == RTK_REAL_F64);
     const int pts = s.piece(size_t(n) * 3 * sizeof(double)), nrm = s.piece(size_t(n) * 3 * sizeof(double));
     const int open = s.linear(size_t(n), h_open != nullptr), bent = s.linear(size_t(n) * 3, h_bent != nullptr);
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(pts, h_points));
-    RTK_HIP(s.upload(nrm, h_normals));
-    const int q = rtk_gather_occlusion(ctx, opts, n, s.ptr<double>(pts), s.ptr<double>(nrm), s.ptr<void>(open), s.ptr<void>(bent));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download_linear(open, h_open);
-    if (e == hipSuccess) e = s.download_linear(bent, h_bent);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{pts, h_points}, {nrm, h_normals}},
+                         [&] { return rtk_gather_occlusion(ctx, opts, n, s.ptr<double>(pts), s.ptr<double>(nrm), s.ptr<void>(open), s.ptr<void>(bent)); },
+                         {{open, h_open, true}, {bent, h_bent, true}});
 }
 
 }  // extern "C"

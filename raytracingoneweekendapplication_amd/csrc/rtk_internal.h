@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -16,6 +17,16 @@ namespace rtk {
 
 extern thread_local std::string g_error;            // text behind rtk_last_error()
 int fail(int code, const char* fmt, ...);           // records the text, returns `code`
+
+// A HIP runtime call inside an entry point: on failure the entry point returns RTK_ERR_HIP, the text naming the call.
+#define RTK_HIP(call)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e_ = (call);                                                                           \
+        if (e_ != hipSuccess) return ::rtk::fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+// What an entry point returns for the HIP result of its launches, its stream wait and its copies: the text names the entry point.
+inline int launched(const char* who, hipError_t e) { return e == hipSuccess ? RTK_OK : fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
 
 // FNV-1a 64 over byte ranges: the scene digest of progressive sessions and the checksum of their checkpoints.
 struct Fnv64 {
@@ -61,10 +72,45 @@ inline int check_real_mode(const char* who, int mode) {
     return mode == RTK_REAL_F64 || mode == RTK_REAL_F32 ? RTK_OK : fail(RTK_ERR_INVALID, "%s: unknown real_mode %d", who, mode);
 }
 
+// f(real{}) for the arithmetic type asked for at run time: a lane-per-ray entry point writes its launch once, as a generic lambda
+// over the tag (rtk_image_pass.h's with_real_demod is the image passes' form, with the demodulation as a second tag).
+template <typename F>
+auto with_real(int real_mode, F&& f) {
+    return real_mode == RTK_REAL_F64 ? f(double{}) : f(float{});
+}
+
+// What a path kernel that is given its rays reads of a camera: ray_color's background, max_depth and the samples per ray.
+inline rtk_camera path_camera(const rtk_vec3& background, int max_depth, int samples) {
+    rtk_camera cam{};
+    cam.background = background;
+    cam.max_depth = max_depth;
+    cam.samples_per_pixel = samples > 0 ? samples : 1;
+    return cam;
+}
+
+// include/rtk.h: an output may not alias an input.  RTK_OK, or RTK_ERR_INVALID naming the output and the first of `inputs` it
+// shares an address with.  A null output overlaps nothing, and neither do arrays of no bytes (n == 0).
+struct Span {
+    const void* p;
+    size_t bytes;
+    const char* name;
+};
+inline int check_apart(const char* who, const Span& out, std::initializer_list<Span> inputs) {
+    if (!out.p) return RTK_OK;
+    const uintptr_t o = reinterpret_cast<uintptr_t>(out.p);
+    for (const Span& in : inputs) {
+        const uintptr_t i = reinterpret_cast<uintptr_t>(in.p);
+        if (!(o + out.bytes <= i || i + in.bytes <= o)) return fail(RTK_ERR_INVALID, "%s: %s overlaps %s", who, out.name, in.name);
+    }
+    return RTK_OK;
+}
+
 // The device side of a *_host entry point: one allocation cut into pieces, each on a 16-byte boundary (guides, AOVs and every
-// 16-byte access need it), freed when the object goes out of scope.  Plan the pieces, alloc(), upload, call the asynchronous
-// entry point with ptr() of each piece, synchronise its stream, download.  A piece planned with wanted = false (an optional
-// output the caller passed as null) takes no memory and has a null ptr(); a download into a null host pointer does nothing.
+// 16-byte access need it), freed when the object goes out of scope.  The entry point plans the pieces; then alloc(), the uploads,
+// the asynchronous entry point called with ptr() of each piece, its stream synchronised, the downloads -- the sequence
+// run_host_form (below) performs for the lane-per-ray families and the image passes still write out.  A piece planned with
+// wanted = false (an optional output the caller passed as null) takes no memory and has a null ptr(); a download into a null
+// host pointer does nothing.
 // "Linear" pieces hold `real`s (double or float, by f64) that the host sees as doubles.
 class HostStaging {
 public:
@@ -112,9 +158,43 @@ private:
     std::vector<float> tmp_;   // the float image between the host's doubles and an F32 piece
 };
 
+// A *_host entry point after its checks, hipSetDevice and the plan of `s`: alloc, the inputs up, `call` (the device form on the
+// staged pieces; RTK_OK or its own refusal, which is returned as it is), `stream` synchronised, the outputs down.  The first
+// HIP error ends it and is the result (RTK_ERR_HIP, the text naming `who`).  A linear array is doubles on the host.
+struct HostIn {
+    int piece;
+    const void* host;
+    bool linear = false;
+};
+struct HostOut {
+    int piece;
+    void* host;
+    bool linear = false;
+};
+template <typename Call>
+int run_host_form(const char* who, hipStream_t stream, HostStaging& s, std::initializer_list<HostIn> inputs, Call&& call, std::initializer_list<HostOut> outputs) {
+    hipError_t e = s.alloc();
+    for (const HostIn& in : inputs)
+        if (e == hipSuccess) e = in.linear ? s.upload_linear(in.piece, static_cast<const double*>(in.host)) : s.upload(in.piece, in.host);
+    if (e != hipSuccess) return launched(who, e);
+    const int rc = call();
+    if (rc != RTK_OK) return rc;
+    e = hipStreamSynchronize(stream);
+    for (const HostOut& out : outputs)
+        if (e == hipSuccess) e = out.linear ? s.download_linear(out.piece, static_cast<double*>(out.host)) : s.download(out.piece, out.host);
+    return launched(who, e);
+}
+
 int ctx_device(const rtk_ctx* ctx);
 // Progressive sessions (rtk_progressive.cpp) -- what they use of a context and of the one-shot frame's rules:
 int ctx_scene(const rtk_ctx* ctx, uint64_t* digest);  // 1 when a scene is uploaded; *digest = its digest
+// The last refusal of a lane-per-ray entry point, after every check that needs no device: the context, then its scene where
+// the entry point reads one.
+inline int check_ctx(const char* who, const rtk_ctx* ctx, bool needs_scene) {
+    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
+    uint64_t digest = 0;
+    return !needs_scene || ctx_scene(ctx, &digest) ? RTK_OK : fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
+}
 uint32_t ctx_features(const rtk_ctx* ctx);            // Feature bits of the uploaded scene (F_MEDIA: rtk_query_occluded's early exit)
 int32_t ctx_n_materials(const rtk_ctx* ctx);          // table sizes of the uploaded description (index checks of rtk_debug_scatter
 int32_t ctx_n_textures(const rtk_ctx* ctx);           // and rtk_debug_texture)

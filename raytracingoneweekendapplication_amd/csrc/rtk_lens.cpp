@@ -1,7 +1,8 @@
 // rtk_lens.cpp -- the C-ABI half of the lens models (include/rtk.h "Lens models"): rtk_lens_look_at, rtk_lens_rays / _render /
-// _aovs / _guides and their _host forms.  Argument checks that need no device, the launches on the caller's stream, the staging
-// of the blocking forms.  The kernels are rtk_trace.hip's (rtk_lens_rays_kernel, rtk_lens_render_kernel and rtk_guide_kernel
-// with the lens generator), next to the radiance query whose path loop they run.
+// _aovs / _guides and their _host forms.  Here: the lens's own argument checks, one launch each on the caller's stream, the
+// pieces a _host form stages; the checks and the staging every lane-per-ray family shares are rtk_internal.h's.  The kernels
+// are rtk_trace.hip's (rtk_lens_rays_kernel, rtk_lens_render_kernel and rtk_guide_kernel with the lens generator), next to the
+// radiance query whose path loop they run.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,12 +10,6 @@
 #include "rtk.h"
 #include "rtk_internal.h"
 #include "rtk_trace.h"
-
-#define RTK_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace rtk {
 namespace {
@@ -25,9 +20,9 @@ constexpr double kPi = 3.14159265358979323846, kTwoPi = 2.0 * kPi;
 
 bool finite3(const rtk_vec3& v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); }
 
-// What every entry point checks of the lens and opts before it touches a device, the ray queries' way: null arguments, then the
-// lens, then opts, then the sample range.  n_samples = the samples per pixel the call makes (min_samples = the fewest it accepts).
-// The context comes afterwards (check_lens_ctx).
+// What every entry point checks of the lens and opts before it touches a device: null arguments, then the lens, then opts, then
+// the sample range.  n_samples = the samples per pixel the call makes (min_samples = the fewest it accepts).  Alignment and the
+// context come afterwards.
 int check_lens_args(const char* who, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, int64_t n_samples, int min_samples,
                     const char* samples_name, const void* out, const char* out_name) {
     if (!lens) return fail(RTK_ERR_INVALID, "%s: null lens", who);
@@ -66,12 +61,6 @@ int check_lens_args(const char* who, const rtk_lens* lens, const rtk_render_opts
     return RTK_OK;
 }
 
-int check_lens_ctx(const char* who, const rtk_ctx* ctx, bool needs_scene) {
-    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    uint64_t digest = 0;
-    return !needs_scene || ctx_scene(ctx, &digest) ? RTK_OK : fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
-}
-
 // What the kernels read of the lens besides its camera: the halves of the extents, defaults resolved (rtk_trace.h).
 LensRec lens_record(const rtk_lens& l) {
     LensRec r{};
@@ -92,8 +81,6 @@ LensRec lens_record(const rtk_lens& l) {
     }
     return r;
 }
-
-int launched(const char* who, hipError_t e) { return e == hipSuccess ? RTK_OK : fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
 
 // vec3.h's operations in their order (host/rtk_math.h): length_squared (x x + y y) + z z, unit_vector = (1 / length) * v.
 rtk_vec3 sub(rtk_vec3 a, rtk_vec3 b) { return rtk_vec3{a.x - b.x, a.y - b.y, a.z - b.z}; }
@@ -123,14 +110,14 @@ int rtk_lens_rays(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opt
     const char* who = "rtk_lens_rays";
     if (check_lens_args(who, lens, opts, first_sample, n_samples, 0, "n_samples", d_rays, "d_rays") != RTK_OK) return RTK_ERR_INVALID;
     if (check_aligned(d_rays, 8, who, "d_rays") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_lens_ctx(who, ctx, false);
+    const int rc = check_ctx(who, ctx, false);
     if (rc != RTK_OK || n_samples == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
     const LensRec rec = lens_record(*lens);
-    return launched(who, opts->real_mode == RTK_REAL_F64
-                             ? launch_lens_rays<double>(rec, device_camera<double>(lens->cam), opts->seed, uint32_t(first_sample), n_samples, d_rays, st)
-                             : launch_lens_rays<float>(rec, device_camera<float>(lens->cam), opts->seed, uint32_t(first_sample), n_samples, d_rays, st));
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        return launch_lens_rays(rec, device_camera<decltype(real)>(lens->cam), opts->seed, uint32_t(first_sample), n_samples, d_rays, st);
+    }));
 }
 
 int rtk_lens_render(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, void* d_linear, float* d_noise) {
@@ -139,28 +126,30 @@ int rtk_lens_render(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* o
         return RTK_ERR_INVALID;
     const size_t real_bytes = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
     if (check_aligned(d_linear, real_bytes, who, "d_linear") != RTK_OK || check_aligned(d_noise, 4, who, "d_noise") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_lens_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
     const LensRec rec = lens_record(*lens);
-    return launched(who, opts->real_mode == RTK_REAL_F64
-                             ? launch_lens_render<double>(ctx_view<double>(ctx), rec, device_camera<double>(lens->cam), opts->seed, uint32_t(first_sample), d_linear, d_noise, st)
-                             : launch_lens_render<float>(ctx_view<float>(ctx), rec, device_camera<float>(lens->cam), opts->seed, uint32_t(first_sample), d_linear, d_noise, st));
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        using R = decltype(real);
+        return launch_lens_render(ctx_view<R>(ctx), rec, device_camera<R>(lens->cam), opts->seed, uint32_t(first_sample), d_linear, d_noise, st);
+    }));
 }
 
 int rtk_lens_aovs(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, float* d_aov) {
     const char* who = "rtk_lens_aovs";
     if (check_lens_args(who, lens, opts, 0, n_samples, 1, "n_samples", d_aov, "d_aov") != RTK_OK) return RTK_ERR_INVALID;
     if (check_aligned16(d_aov, who, "d_aov") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_lens_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
     const LensRec rec = lens_record(*lens);
-    return launched(who, opts->real_mode == RTK_REAL_F64
-                             ? launch_lens_aov<double>(ctx_view<double>(ctx), rec, device_camera<double>(lens->cam), opts->seed, n_samples, d_aov, st)
-                             : launch_lens_aov<float>(ctx_view<float>(ctx), rec, device_camera<float>(lens->cam), opts->seed, n_samples, d_aov, st));
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        using R = decltype(real);
+        return launch_lens_aov(ctx_view<R>(ctx), rec, device_camera<R>(lens->cam), opts->seed, n_samples, d_aov, st);
+    }));
 }
 
 int rtk_lens_guides(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* d_guides) {
@@ -170,65 +159,54 @@ int rtk_lens_guides(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* o
     if (check_lens_args(who, lens, opts, 0, n_samples, 1, "n_samples", d_guides, "d_guides") != RTK_OK) return RTK_ERR_INVALID;
     if (n_samples > (1 << 20)) return fail(RTK_ERR_INVALID, "%s: n_samples must be 1 .. 2^20 (%d)", who, n_samples);
     if (check_aligned16(d_guides, who, "d_guides") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_lens_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
     const LensRec rec = lens_record(*lens);
-    return launched(who, opts->real_mode == RTK_REAL_F64
-                             ? launch_lens_guides<double>(ctx_view<double>(ctx), rec, device_camera<double>(lens->cam), opts->seed, n_samples, follow, max_bounces, d_guides, st)
-                             : launch_lens_guides<float>(ctx_view<float>(ctx), rec, device_camera<float>(lens->cam), opts->seed, n_samples, follow, max_bounces, d_guides, st));
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        using R = decltype(real);
+        return launch_lens_guides(ctx_view<R>(ctx), rec, device_camera<R>(lens->cam), opts->seed, n_samples, follow, max_bounces, d_guides, st);
+    }));
 }
 
 int rtk_lens_rays_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, int32_t n_samples, rtk_ray* h_rays) {
     const char* who = "rtk_lens_rays_host";
     if (check_lens_args(who, lens, opts, first_sample, n_samples, 0, "n_samples", h_rays, "h_rays") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_lens_ctx(who, ctx, false);
+    const int rc = check_ctx(who, ctx, false);
     if (rc != RTK_OK || n_samples == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(true);
     const int rays = s.piece(size_t(lens->cam.image_width) * lens->cam.image_height * n_samples * sizeof(rtk_ray));
-    RTK_HIP(s.alloc());
-    const int q = rtk_lens_rays(ctx, lens, opts, first_sample, n_samples, s.ptr<rtk_ray>(rays));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download(rays, h_rays);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {},
+                         [&] { return rtk_lens_rays(ctx, lens, opts, first_sample, n_samples, s.ptr<rtk_ray>(rays)); }, {{rays, h_rays}});
 }
 
 int rtk_lens_render_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t first_sample, double* h_linear, float* h_noise) {
     const char* who = "rtk_lens_render_host";
     if (check_lens_args(who, lens, opts, first_sample, lens ? lens->cam.samples_per_pixel : 0, 1, "cam.samples_per_pixel", h_linear, "h_linear") != RTK_OK)
         return RTK_ERR_INVALID;
-    const int rc = check_lens_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(opts->real_mode == RTK_REAL_F64);
     const size_t px = size_t(lens->cam.image_width) * lens->cam.image_height;
     const int linear = s.linear(px * 3), noise = s.piece(px * sizeof(float), h_noise != nullptr);
-    RTK_HIP(s.alloc());
-    const int q = rtk_lens_render(ctx, lens, opts, first_sample, s.ptr<void>(linear), s.ptr<float>(noise));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download_linear(linear, h_linear);
-    if (e == hipSuccess) e = s.download(noise, h_noise);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {},
+                         [&] { return rtk_lens_render(ctx, lens, opts, first_sample, s.ptr<void>(linear), s.ptr<float>(noise)); },
+                         {{linear, h_linear, true}, {noise, h_noise}});
 }
 
 int rtk_lens_aovs_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, float* h_aov) {
     const char* who = "rtk_lens_aovs_host";
     if (check_lens_args(who, lens, opts, 0, n_samples, 1, "n_samples", h_aov, "h_aov") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_lens_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(true);
     const int aov = s.piece(size_t(lens->cam.image_width) * lens->cam.image_height * 8 * sizeof(float));
-    RTK_HIP(s.alloc());
-    const int q = rtk_lens_aovs(ctx, lens, opts, n_samples, s.ptr<float>(aov));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download(aov, h_aov);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {}, [&] { return rtk_lens_aovs(ctx, lens, opts, n_samples, s.ptr<float>(aov)); },
+                         {{aov, h_aov}});
 }
 
 int rtk_lens_guides_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_opts* opts, int32_t n_samples, const rtk_guide_opts* gopts, float* h_guides) {
@@ -237,17 +215,13 @@ int rtk_lens_guides_host(rtk_ctx* ctx, const rtk_lens* lens, const rtk_render_op
     if (resolve_guide_opts(gopts, &follow, &max_bounces, who) != RTK_OK) return RTK_ERR_INVALID;
     if (check_lens_args(who, lens, opts, 0, n_samples, 1, "n_samples", h_guides, "h_guides") != RTK_OK) return RTK_ERR_INVALID;
     if (n_samples > (1 << 20)) return fail(RTK_ERR_INVALID, "%s: n_samples must be 1 .. 2^20 (%d)", who, n_samples);
-    const int rc = check_lens_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(true);
     const int guides = s.piece(size_t(lens->cam.image_width) * lens->cam.image_height * 16 * sizeof(float));
-    RTK_HIP(s.alloc());
-    const int q = rtk_lens_guides(ctx, lens, opts, n_samples, gopts, s.ptr<float>(guides));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download(guides, h_guides);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {},
+                         [&] { return rtk_lens_guides(ctx, lens, opts, n_samples, gopts, s.ptr<float>(guides)); }, {{guides, h_guides}});
 }
 
 }  // extern "C"

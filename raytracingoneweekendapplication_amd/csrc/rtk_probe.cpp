@@ -1,18 +1,13 @@
 // rtk_probe.cpp -- the C-ABI half of the light probes' ray side (include/rtk.h "Light probes"): rtk_probe_rays and
-// rtk_probe_bake with their _host forms.  Argument checks that need no device, the launches on the caller's stream, the staging
-// of the blocking forms.  The kernels are rtk_trace.hip's (rtk_probe_rays_kernel, rtk_probe_bake_kernel), next to the radiance
-// query whose path loop they run; the lookup (rtk_probe_irradiance) is rtk_probe.hip.
+// rtk_probe_bake with their _host forms.  Here: the probes' own argument checks, one launch each on the caller's stream, the
+// pieces a _host form stages; the checks and the staging every lane-per-ray family shares are rtk_internal.h's.  The kernels
+// are rtk_trace.hip's (rtk_probe_rays_kernel, rtk_probe_bake_kernel), next to the radiance query whose path loop they run; the
+// lookup (rtk_probe_irradiance) is rtk_probe.hip.
 #include <hip/hip_runtime.h>
 
 #include "rtk.h"
 #include "rtk_internal.h"
 #include "rtk_trace.h"
-
-#define RTK_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace rtk {
 namespace {
@@ -21,8 +16,7 @@ static_assert(sizeof(rtk_probe_opts) == 72 && sizeof(rtk_probe_grid) == 64, "lig
 
 int probe_rays_of(const rtk_probe_opts* opts) { return opts->rays != 0 ? opts->rays : 1024; }
 
-// What both entry points and their _host forms check before they touch a device, in the ray queries' order (check_query_args);
-// the context comes afterwards.
+// What both entry points and their _host forms check before they touch a device; alignment and the context come afterwards.
 int check_probe_args(const char* who, const rtk_probe_opts* opts, int64_t n, const void* positions, const char* positions_name, const void* out,
                      const char* out_name) {
     if (!opts) return fail(RTK_ERR_INVALID, "%s: null opts", who);
@@ -39,14 +33,6 @@ int check_probe_args(const char* who, const rtk_probe_opts* opts, int64_t n, con
     return RTK_OK;
 }
 
-int check_probe_ctx(const char* who, const rtk_ctx* ctx, bool needs_scene) {
-    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    uint64_t digest = 0;
-    return !needs_scene || ctx_scene(ctx, &digest) ? RTK_OK : fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
-}
-
-int launched(const char* who, hipError_t e) { return e == hipSuccess ? RTK_OK : fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
-
 }  // namespace
 }  // namespace rtk
 
@@ -58,7 +44,7 @@ int rtk_probe_rays(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const do
     const char* who = "rtk_probe_rays";
     if (check_probe_args(who, opts, n, d_positions, "d_positions", d_rays, "d_rays") != RTK_OK) return RTK_ERR_INVALID;
     if (check_aligned(d_positions, 8, who, "d_positions") != RTK_OK || check_aligned(d_rays, 8, who, "d_rays") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_probe_ctx(who, ctx, false);
+    const int rc = check_ctx(who, ctx, false);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     return launched(who, launch_probe_rays(n, probe_rays_of(opts), opts->samples > 0 ? opts->samples : 1, opts->first_key, opts->time, d_positions, d_rays,
@@ -70,52 +56,40 @@ int rtk_probe_bake(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const do
     if (check_probe_args(who, opts, n, d_positions, "d_positions", d_sh, "d_sh") != RTK_OK) return RTK_ERR_INVALID;
     const size_t real_bytes = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
     if (check_aligned(d_positions, 8, who, "d_positions") != RTK_OK || check_aligned(d_sh, real_bytes, who, "d_sh") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_probe_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
-    rtk_camera cam{};  // what the kernel reads of a camera, as rtk_query_radiance: background, max_depth and the samples per ray
-    cam.background = opts->background;
-    cam.max_depth = opts->max_depth;
-    cam.samples_per_pixel = opts->samples > 0 ? opts->samples : 1;
+    const rtk_camera cam = path_camera(opts->background, opts->max_depth, opts->samples);
     const int rays = probe_rays_of(opts);
-    return launched(who, opts->real_mode == RTK_REAL_F64
-                             ? launch_probe_bake<double>(ctx_view<double>(ctx), device_camera<double>(cam), opts->seed, opts->first_key, rays, opts->time, n, d_positions, d_sh, st)
-                             : launch_probe_bake<float>(ctx_view<float>(ctx), device_camera<float>(cam), opts->seed, opts->first_key, rays, opts->time, n, d_positions, d_sh, st));
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        using R = decltype(real);
+        return launch_probe_bake(ctx_view<R>(ctx), device_camera<R>(cam), opts->seed, opts->first_key, rays, opts->time, n, d_positions, d_sh, st);
+    }));
 }
 
 int rtk_probe_rays_host(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const double* h_positions, rtk_ray* h_rays) {
     const char* who = "rtk_probe_rays_host";
     if (check_probe_args(who, opts, n, h_positions, "h_positions", h_rays, "h_rays") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_probe_ctx(who, ctx, false);
+    const int rc = check_ctx(who, ctx, false);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(true);
     const int pos = s.piece(size_t(n) * 3 * sizeof(double)), rays = s.piece(size_t(n) * size_t(probe_rays_of(opts)) * sizeof(rtk_ray));
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(pos, h_positions));
-    const int q = rtk_probe_rays(ctx, opts, n, s.ptr<double>(pos), s.ptr<rtk_ray>(rays));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download(rays, h_rays);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{pos, h_positions}},
+                         [&] { return rtk_probe_rays(ctx, opts, n, s.ptr<double>(pos), s.ptr<rtk_ray>(rays)); }, {{rays, h_rays}});
 }
 
 int rtk_probe_bake_host(rtk_ctx* ctx, const rtk_probe_opts* opts, int64_t n, const double* h_positions, double* h_sh) {
     const char* who = "rtk_probe_bake_host";
     if (check_probe_args(who, opts, n, h_positions, "h_positions", h_sh, "h_sh") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_probe_ctx(who, ctx, true);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(opts->real_mode == RTK_REAL_F64);
     const int pos = s.piece(size_t(n) * 3 * sizeof(double)), sh = s.linear(size_t(n) * 3 * RTK_PROBE_COEFFS);
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(pos, h_positions));
-    const int q = rtk_probe_bake(ctx, opts, n, s.ptr<double>(pos), s.ptr<void>(sh));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download_linear(sh, h_sh);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{pos, h_positions}},
+                         [&] { return rtk_probe_bake(ctx, opts, n, s.ptr<double>(pos), s.ptr<void>(sh)); }, {{sh, h_sh, true}});
 }
 
 }  // extern "C"

@@ -126,16 +126,14 @@ int rtk_probe_irradiance(rtk_ctx* ctx, int real_mode, const rtk_probe_grid* grid
     if (check_aligned(d_sh, real_bytes, who, "d_sh") != RTK_OK || check_aligned(d_points, real_bytes, who, "d_points") != RTK_OK ||
         check_aligned(d_normals, real_bytes, who, "d_normals") != RTK_OK || check_aligned(d_irradiance, real_bytes, who, "d_irradiance") != RTK_OK)
         return RTK_ERR_INVALID;
-    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    if (m == 0) return RTK_OK;
+    const int rc = check_ctx(who, ctx, false);
+    if (rc != RTK_OK || m == 0) return rc;
     hipError_t e = hipSetDevice(ctx_device(ctx));
     if (e == hipSuccess) {
         const hipStream_t st = static_cast<hipStream_t>(stream);
-        e = real_mode == RTK_REAL_F64 ? launch_probe_irradiance<double>(*grid, d_sh, m, d_points, d_normals, d_irradiance, st)
-                                      : launch_probe_irradiance<float>(*grid, d_sh, m, d_points, d_normals, d_irradiance, st);
+        e = with_real(real_mode, [&](auto real) { return launch_probe_irradiance<decltype(real)>(*grid, d_sh, m, d_points, d_normals, d_irradiance, st); });
     }
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return RTK_OK;
+    return launched(who, e);
 }
 
 int rtk_probe_irradiance_host(rtk_ctx* ctx, int real_mode, const rtk_probe_grid* grid, const double* h_sh, int64_t m, const double* h_points,
@@ -143,24 +141,16 @@ int rtk_probe_irradiance_host(rtk_ctx* ctx, int real_mode, const rtk_probe_grid*
     const char* who = "rtk_probe_irradiance_host";
     int rc = check_irradiance_args(who, real_mode, grid, h_sh, "h_sh", m, h_points, "h_points", h_normals, "h_normals", h_irradiance, "h_irradiance");
     if (rc != RTK_OK) return rc;
-    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    if (m == 0) return RTK_OK;
-    hipError_t e = hipSetDevice(ctx_device(ctx));
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    rc = check_ctx(who, ctx, false);
+    if (rc != RTK_OK || m == 0) return rc;
+    rc = launched(who, hipSetDevice(ctx_device(ctx)));
+    if (rc != RTK_OK) return rc;
     const size_t probes = size_t(grid->counts[0]) * grid->counts[1] * grid->counts[2];
     HostStaging s(real_mode == RTK_REAL_F64);
     const int sh = s.linear(probes * 3 * RTK_PROBE_COEFFS), points = s.linear(size_t(m) * 3), normals = s.linear(size_t(m) * 3), out = s.linear(size_t(m) * 3);
-    e = s.alloc();
-    if (e == hipSuccess) e = s.upload_linear(sh, h_sh);
-    if (e == hipSuccess) e = s.upload_linear(points, h_points);
-    if (e == hipSuccess) e = s.upload_linear(normals, h_normals);
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    rc = rtk_probe_irradiance(ctx, real_mode, grid, s.ptr(sh), m, s.ptr(points), s.ptr(normals), s.ptr(out), nullptr);
-    if (rc != RTK_OK) return rc;
-    e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess) e = s.download_linear(out, h_irradiance);
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return RTK_OK;
+    return run_host_form(who, nullptr, s, {{sh, h_sh, true}, {points, h_points, true}, {normals, h_normals, true}},
+                         [&] { return rtk_probe_irradiance(ctx, real_mode, grid, s.ptr(sh), m, s.ptr(points), s.ptr(normals), s.ptr(out), nullptr); },
+                         {{out, h_irradiance, true}});
 }
 
 }  // extern "C"

@@ -19,12 +19,6 @@
 
 using namespace rtk;
 
-#define RTK_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 struct rtk_progressive {
     rtk_ctx* ctx = nullptr;
     rtk_camera cam{};
@@ -671,8 +665,7 @@ static int progressive_denoise_host(const char* who, bool guided, rtk_progressiv
     }
     if (e == hipSuccess) e = s.download_linear(lin, h_linear);
     if (e == hipSuccess) e = s.download(rgb8, h_rgb8);
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return RTK_OK;
+    return launched(who, e);
 }
 
 int rtk_progressive_denoise(rtk_progressive* p, int32_t aov_samples, const rtk_denoise_opts* opts, void* d_out_linear, uint8_t* d_out_rgb8) {

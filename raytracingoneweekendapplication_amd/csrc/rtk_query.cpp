@@ -1,37 +1,22 @@
-// rtk_query.cpp -- the C-ABI half of every lane-per-ray entry point.  The ray queries (include/rtk.h "Ray queries"): argument
-// checks that need no device, the launches on the caller's stream, and the blocking _host forms.  The known-answer entry
-// points (rtk_debug_*): host arrays in and out, on the null stream.  The kernels are rtk_trace.hip's, next to the device
-// functions they share with the render, AOV and guide kernels.
+// rtk_query.cpp -- the C-ABI half of the ray queries (include/rtk.h "Ray queries") and of the known-answer entry points
+// (rtk_debug_*).  Here: the queries' own argument checks, one launch each on the caller's stream, the pieces a _host form
+// stages.  What every lane-per-ray family shares -- the alignment, overlap and context checks, with_real, run_host_form -- is
+// rtk_internal.h's.  The known-answer entry points take host arrays in and out, on the null stream.  The kernels are
+// rtk_trace.hip's, next to the device functions they share with the render, AOV and guide kernels.
 #include <hip/hip_runtime.h>
-
-#include <initializer_list>
-#include <utility>
 
 #include "rtk.h"
 #include "rtk_internal.h"
 #include "rtk_trace.h"
-
-#define RTK_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace rtk {
 namespace {
 
 static_assert(sizeof(rtk_ray) == 88 && sizeof(rtk_ray_hit) == 96 && sizeof(rtk_query_opts) == 56, "ray query records");
 
-// include/rtk.h: outputs may not alias d_rays.  RTK_OK, or RTK_ERR_INVALID naming the output whose n elements of `bytes` each
-// share an address with the n ray records (a null output overlaps nothing).
-int check_apart(const void* rays, const void* out, int64_t n, size_t bytes, const char* who, const char* arg) {
-    const uintptr_t r = reinterpret_cast<uintptr_t>(rays), o = reinterpret_cast<uintptr_t>(out);
-    const bool apart = !out || n == 0 || o + uintptr_t(n) * bytes <= r || r + uintptr_t(n) * sizeof(rtk_ray) <= o;
-    return apart ? RTK_OK : fail(RTK_ERR_INVALID, "%s: %s overlaps d_rays", who, arg);
-}
-
-// What every query checks before it touches a device: the arguments the three have in common.  The context comes last, so
-// that every other refusal can be had -- and tested -- where there is no device to make a context on.
+// What every query checks before it touches a device: the arguments the three have in common.  Alignment, overlap (outputs
+// may not alias d_rays) and the context come afterwards, the context last, so that every other refusal can be had -- and
+// tested -- where there is no device to make a context on.
 int check_query_args(const char* who, const rtk_query_opts* opts, int64_t n, const void* rays, const char* rays_name, const void* out, const char* out_name) {
     if (!opts) return fail(RTK_ERR_INVALID, "%s: null opts", who);
     if (n < 0 || n > int64_t(0x7FFFFFFF)) return fail(RTK_ERR_INVALID, "%s: n must be 0 .. 2^31 - 1 (%lld)", who, (long long)n);
@@ -44,36 +29,20 @@ int check_query_args(const char* who, const rtk_query_opts* opts, int64_t n, con
     return RTK_OK;
 }
 
-// ... then the context and its scene.
-int check_scene(const char* who, const rtk_ctx* ctx) {
-    uint64_t digest = 0;
-    return ctx_scene(ctx, &digest) ? RTK_OK : fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
-}
-int check_ctx(const char* who, const rtk_ctx* ctx) { return ctx ? check_scene(who, ctx) : fail(RTK_ERR_INVALID, "%s: null context", who); }
-
-int launched(const char* who, hipError_t e) { return e == hipSuccess ? RTK_OK : fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
+Span ray_span(const rtk_ray* d_rays, int64_t n) { return Span{d_rays, size_t(n) * sizeof(rtk_ray), "d_rays"}; }
 
 // What the known-answer entry points refuse first, in this order: a null or negative argument (args_ok false), a context
 // without a scene (where the entry point reads one), an arithmetic type that is neither F64 nor F32.
 int check_debug_args(const char* who, bool args_ok, const rtk_ctx* scene_of, int real_mode) {
     if (!args_ok) return fail(RTK_ERR_INVALID, "%s: bad argument", who);
-    if (scene_of && check_scene(who, scene_of) != RTK_OK) return RTK_ERR_NO_SCENE;
+    if (scene_of && check_ctx(who, scene_of, true) != RTK_OK) return RTK_ERR_NO_SCENE;
     return check_real_mode(who, real_mode);
 }
 
-// A known-answer call on the device: the staged inputs go up, `launch` (real{}) enqueues the kernel on the null stream, the
-// device drains, the outputs come down; inputs and outputs are {piece, host array}.  The first HIP error ends it and is the result.
+// A known-answer call on the device: run_host_form around `launch` (real{}), which enqueues the kernel on the null stream.
 template <typename Launch>
-int run_debug(const char* who, int real_mode, HostStaging& s, std::initializer_list<std::pair<int, const void*>> inputs, Launch&& launch,
-              std::initializer_list<std::pair<int, void*>> outputs) {
-    hipError_t e = s.alloc();
-    for (const auto& in : inputs)
-        if (e == hipSuccess) e = s.upload(in.first, in.second);
-    if (e == hipSuccess) e = real_mode == RTK_REAL_F64 ? launch(double{}) : launch(float{});
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    for (const auto& out : outputs)
-        if (e == hipSuccess) e = s.download(out.first, out.second);
-    return launched(who, e);
+int run_debug(const char* who, int real_mode, HostStaging& s, std::initializer_list<HostIn> inputs, Launch&& launch, std::initializer_list<HostOut> outputs) {
+    return run_host_form(who, nullptr, s, inputs, [&] { return launched(who, with_real(real_mode, launch)); }, outputs);
 }
 
 }  // namespace
@@ -87,27 +56,27 @@ int rtk_query_hits(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rt
     const char* who = "rtk_query_hits";
     if (check_query_args(who, opts, n, d_rays, "d_rays", d_hits, "d_hits") != RTK_OK) return RTK_ERR_INVALID;
     if (check_aligned(d_rays, 8, who, "d_rays") != RTK_OK || check_aligned(d_hits, 8, who, "d_hits") != RTK_OK) return RTK_ERR_INVALID;
-    if (check_apart(d_rays, d_hits, n, sizeof(rtk_ray_hit), who, "d_hits") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_ctx(who, ctx);
+    if (check_apart(who, {d_hits, size_t(n) * sizeof(rtk_ray_hit), "d_hits"}, {ray_span(d_rays, n)}) != RTK_OK) return RTK_ERR_INVALID;
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
-    return launched(who, opts->real_mode == RTK_REAL_F64 ? launch_query_hits<double>(ctx_view<double>(ctx), opts->seed, n, d_rays, d_hits, st)
-                                                         : launch_query_hits<float>(ctx_view<float>(ctx), opts->seed, n, d_rays, d_hits, st));
+    return launched(who, with_real(opts->real_mode, [&](auto real) { return launch_query_hits(ctx_view<decltype(real)>(ctx), opts->seed, n, d_rays, d_hits, st); }));
 }
 
 int rtk_query_occluded(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* d_rays, int32_t* d_occluded) {
     const char* who = "rtk_query_occluded";
     if (check_query_args(who, opts, n, d_rays, "d_rays", d_occluded, "d_occluded") != RTK_OK) return RTK_ERR_INVALID;
     if (check_aligned(d_rays, 8, who, "d_rays") != RTK_OK || check_aligned(d_occluded, 4, who, "d_occluded") != RTK_OK) return RTK_ERR_INVALID;
-    if (check_apart(d_rays, d_occluded, n, sizeof(int32_t), who, "d_occluded") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_ctx(who, ctx);
+    if (check_apart(who, {d_occluded, size_t(n) * sizeof(int32_t), "d_occluded"}, {ray_span(d_rays, n)}) != RTK_OK) return RTK_ERR_INVALID;
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
     const bool any_hit = (ctx_features(ctx) & F_MEDIA) == 0;  // no constant_medium: the first accepted hit settles the flag
-    return launched(who, opts->real_mode == RTK_REAL_F64 ? launch_query_occluded<double>(ctx_view<double>(ctx), opts->seed, any_hit, n, d_rays, d_occluded, st)
-                                                         : launch_query_occluded<float>(ctx_view<float>(ctx), opts->seed, any_hit, n, d_rays, d_occluded, st));
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        return launch_query_occluded(ctx_view<decltype(real)>(ctx), opts->seed, any_hit, n, d_rays, d_occluded, st);
+    }));
 }
 
 int rtk_query_radiance(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* d_rays, void* d_radiance, uint32_t* d_draws) {
@@ -117,71 +86,55 @@ int rtk_query_radiance(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, cons
     if (check_aligned(d_rays, 8, who, "d_rays") != RTK_OK || check_aligned(d_radiance, real_bytes, who, "d_radiance") != RTK_OK ||
         check_aligned(d_draws, 4, who, "d_draws") != RTK_OK)
         return RTK_ERR_INVALID;
-    if (check_apart(d_rays, d_radiance, n, 3 * real_bytes, who, "d_radiance") != RTK_OK || check_apart(d_rays, d_draws, n, sizeof(uint32_t), who, "d_draws") != RTK_OK)
+    if (check_apart(who, {d_radiance, size_t(n) * 3 * real_bytes, "d_radiance"}, {ray_span(d_rays, n)}) != RTK_OK ||
+        check_apart(who, {d_draws, size_t(n) * sizeof(uint32_t), "d_draws"}, {ray_span(d_rays, n)}) != RTK_OK)
         return RTK_ERR_INVALID;
-    const int rc = check_ctx(who, ctx);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     const hipStream_t st = static_cast<hipStream_t>(opts->stream);
-    rtk_camera cam{};  // what the kernel reads of a camera: ray_color's background, max_depth and the samples per ray
-    cam.background = opts->background;
-    cam.max_depth = opts->max_depth;
-    cam.samples_per_pixel = opts->samples > 0 ? opts->samples : 1;
-    return launched(who, opts->real_mode == RTK_REAL_F64
-                             ? launch_query_radiance<double>(ctx_view<double>(ctx), device_camera<double>(cam), opts->seed, n, d_rays, d_radiance, d_draws, st)
-                             : launch_query_radiance<float>(ctx_view<float>(ctx), device_camera<float>(cam), opts->seed, n, d_rays, d_radiance, d_draws, st));
+    const rtk_camera cam = path_camera(opts->background, opts->max_depth, opts->samples);
+    return launched(who, with_real(opts->real_mode, [&](auto real) {
+        using R = decltype(real);
+        return launch_query_radiance(ctx_view<R>(ctx), device_camera<R>(cam), opts->seed, n, d_rays, d_radiance, d_draws, st);
+    }));
 }
 
 int rtk_query_hits_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, rtk_ray_hit* h_hits) {
     const char* who = "rtk_query_hits_host";
     if (check_query_args(who, opts, n, h_rays, "h_rays", h_hits, "h_hits") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_ctx(who, ctx);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(true);
     const int rays = s.piece(size_t(n) * sizeof(rtk_ray)), hits = s.piece(size_t(n) * sizeof(rtk_ray_hit));
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(rays, h_rays));
-    const int q = rtk_query_hits(ctx, opts, n, s.ptr<rtk_ray>(rays), s.ptr<rtk_ray_hit>(hits));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download(hits, h_hits);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{rays, h_rays}},
+                         [&] { return rtk_query_hits(ctx, opts, n, s.ptr<rtk_ray>(rays), s.ptr<rtk_ray_hit>(hits)); }, {{hits, h_hits}});
 }
 
 int rtk_query_occluded_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, int32_t* h_occluded) {
     const char* who = "rtk_query_occluded_host";
     if (check_query_args(who, opts, n, h_rays, "h_rays", h_occluded, "h_occluded") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_ctx(who, ctx);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(true);
     const int rays = s.piece(size_t(n) * sizeof(rtk_ray)), occ = s.piece(size_t(n) * sizeof(int32_t));
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(rays, h_rays));
-    const int q = rtk_query_occluded(ctx, opts, n, s.ptr<rtk_ray>(rays), s.ptr<int32_t>(occ));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download(occ, h_occluded);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{rays, h_rays}},
+                         [&] { return rtk_query_occluded(ctx, opts, n, s.ptr<rtk_ray>(rays), s.ptr<int32_t>(occ)); }, {{occ, h_occluded}});
 }
 
 int rtk_query_radiance_host(rtk_ctx* ctx, const rtk_query_opts* opts, int64_t n, const rtk_ray* h_rays, double* h_radiance, uint32_t* h_draws) {
     const char* who = "rtk_query_radiance_host";
     if (check_query_args(who, opts, n, h_rays, "h_rays", h_radiance, "h_radiance") != RTK_OK) return RTK_ERR_INVALID;
-    const int rc = check_ctx(who, ctx);
+    const int rc = check_ctx(who, ctx, true);
     if (rc != RTK_OK || n == 0) return rc;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
     HostStaging s(opts->real_mode == RTK_REAL_F64);
     const int rays = s.piece(size_t(n) * sizeof(rtk_ray)), rad = s.linear(size_t(n) * 3), draws = s.piece(size_t(n) * sizeof(uint32_t), h_draws != nullptr);
-    RTK_HIP(s.alloc());
-    RTK_HIP(s.upload(rays, h_rays));
-    const int q = rtk_query_radiance(ctx, opts, n, s.ptr<rtk_ray>(rays), s.ptr<void>(rad), s.ptr<uint32_t>(draws));
-    if (q != RTK_OK) return q;
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download_linear(rad, h_radiance);
-    if (e == hipSuccess) e = s.download(draws, h_draws);
-    return launched(who, e);
+    return run_host_form(who, static_cast<hipStream_t>(opts->stream), s, {{rays, h_rays}},
+                         [&] { return rtk_query_radiance(ctx, opts, n, s.ptr<rtk_ray>(rays), s.ptr<void>(rad), s.ptr<uint32_t>(draws)); },
+                         {{rad, h_radiance, true}, {draws, h_draws}});
 }
 
 // Known-answer entry points (include/rtk.h): n cases in host arrays, staged, run one lane each, read back.
