@@ -1,13 +1,13 @@
 // rtk_api.cpp -- implementation of the C ABI in include/rtk.h (host side of
 // librtk_hip.so; compiled by hipcc).  It validates an rtk_scene_desc, compiles
 // the scene graph into the linear traversal program of rtk_device_layout.h,
-// uploads f64 and f32 images of it to HBM and enqueues the kernels of
-// rtk_trace.hip.  There is no host rendering path: without a gfx950 device every
-// compute entry point fails with RTK_ERR_NO_DEVICE.
+// uploads f64 and f32 images of it to HBM and owns the context's life (struct
+// rtk_ctx: rtk_ctx.h); the frame entry points that enqueue the kernels are
+// rtk_frame_host.cpp's.  There is no host rendering path: without a gfx950 device
+// every compute entry point fails with RTK_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -16,13 +16,12 @@
 #include <map>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "rtk.h"
+#include "rtk_ctx.h"
 #include "rtk_device_layout.h"
 #include "rtk_internal.h"
-#include "rtk_trace.h"
 
 namespace rtk {
 
@@ -246,35 +245,6 @@ int validate_tables(const rtk_scene_desc& sc) {
         if (!mat_ok(sc.media[i].material)) return fail(RTK_ERR_INVALID, "medium %d: material out of range", i);
     return RTK_OK;
 }
-
-// ---------------------------------------------------------------------------
-// Device image of a scene for one arithmetic type
-// ---------------------------------------------------------------------------
-template <typename real>
-struct DeviceScene {
-    std::vector<void*> allocations;
-    SceneView<real> view{};
-    int64_t bytes = 0;
-
-    void release() {
-        for (void* p : allocations) (void)hipFree(p);
-        allocations.clear();
-        view = SceneView<real>{};
-        bytes = 0;
-    }
-    template <typename T>
-    int upload(const std::vector<T>& host, const T** out) {
-        *out = nullptr;
-        if (host.empty()) return RTK_OK;
-        void* d = nullptr;
-        RTK_HIP(hipMalloc(&d, host.size() * sizeof(T)));
-        allocations.push_back(d);
-        RTK_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-        bytes += int64_t(host.size() * sizeof(T));
-        *out = static_cast<const T*>(d);
-        return RTK_OK;
-    }
-};
 
 template <typename real>
 void store3(real* dst, const rtk_vec3& v) {
@@ -921,210 +891,13 @@ CameraRec<real> to_device_camera(const rtk_camera& c) {
 
 }  // namespace
 
-struct rtk_ctx {
-    int device = 0;
-    bool has_scene = false;
-    uint32_t features = 0;
-    int32_t n_ops = 0;
-    int32_t n_materials = 0, n_textures = 0;  // of the uploaded description (index checks of the known-answer entry points)
-    uint64_t scene_digest = 0;                // of the uploaded program and tables (progressive sessions refuse another scene)
-    DeviceScene<double> scene64;
-    DeviceScene<float> scene32;
-    // Words the persistent waves pull tile indices from; one per launch in a
-    // small ring so that back-to-back launches on a stream never share one.
-    unsigned int* tile_counters = nullptr;
-    unsigned int next_counter = 0;
-    // Camera records in device memory (the kernel reads them with scalar loads),
-    // same ring discipline; the host copies stay alive until the async copy ran.
-    unsigned char* d_cameras = nullptr;
-    // Partial-sum workspace [work item][3][64] reals, grown on demand and reused by
-    // successive launches (they are ordered on the caller's stream).
-    void* d_partial = nullptr;
-    size_t partial_bytes = 0;
-    // Longest-processing-time-first tile order, learned from the previous frame of the same shape: the render
-    // kernel accumulates a per-tile cost, rtk_tile_order_kernel turns it into the hand-out order of the next launch.
-    unsigned int* d_tile_cost = nullptr;
-    int32_t* d_tile_order = nullptr;
-    int order_capacity = 0;
-    bool order_valid = false;
-    int order_shape[5] = {0, 0, 0, 0, 0};  // width, height, rank, n_ranks, tiles: what the stored order was measured on
-    std::vector<CameraRec<double>> h_cameras64;
-    std::vector<CameraRec<float>> h_cameras32;
-    // The camera of the previous launch per arithmetic type: a frame loop renders the same camera again and again, and
-    // re-sending 256 bytes through a pageable-memory copy costs a host/stream round trip per frame for nothing.
-    unsigned int next_camera = 0;
-    bool cam_valid[2] = {false, false};
-    rtk_camera cam_last[2];
-    unsigned int cam_slot[2] = {0, 0};
-    // Progress reporting (rtk_set_progress_callback): the work-item counter of the last launch and how many items it
-    // hands out; a blocking render polls the counter with a 4-byte device-to-host copy on a stream of its own.
-    rtk_progress_fn progress_fn = nullptr;
-    void* progress_user = nullptr;
-    int progress_interval_ms = 100;
-    // a frame is up to kMaxPasses launches (one per range of sample chunks): the work-item counter of each and what it hands out
-    const unsigned int* last_tile_counter[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int64_t last_pass_items[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int last_n_passes = 0;
-    int64_t last_n_items = 0;               // of the whole frame
-    hipStream_t progress_stream = nullptr;
-    unsigned int* progress_word = nullptr;  // pinned host memory, one word per pass
-    bool progress_pending = false;
-    // The denoiser's ping-pong colour / variance buffers (rtk_denoise), grown on demand.
-    void* d_denoise = nullptr;
-    size_t denoise_bytes = 0;
-    // rtk_render_tiles: the compacted list of the flagged tiles [list_capacity] and, behind it, the word with its length.
-    int32_t* d_tile_list = nullptr;
-    int list_capacity = 0;
-    // The surface gathers' per-unit partial sums (rtk_gather_*), grown on demand up to their byte budget.
-    void* d_gather = nullptr;
-    size_t gather_bytes = 0;
-    // rtk_render_views: the batch's view records in device memory, grown on demand like the partial-sum workspace and reused
-    // in stream order, and a ring of pinned host buffers they are uploaded from -- a buffer is rewritten only after the
-    // event behind its last upload has passed, so batches enqueued back to back never share one.
-    void* d_views = nullptr;
-    size_t views_bytes = 0;
-    struct ViewStage {
-        void* host = nullptr;
-        size_t bytes = 0;
-        hipEvent_t done = nullptr;
-    };
-    ViewStage view_stage[4];
-    unsigned int next_view_stage = 0;
-};
-// Sample chunks per launch: the partial-sum workspace holds up to this many planes [local tile][3][64] at 1920x1080 f64 (+ one
-// for the running sum of a frame that needs several launches): 21 + 1 planes = 1.09 GB, where the 63 chunks of a 1000-spp
-// frame used to take 3.14 GB per context.  Every launch has a fixed cost -- staging the program, the drain of its last long
-// paths -- measured on the full-size frames (same box, same image): one launch / passes of 16 chunks: C5 999.6 / 1014.6 ms,
-// C3 247.7 / 254.5 ms; 21 chunks per pass makes a 1000-spp frame three launches instead of four.  Frames of up to 168 spp
-// (C2: 13 chunks) are one launch as before.
-constexpr int kMaxPlanesPerPass = 21;
-// The plane count is a BUDGET, not a constant: 22 planes of a 1920x1080 f64 frame = 1.095 GB per context.  A smaller
-// frame -- 800x800, or one rank's share of the tiles on several GPUs -- gets as many planes as that budget holds (up to all
-// 64 chunks: the Cornell box at 1000 spp is one launch again, 247.7 instead of 251.8 ms), a larger one at least 8.
-constexpr size_t kWorkspaceBudgetBytes = size_t(22) * 32400 * 192 * 8;
-constexpr int kMinPlanesPerPass = 8;
-constexpr int kMaxPasses = (rtk::kMaxChunks + kMinPlanesPerPass - 1) / kMinPlanesPerPass;
-static int planes_per_pass_for(size_t plane_bytes, int variant) {
-    if (variant & (1 << 24)) return rtk::kMaxChunks;  // variant bit 24: one pass whatever the chunk count (tests: same image)
-    if (plane_bytes == 0) return rtk::kMaxChunks;
-    const size_t fit = kWorkspaceBudgetBytes / plane_bytes;  // planes the budget holds, one of them the running sum
-    const int planes = fit > size_t(rtk::kMaxChunks) ? rtk::kMaxChunks : (fit < size_t(kMinPlanesPerPass + 1) ? kMinPlanesPerPass : int(fit) - 1);
-    return planes;
-}
-// Samples per chunk: 8, or the smallest size that keeps a pixel's chunks within kMaxChunks -- a function of spp only.
-static int chunk_size_for(int spp, int variant) {
-    const int ab = (variant >> 3) & 3;  // tools/: chunk size A/B (0 = default 8, 1 = 4, 2 = 2, 3 = 16)
-    int size = ab == 0 ? 8 : (ab == 1 ? 4 : (ab == 2 ? 2 : 16));
-    if (variant & 2) size = spp;  // variant bit 1: one lane per pixel for all samples (tests)
-    while ((spp + size - 1) / size > rtk::kMaxChunks) size++;
-    return size;
-}
-static_assert(kMaxPasses <= 8, "rtk_ctx keeps eight pass counters");
-constexpr unsigned int kCounterRing = 256;
-constexpr size_t kCameraStride = 256;
-static_assert(sizeof(CameraRec<double>) <= kCameraStride, "camera stride");
-
 namespace rtk {
+
+constexpr unsigned int kCounterRing = 256;  // (rtk_ctx.h: slots of the rings rtk_init allocates)
 
 int ctx_device(const rtk_ctx* ctx) { return ctx->device; }
 
-// Block until every stream[i] (a stream of ctxs[i]'s device) has drained.  When ctxs[0] has a progress callback, the
-// work-item counters of the launches in flight are sampled meanwhile -- a 4-byte device-to-host copy per context on a
-// stream of its own (the copy engine, not a CU; the persistent kernel is not touched) -- and the callback gets the sums.
-// A sample that has not landed by the next tick is simply skipped, so a copy stuck behind the kernel can only mean
-// fewer reports, never a stall.
-int wait_with_progress(rtk_ctx* const* ctxs, const hipStream_t* streams, int n) {
-    rtk_ctx* reporter = n > 0 ? ctxs[0] : nullptr;
-    if (!reporter || !reporter->progress_fn) {
-        for (int i = 0; i < n; i++) {
-            hipError_t e = hipSetDevice(ctxs[i]->device);
-            if (e == hipSuccess) e = hipStreamSynchronize(streams[i]);
-            if (e != hipSuccess) return fail(RTK_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-        }
-        return RTK_OK;
-    }
-    int64_t total = 0;
-    std::vector<int64_t> seen(size_t(n), 0);
-    for (int i = 0; i < n; i++) {
-        rtk_ctx* c = ctxs[i];
-        total += c->last_n_items;
-        if (!c->progress_stream) {
-            (void)hipSetDevice(c->device);
-            if (hipStreamCreateWithFlags(&c->progress_stream, hipStreamNonBlocking) != hipSuccess) c->progress_stream = nullptr;
-            if (hipHostMalloc(reinterpret_cast<void**>(&c->progress_word), 8 * sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) c->progress_word = nullptr;
-        }
-        c->progress_pending = false;
-    }
-    const auto tick = std::chrono::milliseconds(reporter->progress_interval_ms);
-    auto next_report = std::chrono::steady_clock::now();
-    for (;;) {
-        bool all_done = true;
-        for (int i = 0; i < n; i++) {
-            (void)hipSetDevice(ctxs[i]->device);
-            const hipError_t q = hipStreamQuery(streams[i]);
-            if (q == hipErrorNotReady) all_done = false;
-            else if (q != hipSuccess) return fail(RTK_ERR_HIP, "hipStreamQuery failed: %s", hipGetErrorString(q));
-        }
-        if (all_done) break;
-        if (std::chrono::steady_clock::now() >= next_report) {
-            int64_t done = 0;
-            for (int i = 0; i < n; i++) {
-                rtk_ctx* c = ctxs[i];
-                if (c->progress_stream && c->progress_word && c->last_n_passes > 0) {
-                    (void)hipSetDevice(c->device);
-                    if (c->progress_pending && hipStreamQuery(c->progress_stream) == hipSuccess) {
-                        int64_t sum = 0;  // a pass that has not started yet still shows the zero its counter was reset to at enqueue time ... or an older launch's count: clamp, and count a pass only once every earlier one is complete
-                        bool earlier_done = true;
-                        for (int p = 0; p < c->last_n_passes; p++) {
-                            const int64_t v = earlier_done ? std::min<int64_t>(int64_t(c->progress_word[p]), c->last_pass_items[p]) : 0;
-                            sum += v;
-                            earlier_done = earlier_done && v == c->last_pass_items[p];
-                        }
-                        seen[size_t(i)] = std::max(seen[size_t(i)], sum);
-                        c->progress_pending = false;
-                    }
-                    if (!c->progress_pending) {
-                        bool ok = true;
-                        for (int p = 0; p < c->last_n_passes && ok; p++)
-                            ok = hipMemcpyAsync(c->progress_word + p, c->last_tile_counter[p], sizeof(unsigned int), hipMemcpyDeviceToHost, c->progress_stream) == hipSuccess;
-                        c->progress_pending = ok;
-                    }
-                }
-                done += seen[size_t(i)];
-            }
-            reporter->progress_fn(done, total, reporter->progress_user);
-            next_report = std::chrono::steady_clock::now() + tick;
-        }
-        std::this_thread::sleep_for(std::chrono::microseconds(200));
-    }
-    for (int i = 0; i < n; i++)
-        if (ctxs[i]->progress_stream) {
-            (void)hipSetDevice(ctxs[i]->device);
-            (void)hipStreamSynchronize(ctxs[i]->progress_stream);
-            ctxs[i]->progress_pending = false;
-        }
-    reporter->progress_fn(total, total, reporter->progress_user);
-    return RTK_OK;
-}
-
 }  // namespace rtk
-
-// View batches (rtk_render_views): a view's record as the view kernel reads it.
-static uint32_t seed_hash_of(uint32_t v) {  // pcg_hash (rtk_trace.hip): what the render kernel makes of opts->seed before it keys a sample's stream
-    const uint32_t st = v * 747796405u + 2891336453u;
-    const uint32_t w = ((st >> ((st >> 28u) + 4u)) ^ st) * 277803737u;
-    return (w >> 22u) ^ w;
-}
-
-template <typename real>
-static void fill_view_records(void* dst, int32_t n_views, const rtk_camera* cams, const uint32_t* seeds, uint32_t seed) {
-    auto* out = static_cast<ViewRec<real>*>(dst);
-    for (int32_t v = 0; v < n_views; v++) {
-        out[v].cam = to_device_camera<real>(cams[v]);
-        out[v].seed_hash = seed_hash_of(seeds ? seeds[v] : seed);
-        out[v].reserved = 0;
-    }
-}
 
 extern "C" {
 
@@ -1154,8 +927,7 @@ int rtk_init(int device, rtk_ctx** out_ctx) {
         delete ctx;
         return fail(RTK_ERR_HIP, "hipMalloc(launch state) failed: %s", hipGetErrorString(me));
     }
-    ctx->h_cameras64.resize(kCounterRing);
-    ctx->h_cameras32.resize(kCounterRing);
+    ctx->h_cameras.resize(kCounterRing * kCameraStride);
     *out_ctx = ctx;
     return RTK_OK;
 }
@@ -1341,284 +1113,12 @@ static int upload_scene(rtk_ctx* ctx, const rtk_scene_desc* scene, UploadOrder o
     return RTK_OK;
 }
 
-int64_t rtk_tiles_per_rank(int image_width, int image_height, int n_ranks) {
-    if (image_width <= 0 || image_height <= 0 || n_ranks <= 0) return 0;
-    const int64_t tiles = int64_t((image_width + RTK_TILE_W - 1) / RTK_TILE_W) * ((image_height + RTK_TILE_H - 1) / RTK_TILE_H);
-    return (tiles + n_ranks - 1) / n_ranks;
-}
-
-// What rtk_render_device and rtk_render_tiles share of a frame's set-up.  plan_frame is host arithmetic on camera and options;
-// stage_frame makes the context ready for the launches: the partial-sum workspace grown to the frame's need, the camera record
-// in its device slot (copied on the frame's stream unless it is the cached one).
-struct FramePlan {
-    TileMap tm;  // every chunk of the frame
-    int chunk_size = 0, planes_per_pass = 0, n_passes = 0;
-    size_t plane = 0;  // bytes of one chunk plane [local tile][3][64]
-    unsigned char* d_cam = nullptr;
-    bool allow_lds = true;
-    uint32_t diag = 0;
-    hipStream_t stream = nullptr;
-};
-
-static void plan_frame(const rtk_camera* cam, const rtk_render_opts* opts, bool compact_out, FramePlan& f) {
-    TileMap& tm = f.tm;
-    tm.tiles_x = (cam->image_width + RTK_TILE_W - 1) / RTK_TILE_W;
-    tm.tiles_y = (cam->image_height + RTK_TILE_H - 1) / RTK_TILE_H;
-    tm.rank = opts->rank;
-    tm.n_ranks = opts->n_ranks;
-    tm.n_tiles_local = int32_t(rtk_tiles_per_rank(cam->image_width, cam->image_height, opts->n_ranks));
-    tm.compact = compact_out ? 1 : 0;
-    tm.order_in_lds = 0;
-    tm.order_lds_offset = 0;
-    tm.mats_lds_offset = 0;
-    // Split every pixel's samples into chunks of 8 (at most 64 chunks) so that no lane is stuck with a whole
-    // heavy pixel: a glass pixel's samples cost ~0.2 ms each, and the largest (pixel, chunk) bounds the end of
-    // the frame whatever the GPU count.  Measured on C2 (v16 kernel time, N = 1 / one of 8 shards): 4-sample chunks
-    // 22.8 / 3.21 ms, 8-sample 21.8 / 3.21 ms, 16-sample 21.7 / 3.60 ms (with the v9 kernel, whose refills were
-    // dearer, 4 was the optimum).  A function of spp only.
-    {
-        const int spp = cam->samples_per_pixel;
-        int n = 0;
-        tm.chunk_start[0] = 0;
-        const int size = chunk_size_for(spp, opts->variant);
-        for (int s0 = size; s0 < spp; s0 += size) tm.chunk_start[++n] = int16_t(s0);
-        tm.chunk_start[++n] = int16_t(spp);
-        tm.n_chunks = n;
-        for (int k = n + 1; k <= kMaxChunks; k++) tm.chunk_start[k] = int16_t(spp);
-        f.chunk_size = size;
-    }
-    const size_t elem = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
-    // Up to kMaxPlanesPerPass chunks per launch; a frame with more is rendered in consecutive passes, the resolve kernel
-    // carrying the running sum in one extra plane -- the same additions in the same order as one pass over all chunks.
-    f.plane = size_t(tm.n_tiles_local) * 192 * elem;
-    f.planes_per_pass = planes_per_pass_for(f.plane, opts->variant);
-    f.n_passes = (tm.n_chunks + f.planes_per_pass - 1) / f.planes_per_pass;
-    f.allow_lds = (opts->variant & 1) == 0;            // variant bit 0: keep the program in global memory (A/B)
-    f.diag = uint32_t(opts->variant) & 0xBFFF00u;      // bits 8..21, 23: scheduler policy / program layout A/B used by tools/ and tests only
-    f.stream = static_cast<hipStream_t>(opts->stream);
-}
-
-static int stage_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, FramePlan& f) {
-    const size_t need = f.plane * size_t(f.n_passes > 1 ? f.planes_per_pass + 1 : f.tm.n_chunks);
-    if (need > ctx->partial_bytes) {
-        if (ctx->d_partial) {
-            RTK_HIP(hipDeviceSynchronize());  // earlier launches may still read the old workspace
-            RTK_HIP(hipFree(ctx->d_partial));
-            ctx->d_partial = nullptr;
-            ctx->partial_bytes = 0;
-        }
-        RTK_HIP(hipMalloc(&ctx->d_partial, need));
-        ctx->partial_bytes = need;
-    }
-    const int cam_mode = opts->real_mode == RTK_REAL_F64 ? 0 : 1;
-    const bool cam_cached = ctx->cam_valid[cam_mode] && std::memcmp(&ctx->cam_last[cam_mode], cam, sizeof(rtk_camera)) == 0;
-    const unsigned int cslot = cam_cached ? ctx->cam_slot[cam_mode] : (ctx->next_camera++ % kCounterRing);
-    if (!cam_cached) {
-        // a slot about to be overwritten may still be the other mode's cached camera
-        for (int m = 0; m < 2; m++)
-            if (ctx->cam_valid[m] && ctx->cam_slot[m] == cslot) ctx->cam_valid[m] = false;
-        ctx->cam_last[cam_mode] = *cam;
-        ctx->cam_slot[cam_mode] = cslot;
-        ctx->cam_valid[cam_mode] = true;
-    }
-    f.d_cam = ctx->d_cameras + cslot * kCameraStride;
-    if (!cam_cached) {
-        if (opts->real_mode == RTK_REAL_F64) {
-            ctx->h_cameras64[cslot] = to_device_camera<double>(*cam);
-            RTK_HIP(hipMemcpyAsync(f.d_cam, &ctx->h_cameras64[cslot], sizeof(CameraRec<double>), hipMemcpyHostToDevice, f.stream));
-        } else {
-            ctx->h_cameras32[cslot] = to_device_camera<float>(*cam);
-            RTK_HIP(hipMemcpyAsync(f.d_cam, &ctx->h_cameras32[cslot], sizeof(CameraRec<float>), hipMemcpyHostToDevice, f.stream));
-        }
-    }
-    return RTK_OK;
-}
-
-// rtk_render_device; use_order = false (a view batch's per-view fallback): the frame neither reads nor touches the context's
-// learned tile order -- row-major hand-out, no cost measured, the stored order and the shape it belongs to left as they are.
-static int render_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters,
-                        bool use_order) {
-    if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_device: null argument");
-    if (!ctx->has_scene) return fail(RTK_ERR_NO_SCENE, "rtk_render_device: no scene uploaded");
-    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
-        return fail(RTK_ERR_INVALID, "rtk_render_device: bad camera dimensions (samples_per_pixel must be 1..32767)");
-    if (opts->n_ranks < 1 || opts->rank < 0 || opts->rank >= opts->n_ranks) return fail(RTK_ERR_INVALID, "rtk_render_device: bad rank %d of %d", opts->rank, opts->n_ranks);
-    const bool compact_out = opts->n_ranks > 1 || (opts->variant & (1 << 22)) != 0;  // variant bit 22: the tile-buffer layout for a single rank too
-    if (compact_out && d_rgb8) return fail(RTK_ERR_INVALID, "rtk_render_device: d_rgb8 must be null when n_ranks > 1 (use rtk_tiles_unpermute)");
-    if (opts->count_work && !d_counters) return fail(RTK_ERR_INVALID, "rtk_render_device: count_work needs d_counters");
-    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_render_device: unknown real_mode %d", opts->real_mode);
-    RTK_HIP(hipSetDevice(ctx->device));
-    FramePlan f;
-    plan_frame(cam, opts, compact_out, f);
-    if (const int rc = stage_frame(ctx, cam, opts, f); rc != RTK_OK) return rc;
-    const TileMap& tm = f.tm;
-    const int n_chunks_total = tm.n_chunks, planes_per_pass = f.planes_per_pass, n_passes = f.n_passes;
-    const size_t plane = f.plane;
-    unsigned char* const d_cam = f.d_cam;
-    const bool allow_lds = f.allow_lds;
-    const uint32_t diag = f.diag;
-    hipStream_t stream = f.stream;
-    auto* counters = reinterpret_cast<unsigned long long*>(d_counters);
-    // tile order / cost buffers for this shape
-    const int shape[5] = {cam->image_width, cam->image_height, opts->rank, opts->n_ranks, tm.n_tiles_local};
-    if (use_order && tm.n_tiles_local > ctx->order_capacity) {
-        if (ctx->d_tile_cost) {
-            RTK_HIP(hipDeviceSynchronize());
-            RTK_HIP(hipFree(ctx->d_tile_cost));
-            RTK_HIP(hipFree(ctx->d_tile_order));
-            ctx->d_tile_cost = nullptr;
-            ctx->d_tile_order = nullptr;
-        }
-        RTK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_tile_cost), size_t(tm.n_tiles_local) * sizeof(unsigned int)));
-        RTK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_tile_order), size_t(tm.n_tiles_local) * sizeof(int32_t)));
-        ctx->order_capacity = tm.n_tiles_local;
-        ctx->order_valid = false;
-    }
-    if (use_order && std::memcmp(shape, ctx->order_shape, sizeof shape) != 0) ctx->order_valid = false;
-    const bool learn = use_order && (opts->variant & 4) == 0;  // variant bit 2: fixed row-major tile order (A/B, tests)
-    if (!ctx->order_valid && learn) RTK_HIP(hipMemsetAsync(ctx->d_tile_cost, 0, size_t(tm.n_tiles_local) * sizeof(unsigned int), stream));
-    const int32_t* tile_order = (ctx->order_valid && learn) ? ctx->d_tile_order : nullptr;
-    unsigned int* tile_cost = learn ? ctx->d_tile_cost : nullptr;
-    ctx->last_n_passes = n_passes;
-    ctx->last_n_items = int64_t(tm.n_tiles_local) * n_chunks_total;
-    hipError_t e = hipSuccess;
-    void* const acc = n_passes > 1 ? static_cast<char*>(ctx->d_partial) + plane * size_t(planes_per_pass) : nullptr;
-    unsigned int* pass_counter[kMaxPasses];
-    for (int pass = 0; pass < n_passes; pass++) {  // every pass's work-item counter reads 0 from now on (progress reports add them up)
-        pass_counter[pass] = ctx->tile_counters + (ctx->next_counter++ % kCounterRing);
-        if (n_passes > 1) RTK_HIP(hipMemsetAsync(pass_counter[pass], 0, sizeof(unsigned int), stream));
-    }
-    for (int pass = 0; pass < n_passes && e == hipSuccess; pass++) {
-        const int c0 = pass * planes_per_pass, c1 = std::min(n_chunks_total, c0 + planes_per_pass);
-        TileMap tp = tm;  // this pass's chunks, numbered from 0: planes, work items and chunk boundaries are the pass's own
-        tp.n_chunks = c1 - c0;
-        for (int k = 0; k <= kMaxChunks; k++) tp.chunk_start[k] = tm.chunk_start[std::min(c0 + k, n_chunks_total)];
-        unsigned int* tile_counter = pass_counter[pass];
-        ctx->last_tile_counter[pass] = tile_counter;
-        ctx->last_pass_items[pass] = int64_t(tp.n_tiles_local) * tp.n_chunks;
-        unsigned int* pass_cost = pass == 0 ? tile_cost : nullptr;  // a tile's cost is measured on every pixel's first chunk
-        const bool first = pass == 0, last = pass + 1 == n_passes;
-        if (opts->real_mode == RTK_REAL_F64) {
-            e = launch_render<double>(ctx->scene64.view, reinterpret_cast<const CameraRec<double>*>(d_cam), tp, opts->seed, ctx->features,
-                                      opts->count_work != 0, allow_lds, diag, ctx->d_partial, counters, tile_counter, tile_order, pass_cost, stream);
-            if (e == hipSuccess)
-                e = launch_resolve<double>(ctx->d_partial, tp, cam->image_width, cam->image_height, cam->pixel_samples_scale, d_linear, d_rgb8, acc, first, last, stream);
-        } else {
-            e = launch_render<float>(ctx->scene32.view, reinterpret_cast<const CameraRec<float>*>(d_cam), tp, opts->seed, ctx->features,
-                                     opts->count_work != 0, allow_lds, diag, ctx->d_partial, counters, tile_counter, tile_order, pass_cost, stream);
-            if (e == hipSuccess)
-                e = launch_resolve<float>(ctx->d_partial, tp, cam->image_width, cam->image_height, cam->pixel_samples_scale, d_linear, d_rgb8, acc, first, last, stream);
-        }
-    }
-    if (e == hipSuccess && learn) {  // this frame's costs become the next frame's hand-out order
-        e = launch_tile_order(ctx->d_tile_cost, tm.n_tiles_local, ctx->d_tile_order, stream);
-        ctx->order_valid = e == hipSuccess;
-        std::memcpy(ctx->order_shape, shape, sizeof shape);
-    }
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "render kernel launch failed: %s", hipGetErrorString(e));
-    return RTK_OK;
-}
-
-int rtk_render_device(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters) {
-    return render_frame(ctx, cam, opts, d_linear, d_rgb8, d_counters, true);
-}
-
-int rtk_tiles_unpermute(rtk_ctx* ctx, int image_width, int image_height, int n_ranks, int real_mode, const void* d_gathered, void* d_linear, uint8_t* d_rgb8,
-                        void* stream) {
-    if (!ctx || !d_gathered || image_width <= 0 || image_height <= 0 || n_ranks < 1) return fail(RTK_ERR_INVALID, "rtk_tiles_unpermute: bad argument");
-    RTK_HIP(hipSetDevice(ctx->device));
-    const long long tpr = rtk_tiles_per_rank(image_width, image_height, n_ranks);
-    hipError_t e = real_mode == RTK_REAL_F64
-                       ? launch_unpermute<double>(d_gathered, image_width, image_height, n_ranks, tpr, d_linear, d_rgb8, static_cast<hipStream_t>(stream))
-                       : launch_unpermute<float>(d_gathered, image_width, image_height, n_ranks, tpr, d_linear, d_rgb8, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "unpermute kernel launch failed: %s", hipGetErrorString(e));
-    return RTK_OK;
-}
-
-int rtk_render_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, double* h_linear, uint8_t* h_rgb8, rtk_work_counters* counters) {
-    if (!ctx || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_host: null argument");
-    if (opts->n_ranks != 1) return fail(RTK_ERR_INVALID, "rtk_render_host renders whole images (n_ranks must be 1)");
-    RTK_HIP(hipSetDevice(ctx->device));
-    const size_t n = size_t(cam->image_width) * cam->image_height * 3;
-    const size_t elem = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
-    void* d_linear = nullptr;
-    uint8_t* d_rgb8 = nullptr;
-    rtk_work_counters* d_cnt = nullptr;
-    int rc = RTK_OK;
-    auto cleanup = [&]() {
-        if (d_linear) (void)hipFree(d_linear);
-        if (d_rgb8) (void)hipFree(d_rgb8);
-        if (d_cnt) (void)hipFree(d_cnt);
-    };
-#define RTK_HIP_CLEAN(call)                                                                       \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            cleanup();                                                                            \
-            return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));               \
-        }                                                                                         \
-    } while (0)
-    RTK_HIP_CLEAN(hipMalloc(&d_linear, n * elem));
-    RTK_HIP_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_rgb8), n));
-    rtk_render_opts o = *opts;
-    o.count_work = counters ? 1 : 0;
-    if (counters) {
-        RTK_HIP_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(rtk_work_counters)));
-        RTK_HIP_CLEAN(hipMemsetAsync(d_cnt, 0, sizeof(rtk_work_counters), static_cast<hipStream_t>(o.stream)));
-    }
-    rc = rtk_render_device(ctx, cam, &o, d_linear, d_rgb8, d_cnt);
-    if (rc != RTK_OK) {
-        cleanup();
-        return rc;
-    }
-    {
-        hipStream_t st = static_cast<hipStream_t>(o.stream);
-        rc = rtk::wait_with_progress(&ctx, &st, 1);
-        if (rc != RTK_OK) {
-            cleanup();
-            return rc;
-        }
-    }
-    if (h_linear) {
-        if (opts->real_mode == RTK_REAL_F64) {
-            RTK_HIP_CLEAN(hipMemcpy(h_linear, d_linear, n * sizeof(double), hipMemcpyDeviceToHost));
-        } else {
-            std::vector<float> tmp(n);
-            RTK_HIP_CLEAN(hipMemcpy(tmp.data(), d_linear, n * sizeof(float), hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < n; k++) h_linear[k] = double(tmp[k]);
-        }
-    }
-    if (h_rgb8) RTK_HIP_CLEAN(hipMemcpy(h_rgb8, d_rgb8, n, hipMemcpyDeviceToHost));
-    if (counters) RTK_HIP_CLEAN(hipMemcpy(counters, d_cnt, sizeof(rtk_work_counters), hipMemcpyDeviceToHost));
-    cleanup();
-    return RTK_OK;
-}
-
-int rtk_frame_launches(const rtk_camera* cam, const rtk_render_opts* opts) {
-    if (!cam || !opts || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->image_width <= 0 || cam->image_height <= 0 || opts->n_ranks < 1)
-        return fail(RTK_ERR_INVALID, "rtk_frame_launches: bad camera or options");
-    const int size = chunk_size_for(cam->samples_per_pixel, opts->variant);
-    const int chunks = (cam->samples_per_pixel + size - 1) / size;
-    const size_t elem = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
-    const size_t plane = size_t(rtk_tiles_per_rank(cam->image_width, cam->image_height, opts->n_ranks)) * 192 * elem;
-    const int per_pass = planes_per_pass_for(plane, opts->variant);
-    return (chunks + per_pass - 1) / per_pass;
-}
-
 int rtk_scene_info(rtk_ctx* ctx, int32_t* n_program_ops, int64_t* bytes_f64, int64_t* bytes_f32) {
     if (!ctx || !ctx->has_scene) return fail(RTK_ERR_NO_SCENE, "rtk_scene_info: no scene uploaded");
     if (n_program_ops) *n_program_ops = ctx->scene64.view.n_slots;
     if (bytes_f64) *bytes_f64 = ctx->scene64.bytes;
     if (bytes_f32) *bytes_f32 = ctx->scene32.bytes;
     return RTK_OK;
-}
-
-const char* rtk_kernel_name(rtk_ctx* ctx, int real_mode, int variant) {
-    if (!ctx || !ctx->has_scene) return "";
-    const bool allow_lds = (variant & 1) == 0;
-    const uint32_t diag = uint32_t(variant) & 0xBFFF00u;
-    return real_mode == RTK_REAL_F64 ? render_kernel_name<double>(ctx->scene64.view, ctx->features, false, allow_lds, diag)
-                                     : render_kernel_name<float>(ctx->scene32.view, ctx->features, false, allow_lds, diag);
 }
 
 }  // extern "C"
@@ -1659,10 +1159,6 @@ int32_t ctx_n_materials(const rtk_ctx* ctx) { return ctx->n_materials; }
 
 int32_t ctx_n_textures(const rtk_ctx* ctx) { return ctx->n_textures; }
 
-int frame_chunk_size(int spp) { return chunk_size_for(spp, 0); }
-
-int chunks_per_launch(size_t plane_bytes) { return planes_per_pass_for(plane_bytes, 0); }
-
 size_t camera_record_bytes() { return kCameraStride; }
 
 template <typename real>
@@ -1677,170 +1173,5 @@ template <typename real>
 CameraRec<real> device_camera(const rtk_camera& cam) { return to_device_camera<real>(cam); }
 template CameraRec<double> device_camera<double>(const rtk_camera&);
 template CameraRec<float> device_camera<float>(const rtk_camera&);
-
-hipError_t denoise_workspace(rtk_ctx* ctx, size_t bytes, void** out) {
-    hipError_t e = hipSuccess;
-    if (bytes > ctx->denoise_bytes) {
-        if (ctx->d_denoise) {
-            if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-            if ((e = hipFree(ctx->d_denoise)) != hipSuccess) return e;
-            ctx->d_denoise = nullptr;
-            ctx->denoise_bytes = 0;
-        }
-        if ((e = hipMalloc(&ctx->d_denoise, bytes)) != hipSuccess) return e;
-        ctx->denoise_bytes = bytes;
-    }
-    *out = ctx->d_denoise;
-    return e;
-}
-
-hipError_t gather_workspace(rtk_ctx* ctx, size_t bytes, void** out) {
-    hipError_t e = hipSuccess;
-    if (bytes > ctx->gather_bytes) {
-        if (ctx->d_gather) {
-            if ((e = hipDeviceSynchronize()) != hipSuccess) return e;  // earlier launches may still read the old workspace
-            if ((e = hipFree(ctx->d_gather)) != hipSuccess) return e;
-            ctx->d_gather = nullptr;
-            ctx->gather_bytes = 0;
-        }
-        if ((e = hipMalloc(&ctx->d_gather, bytes)) != hipSuccess) return e;
-        ctx->gather_bytes = bytes;
-    }
-    *out = ctx->d_gather;
-    return e;
-}
-
-hipError_t render_chunks(rtk_ctx* ctx, int real_mode, const void* d_cam, const TileMap& tp, uint32_t seed, unsigned long long* counters,
-                         const int32_t* tile_order, unsigned int* tile_cost, size_t workspace_bytes, hipStream_t stream, void** partial, bool allow_lds,
-                         uint32_t diag) {
-    hipError_t e = hipSuccess;
-    if (workspace_bytes > ctx->partial_bytes) {
-        if (ctx->d_partial) {
-            if ((e = hipDeviceSynchronize()) != hipSuccess) return e;  // earlier launches may still read the old workspace
-            if ((e = hipFree(ctx->d_partial)) != hipSuccess) return e;
-            ctx->d_partial = nullptr;
-            ctx->partial_bytes = 0;
-        }
-        if ((e = hipMalloc(&ctx->d_partial, workspace_bytes)) != hipSuccess) return e;
-        ctx->partial_bytes = workspace_bytes;
-    }
-    *partial = ctx->d_partial;
-    unsigned int* tile_counter = ctx->tile_counters + (ctx->next_counter++ % kCounterRing);
-    const bool count = counters != nullptr;
-    if (real_mode == RTK_REAL_F64)
-        return launch_render<double>(ctx->scene64.view, static_cast<const CameraRec<double>*>(d_cam), tp, seed, ctx->features, count, allow_lds, diag,
-                                     ctx->d_partial, counters, tile_counter, tile_order, tile_cost, stream);
-    return launch_render<float>(ctx->scene32.view, static_cast<const CameraRec<float>*>(d_cam), tp, seed, ctx->features, count, allow_lds, diag, ctx->d_partial,
-                                counters, tile_counter, tile_order, tile_cost, stream);
-}
-
-int frame_chunk_count(int spp, int variant) {
-    const int size = chunk_size_for(spp, variant);
-    return (spp + size - 1) / size;
-}
-
-int render_frame_apart(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8, rtk_work_counters* d_counters) {
-    return render_frame(ctx, cam, opts, d_linear, d_rgb8, d_counters, false);
-}
-
-int stage_view_batch(rtk_ctx* ctx, int32_t n_views, const rtk_camera* cams, const uint32_t* seeds, const rtk_render_opts* opts, ViewBatch& out) {
-    FramePlan f;
-    plan_frame(&cams[0], opts, false, f);  // one view's tiles; the chunk boundaries (a function of spp) are the single frame's
-    out.tm = f.tm;
-    out.tm.n_tiles_local = n_views * f.tm.n_tiles_local;  // local tiles are [view][tile]
-    out.tm.rank = 0;
-    out.tm.n_ranks = 1;
-    out.allow_lds = f.allow_lds;
-    out.diag = f.diag;
-    out.stream = f.stream;
-    const bool f64 = opts->real_mode == RTK_REAL_F64;
-    out.plane = size_t(out.tm.n_tiles_local) * 192 * (f64 ? sizeof(double) : sizeof(float));
-    out.planes_per_pass = planes_per_pass_for(out.plane, opts->variant);
-    out.n_passes = (out.tm.n_chunks + out.planes_per_pass - 1) / out.planes_per_pass;
-    RTK_HIP(hipSetDevice(ctx->device));
-    const size_t need = out.plane * size_t(out.n_passes > 1 ? out.planes_per_pass + 1 : out.tm.n_chunks);
-    if (need > ctx->partial_bytes) {
-        if (ctx->d_partial) {
-            RTK_HIP(hipDeviceSynchronize());  // earlier launches may still read the old workspace
-            RTK_HIP(hipFree(ctx->d_partial));
-            ctx->d_partial = nullptr;
-            ctx->partial_bytes = 0;
-        }
-        RTK_HIP(hipMalloc(&ctx->d_partial, need));
-        ctx->partial_bytes = need;
-    }
-    out.d_partial = ctx->d_partial;
-    const size_t rec_bytes = size_t(n_views) * (f64 ? sizeof(ViewRec<double>) : sizeof(ViewRec<float>));
-    if (rec_bytes > ctx->views_bytes) {
-        if (ctx->d_views) {
-            RTK_HIP(hipDeviceSynchronize());  // earlier batches may still read the old table
-            RTK_HIP(hipFree(ctx->d_views));
-            ctx->d_views = nullptr;
-            ctx->views_bytes = 0;
-        }
-        RTK_HIP(hipMalloc(&ctx->d_views, rec_bytes));
-        ctx->views_bytes = rec_bytes;
-    }
-    out.d_views = ctx->d_views;
-    rtk_ctx::ViewStage& stage = ctx->view_stage[ctx->next_view_stage++ % 4u];
-    if (!stage.done) RTK_HIP(hipEventCreateWithFlags(&stage.done, hipEventDisableTiming));
-    RTK_HIP(hipEventSynchronize(stage.done));  // the upload that last read this buffer (four batches ago) has run
-    if (rec_bytes > stage.bytes) {
-        if (stage.host) RTK_HIP(hipHostFree(stage.host));
-        stage.host = nullptr;
-        stage.bytes = 0;
-        RTK_HIP(hipHostMalloc(&stage.host, rec_bytes, hipHostMallocDefault));
-        stage.bytes = rec_bytes;
-    }
-    if (f64) fill_view_records<double>(stage.host, n_views, cams, seeds, opts->seed);
-    else fill_view_records<float>(stage.host, n_views, cams, seeds, opts->seed);
-    RTK_HIP(hipMemcpyAsync(ctx->d_views, stage.host, rec_bytes, hipMemcpyHostToDevice, out.stream));
-    RTK_HIP(hipEventRecord(stage.done, out.stream));
-    ctx->last_n_passes = out.n_passes;
-    ctx->last_n_items = int64_t(out.tm.n_tiles_local) * out.tm.n_chunks;
-    for (int pass = 0; pass < out.n_passes; pass++) {  // every pass's work-item counter reads 0 from now on (progress reports add them up)
-        out.pass_counter[pass] = ctx->tile_counters + (ctx->next_counter++ % kCounterRing);
-        if (out.n_passes > 1) RTK_HIP(hipMemsetAsync(out.pass_counter[pass], 0, sizeof(unsigned int), out.stream));
-        const int k0 = pass * out.planes_per_pass, k1 = std::min(out.tm.n_chunks, k0 + out.planes_per_pass);
-        ctx->last_tile_counter[pass] = out.pass_counter[pass];
-        ctx->last_pass_items[pass] = int64_t(out.tm.n_tiles_local) * (k1 - k0);
-    }
-    return RTK_OK;
-}
-
-int stage_tile_frame(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const char* who, TileFrame& out) {
-    FramePlan f;
-    plan_frame(cam, opts, false, f);
-    if (f.n_passes > 1)
-        return fail(RTK_ERR_INVALID, "%s: a frame of %d launches (rtk_frame_launches: more sample chunks than the workspace holds planes for) is not supported", who,
-                    f.n_passes);
-    if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    if (!ctx->has_scene) return fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
-    RTK_HIP(hipSetDevice(ctx->device));
-    if (const int rc = stage_frame(ctx, cam, opts, f); rc != RTK_OK) return rc;
-    const int n = f.tm.n_tiles_local;
-    if (n > ctx->list_capacity) {
-        if (ctx->d_tile_list) {
-            RTK_HIP(hipDeviceSynchronize());  // earlier launches may still read the old list
-            RTK_HIP(hipFree(ctx->d_tile_list));
-            ctx->d_tile_list = nullptr;
-            ctx->list_capacity = 0;
-        }
-        RTK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_tile_list), (size_t(n) + 1) * sizeof(int32_t)));
-        ctx->list_capacity = n;
-        // positions beyond the list's length are read (the render kernel stages the whole array) and never used: defined bytes
-        RTK_HIP(hipMemset(ctx->d_tile_list, 0, (size_t(n) + 1) * sizeof(int32_t)));
-    }
-    out.tm = f.tm;
-    out.chunk_size = f.chunk_size;
-    out.workspace_bytes = f.plane * size_t(f.tm.n_chunks);
-    out.d_cam = f.d_cam;
-    out.allow_lds = f.allow_lds;
-    out.diag = f.diag;
-    out.stream = f.stream;
-    out.d_list = ctx->d_tile_list;
-    out.d_count = ctx->d_tile_list + ctx->list_capacity;
-    return RTK_OK;
-}
 
 }  // namespace rtk

@@ -97,18 +97,7 @@ namespace {
         if (e_ != hipSuccess) return fail(RTK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
-int grow(void** p, size_t* have, size_t need) {
-    if (need <= *have) return RTK_OK;
-    if (*p) {
-        RTKM_HIP(hipDeviceSynchronize());
-        RTKM_HIP(hipFree(*p));
-        *p = nullptr;
-        *have = 0;
-    }
-    RTKM_HIP(hipMalloc(p, need));
-    *have = need;
-    return RTK_OK;
-}
+using rtk::grow_device;
 
 }  // namespace
 
@@ -258,7 +247,7 @@ int rtk_multi_frame_plan(int64_t frame, int32_t out[2]) {
 int rtk_render_multi_enqueue(rtk_multi* m, const rtk_camera* cam, const rtk_render_opts* opts, void* d_linear, uint8_t* d_rgb8) {
     if (!m || !cam || !opts) return fail(RTK_ERR_INVALID, "rtk_render_multi_enqueue: null argument");
     if (opts->count_work) return fail(RTK_ERR_INVALID, "rtk_render_multi_enqueue: work counters are per device (use rtk_render_device)");
-    if (opts->real_mode != RTK_REAL_F64 && opts->real_mode != RTK_REAL_F32) return fail(RTK_ERR_INVALID, "rtk_render_multi_enqueue: unknown real_mode %d", opts->real_mode);
+    if (rtk::check_real_mode("rtk_render_multi_enqueue", opts->real_mode) != RTK_OK) return RTK_ERR_INVALID;
     const int n = int(m->ctxs.size());
     if (n == 1 && m->comms.empty()) {  // one device: no tile buffers and no gather, the image directly (with RTK_GATHER_RCCL forced, one
                                        // device still goes through a 1-rank ncclGather: that is how the RCCL path is tested on a 1-GPU box)
@@ -290,12 +279,10 @@ int rtk_render_multi_enqueue(rtk_multi* m, const rtk_camera* cam, const rtk_rend
         }
     }
     RTKM_HIP(hipSetDevice(m->devices[0]));
-    rc = grow(&m->gathered[slot], &m->gathered_bytes[slot], part * size_t(n));
-    if (rc != RTK_OK) return rc;
+    RTKM_HIP(grow_device(&m->gathered[slot], &m->gathered_bytes[slot], part * size_t(n)));
     for (int i = 1; i < n; i++) {
         RTKM_HIP(hipSetDevice(m->devices[size_t(i)]));
-        rc = grow(&m->compact[slot][size_t(i)], &m->compact_bytes[slot][size_t(i)], part);
-        if (rc != RTK_OK) return rc;
+        RTKM_HIP(grow_device(&m->compact[slot][size_t(i)], &m->compact_bytes[slot][size_t(i)], part));
     }
     // 1. every device renders its tiles on its render stream -- device 0 straight into its part of the gather target (for
     //    ncclGather: the in-place send buffer of the root) -- once the frame that used this buffer set has been un-permuted
@@ -380,21 +367,13 @@ int rtk_render_multi(rtk_multi* m, const rtk_camera* cam, const rtk_render_opts*
     const size_t n = size_t(cam->image_width) * cam->image_height * 3;
     const size_t elem = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
     RTKM_HIP(hipSetDevice(m->devices[0]));
-    int rc = grow(&m->image, &m->image_bytes, n * elem);
-    if (rc == RTK_OK) rc = grow(reinterpret_cast<void**>(&m->rgb8), &m->rgb8_bytes, n);
-    if (rc != RTK_OK) return rc;
-    rc = rtk_render_multi_device(m, cam, opts, m->image, m->rgb8);
+    RTKM_HIP(grow_device(&m->image, &m->image_bytes, n * elem));
+    RTKM_HIP(grow_device(&m->rgb8, &m->rgb8_bytes, n));
+    const int rc = rtk_render_multi_device(m, cam, opts, m->image, m->rgb8);
     if (rc != RTK_OK) return rc;
     RTKM_HIP(hipSetDevice(m->devices[0]));
-    if (h_linear) {
-        if (opts->real_mode == RTK_REAL_F64) {
-            RTKM_HIP(hipMemcpy(h_linear, m->image, n * sizeof(double), hipMemcpyDeviceToHost));
-        } else {
-            std::vector<float> tmp(n);
-            RTKM_HIP(hipMemcpy(tmp.data(), m->image, n * sizeof(float), hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < n; k++) h_linear[k] = double(tmp[k]);
-        }
-    }
+    std::vector<float> tmp;
+    if (h_linear) RTKM_HIP(rtk::download_reals(opts->real_mode == RTK_REAL_F64, m->image, n, h_linear, tmp));
     if (h_rgb8) RTKM_HIP(hipMemcpy(h_rgb8, m->rgb8, n, hipMemcpyDeviceToHost));
     return RTK_OK;
 }

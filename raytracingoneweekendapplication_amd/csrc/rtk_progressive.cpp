@@ -2,7 +2,7 @@
 //
 // A session renders one frame in steps into running sums of its own (include/rtk.h, "Progressive, resumable rendering").  A
 // step is the one-shot frame's chunk loop restricted to an absolute chunk range: the render kernel is launched unchanged on a
-// TileMap whose chunk_start holds the step's absolute sample indices (in launches of at most chunks_per_launch chunks, into
+// TileMap whose chunk_start holds the step's absolute sample indices (in launches of at most the plan's planes_per_pass chunks, into
 // the context's partial-sum workspace), and rtk_accumulate_kernel folds every launch's planes into the session's sum in the
 // resolve's order -- so the image does not depend on how the frame was cut into steps.
 #include <hip/hip_runtime.h>
@@ -31,6 +31,8 @@ struct rtk_progressive {
     bool poisoned = false;
     TileMap tm{};        // tile geometry; chunk fields are filled per launch
     size_t elem = 8;     // bytes per real
+    size_t plane = 0;    // bytes of one chunk plane [local tile][3][64] ...
+    int per_launch = 0;  // ... and how many a launch may fill (the one-shot frame's plan)
     void* d_sum = nullptr;              // [local tile][3][64] reals
     double* d_s1 = nullptr;             // [local tile][64]
     double* d_s2 = nullptr;
@@ -105,12 +107,10 @@ void release(rtk_progressive* p) {
 // The kernel's camera record, stored on `stream` from a kernel argument (no host wait, no host memory that outlives the call).
 static_assert(sizeof(CameraRec<double>) % 4 == 0 && sizeof(CameraRec<float>) % 4 == 0, "launch_store_record stores 4-byte words");
 hipError_t upload_camera(const rtk_camera& cam, int real_mode, void* d_dst, hipStream_t stream) {
-    if (real_mode == RTK_REAL_F64) {
-        const CameraRec<double> rec = device_camera<double>(cam);
+    return with_real(real_mode, [&](auto real) {
+        const CameraRec<decltype(real)> rec = device_camera<decltype(real)>(cam);
         return launch_store_record(&rec, sizeof rec, d_dst, stream);
-    }
-    const CameraRec<float> rec = device_camera<float>(cam);
-    return launch_store_record(&rec, sizeof rec, d_dst, stream);
+    });
 }
 
 // Argument checks and device state of a new session.  The state is set up ON THE SESSION'S STREAM, by asynchronous memsets and
@@ -122,11 +122,11 @@ int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opt
     *out = nullptr;
     uint64_t digest = 0;
     if (!ctx_scene(ctx, &digest)) return fail(RTK_ERR_NO_SCENE, "%s: no scene uploaded", who);
-    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
-        return fail(RTK_ERR_INVALID, "%s: bad camera dimensions (samples_per_pixel must be 1..32767)", who);
-    if (opts->n_ranks < 1 || opts->rank < 0 || opts->rank >= opts->n_ranks) return fail(RTK_ERR_INVALID, "%s: bad rank %d of %d", who, opts->rank, opts->n_ranks);
-    if (check_real_mode(who, opts->real_mode) != RTK_OK) return RTK_ERR_INVALID;
+    if (check_frame_camera(who, *cam) != RTK_OK || check_rank(who, *opts) != RTK_OK || check_real_mode(who, opts->real_mode) != RTK_OK) return RTK_ERR_INVALID;
     RTK_HIP(hipSetDevice(ctx_device(ctx)));
+    rtk_render_opts plain = *opts;
+    plain.variant = 0;  // sessions render with variant 0: the default chunk size, compact tile buffers for several ranks only
+    const FramePlan f = plan_frame(*cam, plain);
     auto* p = new rtk_progressive;
     p->ctx = ctx;
     p->cam = *cam;
@@ -136,16 +136,15 @@ int make_session(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opt
     p->n_ranks = opts->n_ranks;
     p->stream = static_cast<hipStream_t>(opts->stream);
     p->target = cam->samples_per_pixel;
-    p->chunk = frame_chunk_size(p->target);
+    p->chunk = f.chunk_size;
     p->digest = digest;
-    p->elem = opts->real_mode == RTK_REAL_F64 ? sizeof(double) : sizeof(float);
+    p->elem = f.elem;
+    p->plane = f.plane;
+    p->per_launch = f.planes_per_pass;
     TileMap& tm = p->tm;
-    tm.tiles_x = (cam->image_width + RTK_TILE_W - 1) / RTK_TILE_W;
-    tm.tiles_y = (cam->image_height + RTK_TILE_H - 1) / RTK_TILE_H;
-    tm.rank = opts->rank;
-    tm.n_ranks = opts->n_ranks;
-    tm.n_tiles_local = int32_t(rtk_tiles_per_rank(cam->image_width, cam->image_height, opts->n_ranks));
-    tm.compact = opts->n_ranks > 1 ? 1 : 0;
+    tm = f.tm;
+    tm.n_chunks = 0;
+    std::memset(tm.chunk_start, 0, sizeof tm.chunk_start);
     const size_t slots = p->n_slots();
     hipError_t e = hipMalloc(&p->d_sum, slots * 3 * p->elem);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_s1), slots * sizeof(double));
@@ -211,13 +210,12 @@ int usable(const rtk_progressive* p, const char* who) {
     return RTK_OK;
 }
 
-// The step's launches: render + accumulate per range of at most chunks_per_launch chunks.
+// The step's launches: render + accumulate per range of at most per_launch chunks (a loop of its own, in absolute chunks of the session: DESIGN.md, "What a frame entry point is made of").
 hipError_t enqueue_step(rtk_progressive* p, int n_samples, void* d_linear, uint8_t* d_rgb8, float* d_noise, rtk_work_counters* d_counters, bool& launched) {
     const int c = p->chunk, s_end = p->done + n_samples;
     const int k0 = p->done / c, k1 = (s_end + c - 1) / c;  // absolute chunk range [k0, k1)
-    const size_t plane = size_t(p->tm.n_tiles_local) * 192 * p->elem;
-    const int per_launch = chunks_per_launch(plane);
-    const size_t workspace = plane * size_t(std::min(per_launch, k1 - k0));
+    const int per_launch = p->per_launch;
+    const size_t workspace = p->plane * size_t(std::min(per_launch, k1 - k0));
     // Adaptive sessions: a fresh session's first step renders every tile (all are active) and learns the cost order like any
     // other; every later step hands out the compacted list of the active tiles, up to its device-side length.
     const bool all_tiles = !p->adaptive || p->done == 0;
@@ -239,22 +237,14 @@ hipError_t enqueue_step(rtk_progressive* p, int n_samples, void* d_linear, uint8
         if (e != hipSuccess) break;
         const bool last = b == k1;
         const int k_full = s_end / c;  // full chunks after the step (every chunk but a final partial one; read on the last launch only)
-        if (p->adaptive) {
-            const bool retire_ok = last && p->min_samples <= s_end && s_end < p->target;
-            e = p->real_mode == RTK_REAL_F64
-                    ? launch_accumulate_adaptive<double>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2,
-                                                         p->d_active, p->d_tile_spp, last, s_end, retire_ok, p->rel_target, d_linear, d_rgb8, d_noise,
-                                                         p->stream)
-                    : launch_accumulate_adaptive<float>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2,
-                                                        p->d_active, p->d_tile_spp, last, s_end, retire_ok, p->rel_target, d_linear, d_rgb8, d_noise,
-                                                        p->stream);
-            continue;
-        }
-        e = p->real_mode == RTK_REAL_F64
-                ? launch_accumulate<double>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2, last,
-                                            1.0 / double(s_end), k_full, d_linear, d_rgb8, d_noise, p->stream)
-                : launch_accumulate<float>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2, last,
-                                           1.0 / double(s_end), k_full, d_linear, d_rgb8, d_noise, p->stream);
+        const bool retire_ok = last && p->min_samples <= s_end && s_end < p->target;
+        e = with_real(p->real_mode, [&](auto real) {
+            using R = decltype(real);
+            return p->adaptive ? launch_accumulate_adaptive<R>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2,
+                                                               p->d_active, p->d_tile_spp, last, s_end, retire_ok, p->rel_target, d_linear, d_rgb8, d_noise, p->stream)
+                               : launch_accumulate<R>(partial, tp, p->cam.image_width, p->cam.image_height, c, a == 0, p->d_sum, p->d_s1, p->d_s2, last,
+                                                      1.0 / double(s_end), k_full, d_linear, d_rgb8, d_noise, p->stream);
+        });
     }
     if (e == hipSuccess && measure) {  // the first step's costs become the hand-out order of every later launch
         e = launch_tile_order(p->d_cost, p->tm.n_tiles_local, p->d_order, p->stream);
@@ -636,9 +626,10 @@ static int progressive_denoise(const char* who, bool guided, rtk_progressive* p,
     if (!p->d_preview) RTK_HIP(hipMalloc(&p->d_preview, px * 3 * p->elem));
     if (!p->d_preview_se) RTK_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_preview_se), px * sizeof(float)));
     const int32_t* spp = p->adaptive ? p->d_tile_spp : nullptr;
-    RTK_HIP(p->real_mode == RTK_REAL_F64
-                ? launch_preview<double>(p->d_sum, p->d_s1, p->d_s2, p->tm, W, H, p->chunk, p->done, spp, p->d_preview, p->d_preview_se, p->stream)
-                : launch_preview<float>(p->d_sum, p->d_s1, p->d_s2, p->tm, W, H, p->chunk, p->done, spp, p->d_preview, p->d_preview_se, p->stream));
+    const hipError_t pe = with_real(p->real_mode, [&](auto real) {
+        return launch_preview<decltype(real)>(p->d_sum, p->d_s1, p->d_s2, p->tm, W, H, p->chunk, p->done, spp, p->d_preview, p->d_preview_se, p->stream);
+    });
+    if (pe != hipSuccess) return launched(who, pe);
     return guided ? rtk_denoise_guided(p->ctx, W, H, p->real_mode, p->d_preview, aov, p->d_preview_se, opts, flags, d_out_linear, d_out_rgb8, p->stream)
                   : rtk_denoise(p->ctx, W, H, p->real_mode, p->d_preview, aov, p->d_preview_se, opts, d_out_linear, d_out_rgb8, p->stream);
 }

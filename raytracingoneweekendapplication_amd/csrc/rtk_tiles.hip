@@ -1,6 +1,6 @@
 // rtk_tiles.hip -- tile lists (include/rtk.h, "Tile lists"): rtk_tiles_select, the kernel that turns per-pixel maps into per-tile
 // flags; rtk_render_tiles, which renders the flagged tiles with the render kernel over a compacted list (the frame set-up is
-// rtk_api.cpp's stage_tile_frame, the list's kernels are rtk_frame.hip's); and their _host forms.  Hand-written HIP for gfx950, wave64.
+// rtk_frame_host.cpp's stage_tile_frame, the list's kernels are rtk_frame.hip's); and their _host forms.  Hand-written HIP for gfx950, wave64.
 //
 // Layout.  One wave per 8x8 tile on the image passes' grid (rtk_image_pass.h), four tiles per 256-thread block.  A tile is
 // flagged when a raw-flagged pixel lies in its window: its in-image pixels grown by r = dilate on every side and clipped to the
@@ -87,8 +87,7 @@ int rtk_tiles_select(rtk_ctx* ctx, int32_t width, int32_t height, const float* d
         rtk_tiles_select_kernel<<<dim3((P.grid.n_tiles + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream)>>>(P, d_below_map, d_above_map, d_tile_flags);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return RTK_OK;
+    return launched(who, e);
 }
 
 int rtk_tiles_select_host(rtk_ctx* ctx, int32_t width, int32_t height, const float* h_below_map, const float* h_above_map, const rtk_tile_select_opts* opts,
@@ -97,57 +96,48 @@ int rtk_tiles_select_host(rtk_ctx* ctx, int32_t width, int32_t height, const flo
     SelectParams P{};
     if (check_select_args(who, width, height, h_below_map, h_above_map, opts, h_tile_flags, P) != RTK_OK) return RTK_ERR_INVALID;
     if (!ctx) return fail(RTK_ERR_INVALID, "%s: null context", who);
-    hipError_t e = hipSetDevice(ctx_device(ctx));
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (const hipError_t e = hipSetDevice(ctx_device(ctx)); e != hipSuccess) return launched(who, e);
     const size_t px = size_t(width) * height;
     HostStaging s(false);
     const int below = s.piece(px * sizeof(float), h_below_map != nullptr), above = s.piece(px * sizeof(float), h_above_map != nullptr);
     const int flags = s.piece(size_t(P.grid.n_tiles) * sizeof(int32_t));
-    e = s.alloc();
-    if (e == hipSuccess && h_below_map) e = s.upload(below, h_below_map);
-    if (e == hipSuccess && h_above_map) e = s.upload(above, h_above_map);
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    const int rc = rtk_tiles_select(ctx, width, height, s.ptr<float>(below), s.ptr<float>(above), opts, s.ptr<int32_t>(flags), nullptr);
-    if (rc != RTK_OK) return rc;
-    e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess) e = s.download(flags, h_tile_flags);
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return RTK_OK;
+    return run_host_form(
+        who, nullptr, s, {{below, h_below_map}, {above, h_above_map}},
+        [&] { return rtk_tiles_select(ctx, width, height, s.ptr<float>(below), s.ptr<float>(above), opts, s.ptr<int32_t>(flags), nullptr); },
+        {{flags, h_tile_flags}});
 }
 
 int rtk_render_tiles(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_opts* opts, const int32_t* d_tile_flags, int32_t max_tiles, void* d_linear,
                      uint8_t* d_rgb8, float* d_noise, float* d_support, int32_t* d_info) {
     const char* who = "rtk_render_tiles";
     if (!cam || !opts) return fail(RTK_ERR_INVALID, "%s: null camera or options", who);
-    if (cam->image_width <= 0 || cam->image_height <= 0 || cam->samples_per_pixel <= 0 || cam->samples_per_pixel > 32767 || cam->max_depth < 0)
-        return fail(RTK_ERR_INVALID, "%s: bad camera dimensions (samples_per_pixel must be 1..32767)", who);
+    if (check_frame_camera(who, *cam) != RTK_OK) return RTK_ERR_INVALID;
     if (opts->n_ranks != 1 || opts->rank != 0) return fail(RTK_ERR_INVALID, "%s: tile lists are one rank's (n_ranks must be 1, rank 0; got %d of %d)", who, opts->rank, opts->n_ranks);
-    if (opts->variant & (1 << 22)) return fail(RTK_ERR_INVALID, "%s: the tile-buffer layout (variant bit 22) is not supported", who);
+    if (decode_variant(opts->variant).compact) return fail(RTK_ERR_INVALID, "%s: the tile-buffer layout (variant bit 22) is not supported", who);
     if (check_real_mode(who, opts->real_mode) != RTK_OK) return RTK_ERR_INVALID;
     if (!d_tile_flags) return fail(RTK_ERR_INVALID, "%s: d_tile_flags is null", who);
     if (max_tiles < 0) return fail(RTK_ERR_INVALID, "%s: max_tiles %d is negative (0 = no limit)", who, max_tiles);
     if (!d_linear && !d_rgb8 && !d_noise && !d_support) return fail(RTK_ERR_INVALID, "%s: no output", who);
-    const bool f64 = opts->real_mode == RTK_REAL_F64;
-    if (check_aligned(d_tile_flags, 4, who, "d_tile_flags") != RTK_OK || check_aligned(d_linear, f64 ? 8 : 4, who, "d_linear") != RTK_OK ||
+    if (check_aligned(d_tile_flags, 4, who, "d_tile_flags") != RTK_OK || check_aligned(d_linear, opts->real_mode == RTK_REAL_F64 ? 8 : 4, who, "d_linear") != RTK_OK ||
         check_aligned(d_noise, 4, who, "d_noise") != RTK_OK || check_aligned(d_support, 4, who, "d_support") != RTK_OK ||
         check_aligned(d_info, 4, who, "d_info") != RTK_OK)
         return RTK_ERR_INVALID;
-    TileFrame f;
-    if (const int rc = stage_tile_frame(ctx, cam, opts, who, f); rc != RTK_OK) return rc;  // more than one launch, null context, no scene
+    TileFrame t;
+    if (const int rc = stage_tile_frame(ctx, cam, opts, who, t); rc != RTK_OK) return rc;  // more than one launch, null context, no scene
+    const FramePlan& f = t.plan;
     // flags -> list (ascending tile index) -> its length, gated by max_tiles -> the render kernel over the list -> the list's resolve
-    hipError_t e = launch_adaptive_compact(d_tile_flags, nullptr, f.tm.n_tiles_local, f.d_list, f.d_count, f.stream);
-    if (e == hipSuccess) e = launch_tile_gate(f.d_count, max_tiles, d_info, f.stream);
+    hipError_t e = launch_adaptive_compact(d_tile_flags, nullptr, f.tm.n_tiles_local, t.d_list, t.d_count, f.stream);
+    if (e == hipSuccess) e = launch_tile_gate(t.d_count, max_tiles, d_info, f.stream);
     TileMap tp = f.tm;
-    tp.active_count = f.d_count;
+    tp.active_count = t.d_count;
     void* partial = nullptr;
     // no counters, no cost buffer: the context's learned tile order is neither read nor replaced
+    if (e == hipSuccess) e = render_chunks(ctx, opts->real_mode, t.d_cam, tp, opts->seed, nullptr, t.d_list, nullptr, f.workspace_bytes(), f.stream, &partial, f.variant);
     if (e == hipSuccess)
-        e = render_chunks(ctx, opts->real_mode, f.d_cam, tp, opts->seed, nullptr, f.d_list, nullptr, f.workspace_bytes, f.stream, &partial, f.allow_lds, f.diag);
-    if (e == hipSuccess)
-        e = f64 ? launch_resolve_tiles<double>(partial, tp, cam->image_width, cam->image_height, f.chunk_size, cam->pixel_samples_scale, f.d_list, f.d_count, d_linear,
-                                               d_rgb8, d_noise, d_support, f.stream)
-                : launch_resolve_tiles<float>(partial, tp, cam->image_width, cam->image_height, f.chunk_size, cam->pixel_samples_scale, f.d_list, f.d_count, d_linear,
-                                              d_rgb8, d_noise, d_support, f.stream);
+        e = with_real(opts->real_mode, [&](auto real) {
+            return launch_resolve_tiles<decltype(real)>(partial, tp, cam->image_width, cam->image_height, f.chunk_size, cam->pixel_samples_scale, t.d_list, t.d_count,
+                                                        d_linear, d_rgb8, d_noise, d_support, f.stream);
+        });
     if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
     return RTK_OK;
 }
@@ -162,33 +152,23 @@ int rtk_render_tiles_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_
     if (!h_linear && !h_rgb8 && !h_noise && !h_support) return fail(RTK_ERR_INVALID, "%s: no output", who);
     // without a context the device form refuses before it touches a buffer: its remaining checks, in its words and its order
     if (!ctx) return rtk_render_tiles(nullptr, cam, opts, h_tile_flags, max_tiles, h_linear, h_rgb8, h_noise, h_support, nullptr);
-    hipError_t e = hipSetDevice(ctx_device(ctx));
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (const hipError_t e = hipSetDevice(ctx_device(ctx)); e != hipSuccess) return launched(who, e);
     const size_t px = size_t(cam->image_width) * cam->image_height;
     const size_t n_tiles = size_t(rtk_tiles_per_rank(cam->image_width, cam->image_height, 1));
     HostStaging s(opts->real_mode == RTK_REAL_F64);
     const int flags = s.piece(n_tiles * sizeof(int32_t)), info = s.piece(2 * sizeof(int32_t));
     const int linear = s.linear(px * 3, h_linear != nullptr), rgb8 = s.piece(px * 3, h_rgb8 != nullptr);
     const int noise = s.piece(px * sizeof(float), h_noise != nullptr), support = s.piece(px * sizeof(float), h_support != nullptr);
-    e = s.alloc();
-    if (e == hipSuccess) e = s.upload(flags, h_tile_flags);
-    if (e == hipSuccess) e = hipMemset(s.ptr(info), 0, 2 * sizeof(int32_t));
-    if (e == hipSuccess && h_linear) e = s.upload_linear(linear, h_linear);
-    if (e == hipSuccess && h_rgb8) e = s.upload(rgb8, h_rgb8);
-    if (e == hipSuccess && h_noise) e = s.upload(noise, h_noise);
-    if (e == hipSuccess && h_support) e = s.upload(support, h_support);
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: device buffers: %s", who, hipGetErrorString(e));
-    const int rc = rtk_render_tiles(ctx, cam, opts, s.ptr<int32_t>(flags), max_tiles, s.ptr(linear), s.ptr<uint8_t>(rgb8), s.ptr<float>(noise), s.ptr<float>(support),
-                                    s.ptr<int32_t>(info));
-    if (rc != RTK_OK) return rc;
-    e = hipStreamSynchronize(static_cast<hipStream_t>(opts->stream));
-    if (e == hipSuccess) e = s.download_linear(linear, h_linear);
-    if (e == hipSuccess) e = s.download(rgb8, h_rgb8);
-    if (e == hipSuccess) e = s.download(noise, h_noise);
-    if (e == hipSuccess) e = s.download(support, h_support);
-    if (e == hipSuccess) e = s.download(info, h_info);
-    if (e != hipSuccess) return fail(RTK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return RTK_OK;
+    // the outputs go up as well: pixels of tiles that are not listed keep the caller's values
+    return run_host_form(
+        who, static_cast<hipStream_t>(opts->stream), s, {{flags, h_tile_flags}, {linear, h_linear, true}, {rgb8, h_rgb8}, {noise, h_noise}, {support, h_support}},
+        [&] {
+            const hipError_t e = hipMemset(s.ptr(info), 0, 2 * sizeof(int32_t));
+            return e != hipSuccess ? launched(who, e)
+                                   : rtk_render_tiles(ctx, cam, opts, s.ptr<int32_t>(flags), max_tiles, s.ptr(linear), s.ptr<uint8_t>(rgb8), s.ptr<float>(noise),
+                                                      s.ptr<float>(support), s.ptr<int32_t>(info));
+        },
+        {{linear, h_linear, true}, {rgb8, h_rgb8}, {noise, h_noise}, {support, h_support}, {info, h_info}});
 }
 
 }  // extern "C"

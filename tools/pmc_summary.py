@@ -77,7 +77,7 @@ for f in newest_per_pass(os.path.join(out, "stats", "**", "*kernel_trace.csv")):
 for f in newest_per_pass(os.path.join(out, "stats", "**", "*kernel_stats.csv")):
     shutil.copy(f, os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats_{cfg}.csv"))
 kernel_ms_profiled = sum(dur) / len(dur) if dur else None
-# A frame with more than 21 sample chunks is SEVERAL launches of the timed kernel (passes over the chunks, csrc/rtk_api.cpp):
+# A frame with more than 21 sample chunks is SEVERAL launches of the timed kernel (passes over the chunks, csrc/rtk_frame_host.cpp):
 # bench.py's kernel_ms brackets the frame, so the additive counters and the duration are scaled from "mean dispatch" to "frame".
 launches = int(line["roofline"].get("launches_per_frame") or 1)
 if launches > 1:
