@@ -1193,6 +1193,8 @@ int rtk_render_tiles_host(rtk_ctx* ctx, const rtk_camera* cam, const rtk_render_
  * wrap), sample = j * S, skip = 0 } -- what rtk_gather_rays writes, [n * R] records, point-major.  L_kj is what
  * rtk_query_radiance returns for that record with samples = S and the call's seed, max_depth and background.
  * Irradiance: E[k][ch] = (pi / R) sum_j L_kj[ch], accumulated in double in both real modes, [n][3] reals of real_mode.
+ * rtk_gather_irradiance checks max_distance and then ignores it, as rtk_query_radiance ignores a record's tmax: E is the same
+ * for every valid value.
  * Occlusion: ray j is open when the flag rtk_query_occluded returns for its record is 0 (in a scene with a constant medium the
  * walk draws from the record's stream, as the query's does).  open[k] = (open rays) / R, [n] reals; bent[k] = (the sum of the
  * world directions d -- the doubles of the record -- of the open rays) / R, [n][3] reals, not normalised, zero when none is
@@ -1223,7 +1225,8 @@ typedef struct rtk_gather_opts {         /* 96 bytes */
     int32_t batch_points;                /* 0 = as many points per launch as the workspace budget holds; else that many */
     rtk_vec3 background;                 /* irradiance only */
     double time;
-    double max_distance;                 /* the records' tmax, so occlusion's reach; 0 = +inf */
+    double max_distance;                 /* the records' tmax, so occlusion's reach; 0 = +inf.  Irradiance ignores it, as the
+                                          * radiance query ignores tmax */
     void* stream;
     int32_t reserved[4];                 /* 0 */
 } rtk_gather_opts;

@@ -1089,15 +1089,16 @@ class Renderer:
         return out
 
     def gather_irradiance(self, points, normals, *, max_depth: int, rays: int = 256, samples: int = 1, background=(0.0, 0.0, 0.0), first_key: int = 0,
-                          rotate: int = 0, batch_points: int = 0, time: float = 0.0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64):
+                          rotate: int = 0, batch_points: int = 0, time: float = 0.0, max_distance: float = 0.0, seed: int = RENDER_SEED,
+                          real_mode: int = RTK_REAL_F64):
         """rtk_gather_irradiance_host: E[k] = (pi / rays) sum_j L_kj over the rays ``gather_rays`` returns: float64 (n, 3), F32
-        results widened."""
+        results widened.  ``max_distance`` is checked and changes nothing: the radiance query ignores a record's tmax."""
         import numpy as np
 
         points, normals = _gather_inputs("gather_irradiance", points, normals)
         n = points.shape[0]
         out = np.zeros((n, 3), np.float64)
-        opts = _gather_opts(seed, real_mode, max_depth, samples, rays, first_key, rotate, batch_points, background, time)
+        opts = _gather_opts(seed, real_mode, max_depth, samples, rays, first_key, rotate, batch_points, background, time, max_distance)
         self._check(self._lib.rtk_gather_irradiance_host(self._ctx, C.byref(opts), n, points.ctypes.data, normals.ctypes.data, out.ctypes.data))
         return out
 
@@ -1123,9 +1124,10 @@ class Renderer:
 
     def gather_irradiance_device(self, n: int, d_points: int, d_normals: int, d_irradiance: int, *, max_depth: int, rays: int = 256, samples: int = 1,
                                  background=(0.0, 0.0, 0.0), first_key: int = 0, rotate: int = 0, batch_points: int = 0, time: float = 0.0,
-                                 seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
-        """rtk_gather_irradiance with raw device pointers ([n][3] reals of ``real_mode`` out); asynchronous on ``stream``."""
-        opts = _gather_opts(seed, real_mode, max_depth, samples, rays, first_key, rotate, batch_points, background, time, 0.0, stream)
+                                 max_distance: float = 0.0, seed: int = RENDER_SEED, real_mode: int = RTK_REAL_F64, stream: int = 0) -> None:
+        """rtk_gather_irradiance with raw device pointers ([n][3] reals of ``real_mode`` out); asynchronous on ``stream``.
+        ``max_distance`` is checked and changes nothing."""
+        opts = _gather_opts(seed, real_mode, max_depth, samples, rays, first_key, rotate, batch_points, background, time, max_distance, stream)
         self._check(self._lib.rtk_gather_irradiance(self._ctx, C.byref(opts), int(n), d_points or None, d_normals or None, d_irradiance or None))
 
     def gather_occlusion_device(self, n: int, d_points: int, d_normals: int, d_open: int, d_bent: int, *, rays: int = 256, samples: int = 1,

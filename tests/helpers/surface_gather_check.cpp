@@ -1,8 +1,10 @@
 // GPU test helper: rtk::surface_gather of the drop-in C++ API (host/rtk_surface_gather.h) on a library scene built exactly as
 // librtk_host.so builds it.  Gathers irradiance and occlusion at the 3 x 2 texels of the Cornell box's red wall and prints, with
 // 17 significant digits, the texels, their normals and every result; the test compares them with what Python computes.
-//   surface_gather_check <scene> <scene_file> <rays> <max_depth> <samples> <real_mode>
-// The quad, the grid, the reach and the keys are the constants below, restated in tests/test_surface_gather.py.
+//   surface_gather_check <scene> <scene_file> <rays> <max_depth> <samples> <real_mode> [<time>]
+// The quad, the grid, the reach and the keys are the constants below, restated in tests/test_surface_gather.py.  With <time>
+// the class's `time` is set to it, the quad is one under single_fog's moving ball that faces it, and the background is the
+// scene's (restated in tests/test_entry_options.py).
 #include "camera.h"
 #include "mesh.h"
 #include "scenes/scene_library.h"
@@ -12,7 +14,7 @@
 #include <vector>
 
 int main(int argc, char** argv) {
-    if (argc != 7) return 2;
+    if (argc != 7 && argc != 8) return 2;
     rtk::seed_scene_rng(0x5EED2025u);  // SCENE_SEED of the Python package
     rtk_scene_def def;
     if (!rtk_build_named_scene(argv[1], argv[2], def)) return 3;
@@ -29,14 +31,18 @@ int main(int argc, char** argv) {
     gather.real_mode = real_mode;
     gather.first_key = 11;
     gather.samples = samples;
+    const bool timed = argc == 8;
+    if (timed) gather.time = std::atof(argv[7]);
+    const color background = timed ? def.view.background : color(0, 0, 0);
     std::vector<point3> points;
     std::vector<vec3> normals;
-    rtk::surface_gather::quad_texels(point3(0, 0, 0), vec3(0, 555, 0), vec3(0, 0, 555), 3, 2, points, normals);
+    if (timed) rtk::surface_gather::quad_texels(point3(-1.5, -1.25, -1.5), vec3(3, 0, 0), vec3(0, 0, -3), 3, 2, points, normals);
+    else rtk::surface_gather::quad_texels(point3(0, 0, 0), vec3(0, 555, 0), vec3(0, 0, 555), 3, 2, points, normals);
     if (points.size() != 6 || normals.size() != 6) return 6;
     for (const point3& p : points) std::printf("point %.17g %.17g %.17g\n", p.x(), p.y(), p.z());
     for (const vec3& n : normals) std::printf("normal %.17g %.17g %.17g\n", n.x(), n.y(), n.z());
     std::vector<color> e;
-    if (!gather.irradiance(points, normals, rays, max_depth, color(0, 0, 0), e) || e.size() != 6) {
+    if (!gather.irradiance(points, normals, rays, max_depth, background, e) || e.size() != 6) {
         std::printf("surface_gather_check: irradiance failed (%d): %s\n", gather.status(), rtk_last_error());
         return 5;
     }
