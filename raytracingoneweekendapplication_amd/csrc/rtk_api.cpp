@@ -22,6 +22,7 @@
 #include "rtk_ctx.h"
 #include "rtk_device_layout.h"
 #include "rtk_internal.h"
+#include "rtk_lds_plan.h"
 
 namespace rtk {
 
@@ -784,7 +785,7 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
     out.view.kind_words = nullptr;
     out.view.box_rank = nullptr;
     out.view.n_cached_boxes = out.view.n_kind_words = out.view.n_rank_words = 0;
-    if (slots.size() * sizeof(Slot<real>) + mats.size() * sizeof(MaterialRec<real>) > size_t(kLdsBytesPerCU)) {
+    if (lds_plan::wants_box_table(slots.size() * sizeof(Slot<real>), mats.size() * sizeof(MaterialRec<real>))) {
         std::vector<BoxRec<real>> boxes;
         std::vector<uint32_t> kind_words((slots.size() + 7) / 8, 0u);
         std::vector<uint2> rank((slots.size() + 31) / 32, uint2{0u, 0u});
@@ -805,9 +806,9 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
             r.y = before;
             before += uint32_t(__builtin_popcount(r.x));
         }
-        const size_t bytes = boxes.size() * sizeof(BoxRec<real>) + ((kind_words.size() * 4 + 7) & ~size_t(7)) + rank.size() * 8;
+        const size_t bytes = lds_plan::box_table_bytes(boxes.size(), sizeof(BoxRec<real>), kind_words.size(), rank.size());
         if (getenv("RTK_DEBUG")) fprintf(stderr, "[rtk] %zu-byte reals: %zu slots, %zu box slots, boxes + tables %zu B\n", sizeof(real), slots.size(), boxes.size(), bytes);
-        if (!boxes.empty() && bytes + 64 <= size_t(kLdsBytesPerCU)) {
+        if (!boxes.empty() && lds_plan::box_table_fits(bytes)) {
             if ((rc = out.upload(boxes, &out.view.box_cache)) != RTK_OK) return rc;
             if ((rc = out.upload(kind_words, &out.view.kind_words)) != RTK_OK) return rc;
             if ((rc = out.upload(rank, &out.view.box_rank)) != RTK_OK) return rc;
@@ -857,7 +858,7 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
                 std::vector<uint32_t> ranks_by_id;
                 build_hot_cold_program(sc, prog, hot, cold, ranks_by_id);
                 if (getenv("RTK_DEBUG")) fprintf(stderr, "[rtk] COMPACT program %zu B; hot part %zu B, cold part %zu B\n", units.size() * 16, hot.size() * 16, cold.size() * 16);
-                if (hot.size() * sizeof(Unit16) + mats.size() * sizeof(MaterialRec<real>) + 64 <= size_t(kLdsBytesPerCU) && hot.size() < (size_t(1) << 24)) {
+                if (lds_plan::hot_fits(hot.size() * sizeof(Unit16), mats.size() * sizeof(MaterialRec<real>)) && hot.size() < (size_t(1) << 24)) {
                     if ((rc = out.upload(hot, &out.view.program_hot)) != RTK_OK) return rc;
                     if ((rc = out.upload(cold, &out.view.program_cold)) != RTK_OK) return rc;
                     if ((rc = out.upload(ranks_by_id, &out.view.tie_rank_hot)) != RTK_OK) return rc;

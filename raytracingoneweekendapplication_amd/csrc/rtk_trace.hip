@@ -34,6 +34,7 @@
 #include "rtk_device_math.h"
 #include "rtk_gather_rule.h"
 #include "rtk_image_pass.h"
+#include "rtk_lds_plan.h"
 #include "rtk_trace.h"
 
 namespace rtk {
@@ -2380,7 +2381,7 @@ static hipError_t plan_launch(Kernel kernel, int kMaxWavesPerBlock, size_t lds_b
     hipError_t e = hipGetDevice(&device);
     if (e != hipSuccess) return e;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (lds_bytes > 64 * 1024) {
+    if (lds_plan::needs_opt_in(lds_bytes)) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes));
         if (e != hipSuccess) return e;
     }
@@ -2390,7 +2391,7 @@ static hipError_t plan_launch(Kernel kernel, int kMaxWavesPerBlock, size_t lds_b
     if (waves_per_cu > 32) waves_per_cu = 32;
     int blocks_per_cu = (waves_per_cu + kMaxWavesPerBlock - 1) / kMaxWavesPerBlock;
     if (lds_bytes > 0) {
-        const int by_lds = int(kLdsBytesPerCU / lds_bytes);
+        const int by_lds = lds_plan::workgroups_per_cu(lds_bytes);
         if (by_lds < 1) return hipErrorInvalidValue;
         if (blocks_per_cu > by_lds) blocks_per_cu = by_lds;
     }
@@ -2408,21 +2409,32 @@ static hipError_t plan_launch(Kernel kernel, int kMaxWavesPerBlock, size_t lds_b
     return hipSuccess;
 }
 
-// Bytes a workgroup stages in LDS: the traversal program (MIXED or slots) followed by the material table.
-// `feat` = the kernel's FEAT word: F_F32_BOX selects the MIXED program (lean family) or the COMPACT one (the others).
-static bool is_compact(uint32_t feat) { return (feat & F_F32_BOX) != 0 && (feat & ~uint32_t(F_F32_BOX | F_MATTE | F_LDS_BOXES)) != kFeatLean; }
+// What a workgroup stages in LDS and where: rtk_lds_plan.h decides, from the scene's record counts and the kernel's FEAT word
+// (F_F32_BOX selects the MIXED program in the lean family and the COMPACT one in the others).
+static_assert(lds_plan::kCapacity == size_t(kLdsBytesPerCU) && lds_plan::kXform == F_XFORM && lds_plan::kTexture == F_TEXTURE && lds_plan::kF32Box == F_F32_BOX &&
+              lds_plan::kMatte == F_MATTE && lds_plan::kLdsBoxes == F_LDS_BOXES && lds_plan::kLeanFamily == kFeatLean, "rtk_lds_plan.h restates rtk_device_layout.h");
+static_assert(lds_plan::kMixedUnitBytes == sizeof(MixedHead) && lds_plan::kUnit16Bytes == sizeof(Unit16), "rtk_lds_plan.h restates rtk_device_layout.h");
 template <typename real>
-static size_t lds_image_bytes(const SceneView<real>& sc, uint32_t feat) {
-    const size_t program = is_compact(feat) ? size_t(sc.n_units16) * sizeof(Unit16)
-                                            : ((feat & F_F32_BOX) ? size_t(sc.n_units) * sizeof(MixedHead) : size_t(sc.n_slots) * sizeof(Slot<real>));
-    return program + size_t(sc.n_materials) * sizeof(MaterialRec<real>);
+static constexpr lds_plan::RecordSizes lds_record_sizes() {
+    constexpr lds_plan::RecordSizes s = sizeof(real) == 8 ? lds_plan::kSizesF64 : lds_plan::kSizesF32;
+    static_assert(s.slot == sizeof(Slot<real>) && s.box == sizeof(BoxRec<real>) && s.material == sizeof(MaterialRec<real>) && s.perlin == sizeof(PerlinRec<real>) &&
+                  s.chain == sizeof(ChainRec<real>), "rtk_lds_plan.h restates rtk_device_layout.h");
+    return s;
 }
-
-// F_LDS_BOXES kernels: the box slots, the kind nibbles (padded to 8 bytes) and the rank table.
 template <typename real>
-static size_t split_lds_bytes(const SceneView<real>& sc, uint32_t feat) {
-    if (is_compact(feat)) return size_t(sc.n_hot_units) * sizeof(Unit16) + size_t(sc.n_materials) * sizeof(MaterialRec<real>);  // COLD: hot program + materials
-    return size_t(sc.n_cached_boxes) * sizeof(BoxRec<real>) + ((size_t(sc.n_kind_words) * 4 + 7) & ~size_t(7)) + size_t(sc.n_rank_words) * 8;
+static lds_plan::Counts lds_counts(const SceneView<real>& sc) {
+    lds_plan::Counts n;
+    n.slots = size_t(sc.n_slots);
+    n.units = size_t(sc.n_units);
+    n.units16 = size_t(sc.n_units16);
+    n.hot_units = size_t(sc.n_hot_units);
+    n.cached_boxes = size_t(sc.n_cached_boxes);
+    n.kind_words = size_t(sc.n_kind_words);
+    n.rank_words = size_t(sc.n_rank_words);
+    n.materials = size_t(sc.n_materials);
+    n.perlins = size_t(sc.n_perlins);
+    n.chains = size_t(sc.n_chains);
+    return n;
 }
 template <typename real, uint32_t FEAT, bool COUNT, bool IN_LDS>
 static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* cam, const TileMap& tmap, uint32_t seed, void* partial,
@@ -2432,44 +2444,18 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
     if (n_items <= 0) return hipSuccess;
     if (views != nullptr && !has_view_kernel(FEAT, COUNT, IN_LDS)) return hipErrorInvalidValue;  // (the caller asks view_kernel_name first)
     auto kernel = rtk_render_kernel<real, FEAT, COUNT, IN_LDS>;
-    size_t lds = IN_LDS ? lds_image_bytes(sc, FEAT) : ((FEAT & F_LDS_BOXES) ? split_lds_bytes(sc, FEAT) : 0);
+    const lds_plan::Plan plan = lds_plan::plan(lds_counts(sc), lds_record_sizes<real>(), FEAT, IN_LDS, size_t(tmap.n_tiles_local), tile_order != nullptr);
+    const size_t lds = plan.total;
     TileMap tm = tmap;
-    tm.mats_lds_offset = 0;
-    tm.perlin_lds_offset = 0;
-    if constexpr ((FEAT & F_LDS_BOXES) != 0) {  // boxes-in-LDS kernels: the material table too, if it is small and there is room
-        const size_t mat_bytes = size_t(sc.n_materials) * sizeof(MaterialRec<real>);
-        const size_t at = (lds + 15) & ~size_t(15);
-        if (!is_compact(FEAT) /* (COLD kernels always stage it, right behind the hot program) */ && mat_bytes <= 16 * 1024 &&
-            at + mat_bytes + 64 <= size_t(kLdsBytesPerCU)) {
-            tm.mats_lds_offset = int32_t(at);
-            lds = at + mat_bytes;
-        }
-        // ... and the Perlin tables (book-2's noise sphere: 7.8 % of the C5 frame went into perlin::turb's dependent gathers from memory)
-        const size_t perlin_bytes = size_t(sc.n_perlins) * sizeof(PerlinRec<real>);
-        const size_t pat = (lds + 15) & ~size_t(15);
-        if ((FEAT & F_TEXTURE) != 0 && perlin_bytes > 0 && pat + perlin_bytes + 64 <= size_t(kLdsBytesPerCU)) {
-            tm.perlin_lds_offset = int32_t(pat);
-            lds = pat + perlin_bytes;
-        }
-    }
-    tm.chains_lds_offset = 0;
-    if constexpr ((FEAT & F_XFORM) != 0 && (IN_LDS || (FEAT & F_LDS_BOXES) != 0)) {
-        const size_t chain_bytes = size_t(sc.n_chains) * sizeof(ChainRec<real>);
-        const size_t cat = (lds + 15) & ~size_t(15);
-        if (sc.n_chains > 1 && chain_bytes <= 8192 && cat + chain_bytes + 64 <= size_t(kLdsBytesPerCU)) {
-            tm.chains_lds_offset = int32_t(cat);
-            lds = cat + chain_bytes;
-        }
-    }
-    // room for the tile order behind the program?  (never at the price of a second resident workgroup's LDS)
-    tm.order_in_lds = 0;
-    tm.order_lds_offset = int32_t((lds + 15) & ~size_t(15));
-    const size_t order_bytes = size_t(tmap.n_tiles_local) * sizeof(int32_t);
-    if (tile_order && size_t(tm.order_lds_offset) + order_bytes <= size_t(kLdsBytesPerCU) &&
-        (lds == 0 || kLdsBytesPerCU / lds == kLdsBytesPerCU / (size_t(tm.order_lds_offset) + order_bytes))) {
-        tm.order_in_lds = 1;
-        lds = size_t(tm.order_lds_offset) + order_bytes;
-    }
+    tm.mats_lds_offset = plan.mats_lds_offset;
+    tm.perlin_lds_offset = plan.perlin_lds_offset;
+    tm.chains_lds_offset = plan.chains_lds_offset;
+    tm.order_in_lds = plan.order_in_lds;
+    tm.order_lds_offset = plan.order_lds_offset;
+    if (getenv("RTK_DEBUG"))
+        fprintf(stderr, "[rtk] lds plan: real %zu FEAT %u IN_LDS %d views %d: total %zu B, mats_lds_offset %d, perlin_lds_offset %d, chains_lds_offset %d, order_in_lds %d, order_lds_offset %d\n",
+                sizeof(real), unsigned(FEAT), int(IN_LDS), int(views != nullptr), lds, int(tm.mats_lds_offset), int(tm.perlin_lds_offset), int(tm.chains_lds_offset),
+                int(tm.order_in_lds), int(tm.order_lds_offset));
     int blocks = 0, threads = 0;
     if constexpr (has_view_kernel(FEAT, COUNT, IN_LDS)) {
         if (views != nullptr) {  // the view kernel: the same staging plan, its own occupancy
@@ -2538,12 +2524,11 @@ static KernelChoice choose_kernel(const SceneView<real>& sc, uint32_t features, 
         // than the slot program split the same way, measured: C4 with 4 494 ops 175 ms against 95 ms, C5 714 against 838
         // Msamples/s (there the coordinates run into the thousands -- a fog boundary of radius 5000 -- and the 2^-19 x extent
         // margin exceeds a quad's own box thickness: +55 % quad tests).
-        const size_t bytes = size_t(sc.n_units16) * sizeof(Unit16) + size_t(sc.n_materials) * sizeof(MaterialRec<real>);
-        if (!(allow_lds && bytes <= size_t(kLdsBytesPerCU)) || (diag & (1u << 23)) != 0) {  // (variant bit 23: the hot/cold form although the whole would fit)
+        const size_t mat_bytes = size_t(sc.n_materials) * sizeof(MaterialRec<real>);
+        if (!(allow_lds && lds_plan::whole_fits(size_t(sc.n_units16) * sizeof(Unit16), mat_bytes)) || (diag & (1u << 23)) != 0) {  // (variant bit 23: the hot/cold form although the whole would fit)
             // ... unless its hot part does (COLD kernels: quads and triangles stay in memory, everything else in LDS) -- full-feature family, timed kernels
-            const size_t hot = size_t(sc.n_hot_units) * sizeof(Unit16) + size_t(sc.n_materials) * sizeof(MaterialRec<real>);
             const uint32_t scene = features & ~uint32_t(F_FMA_BOX | F_MATTE | F_SPHERE_MEDIA_ONLY);
-            cold = allow_lds && !count && sc.program_hot != nullptr && hot + 64 <= size_t(kLdsBytesPerCU) && (diag & (1u << 21)) == 0 &&
+            cold = allow_lds && !count && sc.program_hot != nullptr && lds_plan::hot_fits(size_t(sc.n_hot_units) * sizeof(Unit16), mat_bytes) && (diag & (1u << 21)) == 0 &&
                    (scene & ~kFeatQuadBox) != 0 && (scene & ~kFeatMesh) != 0;
             compact = cold;
         }
@@ -2551,9 +2536,9 @@ static KernelChoice choose_kernel(const SceneView<real>& sc, uint32_t features, 
     // the matte variants pay off in f64 only (C3: f64 34.8 -> 31.9 ms, f32 26.6 -> 36.5 ms at one more wave per SIMD)
     KernelChoice k{kernel_features(sizeof(real) == 8 ? features : (features & ~uint32_t(F_MATTE)), count, mixed, compact), count, false};
     const uint32_t scene = k.feat & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE | F_SPHERE_MEDIA_ONLY);
-    const bool fits = allow_lds && lds_image_bytes(sc, k.feat) <= size_t(kLdsBytesPerCU);
+    const bool fits = allow_lds && lds_plan::whole_fits(lds_plan::image_bytes(lds_counts(sc), lds_record_sizes<real>(), k.feat), 0);
     if (count) {  // counting builds: only the MIXED one stages its program (it is the timed kernel with counters)
-        k.in_lds = fits && (k.feat & F_F32_BOX) != 0 && !is_compact(k.feat);
+        k.in_lds = fits && (k.feat & F_F32_BOX) != 0 && !lds_plan::is_compact(k.feat);
         return k;
     }
     k.in_lds = fits;
