@@ -46,6 +46,7 @@
 #include <cstring>
 #include <limits>
 #include <new>
+#include <queue>
 #include <unordered_set>
 #include <utility>
 #include <vector>
@@ -120,7 +121,6 @@ struct Optimizer {
     bool failed = false;
     bool has_media = false;
     double margin = 0.0, tri_margin = 0.0;
-    int split_depth = 0;
     bool has_triangles = false;
     int64_t n_bvh_in = 0;
 
@@ -378,21 +378,34 @@ struct Optimizer {
         return !(e && e[0] == '0');
     }();
 
-    // One side of a split: the cheaper of "test the items one after the other" and "a box, then recurse".
-    Built represent(std::vector<Item>& items, size_t begin, size_t end, const Box& parent) {
+    // build_items works in three stages over the same items: BUILD a plain binary tree by full-sweep SAH splits, REFINE it by
+    // subtree reinsertion, EMIT it bottom-up into output nodes under the pricing rules.  RTK_OPT_REINSERT=0 skips the second
+    // stage (tools/: A/B); the emitted description then is node for node what the greedy pass alone gives.
+    bool reinsert = true;
+
+    // ---- stage 1: build.  Leaves are items, an inner node is the box of its items plus two children; `left` is the lower side
+    // of the split.  Nothing is priced and nothing is emitted here.
+    struct TNode {
+        Box box;
+        double linear;  // sum of the items' costs: what testing them one after the other costs (a leaf: the item's cost)
+        int32_t parent, left, right;
+        int32_t item;   // a leaf: its item's position
+        int32_t count;  // items below
+    };
+    struct Tree {
+        std::vector<TNode> n;
+        int32_t root = -1;
+        int depth = 0;
+    };
+
+    // The tree over items[begin, end): full-sweep SAH on the three axes.  The items are sorted in place, so that afterwards
+    // the leaves, left to right, are the items in array order.
+    int32_t build_tree(std::vector<Item>& items, size_t begin, size_t end, Tree& t, int depth) {
+        const int32_t self = int32_t(t.n.size());
+        t.depth = std::max(t.depth, depth);
         if (end - begin == 1) {
-            // An expensive item (an instance, a medium) whose own box is much smaller than the box it sits in gets a
-            // slab test of its own: a bvh_node whose second child is an empty list.
-            const Item& it = items[begin];
-            const double pa = parent.area();
-            const double boxed = kBoxCost + (pa > 0 ? std::min(1.0, it.box.area() / pa) : 1.0) * it.cost;
-            if (boxed < it.cost) {
-                const Box padded = grown(it.box, margin);
-                out.boxes.push_back(rtk_aabb{padded.lo[0], padded.hi[0], padded.lo[1], padded.hi[1], padded.lo[2], padded.hi[2]});
-                const int32_t nothing = push_node(RTK_NODE_LIST, int32_t(out.children.size()), 0, 0);
-                return Built{push_node(RTK_NODE_BVH, it.node, nothing, int32_t(out.boxes.size()) - 1), boxed, kBoxCost};
-            }
-            return Built{it.node, it.cost, it.cost};
+            t.n.push_back(TNode{items[begin].box, items[begin].cost, -1, -1, -1, int32_t(begin), 1});
+            return self;
         }
         double linear = 0;
         Box b = Box::empty();
@@ -400,48 +413,7 @@ struct Optimizer {
             linear += items[k].cost;
             b.grow(items[k].box);
         }
-        const size_t nodes_mark = out.nodes.size(), child_mark = out.children.size(), box_mark = out.boxes.size();
-        Built l{-1, 0, 0}, r{-1, 0, 0};
-        Built inner = split(items, begin, end, b, &l, &r);
-        const double pa = parent.area();
-        const double pb = pa > 0 ? std::min(1.0, b.area() / pa) : 1.0;
-        const double boxed = kBoxCost + pb * inner.cost;
-        const double bare = flatten ? pb * inner.cost + (1.0 - pb) * (l.first + r.first) : std::numeric_limits<double>::infinity();
-        if (int(end - begin) <= opts.max_leaf && linear <= boxed && linear <= bare) {
-            out.nodes.resize(nodes_mark);  // discard the subtree just built (primitive nodes were created earlier)
-            out.children.resize(child_mark);
-            out.boxes.resize(box_mark);
-            // nearest first inside a leaf as well
-            order_items(items, begin, end);
-            return Built{emit_list(items, begin, end), linear, linear};
-        }
-        if (bare < boxed && inner.node == int32_t(out.nodes.size()) - 1 && out.nodes.back().kind == RTK_NODE_BVH &&
-            out.nodes.back().c == int32_t(out.boxes.size()) - 1) {
-            // the pair's own node and box were pushed last: drop them, hand its two members (in their visiting order) to the caller
-            const int32_t first_member = out.nodes.back().a, second_member = out.nodes.back().b;
-            out.nodes.pop_back();
-            out.boxes.pop_back();
-            const int32_t at = int32_t(out.children.size());
-            out.children.push_back(first_member);
-            out.children.push_back(second_member);
-            return Built{push_node(RTK_NODE_LIST, at, 2, 0), bare, l.first + r.first};
-        }
-        return Built{inner.node, boxed, kBoxCost};
-    }
-
-    void order_items(std::vector<Item>& items, size_t begin, size_t end) {
-        if (!opts.has_eye) return;
-        const double eye[3] = {opts.eye.x, opts.eye.y, opts.eye.z};
-        std::stable_sort(items.begin() + long(begin), items.begin() + long(end),
-                         [&](const Item& a, const Item& b) { return key(a.box, eye) < key(b.box, eye); });
-    }
-    static double key(const Box& b, const double eye[3]) {
-        const double c[3] = {b.centre(0) - eye[0], b.centre(1) - eye[1], b.centre(2) - eye[2]};
-        return b.distance2(eye) + 1e-6 * (c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-    }
-
-    // A BVH node over items[begin, end) (>= 2 items) whose box is `b`: full-sweep SAH on the three axes.
-    Built split(std::vector<Item>& items, size_t begin, size_t end, const Box& b, Built* left_out = nullptr, Built* right_out = nullptr) {
+        t.n.push_back(TNode{b, linear, -1, -1, -1, -1, int32_t(end - begin)});
         const size_t n = end - begin;
         int best_axis = -1;
         size_t best_k = 0;
@@ -475,7 +447,7 @@ struct Optimizer {
         }
         // Degenerate inputs (thousands of coincident boxes) can make the heuristic peel off one item per level; past a
         // depth no sane hierarchy needs, split at the median instead so that recursion depth and work stay bounded.
-        if (split_depth > 48 && (best_k == 1 || best_k + 1 == n)) best_k = n / 2;
+        if (depth > 48 && (best_k == 1 || best_k + 1 == n)) best_k = n / 2;
         if (best_axis < 0) {  // no finite cost at all (cannot happen for the finite boxes convert() lets through): median of the last sort
             best_axis = 2;
             best_k = n / 2;
@@ -486,16 +458,320 @@ struct Optimizer {
                 return cx != cy ? cx < cy : x.node < y.node;
             });
         const size_t mid = begin + best_k;
-        split_depth++;
-        Built l = represent(items, begin, mid, b);
-        Built r = represent(items, mid, end, b);
-        split_depth--;
+        const int32_t l = build_tree(items, begin, mid, t, depth + 1);
+        const int32_t r = build_tree(items, mid, end, t, depth + 1);
+        t.n[size_t(self)].left = l;
+        t.n[size_t(self)].right = r;
+        t.n[size_t(l)].parent = t.n[size_t(r)].parent = self;
+        return self;
+    }
+
+    // ---- stage 2: refine.  Insertion-based optimisation (Bittner, Hapala, Havran 2013): the greedy build never revisits a
+    // split, so one large item that lands deep in the tree (a unit sphere among the small ones of the book-1 scene) inflates
+    // every box above it.  A move takes an inner node out, hands its sibling to the grandparent, and puts the node's two
+    // children back one by one where the tree's cost grows least; it is priced exactly and taken back unless it pays.
+    // The tree's cost is what the pricing rules of stage 3 come to without lists and dropped boxes: every inner node pays its
+    // area times one slab test, every item its cost times the area of the box it sits in -- or a slab test there and its
+    // cost in its own box, where that is cheaper.  A round goes through the inner nodes, worst first.  Everything is
+    // ordered by value, then by node index, and nothing depends on an address: two runs on one input give the same tree.
+    static constexpr int kReinsertRounds = 2;       // the first round gives nearly all there is; the host time is per upload
+    static constexpr double kReinsertGain = 1e-3;   // a round that gains less ends the stage
+    static constexpr int kReinsertVisits = 64;      // nodes one search may open: bounds the work on degenerate inputs (nested boxes)
+    static constexpr int kReinsertDepth = 96;       // a refined tree deeper than this is not taken
+
+    static double tree_cost(const Tree& t) {
+        double c = 0;
+        for (const TNode& v : t.n) {
+            if (v.left < 0) continue;
+            c += contribution(t, v);
+        }
+        return c;
+    }
+    static bool same_box(const Box& a, const Box& b) { return std::memcmp(&a, &b, sizeof(Box)) == 0; }
+    // A move keeps the earlier state of every node it changes, so that it can be priced exactly and taken back.
+    struct Undo {
+        std::vector<std::pair<int32_t, TNode>> was;
+        std::vector<int32_t> stamp;  // node -> the last move that saved it
+        int32_t move = 0;
+    };
+    static TNode& touch(Tree& t, Undo& u, int32_t v) {
+        if (u.stamp[size_t(v)] != u.move) {
+            u.stamp[size_t(v)] = u.move;
+            u.was.push_back({v, t.n[size_t(v)]});
+        }
+        return t.n[size_t(v)];
+    }
+    // boxes from `v` up to the root, after something below `v` was taken out
+    static void refit_up(Tree& t, Undo& u, int32_t v) {
+        for (; v >= 0; v = t.n[size_t(v)].parent) {
+            const TNode& x = t.n[size_t(v)];
+            Box b = t.n[size_t(x.left)].box;
+            b.grow(t.n[size_t(x.right)].box);
+            if (same_box(b, x.box)) break;
+            touch(t, u, v).box = b;
+        }
+    }
+    // What a ray that enters a box of area `area` pays for the child `c` on top of the box's own slab test, times that area:
+    // nothing for an inner node (it pays for itself), an item's cost -- or, where that is cheaper, a slab test of its own and
+    // its cost only inside its own box (represent() gives an expensive item in a much larger box just that).
+    static double pays(const TNode& c, double area) {
+        if (c.left >= 0) return 0.0;
+        return std::min(area * c.linear, area * kBoxCost + c.box.area() * c.linear);
+    }
+    static double contribution(const Tree& t, const TNode& v, double area) {
+        return area * kBoxCost + pays(t.n[size_t(v.left)], area) + pays(t.n[size_t(v.right)], area);
+    }
+    static double contribution(const Tree& t, const TNode& v) { return contribution(t, v, v.box.area()); }
+    // The node beside which the detached subtree `sub` raises the tree's cost least.  Beside `x`, under x's parent p: a new
+    // pair's box, in which `sub` and `x` pay from now on; every box above grows by `sub`, and what it and its items pay grows
+    // with it; an item `x` no longer pays in p's box.  Branch and bound from the root, least growth first: below `x` a
+    // position costs at least the growth so far plus a pair's box no larger than `sub`'s.  (Less what an item `x` saves by
+    // moving into a smaller box -- the bound ignores that, so the search is a heuristic there; refine() prices every move
+    // exactly and takes back one that does not pay.)
+    static int32_t find_position(const Tree& t, int32_t sub) {
+        struct Open {
+            double bound, induced;
+            int32_t node;
+        };
+        const auto later = [](const Open& a, const Open& b) { return a.bound != b.bound ? a.bound > b.bound : a.node > b.node; };
+        std::priority_queue<Open, std::vector<Open>, decltype(later)> open(later);
+        const TNode& s = t.n[size_t(sub)];
+        const double sa = s.box.area(), least = sa * kBoxCost + pays(s, sa);
+        double best = std::numeric_limits<double>::infinity();
+        int32_t best_node = t.root;
+        open.push(Open{-best, 0.0, t.root});
+        for (int visits = 0; !open.empty() && visits < kReinsertVisits; visits++) {
+            const Open o = open.top();
+            open.pop();
+            if (o.bound >= best) break;
+            const TNode& x = t.n[size_t(o.node)];
+            Box u = x.box;
+            u.grow(s.box);
+            const double ua = u.area();
+            double total = o.induced + ua * kBoxCost + pays(s, ua) + pays(x, ua);
+            if (x.left < 0 && x.parent >= 0) {
+                Box pu = t.n[size_t(x.parent)].box;
+                pu.grow(s.box);
+                total -= pays(x, pu.area());
+            }
+            if (total < best) {
+                best = total;
+                best_node = o.node;
+            }
+            if (x.left < 0) continue;
+            const double induced = o.induced + (contribution(t, x, ua) - contribution(t, x));
+            const double bound = induced + least;
+            if (bound < best) {
+                open.push(Open{bound, induced, x.left});
+                open.push(Open{bound, induced, x.right});
+            }
+        }
+        return best_node;
+    }
+    // `sub` (detached) goes beside the best position, under the free inner node `slot`
+    static void insert_at_best(Tree& t, Undo& u, int32_t sub, int32_t slot) {
+        const int32_t x = find_position(t, sub);
+        const int32_t px = t.n[size_t(x)].parent;
+        const Box sb = t.n[size_t(sub)].box;
+        TNode& s = touch(t, u, slot);
+        s.left = x;
+        s.right = sub;
+        s.parent = px;
+        s.box = t.n[size_t(x)].box;
+        s.box.grow(sb);
+        touch(t, u, x).parent = slot;
+        touch(t, u, sub).parent = slot;
+        if (px < 0) {
+            t.root = slot;
+            return;
+        }
+        TNode& above = touch(t, u, px);
+        (above.left == x ? above.left : above.right) = slot;
+        for (int32_t a = px; a >= 0; a = t.n[size_t(a)].parent) {
+            Box b = t.n[size_t(a)].box;
+            b.grow(sb);
+            if (same_box(b, t.n[size_t(a)].box)) break;
+            touch(t, u, a).box = b;
+        }
+    }
+    // count, linear and depth of every node from the links (boxes are kept exact by the moves themselves); false: too deep
+    static bool settle(Tree& t) {
+        std::vector<std::pair<int32_t, int>> stack{{t.root, 0}};  // node, depth: pre-order ...
+        std::vector<int32_t> order;
+        order.reserve(t.n.size());
+        t.depth = 0;
+        while (!stack.empty()) {
+            const auto [v, d] = stack.back();
+            stack.pop_back();
+            order.push_back(v);
+            t.depth = std::max(t.depth, d);
+            if (t.n[size_t(v)].left >= 0) {
+                stack.push_back({t.n[size_t(v)].right, d + 1});
+                stack.push_back({t.n[size_t(v)].left, d + 1});
+            }
+        }
+        if (t.depth > kReinsertDepth) return false;
+        for (size_t k = order.size(); k-- > 0;) {  // ... reversed: children before parents
+            TNode& x = t.n[size_t(order[k])];
+            if (x.left < 0) continue;
+            x.count = t.n[size_t(x.left)].count + t.n[size_t(x.right)].count;
+            x.linear = t.n[size_t(x.left)].linear + t.n[size_t(x.right)].linear;
+        }
+        return true;
+    }
+    // true: `t` is now a tree of lower cost (false: `t` is of no use)
+    bool refine(Tree& t) {
+        if (t.n.size() < 5) return false;  // two items: one shape only
+        const double greedy_cost = tree_cost(t);
+        double cost = greedy_cost;
+        Undo u;
+        u.stamp.assign(t.n.size(), 0);
+        std::vector<std::pair<double, int32_t>> worst;
+        for (int round = 0; round < kReinsertRounds; round++) {
+            worst.clear();
+            for (int32_t v = 0; v < int32_t(t.n.size()); v++) {
+                const TNode& x = t.n[size_t(v)];
+                if (x.left < 0 || x.parent < 0) continue;
+                const double a = x.box.area(), m = std::min(t.n[size_t(x.left)].box.area(), t.n[size_t(x.right)].box.area());
+                worst.push_back({a * (a / std::max(m, 1e-300)), v});
+            }
+            std::stable_sort(worst.begin(), worst.end(), [](const std::pair<double, int32_t>& a, const std::pair<double, int32_t>& b) {
+                return a.first != b.first ? a.first > b.first : a.second < b.second;
+            });
+            for (const auto& w : worst) {
+                const int32_t v = w.second, p = t.n[size_t(v)].parent;
+                if (p < 0) continue;  // an earlier move of this round made it the root
+                u.move++;
+                u.was.clear();
+                const int32_t old_root = t.root;
+                const int32_t l = t.n[size_t(v)].left, r = t.n[size_t(v)].right, g = t.n[size_t(p)].parent;
+                const int32_t s = t.n[size_t(p)].left == v ? t.n[size_t(p)].right : t.n[size_t(p)].left;
+                touch(t, u, v);
+                touch(t, u, p);
+                touch(t, u, s).parent = g;
+                if (g < 0) {
+                    t.root = s;
+                } else {
+                    TNode& above = touch(t, u, g);
+                    (above.left == p ? above.left : above.right) = s;
+                    refit_up(t, u, g);
+                }
+                touch(t, u, l).parent = -1;
+                touch(t, u, r).parent = -1;
+                const bool left_first = t.n[size_t(l)].box.area() >= t.n[size_t(r)].box.area();  // the larger one first
+                insert_at_best(t, u, left_first ? l : r, v);
+                insert_at_best(t, u, left_first ? r : l, p);
+                // what the move did to the tree's cost: only the saved nodes pay differently (an item keeps its cost, and the
+                // box it pays in is its parent's, saved whenever it changed)
+                double before = 0, after = 0;
+                for (const auto& [k, old] : u.was) {
+                    if (old.left < 0) continue;
+                    before += contribution(t, old);
+                    after += contribution(t, t.n[size_t(k)]);
+                }
+                if (after < before) continue;
+                for (size_t k = u.was.size(); k-- > 0;) t.n[size_t(u.was[k].first)] = u.was[k].second;
+                t.root = old_root;
+            }
+            // A round that gains less than kReinsertGain ends the stage -- relative to what lies below the root: the root's own
+            // term hardly moves, and where one huge item sits beside everything else (the ground sphere of the book scenes) it
+            // is all but the whole sum.
+            const double c = tree_cost(t);
+            const TNode& top = t.n[size_t(t.root)];
+            const bool enough = cost - c > kReinsertGain * (cost - contribution(t, top));
+            cost = c;
+            if (!enough) break;
+        }
+        return cost < greedy_cost && settle(t);
+    }
+
+    // ---- stage 3: emit.  The items in the order of the tree's leaves, left to right; every node owns a range of them.
+    struct Emitter {
+        const Tree& t;
+        std::vector<Item> items;
+        std::vector<int32_t> first;  // node -> where its range starts (it is `count` long)
+    };
+    void lay_out(Emitter& e, const std::vector<Item>& items, int32_t v) {
+        const TNode& x = e.t.n[size_t(v)];
+        e.first[size_t(v)] = int32_t(e.items.size());
+        if (x.left < 0) {
+            e.items.push_back(items[size_t(x.item)]);
+            return;
+        }
+        lay_out(e, items, x.left);
+        lay_out(e, items, x.right);
+    }
+
+    // One side of a pair: the cheaper of "test the items one after the other" and "a box, then recurse".
+    Built represent(Emitter& e, int32_t v, const Box& parent) {
+        const TNode& x = e.t.n[size_t(v)];
+        std::vector<Item>& items = e.items;
+        const size_t begin = size_t(e.first[size_t(v)]), end = begin + size_t(x.count);
+        if (x.left < 0) {
+            // An expensive item (an instance, a medium) whose own box is much smaller than the box it sits in gets a
+            // slab test of its own: a bvh_node whose second child is an empty list.
+            const Item& it = items[begin];
+            const double pa = parent.area();
+            const double boxed = kBoxCost + (pa > 0 ? std::min(1.0, it.box.area() / pa) : 1.0) * it.cost;
+            if (boxed < it.cost) {
+                const Box padded = grown(it.box, margin);
+                out.boxes.push_back(rtk_aabb{padded.lo[0], padded.hi[0], padded.lo[1], padded.hi[1], padded.lo[2], padded.hi[2]});
+                const int32_t nothing = push_node(RTK_NODE_LIST, int32_t(out.children.size()), 0, 0);
+                return Built{push_node(RTK_NODE_BVH, it.node, nothing, int32_t(out.boxes.size()) - 1), boxed, kBoxCost};
+            }
+            return Built{it.node, it.cost, it.cost};
+        }
+        const double linear = x.linear;
+        const Box& b = x.box;
+        const size_t nodes_mark = out.nodes.size(), child_mark = out.children.size(), box_mark = out.boxes.size();
+        Built l{-1, 0, 0}, r{-1, 0, 0};
+        Built inner = pair(e, v, &l, &r);
+        const double pa = parent.area();
+        const double pb = pa > 0 ? std::min(1.0, b.area() / pa) : 1.0;
+        const double boxed = kBoxCost + pb * inner.cost;
+        const double bare = flatten ? pb * inner.cost + (1.0 - pb) * (l.first + r.first) : std::numeric_limits<double>::infinity();
+        if (x.count <= opts.max_leaf && linear <= boxed && linear <= bare) {
+            out.nodes.resize(nodes_mark);  // discard the subtree just emitted (primitive nodes were created earlier)
+            out.children.resize(child_mark);
+            out.boxes.resize(box_mark);
+            // nearest first inside a leaf as well
+            order_items(items, begin, end);
+            return Built{emit_list(items, begin, end), linear, linear};
+        }
+        if (bare < boxed && inner.node == int32_t(out.nodes.size()) - 1 && out.nodes.back().kind == RTK_NODE_BVH &&
+            out.nodes.back().c == int32_t(out.boxes.size()) - 1) {
+            // the pair's own node and box were pushed last: drop them, hand its two members (in their visiting order) to the caller
+            const int32_t first_member = out.nodes.back().a, second_member = out.nodes.back().b;
+            out.nodes.pop_back();
+            out.boxes.pop_back();
+            const int32_t at = int32_t(out.children.size());
+            out.children.push_back(first_member);
+            out.children.push_back(second_member);
+            return Built{push_node(RTK_NODE_LIST, at, 2, 0), bare, l.first + r.first};
+        }
+        return Built{inner.node, boxed, kBoxCost};
+    }
+
+    void order_items(std::vector<Item>& items, size_t begin, size_t end) {
+        if (!opts.has_eye) return;
+        const double eye[3] = {opts.eye.x, opts.eye.y, opts.eye.z};
+        std::stable_sort(items.begin() + long(begin), items.begin() + long(end),
+                         [&](const Item& a, const Item& b) { return key(a.box, eye) < key(b.box, eye); });
+    }
+    static double key(const Box& b, const double eye[3]) {
+        const double c[3] = {b.centre(0) - eye[0], b.centre(1) - eye[1], b.centre(2) - eye[2]};
+        return b.distance2(eye) + 1e-6 * (c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    }
+
+    // The BVH node of the inner tree node `v`: its two sides, then its own box and node.
+    Built pair(Emitter& e, int32_t v, Built* left_out = nullptr, Built* right_out = nullptr) {
+        const TNode& x = e.t.n[size_t(v)];
+        Built l = represent(e, x.left, x.box);
+        Built r = represent(e, x.right, x.box);
         // visiting order of the two children (bvh.h:68-69 visits `left` first): nearer to the eye first; without
         // an eye, the side that is more likely to be hit
         bool swap = false;
-        Box lb = Box::empty(), rb = Box::empty();
-        for (size_t k = begin; k < mid; k++) lb.grow(items[k].box);
-        for (size_t k = mid; k < end; k++) rb.grow(items[k].box);
+        const Box &lb = e.t.n[size_t(x.left)].box, &rb = e.t.n[size_t(x.right)].box;
         if (opts.has_eye) {
             const double eye[3] = {opts.eye.x, opts.eye.y, opts.eye.z};
             swap = key(rb, eye) < key(lb, eye);
@@ -503,12 +779,31 @@ struct Optimizer {
             swap = rb.area() > lb.area();
         }
         if (swap) std::swap(l, r);
-        const Box padded = grown(b, margin);
+        const Box padded = grown(x.box, margin);
         out.boxes.push_back(rtk_aabb{padded.lo[0], padded.hi[0], padded.lo[1], padded.hi[1], padded.lo[2], padded.hi[2]});
         const int32_t node = push_node(RTK_NODE_BVH, l.node, r.node, int32_t(out.boxes.size()) - 1);
         if (left_out) *left_out = l;
         if (right_out) *right_out = r;
         return Built{node, l.cost + r.cost, l.first + r.first};
+    }
+
+    // The whole tree as one output node: the cheaper of a plain list and the hierarchy.  `linear`: the items' summed cost.
+    int32_t emit_tree(const Tree& t, const std::vector<Item>& items, double linear, double& cost) {
+        Emitter e{t, {}, std::vector<int32_t>(t.n.size(), 0)};
+        e.items.reserve(items.size());
+        lay_out(e, items, t.root);
+        const size_t nodes_mark = out.nodes.size(), child_mark = out.children.size(), box_mark = out.boxes.size();
+        Built inner = pair(e, t.root);
+        if (int(items.size()) <= opts.max_leaf && linear <= kBoxCost + inner.cost) {
+            out.nodes.resize(nodes_mark);
+            out.children.resize(child_mark);
+            out.boxes.resize(box_mark);
+            order_items(e.items, 0, e.items.size());
+            cost = linear;
+            return emit_list(e.items, 0, e.items.size());
+        }
+        cost = kBoxCost + inner.cost;
+        return inner.node;
     }
 
     int32_t build_group(int32_t node, Box& box, double& cost, int depth) {
@@ -668,18 +963,28 @@ struct Optimizer {
             cost = items[0].cost;
             return items[0].node;
         }
+        Tree greedy;
+        greedy.n.reserve(2 * items.size());
+        greedy.root = build_tree(items, 0, items.size(), greedy, 0);
         const size_t nodes_mark = out.nodes.size(), child_mark = out.children.size(), box_mark = out.boxes.size();
-        Built inner = split(items, 0, items.size(), box);
-        if (int(items.size()) <= opts.max_leaf && linear <= kBoxCost + inner.cost) {
+        int32_t node = emit_tree(greedy, items, linear, cost);
+        if (!reinsert) return node;
+        Tree refined = greedy;
+        if (refine(refined)) {
+            // never worse by the model: the refined tree is taken only when what it emits is priced lower
+            const double greedy_cost = cost;
             out.nodes.resize(nodes_mark);
             out.children.resize(child_mark);
             out.boxes.resize(box_mark);
-            order_items(items, 0, items.size());
-            cost = linear;
-            return emit_list(items, 0, items.size());
+            node = emit_tree(refined, items, linear, cost);
+            if (!(cost < greedy_cost)) {
+                out.nodes.resize(nodes_mark);
+                out.children.resize(child_mark);
+                out.boxes.resize(box_mark);
+                node = emit_tree(greedy, items, linear, cost);
+            }
         }
-        cost = kBoxCost + inner.cost;
-        return inner.node;
+        return node;
     }
 
     // Scene extent for the rounding margin: boxes of all primitives in their own spaces plus the transforms'
@@ -738,7 +1043,7 @@ size_t hot_program_lds_bytes(const rtk_scene_desc* scene);  // rtk_api.cpp
 
 extern "C" {
 
-static int optimize_once(const rtk_scene_desc* scene, const rtk_optimize_opts* opts_in, rtk_scene_desc** out_scene, rtk_optimize_info* info) {
+static int optimize_once(const rtk_scene_desc* scene, const rtk_optimize_opts* opts_in, rtk_scene_desc** out_scene, rtk_optimize_info* info, bool reinsert) {
     if (!scene || !out_scene) return RTK_ERR_INVALID;
     *out_scene = nullptr;
     if (scene->abi_version != RTK_ABI_VERSION || scene->n_nodes <= 0 || !scene->nodes || scene->root < 0 || scene->root >= scene->n_nodes) return RTK_ERR_INVALID;
@@ -750,6 +1055,7 @@ static int optimize_once(const rtk_scene_desc* scene, const rtk_optimize_opts* o
     Holder* h = new (std::nothrow) Holder;
     if (!h) return RTK_ERR_INVALID;
     Optimizer op(*scene, opts, *h);
+    op.reinsert = reinsert;
     op.keep_media_order = opts.free_media_order == 0;
     if (!op.scan_media(scene->root)) {
         delete h;
@@ -934,54 +1240,61 @@ static bool gets_mixed_program(const rtk_scene_desc& d) {
 //    step by step (fewer, larger leaves: fewer boxes) until that part fits; failing that, until at least the box
 //    records of the slot program do (the boxes-in-LDS kernels).
 // An explicit scale is honoured as given.
-int rtk_scene_optimize(const rtk_scene_desc* scene, const rtk_optimize_opts* opts_in, rtk_scene_desc** out_scene, rtk_optimize_info* info) {
-    if (!scene || !out_scene) return RTK_ERR_INVALID;
-    rtk_optimize_opts o;
-    std::memset(&o, 0, sizeof o);
-    if (opts_in) o = *opts_in;
-    if (o.prim_cost_scale > 0) return optimize_once(scene, &o, out_scene, info);
+// How well the f64 kernels can hold the program of `candidate`, re-grouped at `scale`: 2 -- whole (or its hot part) in one CU's
+// LDS, 1 -- at least the slot program or its box records, 0 -- neither.
+static int lds_fit(const rtk_scene_desc* scene, const rtk_scene_desc* candidate, double scale) {
     const size_t budget = size_t(160) * 1024 - 2048;  // the kernel's own LDS words
+    const bool full_feature = scene->n_media > 0 || scene->n_translates > 0 || scene->n_rotates > 0;  // only those kernels have the hot/cold form
+    if (compact_program_bytes(*candidate, gets_mixed_program(*scene)) <= budget) return 2;  // sized in the layout the upload will use
+    if (scale <= 1.0 && full_feature) {
+        // the hot part (rtk_api.cpp compiles the program: exact), and the Perlin tables behind it: book-2's noise sphere
+        // costs 4 % of the frame when perlin::turb gathers from memory instead
+        const size_t hot = rtk::hot_program_lds_bytes(candidate);
+        if (hot > 0 && hot + size_t(scene->n_perlins) * 9216 <= budget) return 2;
+    }
+    if (scale <= 1.0) {
+        size_t n_slots = 0, n_boxes = 0;
+        slot_program_counts(*candidate, n_slots, n_boxes);
+        const size_t whole = n_slots * 64 + size_t(scene->n_materials) * 48;
+        const size_t boxes_only = n_boxes * 56 + n_slots / 2 + n_slots / 4 + 64 + 2048;  // + a small material table
+        if (whole <= budget || boxes_only <= budget) return 1;
+    }
+    return 0;
+}
+
+// The scale search above, with the greedy hierarchy alone; `scale` and `fit` say what was chosen.
+static int optimize_auto(const rtk_scene_desc* scene, rtk_optimize_opts o, rtk_scene_desc** out_scene, rtk_optimize_info* info, double* scale, int* fit) {
     static const double kScalesNoQuads[] = {1.5, 1.4, 1.2, 1.0, 0.85, 0.7, 0.6, 0.5, 0.4};
     static const double kScalesQuads[] = {2.0, 1.0, 0.85, 0.7, 0.6, 0.5, 0.4};
     const double* kScales = scene->n_quads == 0 ? kScalesNoQuads : kScalesQuads;
     const int n_scales = scene->n_quads == 0 ? int(sizeof kScalesNoQuads / sizeof kScalesNoQuads[0]) : int(sizeof kScalesQuads / sizeof kScalesQuads[0]);
-    const bool full_feature = scene->n_media > 0 || scene->n_translates > 0 || scene->n_rotates > 0;  // only those kernels have the hot/cold form
-    const bool mixed_layout = gets_mixed_program(*scene);
+    const bool full_feature = scene->n_media > 0 || scene->n_translates > 0 || scene->n_rotates > 0;
     rtk_scene_desc* fallback = nullptr;  // the first hierarchy whose slot program at least keeps its boxes in LDS
     rtk_optimize_info fallback_info;
     for (int k = 0; k < n_scales; k++) {
         o.prim_cost_scale = kScales[k];
         rtk_optimize_info local;
         rtk_scene_desc* candidate = nullptr;
-        const int rc = optimize_once(scene, &o, &candidate, &local);
+        const int rc = optimize_once(scene, &o, &candidate, &local, false);
         if (rc != RTK_OK) {
             if (fallback) rtk_scene_optimized_free(fallback);
             return rc;
         }
-        bool accept = compact_program_bytes(*candidate, mixed_layout) <= budget;  // sized in the layout the upload will use
-        if (!accept && kScales[k] <= 1.0 && full_feature) {
-            // the hot part (rtk_api.cpp compiles the program: exact), and the Perlin tables behind it: book-2's noise sphere
-            // costs 4 % of the frame when perlin::turb gathers from memory instead
-            const size_t hot = rtk::hot_program_lds_bytes(candidate);
-            accept = hot > 0 && hot + size_t(scene->n_perlins) * 9216 <= budget;
-        }
-        if (accept) {
+        const int level = lds_fit(scene, candidate, kScales[k]);
+        if (level == 2) {
             if (fallback) rtk_scene_optimized_free(fallback);
             *out_scene = candidate;
-            if (info) *info = local;
+            *info = local;
+            *scale = kScales[k];
+            *fit = level;
             return RTK_OK;
         }
-        bool keep = false;
-        if (!fallback && kScales[k] <= 1.0) {
-            size_t n_slots = 0, n_boxes = 0;
-            slot_program_counts(*candidate, n_slots, n_boxes);
-            const size_t whole = n_slots * 64 + size_t(scene->n_materials) * 48;
-            const size_t boxes_only = n_boxes * 56 + n_slots / 2 + n_slots / 4 + 64 + 2048;  // + a small material table
-            keep = whole <= budget || boxes_only <= budget || k + 1 == n_scales;
-        }
+        const bool keep = !fallback && kScales[k] <= 1.0 && (level == 1 || k + 1 == n_scales);
         if (keep || (!fallback && k + 1 == n_scales)) {
             fallback = candidate;
             fallback_info = local;
+            *scale = kScales[k];
+            *fit = level;
         } else {
             rtk_scene_optimized_free(candidate);
         }
@@ -989,7 +1302,39 @@ int rtk_scene_optimize(const rtk_scene_desc* scene, const rtk_optimize_opts* opt
     }
     if (!fallback) return RTK_ERR_INVALID;  // not reached: the last scale is always kept
     *out_scene = fallback;
-    if (info) *info = fallback_info;
+    *info = fallback_info;
+    return RTK_OK;
+}
+
+// The scale is searched with the greedy hierarchy; the refined one (stage 2 of build_items) is then built at the scale
+// found and taken when the kernels can hold it as well as the greedy one: reinsertion gives more items a box of their own,
+// and a program that has to leave LDS loses far more than fewer slab tests gain.  RTK_OPT_REINSERT=0 keeps the greedy one.
+int rtk_scene_optimize(const rtk_scene_desc* scene, const rtk_optimize_opts* opts_in, rtk_scene_desc** out_scene, rtk_optimize_info* info) {
+    if (!scene || !out_scene) return RTK_ERR_INVALID;
+    rtk_optimize_opts o;
+    std::memset(&o, 0, sizeof o);
+    if (opts_in) o = *opts_in;
+    const char* e = std::getenv("RTK_OPT_REINSERT");
+    const bool reinsert = !(e && e[0] == '0');
+    if (o.prim_cost_scale > 0) return optimize_once(scene, &o, out_scene, info, reinsert);
+    rtk_optimize_info greedy_info;
+    double scale = 0;
+    int fit = 0;
+    const int rc = optimize_auto(scene, o, out_scene, &greedy_info, &scale, &fit);
+    if (rc != RTK_OK) return rc;
+    if (info) *info = greedy_info;
+    if (!reinsert) return RTK_OK;
+    o.prim_cost_scale = scale;
+    rtk_scene_desc* refined = nullptr;
+    rtk_optimize_info refined_info;
+    if (optimize_once(scene, &o, &refined, &refined_info, true) != RTK_OK) return RTK_OK;
+    if (lds_fit(scene, refined, scale) >= fit) {
+        rtk_scene_optimized_free(*out_scene);
+        *out_scene = refined;
+        if (info) *info = refined_info;
+    } else {
+        rtk_scene_optimized_free(refined);
+    }
     return RTK_OK;
 }
 
