@@ -1271,6 +1271,14 @@ int rtk_debug_get_ray(rtk_ctx* ctx, int real_mode, const rtk_camera* cam, uint32
  * for the byte model): number of program slots (fused records) and device bytes per mode. */
 int rtk_scene_info(rtk_ctx* ctx, int32_t* n_program_ops, int64_t* bytes_f64, int64_t* bytes_f32);
 
+/* The MIXED traversal program of a sphere-only description in the fast order, as rtk_scene_upload_optimized would build it
+ * (host-only, no device; for tests): its 32-byte units as they lie in memory (h_units) and the image of them that the kernel
+ * which stages the program copies into LDS (h_image).  eye_extent: the largest |coordinate| of the eye (0: none).  Each
+ * buffer is null or holds capacity_units x 32 bytes; *n_units is set even when the buffers are too small (RTK_ERR_INVALID
+ * then).  RTK_ERR_INVALID for a description with anything but spheres. */
+int rtk_debug_mixed_program(const rtk_scene_desc* optimized, double eye_extent, int32_t capacity_units, int32_t* n_units, float* extent, void* h_units,
+                            void* h_image);
+
 /* Render-kernel launches one frame takes (host-only): a pixel's samples are split into chunks of 8 (at most 64 chunks); the
  * partial-sum workspace is budgeted at 1.095 GB per context (22 planes of a 1920x1080 f64 frame), and a frame with more
  * chunks than the budget holds planes for is rendered in consecutive passes over the chunks whose running sums the resolve

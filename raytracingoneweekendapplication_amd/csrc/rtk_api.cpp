@@ -356,6 +356,29 @@ static void build_mixed_program(const rtk_scene_desc& sc, const Program& prog, d
     extent_out = float(extent);
 }
 
+// The image of a MIXED program that the kernel which stages it copies into LDS (rtk_device_layout.h MixedImg): the same
+// units and values with every head's words permuted, so that the first 16 bytes of any record tell its kind.
+static void build_mixed_lds_image(const std::vector<MixedHead>& units, std::vector<MixedImg>& image) {
+    image.assign(units.size(), MixedImg{});
+    std::memcpy(image.data(), units.data(), units.size() * sizeof(MixedHead));  // continuation units stay as they are
+    for (size_t u = 0; u < units.size();) {
+        const MixedHead& src = units[u];
+        MixedImg& dst = image[u];
+        const uint32_t kind = src.kind_payload & 15u;
+        if (kind == OP_BOX) {
+            for (int k = 0; k < 3; k++) dst.w[k] = src.w[k], dst.w[4 + k] = src.w[3 + k];
+            dst.w[3] = src.aux;  // the link: a multiple of 32, low nibble 0 = OP_BOX ^ kImageKindXor
+            dst.w[7] = src.kind_payload;
+        } else {
+            dst.w[0] = src.w[0], dst.w[1] = src.w[1];
+            dst.w[2] = src.aux;
+            dst.w[3] = src.kind_payload ^ kImageKindXor;
+            for (int k = 0; k < 4; k++) dst.w[4 + k] = src.w[2 + k];
+        }
+        u += size_t(mixed_units(kind));
+    }
+}
+
 // Largest coordinate magnitude the f32 culling boxes of a scene have to cope with: every box bound and primitive
 // extent (each in its own space), every instance offset, the eye.
 static double scene_extent(const rtk_scene_desc& sc, double eye_extent) {
@@ -778,6 +801,7 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
     out.view.n_perlins = sc.n_perlins;
     out.view.n_chains = int32_t(chains.size());
     out.view.program_mixed = nullptr;
+    out.view.program_mixed_lds = nullptr;
     out.view.n_units = 0;
     out.view.extent = 0.0f;
     // Programs that cannot be staged in LDS whole: the box slots alone, with the tables that find them (F_LDS_BOXES).
@@ -841,6 +865,9 @@ int build_device_scene(const rtk_scene_desc& sc, const Program& prog, DeviceScen
             std::vector<uint32_t> ranks;
             build_mixed_program(sc, prog, eye_extent, units, ranks, out.view.extent);
             if ((rc = out.upload(units, &out.view.program_mixed)) != RTK_OK) return rc;
+            std::vector<MixedImg> image;
+            build_mixed_lds_image(units, image);
+            if ((rc = out.upload(image, &out.view.program_mixed_lds)) != RTK_OK) return rc;
             if ((rc = out.upload(ranks, &out.view.tie_rank)) != RTK_OK) return rc;
             out.view.n_units = int32_t(units.size());
         } else if (fast_order) {
@@ -1112,6 +1139,34 @@ static int upload_scene(rtk_ctx* ctx, const rtk_scene_desc* scene, UploadOrder o
     ctx->scene_digest = scene_digest(*scene, prog, ctx->features, fast_order, eye_extent);
     ctx->has_scene = true;
     return RTK_OK;
+}
+
+int rtk_debug_mixed_program(const rtk_scene_desc* optimized, double eye_extent, int32_t capacity_units, int32_t* n_units, float* extent, void* h_units,
+                            void* h_image) {
+    if (!optimized || !n_units) return fail(RTK_ERR_INVALID, "rtk_debug_mixed_program: null argument");
+    try {
+        Program prog;
+        const int rc = compile_scene(optimized, prog);
+        if (rc != RTK_OK) return rc;
+        if (prog.features != kFeatLean || prog.chains.size() > 1) return fail(RTK_ERR_INVALID, "rtk_debug_mixed_program: not a sphere-only scene");
+        std::vector<MixedHead> units;
+        std::vector<uint32_t> ranks;
+        float ext = 0.0f;
+        build_mixed_program(*optimized, prog, eye_extent, units, ranks, ext);
+        *n_units = int32_t(units.size());
+        if (extent) *extent = ext;
+        if (size_t(capacity_units < 0 ? 0 : capacity_units) < units.size() && (h_units || h_image))
+            return fail(RTK_ERR_INVALID, "rtk_debug_mixed_program: %zu units, room for %d", units.size(), capacity_units);
+        if (h_units) std::memcpy(h_units, units.data(), units.size() * sizeof(MixedHead));
+        if (h_image) {
+            std::vector<MixedImg> image;
+            build_mixed_lds_image(units, image);
+            std::memcpy(h_image, image.data(), image.size() * sizeof(MixedImg));
+        }
+        return RTK_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(RTK_ERR_INVALID, "rtk_debug_mixed_program: out of memory");
+    }
 }
 
 int rtk_scene_info(rtk_ctx* ctx, int32_t* n_program_ops, int64_t* bytes_f64, int64_t* bytes_f32) {

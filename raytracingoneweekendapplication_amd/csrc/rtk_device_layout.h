@@ -118,8 +118,31 @@ struct alignas(16) MixedHead {
         w[2 * k] = uint32_t(v);
         w[2 * k + 1] = uint32_t(v >> 32);
     }
+    // what the steps that serve both this record and MixedImg ask of either
+    constexpr uint32_t kind() const { return kind_payload & 15u; }
+    constexpr uint32_t aux_word() const { return aux; }
 };
 static_assert(sizeof(MixedHead) == 32, "mixed unit size");
+// The same program as the lean MIXED kernel stages it in LDS (SceneView::program_mixed_lds; built by the host,
+// rtk_api.cpp build_mixed_lds_image): same units, same unit count, same values, the words of every HEAD unit permuted so that
+// the first 16 bytes of any record -- one ds_read_b128 -- tell its kind, in the low nibble of word 3 as kind ^ kImageKindXor:
+// a box (OP_BOX = 1) reads as 0, so a box's word 3 is its link (a multiple of 32), usable as read.
+//   OP_BOX           w[0..2] = centre (floats), w[3] = link, w[4..6] = half-extent (floats), w[7] = kind_payload
+//   any other head   w[0..1] = d[0], w[2] = aux, w[3] = kind_payload ^ 1, w[4..7] = d[1], d[2]
+// Continuation units (a sphere's radius, ...) are MixedHead's.
+constexpr uint32_t kImageKindXor = 1u;
+struct alignas(16) MixedImg {
+    uint32_t w[8];
+    constexpr double d(int k) const {
+        const int at = k == 0 ? 0 : 2 + 2 * k;
+        return __builtin_bit_cast(double, (unsigned long long)(w[at]) | ((unsigned long long)(w[at + 1]) << 32));
+    }
+    constexpr float f(int k) const { return __builtin_bit_cast(float, w[k < 3 ? k : k + 1]); }  // a box: centre 0..2, half-extent 3..5
+    constexpr uint32_t kind() const { return (w[3] & 15u) ^ kImageKindXor; }
+    constexpr uint32_t aux_word() const { return w[2]; }
+    constexpr uint32_t link() const { return w[3]; }
+};
+static_assert(sizeof(MixedImg) == 32, "mixed unit size");
 inline constexpr int mixed_units(uint32_t kind) { return kind == OP_SPHERE ? 2 : (kind == OP_SPHERE_MOVING ? 3 : 1); }
 
 // The COMPACT traversal program: the MIXED idea for EVERY scene of the fast order (f64 kernels) -- f32 culling boxes, exact
@@ -254,6 +277,8 @@ struct SceneView {  // device pointers, passed to the kernel by value
     const MixedHead* program_mixed;
     int32_t n_units;
     float extent;
+    // ... and the image of that program that the kernel which stages it in LDS copies instead (MixedImg: the same values)
+    const MixedImg* program_mixed_lds;
     // COMPACT program (F_F32_BOX kernels of the other families; null when the scene has a MIXED program or was uploaded in
     // the reference order) -- same `extent` rule, applied to the object-space origin under instance transforms
     const Unit16* program_compact;

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(64) void lds_chain_kernel(int iters, unsigned long 
     if (at == 0xFFFFFFFFu) *sink = at;
 }
 
-enum IssueClass { I_FMA_F32, I_FMA_F64, I_MUL_F64, I_ADD_F64, I_MUL_LO_U32, I_RCP_F32, I_SQRT_F32, I_RCP_F64, I_RSQ_F64, I_SQRT_F64, I_CNDMASK, I_MAX3_F32, I_PK_FMA_F32, I_PK_MUL_F32, I_FMAC_F32, I_MUL_F32, I_COUNT };
+enum IssueClass { I_FMA_F32, I_FMA_F64, I_MUL_F64, I_ADD_F64, I_MUL_LO_U32, I_RCP_F32, I_SQRT_F32, I_RCP_F64, I_RSQ_F64, I_SQRT_F64, I_CNDMASK, I_MAX3_F32, I_PK_FMA_F32, I_PK_MUL_F32, I_FMAC_F32, I_MUL_F32, I_FMA_MIX_F32, I_COUNT };
 
 // 8 independent chains per lane x 8 * kIssueReps instructions per trip (128: the loop's own scalar instructions and its taken
 // branch are 2 % of the stream)
@@ -108,6 +108,7 @@ __global__ __launch_bounds__(1024) void issue_kernel(int iters, unsigned long lo
     const float fb = 0.999f, fc = 0.001f;
     const double db = 0.999, dc = 0.001;
     const unsigned um = 0x9E3779B1u;
+    const unsigned hb = 0x3BFE3BFEu;  // two binary16 0.999
     const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
     for (int it = 0; it < iters; it++) {
@@ -131,6 +132,8 @@ __global__ __launch_bounds__(1024) void issue_kernel(int iters, unsigned long lo
                 if (CLS == I_PK_MUL_F32) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(d[k]) : "v"(db));
                 if (CLS == I_FMAC_F32) asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(f[k]) : "v"(fb), "v"(fc));   // VOP2: two sources + the accumulator
                 if (CLS == I_MUL_F32) asm volatile("v_mul_f32 %0, %0, %1" : "+v"(f[k]) : "v"(fb));            // VOP2: two sources
+                // one f32 fused multiply-add whose first source is the low binary16 half of a register, widened as a source modifier
+                if (CLS == I_FMA_MIX_F32) asm volatile("v_fma_mix_f32 %0, %1, %0, %2 op_sel_hi:[1,0,0]" : "+v"(f[k]) : "v"(hb), "v"(fc));
             }
         }
     }
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(1024) void issue_kernel(int iters, unsigned long lo
 const char* kNames =
     "hbm_copy_GBps,hbm_read_GBps,lds_read_b128_GBps,lds_read_b128_random_GBps,lds_roundtrip_cycles,shader_clock_GHz,"
     "issue_v_fma_f32,issue_v_fma_f64,issue_v_mul_f64,issue_v_add_f64,issue_v_mul_lo_u32,issue_v_rcp_f32,issue_v_sqrt_f32,issue_v_rcp_f64,issue_v_rsq_f64,"
-    "issue_v_sqrt_f64,issue_v_cndmask_b32,issue_v_max3_f32,issue_v_pk_fma_f32,issue_v_pk_mul_f32,issue_v_fmac_f32,issue_v_mul_f32,clock_dense_valu_GHz,clock_light_load_GHz,"
+    "issue_v_sqrt_f64,issue_v_cndmask_b32,issue_v_max3_f32,issue_v_pk_fma_f32,issue_v_pk_mul_f32,issue_v_fmac_f32,issue_v_mul_f32,issue_v_fma_mix_f32,clock_dense_valu_GHz,clock_light_load_GHz,"
     "issue_v_fma_f32_1wave,issue_v_fma_f32_2waves,issue_v_fma_f32_4waves,issue_v_fma_f32_8waves";
 constexpr int kResults = 6 + I_COUNT + 2 + 4;
 
@@ -301,6 +304,7 @@ int rtk_microbench_run(int device, double* out, int n_out) {
     if (rc == 0) rc = run_issue<I_PK_MUL_F32>(cus, bw, bt, d_cycles, d_real, d_fsink, &out[6 + I_PK_MUL_F32], nullptr);
     if (rc == 0) rc = run_issue<I_FMAC_F32>(cus, bw, bt, d_cycles, d_real, d_fsink, &out[6 + I_FMAC_F32], nullptr);
     if (rc == 0) rc = run_issue<I_MUL_F32>(cus, bw, bt, d_cycles, d_real, d_fsink, &out[6 + I_MUL_F32], nullptr);
+    if (rc == 0) rc = run_issue<I_FMA_MIX_F32>(cus, bw, bt, d_cycles, d_real, d_fsink, &out[6 + I_FMA_MIX_F32], nullptr);
     // ---- the clock the chip holds (DVFS): dense VALU issue after a warm-up of back-to-back launches, then a nearly idle chip
     if (rc == 0) {
         const int blocks = cus * bw, iters = 40000 / kIssueReps;

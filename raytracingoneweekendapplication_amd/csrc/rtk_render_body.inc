@@ -28,6 +28,9 @@
     // or triangles is ONE two-unit record {kind, count, first unit in the cold array}; the quads and triangles themselves
     // ("cold": 144 / 80 bytes each, tested a few times per sample) stay in memory (SceneView::program_cold).
     constexpr bool CH = MIXED && !COMPACT;  // the MIXED program's boxes are centre / half-extent records
+    // ... which the kernel that stages that program copies from its host-built LDS image (MixedImg: the same values; every head
+    // tells its kind in its first 16 bytes, a box's link sits beside its centre)
+    constexpr bool IMG = CH && IN_LDS;
     constexpr bool CHE = COMPACT && kCompactChStatic<FEAT>;  // ... and so are the COMPACT programs' of the mesh family, with a per-ray slack
     constexpr bool CHE_RT = COMPACT && COUNT && !CHE;  // the counting kernel on any family's COMPACT program: asks the scene
     [[maybe_unused]] const bool che_rt = CHE_RT && sc.compact_ch != 0;
@@ -36,12 +39,13 @@
     constexpr bool COLD = LDS_PART && COMPACT;
     static_assert(!LDS_PART || !MIXED || COMPACT, "F_LDS_BOXES with f32 boxes: the COMPACT program");
     constexpr bool XF = (FEAT & F_XFORM) != 0;
-    using ProgRec = std::conditional_t<COMPACT, Unit16, std::conditional_t<MIXED, MixedHead, Slot<real>>>;  // what pc counts
-    using CurRec = std::conditional_t<MIXED, MixedHead, Slot<real>>;                                      // the record head a step holds in registers
+    using ProgRec = std::conditional_t<COMPACT, Unit16, std::conditional_t<MIXED, std::conditional_t<IMG, MixedImg, MixedHead>, Slot<real>>>;  // what pc counts
+    using CurRec = std::conditional_t<MIXED, std::conditional_t<IMG, MixedImg, MixedHead>, Slot<real>>;                                      // the record head a step holds in registers
     constexpr uint32_t kBoxUnits = COMPACT ? 2u : 1u, kSphereUnits = COMPACT ? 3u : (MIXED ? 2u : 1u), kQuadUnits = COMPACT ? 9u : 3u, kTriUnits = COMPACT ? 5u : 2u;
     const ProgRec* prog;
     if constexpr (COLD) prog = sc.program_hot;
     else if constexpr (COMPACT) prog = sc.program_compact;
+    else if constexpr (IMG) prog = sc.program_mixed_lds;
     else if constexpr (MIXED) prog = sc.program_mixed;
     else prog = sc.program;
     const int n_records = COLD ? sc.n_hot_units : (COMPACT ? sc.n_units16 : (MIXED ? sc.n_units : sc.n_slots));  // units of sizeof(ProgRec)
@@ -131,6 +135,7 @@
     auto kind_of = [&](uint32_t pc) -> uint32_t {
         if constexpr (SPLIT) return (lds_kinds[pc >> 3] >> ((pc & 7u) * 4u)) & 15u;
         else if constexpr (COMPACT) return prog[(pc & kPcMask) + 1].w[2] & 15u;
+        else if constexpr (MIXED) return rec_at(pc)->kind();
         else return rec_at(pc)->kind_payload & 15u;
     };
     [[maybe_unused]] auto box_at = [&](uint32_t pc) -> CurRec {
@@ -379,6 +384,49 @@
         else if (n_shd >= n_oth) pick = W_SHADE;
         else pick = W_OTHER;
         if (pick == W_BOX) {
+          if constexpr (IMG) {
+            // The box loop on the LDS image (the loop of every other kernel follows, with the measurements behind its shape).  A
+            // step holds the record at L.pc as its two 16-byte halves: `a` = centre and link -- or any other head's first half,
+            // whose word 3 tells the kind as kind ^ 1, so a box's link is usable as read -- and `b` = half-extent, or a sphere's
+            // y and z.  `k` is that code; lanes get their kind back when the loop ends.
+            const int sel = int(diag >> 8) & 7;  // tools/: A/B of the loop-exit threshold, as below
+            const int frac = (n_box * (sel == 0 ? 2 : sel)) >> 3;
+            const int keep = frac > 8 ? frac : 8;
+            typedef const rtk_u32x4 __attribute__((address_space(3))) * lds_uint4_t;
+            rtk_u32x4 a, b;
+            uint32_t k = kind ^ kImageKindXor;
+            auto fetch = [&]() {
+                a = *(lds_uint4_t)(size_t)L.pc;
+                b = *(lds_uint4_t)(size_t)(L.pc + 16u);
+                k = a.w & 15u;
+            };
+            a = *(lds_uint4_t)(size_t)L.pc;
+            b = *(lds_uint4_t)(size_t)(L.pc + 16u);
+            const uint32_t box_code = L.box_kind ^ kImageKindXor;  // a lane with an irregular ray matches nothing here
+            constexpr uint32_t sphere_code = uint32_t(OP_SPHERE) ^ kImageKindXor;
+            int remaining;
+            __builtin_amdgcn_s_setprio(kBoxLoopPrio);
+            do {
+                #pragma unroll
+                for (int step = 0; step < kUnrollMixed; step++) {
+                    if (k == box_code) {
+                        step_box_img(L, a, b, cnt);
+                        fetch();
+                    }
+                }
+                if ([[maybe_unused]] const int n_ride = popcount64(__ballot(k == sphere_code)); n_ride >= sphere_min) {  // sphere tests ride along
+                    if (k == sphere_code) {
+                        step_sphere_img<kPcUnit>(L, a, b, rec_at(L.pc), cnt, tie, extent);
+                        fetch();
+                    }
+                    RTK_PROF_MARK(2, 1, n_ride)
+                }
+                remaining = popcount64(__ballot(k == box_code));
+                RTK_PROF_MARK(1, 1, remaining)
+            } while (remaining >= keep);
+            __builtin_amdgcn_s_setprio(0);
+            L.kind = k ^ kImageKindXor;
+          } else {
             // Box tests dominate (about 100 per sample against a dozen sphere tests), so
             // the vote is amortised: keep stepping boxes -- one ballot and one branch per
             // step -- until fewer than `keep` lanes are still sitting on a box record.  A low
@@ -498,6 +546,7 @@
                 RTK_PROF_MARK(1, 1, remaining)
             } while (remaining >= keep);
             __builtin_amdgcn_s_setprio(0);
+          }
         } else if (pick == W_SPHERE) {
             // A bvh leaf usually holds two spheres in a row: same amortisation, half the starters.
             const int ssel = int(diag >> 11) & 7;  // tools/: same for the sphere loop (0 = default)
@@ -517,7 +566,8 @@
                         if (k == OP_SPHERE) cur = head_at(L.pc);
                     } else {
                         cur = head_at(L.pc);
-                        k = cur.kind_payload & 15u;
+                        if constexpr (IMG) k = cur.kind();
+                        else k = cur.kind_payload & 15u;
                     }
                     L.kind = k;
                 }

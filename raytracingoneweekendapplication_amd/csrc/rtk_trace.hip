@@ -732,6 +732,20 @@ RTK_DEV void step_box32_ch(Lane<real>& L, const MixedHead& rec, Counters<COUNT>&
     const bool hit = slab_test32_chs(rec, L.oi32s, L.inv32s);
     L.pc = hit ? L.pc + kChPcUnit : rec.aux;  // (pcs of this kernel count bytes, and so does the link)
 }
+// The same step on the program's LDS image (rtk_device_layout.h MixedImg): `a` = the first 16 bytes of the record (centre,
+// link), `b` = the second (half-extent).  The arithmetic is slab_test32_chs's, on the same values.
+typedef uint32_t rtk_u32x4 __attribute__((ext_vector_type(4)));  // 16 bytes of an LDS record as one ds_read_b128 returns them
+template <typename real, bool COUNT>
+RTK_DEV void step_box_img(Lane<real>& L, rtk_u32x4 a, rtk_u32x4 b, Counters<COUNT>& cnt) {
+    cnt.inc(C_BOX);
+    // (vector elements are copied to scalars first: __builtin_bit_cast applied to the element expression itself reads element 0
+    // every time with the compiler in use)
+    const uint32_t a0 = a.x, a1 = a.y, a2 = a.z, b0 = b.x, b1 = b.y, b2 = b.z;
+    MixedHead rec;
+    rec.w[0] = a0, rec.w[1] = a1, rec.w[2] = a2, rec.w[3] = b0, rec.w[4] = b1, rec.w[5] = b2;
+    const bool hit = slab_test32_chs(rec, L.oi32s, L.inv32s);
+    L.pc = hit ? L.pc + kChPcUnit : a.w;  // (a box's word 3 is its link as stored: byte pcs, kind nibble 0)
+}
 // A box of those programs for a ray the float test must not judge (zero / out-of-range direction component, origin
 // outside the sized bound): aabb::hit's literal form in f64 on the (outward-rounded, hence still enclosing) bounds.
 template <bool XF = false, uint32_t UNITS = 1, uint32_t PCU = 1, typename real, bool COUNT>
@@ -752,10 +766,20 @@ RTK_DEV void step_box_mixed_exact(Lane<real>& L, const MixedHead& rec, Counters<
     L.pc = hit ? L.pc + UNITS * PCU : rec.aux;
 }
 // sphere::hit on a MIXED record: centre in the head unit, radius in the next one.
-template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie>
-RTK_DEV void step_sphere_mixed(Lane<real>& L, const MixedHead& head, const MixedHead* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie, float extent) {
+template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie, typename Rec>
+RTK_DEV void step_sphere_mixed(Lane<real>& L, const Rec& head, const Rec* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie, float extent) {
     const double radius2 = reinterpret_cast<const double*>(rec + 1)[2];  // radius * radius from the upload: the same product, once
     hit_sphere<false, true, true, true>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), real(radius2), 2u * PCU, cnt, tie, extent);
+}
+// ... with the head of a MixedImg record as the box loop holds it: its first 16 bytes `a` (centre x) and its second `b` (y, z)
+template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie>
+RTK_DEV void step_sphere_img(Lane<real>& L, rtk_u32x4 a, rtk_u32x4 b, const MixedImg* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie, float extent) {
+    const double radius2 = reinterpret_cast<const double*>(rec + 1)[2];
+    const unsigned long long xw = (unsigned long long)(a.x) | ((unsigned long long)(a.y) << 32);
+    const unsigned long long yw = (unsigned long long)(b.x) | ((unsigned long long)(b.y) << 32);
+    const unsigned long long zw = (unsigned long long)(b.z) | ((unsigned long long)(b.w) << 32);
+    const double cx = __builtin_bit_cast(double, xw), cy = __builtin_bit_cast(double, yw), cz = __builtin_bit_cast(double, zw);
+    hit_sphere<false, true, true, true>(L, mk(real(cx), real(cy), real(cz)), real(radius2), 2u * PCU, cnt, tie, extent);
 }
 // ... and on a COMPACT record (3 units): the head (centre) is usually in registers already, the radius follows it.
 template <bool XF, typename real, bool COUNT, typename Tie>
@@ -763,11 +787,18 @@ RTK_DEV void step_sphere_compact(Lane<real>& L, const MixedHead& head, const Uni
     hit_sphere<XF, true>(L, mk(real(head.d(0)), real(head.d(1)), real(head.d(2))), packed<real, 3>(rec) * packed<real, 3>(rec), 3u, cnt, tie);
 }
 // The remaining record kinds of a sphere-only program: a moving sphere, or a box for an irregular ray.
-template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie>
-RTK_DEV void step_other_mixed(Lane<real>& L, const MixedHead* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie, float extent) {
-    const uint32_t kind = rec->kind_payload & 15u;
+template <uint32_t PCU = 1, typename real, bool COUNT, typename Tie, typename Rec>
+RTK_DEV void step_other_mixed(Lane<real>& L, const Rec* __restrict__ rec, Counters<COUNT>& cnt, const Tie& tie, float extent) {
+    const uint32_t kind = rec->kind();
     if (kind == OP_BOX) {
-        step_box_mixed_exact<false, 1, PCU>(L, *rec, cnt);
+        if constexpr (std::is_same_v<Rec, MixedImg>) {
+            MixedHead box;  // the record's six values and its link, as step_box_mixed_exact reads them
+            for (int k = 0; k < 6; k++) box.w[k] = __builtin_bit_cast(uint32_t, rec->f(k));
+            box.aux = rec->link();
+            step_box_mixed_exact<false, 1, PCU>(L, box, cnt);
+        } else {
+            step_box_mixed_exact<false, 1, PCU>(L, *rec, cnt);
+        }
     } else if (kind == OP_SPHERE_MOVING) {
         const double* cont = reinterpret_cast<const double*>(rec + 1);
         const V3<real> cc = mk(real(rec->d(0)), real(rec->d(1)), real(rec->d(2))) + scale(L.tm, mk(real(cont[2]), real(cont[3]), real(cont[4])));
@@ -1050,12 +1081,12 @@ struct Surface {  // hit_record (hittable.h:11-27)
 };
 
 // The deferred hit record of a MIXED program's winner (sphere.h:50-56; solid colours only: no uv).
-template <typename real>
-RTK_DEV void make_surface_mixed(const MixedHead* __restrict__ prog, uint32_t best_pc, real t, V3<real> wo, V3<real> wd, real tm, Surface<real>& sf) {
-    const MixedHead* rec = prog + best_pc;
-    const uint32_t kind = rec->kind_payload & 15u;
+template <typename real, typename Rec>
+RTK_DEV void make_surface_mixed(const Rec* __restrict__ prog, uint32_t best_pc, real t, V3<real> wo, V3<real> wd, real tm, Surface<real>& sf) {
+    const Rec* rec = prog + best_pc;
+    const uint32_t kind = rec->kind();
     const double* cont = reinterpret_cast<const double*>(rec + 1);
-    sf.material = int(rec->aux >> 8);
+    sf.material = int(rec->aux_word() >> 8);
     sf.p = wo + scale(t, wd);
     sf.u = real(0);
     sf.v = real(0);
@@ -1321,7 +1352,7 @@ RTK_DEV bool shade(Lane<real>& L, const ProgT* __restrict__ hit_rec, const Scene
     cnt.inc(C_SURFACE);
     RTK_SHADE_PROF(2)
     Surface<real> sf;
-    if constexpr (std::is_same_v<ProgT, MixedHead>) make_surface_mixed(hit_rec, 0u, L.best_t, L.ro, L.rd, L.tm, sf);  // lean MIXED program
+    if constexpr (std::is_same_v<ProgT, MixedHead> || std::is_same_v<ProgT, MixedImg>) make_surface_mixed(hit_rec, 0u, L.best_t, L.ro, L.rd, L.tm, sf);  // lean MIXED program
     else make_surface<real, FEAT>(hit_rec, sc, mats, 0u, L.best_t, L.ro, L.rd, L.tm, sf);                             // slot or COMPACT program
     RTK_SHADE_PROF(0)
     return shade_surface<real, FEAT>(L, sf, sc, mats, cnt RTK_SHADE_PROF_ARG);
@@ -2866,11 +2897,14 @@ __global__ __launch_bounds__(1024) void rtk_isa_probe(Lane<double>* __restrict__
     const NoTie tie{};
     const MixedHead* rec = reinterpret_cast<const MixedHead*>(reinterpret_cast<const unsigned char*>(prog) + L.pc);
     if constexpr (KIND == PROBE_BOX) {  // one box step: the slab test on the record in registers, then the next record and its kind
-        MixedHead cur = *rec;
-        step_box32_ch(L, cur, cnt);
-        cur = *reinterpret_cast<const MixedHead*>(reinterpret_cast<const unsigned char*>(prog) + L.pc);
-        L.kind = cur.kind_payload & 15u;
-        L.oi32_lo.x = cur.f(0);  // (keeps the fetched record alive, as the next step's slab test does)
+        // (on the LDS image's record form, as the timed kernel <double, 256u, false, true> steps it: two 16-byte reads, kind and link in the first)
+        const rtk_u32x4* at = reinterpret_cast<const rtk_u32x4*>(rec);
+        rtk_u32x4 a = at[0], b = at[1];
+        step_box_img(L, a, b, cnt);
+        at = reinterpret_cast<const rtk_u32x4*>(reinterpret_cast<const unsigned char*>(prog) + L.pc);
+        a = at[0], b = at[1];
+        L.kind = a.w & 15u;
+        L.oi32_lo.x = __builtin_bit_cast(float, uint32_t(a.x)) + __builtin_bit_cast(float, uint32_t(b.x));  // (keeps the fetched record alive, as the next step's slab test does)
     } else if constexpr (KIND == PROBE_SPHERE) {
         MixedHead cur = *rec;
         step_sphere_mixed<kChPcUnit>(L, cur, rec, cnt, tie, extent);
