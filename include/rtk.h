@@ -213,6 +213,9 @@ typedef struct rtk_render_opts {
                              * computed: 1 = keep the traversal program in global memory (no LDS staging);
                              * 2 = one sample chunk per pixel; 4 = fixed row-major tile order (no cost-ordered
                              * hand-out); bits 3-4 = chunk size (0: 8 samples, 1: 4, 2: 2, 3: 16);
+                             * bits 5-7 = grid cap k, read by the host only (tests, tools): 0 = none, k = 1..7 = the launch has at
+                             * most 2^(k-1) waves (1, 2, 4, ... 64), so that a small frame's waves each take many work items;
+                             * the kernel chosen, its name and rtk_frame_launches do not depend on it; progressive sessions ignore it;
                              * bits 8-13 = scheduler loop-exit thresholds, bits 14-16 = refill batch size, bits 17-19 = lanes needed
                              * for a sphere step inside the box loop, bit 20 = f64 boxes instead of the MIXED program, bit 21 = no boxes-in-LDS
                              * kernel for programs larger than LDS (see csrc/rtk_trace.hip); bit 22 = write the compact tile

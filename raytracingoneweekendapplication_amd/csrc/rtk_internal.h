@@ -243,12 +243,12 @@ struct Variant {
     bool whole_pixel;  // bit 1: one lane per pixel for all samples (tests)
     bool fixed_order;  // bit 2: row-major tile hand-out, no order learned (A/B, tests)
     int chunk_ab;      // bits 3..4, tools/: chunk size A/B (0 = default 8, 1 = 4, 2 = 2, 3 = 16)
-    uint32_t diag;     // bits 8..21, 23: scheduler policy / program layout A/B used by tools/ and tests only
+    uint32_t diag;     // bits 5..7: grid cap, host only (rtk_grid_plan.h; tests, tools); bits 8..21, 23: scheduler policy / program layout A/B used by tools/ and tests only
     bool compact;      // bit 22: the tile-buffer layout for a single rank too
     bool one_pass;     // bit 24: one pass whatever the chunk count (tests: same image)
 };
 inline Variant decode_variant(int v) {
-    return Variant{(v & 1) == 0, (v & 2) != 0, (v & 4) != 0, (v >> 3) & 3, uint32_t(v) & 0xBFFF00u, (v & (1 << 22)) != 0, (v & (1 << 24)) != 0};
+    return Variant{(v & 1) == 0, (v & 2) != 0, (v & 4) != 0, (v >> 3) & 3, uint32_t(v) & 0xBFFFE0u, (v & (1 << 22)) != 0, (v & (1 << 24)) != 0};
 }
 
 // The arithmetic of a frame, host only: the tile map of a camera and a rank with every chunk boundary, the bytes of a chunk

@@ -34,6 +34,7 @@
 #include "rtk_device_math.h"
 #include "rtk_gather_rule.h"
 #include "rtk_image_pass.h"
+#include "rtk_grid_plan.h"
 #include "rtk_lds_plan.h"
 #include "rtk_trace.h"
 
@@ -2405,9 +2406,10 @@ __global__ __launch_bounds__(256) void rtk_lens_render_kernel(LensLanes lanes, S
 
 // Geometry of a persistent launch: waves per workgroup and workgroups per CU so
 // that (a) the register-limited wave count per CU is reached and (b) every
-// resident workgroup's LDS copy of the program fits.
+// resident workgroup's LDS copy of the program fits.  The arithmetic is rtk_grid_plan.h's;
+// `cap` = variant bits 5..7 (tests and tools: at most 2^(cap - 1) waves, 0 = no cap).
 template <typename Kernel>
-static hipError_t plan_launch(Kernel kernel, int kMaxWavesPerBlock, size_t lds_bytes, int n_tiles, int& blocks, int& threads) {
+static hipError_t plan_launch(Kernel kernel, int kMaxWavesPerBlock, size_t lds_bytes, int n_tiles, int cap, int& blocks, int& threads) {
     int device = 0, cus = 256, waves_per_cu = 0;
     hipError_t e = hipGetDevice(&device);
     if (e != hipSuccess) return e;
@@ -2418,25 +2420,17 @@ static hipError_t plan_launch(Kernel kernel, int kMaxWavesPerBlock, size_t lds_b
     }
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu, kernel, 64, 0);  // register-limited waves per CU
     if (e != hipSuccess) return e;
-    if (waves_per_cu < 4) waves_per_cu = 4;
-    if (waves_per_cu > 32) waves_per_cu = 32;
-    int blocks_per_cu = (waves_per_cu + kMaxWavesPerBlock - 1) / kMaxWavesPerBlock;
+    int by_lds = 0;  // (no LDS staged: no limit)
     if (lds_bytes > 0) {
-        const int by_lds = lds_plan::workgroups_per_cu(lds_bytes);
+        by_lds = lds_plan::workgroups_per_cu(lds_bytes);
         if (by_lds < 1) return hipErrorInvalidValue;
-        if (blocks_per_cu > by_lds) blocks_per_cu = by_lds;
     }
-    int waves_per_block = waves_per_cu / blocks_per_cu;
-    if (waves_per_block > kMaxWavesPerBlock) waves_per_block = kMaxWavesPerBlock;
-    if (waves_per_block < 1) waves_per_block = 1;
-    threads = waves_per_block * 64;
-    blocks = cus * blocks_per_cu;
-    const int needed = (n_tiles + waves_per_block - 1) / waves_per_block;
-    if (blocks > needed) blocks = needed;
-    if (blocks < 1) blocks = 1;
+    const grid_plan::Grid g = grid_plan::plan(cus, waves_per_cu, kMaxWavesPerBlock, by_lds, n_tiles, cap);
+    blocks = g.blocks;
+    threads = g.threads;
     if (getenv("RTK_DEBUG"))
         fprintf(stderr, "[rtk] launch plan: occupancy API %d waves/CU, %d workgroup(s)/CU x %d waves, grid %d x %d threads, LDS %zu B/workgroup\n",
-                waves_per_cu, blocks_per_cu, waves_per_block, blocks, threads, lds_bytes);
+                g.waves_per_cu, g.blocks_per_cu, g.waves_per_block, blocks, threads, lds_bytes);
     return hipSuccess;
 }
 
@@ -2491,7 +2485,7 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
     if constexpr (has_view_kernel(FEAT, COUNT, IN_LDS)) {
         if (views != nullptr) {  // the view kernel: the same staging plan, its own occupancy
             auto view_kernel = rtk_view_batch_kernel<real, FEAT, IN_LDS>;
-            hipError_t ev = plan_launch(view_kernel, max_threads<real, FEAT, IN_LDS>() / 64, lds, n_items, blocks, threads);
+            hipError_t ev = plan_launch(view_kernel, max_threads<real, FEAT, IN_LDS>() / 64, lds, n_items, int(diag >> 5) & 7, blocks, threads);
             if (ev != hipSuccess) return ev;
             ev = hipMemsetAsync(tile_counter, 0, sizeof(unsigned int), stream);
             if (ev != hipSuccess) return ev;
@@ -2499,7 +2493,7 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
             return hipGetLastError();
         }
     }
-    hipError_t e = plan_launch(kernel, max_threads<real, FEAT, IN_LDS>() / 64, lds, n_items, blocks, threads);
+    hipError_t e = plan_launch(kernel, max_threads<real, FEAT, IN_LDS>() / 64, lds, n_items, int(diag >> 5) & 7, blocks, threads);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(tile_counter, 0, sizeof(unsigned int), stream);
     if (e != hipSuccess) return e;
