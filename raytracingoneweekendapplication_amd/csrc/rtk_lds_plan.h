@@ -1,6 +1,6 @@
 // rtk_lds_plan.h -- what a workgroup of the render kernels stages in LDS, and at which byte offsets of its dynamic
 // segment.  Host arithmetic only (no HIP, no SceneView): the upload (rtk_api.cpp) asks it which tables to build,
-// choose_kernel and launch_one (rtk_trace.hip) ask it which kernel form a scene takes and where its tables go, and
+// kernel_choice::choose (rtk_kernel_choice.h) and launch_one (rtk_trace.hip) ask it which kernel form a scene takes and where its tables go, and
 // tests/helpers/lds_plan_check.cpp asks it the same questions without a device.  The kernel body (rtk_render_body.inc)
 // trusts the offsets of a Plan without checking them; DESIGN.md, "The LDS staging plan", states the rule in words.
 // Every comparison with the LDS capacity of a CU is in this file.

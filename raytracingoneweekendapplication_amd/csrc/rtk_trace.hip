@@ -35,6 +35,7 @@
 #include "rtk_gather_rule.h"
 #include "rtk_image_pass.h"
 #include "rtk_grid_plan.h"
+#include "rtk_kernel_choice.h"
 #include "rtk_lds_plan.h"
 #include "rtk_trace.h"
 
@@ -1473,33 +1474,6 @@ RTK_DEV void store_partial(real* __restrict__ partial, int item, int pix, V3<rea
     base[128] = sum.z;
 }
 
-// Workgroup-size bound = register budget: 1024 threads -> 4 waves per SIMD, 128 VGPRs; 768 -> 3 waves, 168 VGPRs;
-// 512 -> 2 waves, 256 VGPRs.  Measured on C2 (lean f64 kernel): 2 waves 93.8 ms, 3 waves 73.5 ms, 4 waves 68.5 ms
-// per frame (the 4-wave build spills a few values in the shade path).  Same-box A/B for the other f64 kernels
-// (tools/ab/run_ab.sh): quad/box subset on C3 43.3 ms at 4 waves vs 48.7 at 3; mesh subset on C4 no difference;
-// the full-feature kernel, which needs far more registers (~560 B/lane of spills at 168), is fastest at 2 waves.
-constexpr int kThreadsAllF64 = 768;    // workgroup bound of the full-feature f64 kernels: 3 waves per SIMD, 168 VGPRs (measured against 512 = 2 waves and 1024 = 4)
-constexpr int kThreadsMeshF64 = 1024;  // workgroup bound of the f64 mesh kernels: 4 waves per SIMD, 128 VGPRs (C4 60.1 -> 53.0 ms; 768 = 3 waves)
-// (round 3) the f64 mesh kernels run at four waves per SIMD when the whole program is staged in LDS (C4 60.1 -> 53.0 ms, 44 B of
-// scratch); with the program, or all but its boxes, in memory a fourth wave only adds pressure on L2 (C4, program in global
-// memory: 23.2 ms at three waves, 33.6 at four), so those keep 768 threads.
-template <typename real>
-constexpr int max_threads_of(uint32_t feat, bool in_lds) {
-    const uint32_t scene_feat = feat & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE | F_LDS_BOXES | F_SPHERE_MEDIA_ONLY);
-    // ... and the full-feature f64 kernels run at three waves where the traversal data is in LDS -- the whole program, or the
-    // hot part of a COMPACT program (F_LDS_BOXES | F_F32_BOX: C5 at 16 spp 21.1 -> 17.7 ms) -- and stay at two where records
-    // come from memory (program in global memory 25.5 vs 29.1 ms at three; slot program with its boxes in LDS 25.6 vs 29.0).
-    const bool hot_cold = (feat & F_LDS_BOXES) != 0 && (feat & F_F32_BOX) != 0;
-    if (sizeof(real) == 8)
-        return scene_feat == kFeatAll ? ((in_lds || hot_cold) ? kThreadsAllF64 : 512)
-                                      : ((scene_feat == kFeatLean || scene_feat == kFeatQuadBox) ? 1024 : (in_lds ? kThreadsMeshF64 : 768));
-    return 768;
-}
-template <typename real, uint32_t FEAT, bool IN_LDS>
-constexpr int max_threads() {
-    return max_threads_of<real>(FEAT, IN_LDS);
-}
-
 // Wave priorities (s_setprio) by scheduler phase.  The SIMD's instruction arbiter serves the higher priority first (then the
 // older wave); waves inside a traversal loop -- short dependent chains, an LDS round trip per step -- lose issue slots to
 // waves that are in a shade step (long independent runs of arithmetic) exactly when a stall costs them most.  Measured on
@@ -1528,7 +1502,7 @@ constexpr int kTriRide = 16, kQuadRide = 16;
 
 // The render kernel's body is rtk_render_body.inc: the view kernel below runs the same text.
 template <typename real, uint32_t FEAT_ALL, bool COUNT, bool IN_LDS>
-__global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_render_kernel(SceneView<real> sc, const CameraRec<real>* __restrict__ cam_ptr, TileMap tmap, uint32_t seed,
+__global__ __launch_bounds__(kernel_choice::max_threads(sizeof(real), FEAT_ALL, IN_LDS)) void rtk_render_kernel(SceneView<real> sc, const CameraRec<real>* __restrict__ cam_ptr, TileMap tmap, uint32_t seed,
                                                           real* __restrict__ partial, unsigned long long* __restrict__ counters,
                                                           unsigned int* __restrict__ tile_counter, const int32_t* __restrict__ tile_order,
                                                           unsigned int* __restrict__ tile_cost, uint32_t diag) {
@@ -1542,7 +1516,7 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_r
 // partial[chunk][view * tiles + tile][3][64]; no tile order, no tile cost, no counters (a counting batch is rendered view by
 // view with the plain kernel).  No static LDS here either: the lean MIXED form uses byte pcs as LDS addresses.
 template <typename real, uint32_t FEAT_ALL, bool IN_LDS>
-__global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_view_batch_kernel(SceneView<real> sc, const ViewRec<real>* __restrict__ views, TileMap tmap,
+__global__ __launch_bounds__(kernel_choice::max_threads(sizeof(real), FEAT_ALL, IN_LDS)) void rtk_view_batch_kernel(SceneView<real> sc, const ViewRec<real>* __restrict__ views, TileMap tmap,
                                                                                                    real* __restrict__ partial, unsigned int* __restrict__ tile_counter,
                                                                                                    uint32_t diag) {
     constexpr bool COUNT = sizeof(real) == 0;  // false, and dependent: the body's `if constexpr (COUNT)` branches are not instantiated
@@ -1554,8 +1528,6 @@ __global__ __launch_bounds__((max_threads<real, FEAT_ALL, IN_LDS>())) void rtk_v
 #include "rtk_render_body.inc"
 #undef RTK_BODY_VIEWS
 }
-// Which instantiations have a view kernel: the non-counting ones that stage the program, its hot part or its boxes in LDS.
-constexpr bool has_view_kernel(uint32_t feat, bool count, bool in_lds) { return !count && (in_lds || (feat & F_LDS_BOXES) != 0); }
 
 // hittable::hit of the scene root on the query interval L.tmin .. L.best_t (set up by begin_segment<true>): the slot program
 // walked one lane at a time, with every record kind and the tie table (inert for reference-order uploads).  L.best_pc /
@@ -2439,6 +2411,8 @@ static hipError_t plan_launch(Kernel kernel, int kMaxWavesPerBlock, size_t lds_b
 static_assert(lds_plan::kCapacity == size_t(kLdsBytesPerCU) && lds_plan::kXform == F_XFORM && lds_plan::kTexture == F_TEXTURE && lds_plan::kF32Box == F_F32_BOX &&
               lds_plan::kMatte == F_MATTE && lds_plan::kLdsBoxes == F_LDS_BOXES && lds_plan::kLeanFamily == kFeatLean, "rtk_lds_plan.h restates rtk_device_layout.h");
 static_assert(lds_plan::kMixedUnitBytes == sizeof(MixedHead) && lds_plan::kUnit16Bytes == sizeof(Unit16), "rtk_lds_plan.h restates rtk_device_layout.h");
+static_assert(kernel_choice::kFmaBox == F_FMA_BOX && kernel_choice::kSphereMediaOnly == F_SPHERE_MEDIA_ONLY && kernel_choice::kMeshFamily == kFeatMesh &&
+              kernel_choice::kQuadBoxFamily == kFeatQuadBox && kernel_choice::kFullFamily == kFeatAll, "rtk_kernel_choice.h restates rtk_device_layout.h");
 template <typename real>
 static constexpr lds_plan::RecordSizes lds_record_sizes() {
     constexpr lds_plan::RecordSizes s = sizeof(real) == 8 ? lds_plan::kSizesF64 : lds_plan::kSizesF32;
@@ -2467,7 +2441,7 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
                              hipStream_t stream, const ViewRec<real>* views = nullptr) {
     const int n_items = tmap.n_tiles_local * tmap.n_chunks;
     if (n_items <= 0) return hipSuccess;
-    if (views != nullptr && !has_view_kernel(FEAT, COUNT, IN_LDS)) return hipErrorInvalidValue;  // (the caller asks view_kernel_name first)
+    if (views != nullptr && !kernel_choice::has_view_kernel(FEAT, COUNT, IN_LDS)) return hipErrorInvalidValue;  // (the caller asks view_kernel_name first)
     auto kernel = rtk_render_kernel<real, FEAT, COUNT, IN_LDS>;
     const lds_plan::Plan plan = lds_plan::plan(lds_counts(sc), lds_record_sizes<real>(), FEAT, IN_LDS, size_t(tmap.n_tiles_local), tile_order != nullptr);
     const size_t lds = plan.total;
@@ -2482,10 +2456,10 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
                 sizeof(real), unsigned(FEAT), int(IN_LDS), int(views != nullptr), lds, int(tm.mats_lds_offset), int(tm.perlin_lds_offset), int(tm.chains_lds_offset),
                 int(tm.order_in_lds), int(tm.order_lds_offset));
     int blocks = 0, threads = 0;
-    if constexpr (has_view_kernel(FEAT, COUNT, IN_LDS)) {
+    if constexpr (kernel_choice::has_view_kernel(FEAT, COUNT, IN_LDS)) {
         if (views != nullptr) {  // the view kernel: the same staging plan, its own occupancy
             auto view_kernel = rtk_view_batch_kernel<real, FEAT, IN_LDS>;
-            hipError_t ev = plan_launch(view_kernel, max_threads<real, FEAT, IN_LDS>() / 64, lds, n_items, int(diag >> 5) & 7, blocks, threads);
+            hipError_t ev = plan_launch(view_kernel, kernel_choice::max_threads(sizeof(real), FEAT, IN_LDS) / 64, lds, n_items, int(diag >> 5) & 7, blocks, threads);
             if (ev != hipSuccess) return ev;
             ev = hipMemsetAsync(tile_counter, 0, sizeof(unsigned int), stream);
             if (ev != hipSuccess) return ev;
@@ -2493,7 +2467,7 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
             return hipGetLastError();
         }
     }
-    hipError_t e = plan_launch(kernel, max_threads<real, FEAT, IN_LDS>() / 64, lds, n_items, int(diag >> 5) & 7, blocks, threads);
+    hipError_t e = plan_launch(kernel, kernel_choice::max_threads(sizeof(real), FEAT, IN_LDS) / 64, lds, n_items, int(diag >> 5) & 7, blocks, threads);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(tile_counter, 0, sizeof(unsigned int), stream);
     if (e != hipSuccess) return e;
@@ -2501,151 +2475,34 @@ static hipError_t launch_one(const SceneView<real>& sc, const CameraRec<real>* c
     return hipGetLastError();
 }
 
-// The f32-culling-box programs are used whenever the upload built one (f64, fast order): the MIXED program of a sphere-only
-// scene, the COMPACT program of any other; variant bit 20 keeps the f64 boxes of the slot program instead (A/B, tests).
+// Which kernel a launch runs is rtk_kernel_choice.h's decision: this is the one place that tells it what the upload built.
 template <typename real>
-static bool use_mixed_program(const SceneView<real>& sc, uint32_t diag) {
-    return sizeof(real) == 8 && sc.program_mixed != nullptr && (diag & (1u << 20)) == 0;
-}
-template <typename real>
-static bool use_compact_program(const SceneView<real>& sc, uint32_t diag) {
-    return sizeof(real) == 8 && sc.program_compact != nullptr && (diag & (1u << 20)) == 0;
+static kernel_choice::Choice choose_for_scene(const SceneView<real>& sc, uint32_t features, bool count, bool allow_lds, uint32_t diag) {
+    const kernel_choice::Inputs in{sizeof(real), features, count, allow_lds, diag, sc.program_mixed != nullptr, sc.program_compact != nullptr,
+                                   sc.program_hot != nullptr, sc.box_cache != nullptr, lds_counts(sc)};
+    return kernel_choice::choose(in);
 }
 
-// Kernel instantiation for a scene: the leanest feature subset that covers it, with or without the fused slab test;
-// `mixed` / `compact` = the scene has that program and the caller did not ask for the f64 boxes.
-static uint32_t kernel_features_base(uint32_t features, bool count, bool mixed, bool compact);
-static uint32_t kernel_features(uint32_t features, bool count, bool mixed, bool compact) {
-    const uint32_t sphere_media = count ? 0u : (features & F_SPHERE_MEDIA_ONLY);  // (the counting kernels serve every scene: no restriction)
-    features &= ~uint32_t(F_SPHERE_MEDIA_ONLY);
-    const uint32_t base = kernel_features_base(features, count, mixed, compact);
-    return base == (kFeatAll | uint32_t(F_F32_BOX)) ? (base | sphere_media) : base;  // the COMPACT full-feature kernels (what bench.py times on C5) have the restricted variant
-}
-static uint32_t kernel_features_base(uint32_t features, bool count, bool mixed, bool compact) {
-    const uint32_t fma = features & F_FMA_BOX, matte = features & F_MATTE, scene = features & ~uint32_t(F_FMA_BOX | F_MATTE);
-    const uint32_t f32box = uint32_t(F_F32_BOX);
-    // counting instantiations: the MIXED program has its own (the kernel bench.py times on sphere-only scenes, with
-    // counters), the COMPACT program counts with the full-feature kernel on that program, everything else with the
-    // full-feature kernel on the slot program (exact boxes: these counters equal the oracle's)
-    if (count) return (mixed && scene == kFeatLean) ? (kFeatLean | f32box) : (compact ? (kFeatAll | f32box) : (kFeatAll | fma));
-    if (scene == kFeatLean) return mixed ? (kFeatLean | f32box) : (kFeatLean | fma);
-    if ((scene & ~kFeatQuadBox) == 0) return kFeatQuadBox | matte | (compact ? f32box : 0u);  // slot program: no registers to spare for o*inv at 4 waves/SIMD (it spills): exact slab test, A/B on C3 40.7 vs 42.2 ms
-    if ((scene & ~kFeatMesh) == 0) return kFeatMesh | matte | (compact ? f32box : fma);
-    return kFeatAll | (compact ? f32box : fma);
-}
+#ifndef RTK_DEV_ONLY_ALL
+#define RTK_DEV_ONLY_ALL 0   // tools/kernel_resources.py -DRTK_DEV_ONLY_ALL: only the full-feature family (quick register experiments)
+#endif
 
-// Which instantiation a launch uses -- decided in ONE place, for the launcher and for rtk_kernel_name alike.
-struct KernelChoice {
-    uint32_t feat;   // template FEAT word, F_LDS_BOXES included
-    bool count, in_lds;
-};
-template <typename real>
-static KernelChoice choose_kernel(const SceneView<real>& sc, uint32_t features, bool count, bool allow_lds, uint32_t diag) {
-    const bool mixed = use_mixed_program(sc, diag);
-    bool compact = use_compact_program(sc, diag);
-    bool cold = false;
-    if (compact) {
-        // Only when it fits one CU's LDS.  A COMPACT program split between LDS (box heads) and memory (primitives) is slower
-        // than the slot program split the same way, measured: C4 with 4 494 ops 175 ms against 95 ms, C5 714 against 838
-        // Msamples/s (there the coordinates run into the thousands -- a fog boundary of radius 5000 -- and the 2^-19 x extent
-        // margin exceeds a quad's own box thickness: +55 % quad tests).
-        const size_t mat_bytes = size_t(sc.n_materials) * sizeof(MaterialRec<real>);
-        if (!(allow_lds && lds_plan::whole_fits(size_t(sc.n_units16) * sizeof(Unit16), mat_bytes)) || (diag & (1u << 23)) != 0) {  // (variant bit 23: the hot/cold form although the whole would fit)
-            // ... unless its hot part does (COLD kernels: quads and triangles stay in memory, everything else in LDS) -- full-feature family, timed kernels
-            const uint32_t scene = features & ~uint32_t(F_FMA_BOX | F_MATTE | F_SPHERE_MEDIA_ONLY);
-            cold = allow_lds && !count && sc.program_hot != nullptr && lds_plan::hot_fits(size_t(sc.n_hot_units) * sizeof(Unit16), mat_bytes) && (diag & (1u << 21)) == 0 &&
-                   (scene & ~kFeatQuadBox) != 0 && (scene & ~kFeatMesh) != 0;
-            compact = cold;
-        }
-    }
-    // the matte variants pay off in f64 only (C3: f64 34.8 -> 31.9 ms, f32 26.6 -> 36.5 ms at one more wave per SIMD)
-    KernelChoice k{kernel_features(sizeof(real) == 8 ? features : (features & ~uint32_t(F_MATTE)), count, mixed, compact), count, false};
-    const uint32_t scene = k.feat & ~uint32_t(F_FMA_BOX | F_F32_BOX | F_MATTE | F_SPHERE_MEDIA_ONLY);
-    const bool fits = allow_lds && lds_plan::whole_fits(lds_plan::image_bytes(lds_counts(sc), lds_record_sizes<real>(), k.feat), 0);
-    if (count) {  // counting builds: only the MIXED one stages its program (it is the timed kernel with counters)
-        k.in_lds = fits && (k.feat & F_F32_BOX) != 0 && !lds_plan::is_compact(k.feat);
-        return k;
-    }
-    k.in_lds = fits;
-    if (!fits && !cold) k.feat &= ~uint32_t(F_SPHERE_MEDIA_ONLY);  // (the restricted variant exists for the LDS-resident forms only)
-    if (cold) {
-        k.in_lds = false;
-        k.feat |= uint32_t(F_LDS_BOXES);
-        return k;
-    }
-    // a program larger than LDS whose box records are not: the boxes-in-LDS kernel (mesh and full-feature families)
-    if (!fits && !(k.feat & F_F32_BOX) && sc.box_cache != nullptr && (scene == kFeatMesh || scene == kFeatAll) && (diag & (1u << 21)) == 0) k.feat |= uint32_t(F_LDS_BOXES);
-    return k;
-}
-
-template <typename real, uint32_t FEAT>
-static hipError_t launch_feat(const KernelChoice& k, const SceneView<real>& sc, const CameraRec<real>* cam, const TileMap& tmap, uint32_t seed, uint32_t diag,
-                              void* partial, unsigned long long* counters, unsigned int* tile_counter, const int32_t* tile_order, unsigned int* tile_cost,
-                              hipStream_t stream, const ViewRec<real>* views) {
-#define RTK_GO(FF, C, L) return launch_one<real, FF, C, L>(sc, cam, tmap, seed, partial, counters, tile_counter, tile_order, tile_cost, diag, stream, views)
-    if constexpr ((FEAT & ~uint32_t(F_FMA_BOX)) == kFeatAll) {
-        if (k.count) RTK_GO(FEAT, true, false);
-    }
-    if constexpr (FEAT == (kFeatLean | uint32_t(F_F32_BOX))) {  // the timed sphere-scene kernel with work counters: same program, same steps, same LDS staging
-        if (k.count) {
-            if (k.in_lds) RTK_GO(FEAT, true, true);
-            RTK_GO(FEAT, true, false);
-        }
-    }
-    if constexpr (FEAT == (kFeatAll | uint32_t(F_F32_BOX))) {  // work counters on the COMPACT program (any family's scene)
-        if (k.count) RTK_GO(FEAT, true, false);
-        constexpr uint32_t SMO = uint32_t(F_SPHERE_MEDIA_ONLY);  // every medium of the scene is sphere-bounded: the variant without the generic bracket
-        if (k.feat & F_LDS_BOXES) {  // COLD: hot program in LDS, quads / triangles in memory
-            if (k.feat & SMO) RTK_GO(FEAT | uint32_t(F_LDS_BOXES) | SMO, false, false);
-            RTK_GO(FEAT | uint32_t(F_LDS_BOXES), false, false);
-        }
-        if (k.in_lds && (k.feat & SMO)) RTK_GO(FEAT | SMO, false, true);
-    }
-    if constexpr ((FEAT & F_F32_BOX) == 0 && ((FEAT & ~uint32_t(F_FMA_BOX | F_MATTE)) == kFeatMesh || (FEAT & ~uint32_t(F_FMA_BOX | F_MATTE)) == kFeatAll)) {
-        if (k.feat & F_LDS_BOXES) RTK_GO(FEAT | uint32_t(F_LDS_BOXES), false, false);  // (slot programs only: see choose_kernel)
-    }
-    if (k.in_lds) RTK_GO(FEAT, false, true);
-    // a COMPACT program outside the hot/cold form is always staged whole (choose_kernel keeps it only when it fits LDS, and
-    // `fits` is computed from the same byte count): no all-in-memory instantiation of those kernels
-    if constexpr ((FEAT & F_F32_BOX) != 0 && (FEAT & ~uint32_t(F_F32_BOX | F_MATTE)) != kFeatLean) return hipErrorInvalidValue;
-    else RTK_GO(FEAT, false, false);
-#undef RTK_GO
-}
-
-// launch_render (views = null) and launch_view_batch: one decision, one chain of instantiations.
+// launch_render (views = null) and launch_view_batch: one decision, then the row of the table that it names -- exactly that
+// row, or an error: a choice that is not compiled never runs a neighbouring kernel.
 template <typename real>
 static hipError_t launch_chosen(const SceneView<real>& sc, const CameraRec<real>* cam, const TileMap& tmap, uint32_t seed, uint32_t features, bool count,
                                 bool allow_lds, uint32_t diag, void* partial, unsigned long long* counters, unsigned int* tile_counter,
                                 const int32_t* tile_order, unsigned int* tile_cost, hipStream_t stream, const ViewRec<real>* views) {
-    const KernelChoice k = choose_kernel(sc, features, count, allow_lds, diag);
-#define RTK_LAUNCH_CASE(F) \
-    case F: return launch_feat<real, F>(k, sc, cam, tmap, seed, diag, partial, counters, tile_counter, tile_order, tile_cost, stream, views);
-#define RTK_LAUNCH_CASE_F64(F) \
-    case F:                      \
-        if constexpr (sizeof(real) == 8) return launch_feat<real, F>(k, sc, cam, tmap, seed, diag, partial, counters, tile_counter, tile_order, tile_cost, stream, views); \
-        break;
-    switch (k.feat & ~uint32_t(F_LDS_BOXES | F_SPHERE_MEDIA_ONLY)) {
-#if !defined(RTK_DEV_ONLY_ALL)   // tools/kernel_resources.py -DRTK_DEV_ONLY_ALL: only the full-feature family (quick register experiments)
-        RTK_LAUNCH_CASE(kFeatLean)
-        RTK_LAUNCH_CASE(kFeatQuadBox)
-        RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_MATTE)  // (choose_kernel strips F_MATTE from the f32 kernels: the matte variants pay off in f64 only)
-        RTK_LAUNCH_CASE(kFeatMesh)
-        RTK_LAUNCH_CASE(kFeatLean | F_FMA_BOX)
-        RTK_LAUNCH_CASE(kFeatMesh | F_FMA_BOX)
-        RTK_LAUNCH_CASE_F64(kFeatMesh | F_MATTE)
-        RTK_LAUNCH_CASE_F64(kFeatMesh | F_FMA_BOX | F_MATTE)
-        RTK_LAUNCH_CASE_F64(kFeatLean | F_F32_BOX)
-        RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_F32_BOX)
-        RTK_LAUNCH_CASE_F64(kFeatQuadBox | F_MATTE | F_F32_BOX)
-        RTK_LAUNCH_CASE_F64(kFeatMesh | F_F32_BOX)
-        RTK_LAUNCH_CASE_F64(kFeatMesh | F_MATTE | F_F32_BOX)
-#endif
-        RTK_LAUNCH_CASE(kFeatAll)
-        RTK_LAUNCH_CASE(kFeatAll | F_FMA_BOX)
-        RTK_LAUNCH_CASE_F64(kFeatAll | F_F32_BOX)
-#undef RTK_LAUNCH_CASE_F64
+    const kernel_choice::Choice k = choose_for_scene(sc, features, count, allow_lds, diag);
+#define RTK_LAUNCH_ROW(F, C, L)                                                                                        \
+    if constexpr (sizeof(real) != 0 && (!RTK_DEV_ONLY_ALL || kernel_choice::family(F) == kernel_choice::kFullFamily)) \
+        if (k.feat == F && k.count == C && k.in_lds == L)                                                              \
+            return launch_one<real, F, C, L>(sc, cam, tmap, seed, partial, counters, tile_counter, tile_order, tile_cost, diag, stream, views);
+    RTK_RENDER_KERNELS_BOTH(RTK_LAUNCH_ROW)
+    if constexpr (sizeof(real) == 8) {
+        RTK_RENDER_KERNELS_F64(RTK_LAUNCH_ROW)
     }
-#undef RTK_LAUNCH_CASE
+#undef RTK_LAUNCH_ROW
     return hipErrorInvalidValue;
 }
 template <typename real>
@@ -2671,23 +2528,21 @@ template hipError_t launch_view_batch<float>(const SceneView<float>&, const View
 template <typename real>
 const char* render_kernel_name(const SceneView<real>& sc, uint32_t features, bool count, bool allow_lds, uint32_t diag) {
     static thread_local char name[96];
-    const KernelChoice k = choose_kernel(sc, features, count, allow_lds, diag);
-    snprintf(name, sizeof name, "rtk_render_kernel<%s, %uu, %s, %s>", sizeof(real) == 8 ? "double" : "float", k.feat, k.count ? "true" : "false", k.in_lds ? "true" : "false");
+    kernel_choice::format_name(name, sizeof name, sizeof(real), choose_for_scene(sc, features, count, allow_lds, diag), false);
     return name;
 }
 template const char* render_kernel_name<double>(const SceneView<double>&, uint32_t, bool, bool, uint32_t);
 template const char* render_kernel_name<float>(const SceneView<float>&, uint32_t, bool, bool, uint32_t);
 
-// What a view batch dispatches: the view kernel of the instantiation choose_kernel picks, or -- where that one has none (the
+// What a view batch dispatches: the view kernel of the instantiation the choice names, or -- where that one has none (the
 // program in global memory) -- the plain kernel, launched once per view.
 template <typename real>
 const char* view_kernel_name(const SceneView<real>& sc, uint32_t features, bool allow_lds, uint32_t diag, bool* is_view_kernel) {
     static thread_local char name[96];
-    const KernelChoice k = choose_kernel(sc, features, false, allow_lds, diag);
-    const bool view = has_view_kernel(k.feat, k.count, k.in_lds);
+    const kernel_choice::Choice k = choose_for_scene(sc, features, false, allow_lds, diag);
+    const bool view = kernel_choice::has_view_kernel(k.feat, k.count, k.in_lds);
     if (is_view_kernel) *is_view_kernel = view;
-    if (!view) return render_kernel_name(sc, features, false, allow_lds, diag);
-    snprintf(name, sizeof name, "rtk_view_batch_kernel<%s, %uu, %s>", sizeof(real) == 8 ? "double" : "float", k.feat, k.in_lds ? "true" : "false");
+    kernel_choice::format_name(name, sizeof name, sizeof(real), k, view);
     return name;
 }
 template const char* view_kernel_name<double>(const SceneView<double>&, uint32_t, bool, uint32_t, bool*);

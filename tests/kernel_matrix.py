@@ -1,5 +1,5 @@
 """The table of rtk_render_kernel<real, FEAT, COUNT, IN_LDS> instantiations (csrc/rtk_trace.hip): one row per instantiation
-that choose_kernel can select, with a scene, an upload order, a real mode, a variant word and count_work that select it.
+that kernel_choice::choose (csrc/rtk_kernel_choice.h) can select, with a scene, an upload order, a real mode, a variant word and count_work that select it.
 Data and scene builders only -- the tests are in test_abi_and_host.py (the compiled set == the table, CPU) and
 test_kernel_matrix.py (every row rendered on the device, and the dispatched names read back from a kernel trace).
 
@@ -20,7 +20,7 @@ from tests.scene_cases import IMAGE_CASES, SCENE_SEED, scene_file
 
 F64, F32 = "f64", "f32"
 REFERENCE, FAST = "reference", "fast"          # rtk_scene_upload / rtk_scene_upload_fast (F_FMA_BOX, MIXED / COMPACT programs)
-# variant bits that choose_kernel reads
+# variant bits that kernel_choice::choose reads
 V_GLOBAL = 1                # bit 0: the program stays in global memory (allow_lds = false)
 V_SLOT = 1 << 20            # the slot program although the upload built a MIXED / COMPACT one
 V_NO_LDS_BOXES = 1 << 21    # no F_LDS_BOXES
@@ -41,7 +41,7 @@ def row_id(row):
 
 
 def kernel_name(expect):
-    """What rtk_kernel_name prints (render_kernel_name, rtk_trace.hip) and a kernel trace shows behind `rtk::`."""
+    """What rtk_kernel_name prints (kernel_choice::format_name, rtk_kernel_choice.h) and a kernel trace shows behind `rtk::`."""
     real, feat, count, in_lds = expect
     return f"rtk_render_kernel<{'double' if real == F64 else 'float'}, {feat}u, {'true' if count else 'false'}, {'true' if in_lds else 'false'}>"
 
@@ -147,7 +147,7 @@ def upload(renderer, scene, cam, order):
 
 
 # ------------------------------------------------------------------------------------------------ rows
-# COUNT = true rows: rtk_kernel_name always asks with count = false, so their tuples follow kernel_features_base's counting rule
+# COUNT = true rows: rtk_kernel_name always asks with count = false, so their tuples follow kernel_choice::kernel_features_base's counting rule
 # (MIXED program on a lean scene: its own instantiation, staged like the timed one; COMPACT: full-feature | F_F32_BOX, in memory;
 # slot program: full-feature | the order's F_FMA_BOX, in memory) and only the trace test confirms them.
 _DUP_REF = "the all-in-memory twin of this scene's F_LDS_BOXES row: the f32 bit-identity of that row is this comparison"
@@ -165,7 +165,7 @@ ROWS = [
     _row("three_spheres", FAST, F64, V_SLOT | V_GLOBAL, False, 128, False),
     _row("three_spheres", FAST, F32, 0, False, 128, True),
     _row("three_spheres", FAST, F32, V_GLOBAL, False, 128, False),
-    # quad/box family without F_MATTE (f64: choose_kernel strips F_MATTE from f32, whose quad/box rows cornell_box serves)
+    # quad/box family without F_MATTE (f64: kernel_choice::choose strips F_MATTE from f32, whose quad/box rows cornell_box serves)
     _row("quadbox_metal", REFERENCE, F64, 0, False, 69, True),
     _row("quadbox_metal", REFERENCE, F64, V_GLOBAL, False, 69, False),
     _row("quadbox_metal", FAST, F64, 0, False, 325, True),                      # COMPACT
@@ -231,7 +231,7 @@ ROWS = [
 # test_fast_order_on_the_device uses for the scene's class); rows on the slot program must equal the oracle's counters.
 CULLING_SLACK = {"three_spheres": 0.03, "material_zoo": 0.25}
 
-# Compiled instantiations that choose_kernel cannot select: tuple -> the condition that excludes it.
+# Compiled instantiations that kernel_choice::choose cannot select: tuple -> the condition that excludes it.
 UNREACHABLE = {}
 
 # f32 sample coherence with the f64 kernel at spp = 1 (tests/test_f32_parity.py: TAU, COHERENT_P99 and the rule for the bound)

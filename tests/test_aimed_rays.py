@@ -56,7 +56,7 @@ UNREACHED = {
 }
 
 # The program forms the variant word can steer each family's scene to in the fast order, f64: variant -> (FEAT, IN_LDS) of
-# rtk_render_kernel<double, FEAT, false, IN_LDS> by choose_kernel's rules (rtk_trace.hip) -- the MIXED / COMPACT program staged or (lean)
+# rtk_render_kernel<double, FEAT, false, IN_LDS> by kernel_choice::choose's rules (rtk_kernel_choice.h) -- the MIXED / COMPACT program staged or (lean)
 # in memory, the slot program with the fused f64 test (quad/box: the literal test) staged, in memory or behind a box table, the
 # hot/cold form.  The slot program of 576 triangles does not fit one CU's LDS (447 KB): that family stages the box table instead.
 S, B = 2048, 1024            # F_SPHERE_MEDIA_ONLY: the full family's fog ball has a stationary sphere for a boundary; F_LDS_BOXES

@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) over tests/kernel_matrix.py: every rtk_render_kernel instantiation that choose_kernel can select is
+"""GPU tests (-m gpu) over tests/kernel_matrix.py: every rtk_render_kernel instantiation that kernel_choice::choose can select is
 launched by the row that selects it and checked there --
 
   every row      rtk_kernel_name's answer is the row's name, character for character (COUNT = false rows: the entry point
@@ -11,8 +11,8 @@ launched by the row that selects it and checked there --
                  COUNT rows are on material_zoo, whose non-counting kernel is the full-feature template as well.
                  Coherence with the f64 kernel at 1 spp for the (scene, order) pairs tests/test_f32_parity.py does not run.
   the trace      one child process renders every row under `rocprofv3 --kernel-trace`; the set of dispatched
-                 rtk::rtk_render_kernel<...> names must be the set the rows expect -- what confirms that the kernel named is the
-                 kernel launched (launch_feat's own if-constexpr chain) and the COUNT rows.
+                 rtk::rtk_render_kernel<...> names must be the set the rows expect -- what confirms that the launch of the
+                 table row (launch_chosen) reaches the device under the printed name, and the COUNT rows.
 """
 import os
 import shutil
@@ -129,7 +129,8 @@ TRACE_TIMEOUT = 3 * TRACE_RUN_SECONDS
 
 def test_every_row_dispatches_the_kernel_it_names(tmp_path):
     """The names in a kernel trace of one process that renders every row == the names the rows expect: rtk_kernel_name prints
-    choose_kernel's result, the launch goes through launch_feat's chain -- this is where the two are compared, COUNT rows included."""
+    kernel_choice::choose's result and launch_chosen launches the table row with that tuple (tests/test_kernel_choice.py, CPU) -- here the
+    launch is seen to reach the device under that name, COUNT rows included."""
     rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(rocprof):
         pytest.skip("rocprofv3 not present")

@@ -185,7 +185,7 @@ def test_row_a_whole_program_and_materials(ask, real, feat, name, rec, material_
         n_max = last_true(lambda k: k * rec + m * mat <= CAPACITY)
         assert CAPACITY - rec < n_max * rec + m * mat <= CAPACITY
         assert ask(["whole %d %d" % (n_max * rec, m * mat), "whole %d %d" % ((n_max + 1) * rec, m * mat)]) == [(1,), (0,)]
-        # the whole_fits(image, 0) form choose_kernel uses
+        # the whole_fits(image, 0) form kernel_choice::choose uses
         assert ask(["whole %d 0" % (n_max * rec + m * mat), "whole %d 0" % ((n_max + 1) * rec + m * mat)]) == [(1,), (0,)]
         got = check_plans(ask, [(real, feat, True, 15, order, counts(**{name: n_max, "materials": m})) for order in (False, True)])
         assert got[0][0] == n_max * rec + m * mat
